@@ -7,12 +7,20 @@ Default workload (BASELINE.json config 4, per-GPU shard; weak scaling):
   batch (distance AND canonical edit script for every pair), inputs resident
   in HBM.  At --gpus 8 that is exactly config 4 (64k pairs).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload c4|c3|c2]
+    python bench.py [--gpus N --steps K --warmup W] [--workload c4|c3|c2] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the
+roofline and VALU figures in it come from the HIP events of the timed steps).
+--full adds everything that takes work of its own: the script property check
+over all pairs, the C-oracle and pure-Python CPU legs with the bit-exact rate,
+the rocprofv3 counter passes (HBM traffic, VALU/SALU issue) and, for N > 1, the
+gather to rank 0 with its verification.  --dump-outputs DIR writes what the last
+timed step computed (distance, length, script words) as DIR/<name>.npy.
 
 For N > 1 run under torch.distributed.run (one rank per GPU); each rank
 generates its own pair-index shard (no input scatter), the steps run with no
-data-path collective, and the per-pair results are gathered to rank 0 over
-RCCL once, after the timed region (timed separately as gather_ms).
+data-path collective, and with --full the per-pair results are gathered to
+rank 0 over RCCL once, after the timed region (timed separately as gather_ms).
 Rank 0 prints one JSON line.
 """
 import argparse
@@ -287,7 +295,7 @@ def pmc_pass(counters, kernels, timeout=240):
     d = tempfile.mkdtemp(prefix="sedpmc_", dir="/tmp")
     # argparse keeps the last occurrence of each flag
     child = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + [
-        "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--traffic", "none"]
+        "--steps", "1", "--warmup", "0", "--no-full", "--dump-outputs", ""]
     cmd = ["timeout", "-s", "KILL", str(timeout), rp, "--pmc"] + list(counters) + [
         "-T", "-d", d, "-o", "pmc", "--output-format", "csv", "--"] + child
     try:
@@ -521,12 +529,43 @@ def verify_gathered(args, plan, P, n, m, world, gdist, glen, gops, want_script, 
     return out
 
 
+DUMP_BUDGET = 64 << 20  # bytes --dump-outputs may write in all
+DUMP_SEED = 20261019
+
+
+def dump_outputs(path, dist, ln, ops):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step (Batch.results()), as
+    path/<name>.npy: dist (float64, one per pair), len (float64: script length, -1 where none was asked for) and,
+    in script mode, ops (float64: the packed script words, 16 2-bit ops per word, exact in a double).  Script
+    words beyond the budget are cut to a fixed, seeded, sorted sample of word indices (the same for every run of
+    the same arguments).  Returns {name: elements written}."""
+    os.makedirs(path, exist_ok=True)
+    out = {"dist": np.asarray(dist, np.float64), "len": np.asarray(ln, np.float64)}
+    if ops is not None:
+        room = (DUMP_BUDGET - out["dist"].nbytes - out["len"].nbytes) // 8 - 64  # .npy headers are 128 B each
+        if len(ops) > room:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, len(ops), size=room))
+            ops = ops[idx]
+        out["ops"] = np.asarray(ops, np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: int(a.size) for name, a in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs (= ranks).  Outside a launcher, N > 1 starts torch.distributed.run with N ranks")
     ap.add_argument("--steps", type=int, default=20)  # per-cell-code batches pipeline traceback k beside DP k+1 (the last one is not overlapped); checkpoint batches run DP then traceback
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action=argparse.BooleanOptionalAction, default=False,
+                    help="also run what the headline figure does not need: the script property check over all pairs, "
+                         "the CPU legs and the bit-exact rate (--cpu-seconds, --no-cpu-baseline, --no-python-baseline), "
+                         "the rocprofv3 counter passes (--traffic), the instrumented pass of --timing-every != 1 and, "
+                         "for N > 1, the gather to rank 0 with its verification")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last step's results as DIR/dist.npy, DIR/len.npy and (script "
+                         "mode) DIR/ops.npy (float64; at most 64 MB in all; N > 1: rank 0's shard)")
     ap.add_argument("--workload", default="c4", choices=sorted(WORKLOADS))
     ap.add_argument("--pairs", type=int, default=0, help="override pairs per GPU")
     ap.add_argument("--shape", default="", help="override the pair shape NxM (experiments; fixed-shape workloads)")
@@ -662,7 +701,12 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     time_pass = "the timed region"
-    if args.timing_every != 1:  # kernel times from an instrumented pass of the same steps (untimed by the bench)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else runs the batch again: the last timed step's results
+        d_out, _, ln_out, ops_out = batch.results()
+        dumped = dump_outputs(args.dump_outputs, d_out, ln_out, ops_out)
+        del d_out, ln_out, ops_out
+    if args.timing_every != 1 and args.full:  # kernel times from an instrumented pass of the same steps (untimed by the bench)
         batch.set_timing(1)
         batch.reset_times()
         for _ in range(args.steps):
@@ -686,7 +730,7 @@ def main():
     # ---- results: gather to rank 0 over RCCL (timed separately) ----
     gather_ms = None
     got = None
-    if dist is not None:
+    if dist is not None and args.full:
         import sedshard
         words = int(packed.ops_off[P])
         t_dist = torch.empty(P, dtype=torch.float64, device="cuda")
@@ -707,7 +751,9 @@ def main():
     check = {}
     cpu = None
     threads = cpu_share()
-    if dist is not None:
+    if not args.full:
+        pass  # a plain run prints the line from the timed steps alone
+    elif dist is not None:
         if rank == 0:
             gd = got[0].cpu().numpy()
             gl = got[1].cpu().numpy()
@@ -748,7 +794,7 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    dp_avg = float(np.mean(dp_ms))
+    dp_avg = float(np.mean(dp_ms)) if len(dp_ms) else None  # None: no timing events and no instrumented pass
     # A checkpoint batch of >= 2048 pairs runs in parts on as many streams (SED_CK_HALVES), and pipelined batches
     # put consecutive runs' DP kernels on two streams: launches overlap.  The roofline therefore divides a step's
     # bytes and cells by the DP kernels' busy time per step, the union of every DP launch's event interval over the
@@ -757,7 +803,11 @@ def main():
     launches = batch.dp_launches
     algo_launch, design_launch, cells_launch = algo_bytes / launches, design_bytes / launches, cells / launches
     dp_busy = interval_union([(s[0], s[1]) for run in spans for s in run]) / max(1, len(spans))
-    if args.timing_every != 1:
+    if args.timing_every != 1 and not args.full:
+        dp_busy = ms_per_step
+        time_pass = "the timed region's step time (timing events on %s; the instrumented pass runs with --full)" % (
+            "no run" if args.timing_every == 0 else "every %d-th run" % args.timing_every)
+    elif args.timing_every != 1:
         # the instrumented pass enqueues slower (timing events cost the host ~5 us per run, tools/host_overhead.py),
         # so its overlap differs from the timed region's: the roofline takes the timed step itself as the kernels'
         # busy time (an upper bound), and the pass's union stays beside it
@@ -765,7 +815,7 @@ def main():
         time_pass = "the timed region's step time (no timing events in it; the union over %s was %.4g ms)" % (
             time_pass, dp_busy_pass)
     achieved = algo_bytes / (dp_busy * 1e-3) / 1e9
-    achieved_launch = algo_launch / (dp_avg * 1e-3) / 1e9
+    achieved_launch = algo_launch / (dp_avg * 1e-3) / 1e9 if dp_avg else None
     nl, npk, nbp = batch.lane_pairs, batch.packed_pairs, batch.bitpar_pairs
     lane_x2 = batch.mode == "i32" and not want_script and nl > 0 and not args.no_pack and nbp == 0
     wave_x2 = npk - (nl if lane_x2 else 0)  # wave pairs computed two per wave
@@ -805,6 +855,8 @@ def main():
                       1: ["sed_traceback_kernel", "sed_traceback_window_kernel"]}.get(batch.traceback_mode, [])
     kname = "+".join(parts)
     traffic, traffic_src, issue, issue_src = None, None, None, None
+    if not args.full:
+        args.traffic = "none"
     if args.traffic == "measure" and world == 1:
         traffic, detail = measure_traffic(set(parts))
         traffic_src = {"measured": "rocprofv3 --pmc, this workload, one step per counter", **detail} \
@@ -821,7 +873,7 @@ def main():
     env = {k: v for k, v in sorted(os.environ.items()) if k.startswith("SED_")}
     line = {
         "metric": METRIC, "value": value, "unit": "cells/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+        "warmup": args.warmup, "full": args.full, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "u32" if batch.mode == "i32" else "f64", "data": "synthetic",
         "config": {"workload": desc, "pairs_per_gpu": P, "timing_every": args.timing_every, "n": n, "m": m, "costs": costs_file,
                    "script": want_script, "pipeline": pipeline and batch.traceback_mode != 2, "mode": batch.mode,
@@ -849,7 +901,7 @@ def main():
                      "algo_bytes_def": "SURVEY.md 8(d): per pair (n+m)/4 in + 8 out" +
                                        (" + 0.25 B/cell traceback + (n+m) reads + (n+m)/4 ops out" if want_script
                                         else ""),
-                     "frac_per_launch_overlapped": achieved_launch / HBM_PEAK_GBS,
+                     "frac_per_launch_overlapped": None if achieved_launch is None else achieved_launch / HBM_PEAK_GBS,
                      "frac_step": algo_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                      "design_bytes_per_step": design_bytes,
                      "design_frac": design_bytes / (dp_busy * 1e-3) / 1e9 / HBM_PEAK_GBS},
@@ -859,7 +911,7 @@ def main():
             "achieved": rate, "peak": valu_peak, "unit": "cells/s", "frac": rate / valu_peak,
             "time_basis": "kernel_ms_per_step"},
         "issue": issue, "issue_source": issue_src,
-        "traceback_ms": float(np.mean(tb_ms)) if want_script else None,
+        "traceback_ms": float(np.mean(tb_ms)) if want_script and len(tb_ms) else None,
         "gather_ms": gather_ms,
         # each rank's [first, stop) pair ids (config 5: query rows), regenerated from the seeds on rank 0 to verify
         "shards": [list(shard_bounds(args.workload, Pw, world, r)) for r in range(world)],
@@ -870,6 +922,8 @@ def main():
         if dom:
             line["valu"]["issue_util"] = issue[dom[0]]["valu_issue"]
     line.update(check)
+    if dumped is not None:
+        line["dumped"] = {"dir": args.dump_outputs, "elements": dumped}
     print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ TAG=${1:-r01}
 export TMPDIR=/tmp
 O=gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.log
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d $O/kt -o kt --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --traffic none > $O/kt_bench.json 2> $O/kt_bench.log
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -T -d $O/fetch -o pmc --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-pipeline --traffic none > $O/fetch_bench.json 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -T -d $O/write -o pmc --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-pipeline --traffic none > $O/write_bench.json 2>&1

@@ -4,7 +4,7 @@ set -e
 out=gpurun_out/sweep.jsonl
 : > $out
 run() {
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > gpurun_out/sw.json 2> gpurun_out/sw.log
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > $(dirname $out)/sw.json 2> $(dirname $out)/sw.log
   python3 -c "
 import json,sys; d=json.load(open('gpurun_out/sw.json'))
 print(json.dumps({'args': sys.argv[1:], 'value': d['value'], 'ms_step': d['ms_per_step'], 'dp_ms': d['roofline']['kernel_ms'],
