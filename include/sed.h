@@ -100,6 +100,12 @@ enum {
 #define SED_OPT_ZEROCOPY 15     /* small batches (the per-call path) whose kernels write results and scripts with plain
                                    stores: the kernels write them into the batch's pinned host block, so no download
                                    follows the run: 0 auto (on), 2 never */
+#define SED_OPT_BAND 16         /* checkpoint script batches of the stripe kernel (sed_batch_traceback_mode 2, not CHAIN):
+                                   the forward skips the 64-step chunks of every stripe that no optimal path can reach,
+                                   by the cost of the plain diagonal path as an upper bound on the distance (computed on
+                                   the device in every run; substitution costs must be >= 0, else off): 0 auto (on),
+                                   2 never.  Environment SED_BAND=0 turns it off for the process.  Results are the same
+                                   bit for bit. */
 #define SED_OPT_DEBUG_CORRUPT 9 /* testing only: p + 1 overwrites one checkpoint word of pair p before its traceback,
                                    which must then fail with SED_E_DEVICE naming the pair; 0 off */
 
@@ -184,6 +190,21 @@ int sed_dot_factor(const double *sub, double ins, double del, int maxmin, int la
 int sed_batch_dot_keys(const sed_batch *b);           /* bit 0: the checkpoint forward kernel runs dot keys, bit 1: the
                                                          CHAIN kernel runs ladder dot keys (SED_OPT_DOT), bit 2: over
                                                          the wide ladder (L unit 16) */
+/* Band pruning (SED_OPT_BAND).  The three functions below are for tests and diagnostics only: they restate the shared
+ * bound without a device, and no caller of the engine needs them.
+ * sed_band_bounds: out[0..1] = the lowest and highest diagonal e = j - i an optimal path of an n x m pair can touch when
+ *   some path costs ub: e <= (ub + delete (m - n)) / (insert + delete), -e <= (ub - insert (m - n)) / (insert + delete).
+ * sed_band_chunk_range: out[0..1] = the first and last 64-step chunk stripe `stripe` (64 rows_per_lane rows) runs for
+ *   that window, out[2] = the chunks of an unpruned stripe.  A stripe starts at column 64 out[0] + 1.
+ * sed_band_cells: the cells the forward computes for one pair of codes 0..3 under the 4 x 4 table sub (a -> b,
+ *   row-major), with ub = the cost of the plain diagonal path; negative on bad arguments.
+ * sed_batch_band_cells: the same summed over the batch's pairs (= sum n*m when the batch is not pruned). */
+int sed_band_bounds(int32_t n, int32_t m, double ins, double del, double ub, int32_t *out);
+int sed_band_chunk_range(int32_t n, int32_t m, int32_t rows_per_lane, int32_t elo, int32_t ehi, int32_t stripe,
+                         int32_t *out);
+double sed_band_cells(const double *sub, double ins, double del, const uint8_t *codes_a, int32_t n,
+                      const uint8_t *codes_b, int32_t m, int32_t rows_per_lane);
+double sed_batch_band_cells(const sed_batch *b);
 int sed_batch_traceback_mode(const sed_batch *b);     /* 0 no script, 1 per-cell codes, 2 checkpoints (SED_OPT_TB),
                                                          3 per-cell codes walked stripe-parallel (<= 64 pairs, R = 4),
                                                          4 SPLIT checkpoints recomputed into per-cell codes
@@ -223,7 +244,8 @@ int sed_batch_device_results(const sed_batch *b, uint64_t *d_dist, uint64_t *d_i
 /* Copy dist (f64[npairs]), len (i32[npairs]) and the packed scripts (u32[ops_words]) of the last
  * run into caller device memory (e.g. tensors an RCCL gather sends); any pointer may be 0. Blocking. */
 int sed_batch_export(sed_batch *b, uint64_t d_dist, uint64_t d_len, uint64_t d_ops);
-/* Algorithmic counts of one run: DP cells (sum n*m) and HBM bytes (inputs + traceback + outputs). */
+/* Algorithmic counts of one run: DP cells (sum n*m, nominal: pruned cells count too) and HBM bytes (inputs +
+ * traceback + outputs; with band pruning the checkpoints of the chunks that run). */
 int sed_batch_work(const sed_batch *b, double *cells, double *algo_bytes);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):

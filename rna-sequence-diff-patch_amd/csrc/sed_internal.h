@@ -33,6 +33,7 @@ struct sed_result {
 #define SED_ERR_TB_STALL 3       // traceback: a tile visit made no progress
 #define SED_ERR_TB_GUARD 4       // traceback: more tile visits than any path can need
 #define SED_ERR_TB_LENGTH 5      // traceback: the walk's op count differs from the sink's L
+#define SED_ERR_TB_BAND 6        // CK traceback: the walk left the band the forward computed (band pruning)
 
 #ifdef __HIPCC__  // (device helpers: the runtime, compiled by g++, does not see them)
 // Script padding.  A pair's script region holds ceil((n+m)/16) words; its ops fill ceil(len/16) of them.  Every walk
@@ -130,6 +131,10 @@ struct sed_launch {
     bool tb_ladder;     // traceback codes of the integer kernels carry the row's ladder rung (sed_kernels.hip)
     bool tb_wide;       // ... of the wide ladder (ladder dot keys, LadderW: the CHAIN kernel's LDOT batches)
     bool ck;            // integer R = 16 wave kernel: tb holds checkpoints, the traceback recomputes tiles
+    // band pruning (checkpoint batches of the stripe kernel): band[pair] = the window of diagonals the forward computes
+    // and the traceback assumes, written by sed_band_kernel before every forward with bandp's costs; nullptr = off
+    struct sed_band *band;
+    const struct sed_band_params *bandp;
     // timing events carried by the launches themselves (hipExtLaunchKernelGGL: timestamps on the dispatch
     // packet, no marker packet between kernels): the launcher's first kernel records ev0 at its start, its last
     // kernel ev1 at its end; nullptr = none
@@ -218,6 +223,65 @@ __host__ __device__ inline uint64_t sed_ck_row_word(int R, int k, int ngroups, i
     return ((uint64_t)k * (uint64_t)ngroups + (uint64_t)(s / G)) * (uint64_t)SED_CK_RW + (uint64_t)(t / GH) * (uint64_t)G +
            (uint64_t)(s % G);
 }
+// Band pruning of checkpoint script batches of the stripe kernel.  With substitution costs >= 0, any
+// path through cell (i, j), e = j - i, costs at least insert (e+ + (D - e)+) + delete ((-e)+ + (e - D)+), D = m - n.
+// UB = the cost of the plain diagonal path (sum of sub(a_i, b_i) over i < min(n, m), plus |D| inserts or deletes) bounds
+// the distance from above, so only cells with elo <= e <= ehi can lie on an optimal path:
+//   e <= (UB + delete D) / (insert + delete),   -e <= (UB - insert D) / (insert + delete)     (integer floor).
+// Both numerators are >= 0 (UB >= insert D+ + delete (-D)+), and elo <= min(0, D), ehi >= max(0, D).
+struct sed_band {
+    int32_t elo, ehi;
+};
+#define SED_BAND_OPEN_LO (-0x20000000)
+#define SED_BAND_OPEN_HI 0x20000000
+__host__ __device__ inline sed_band sed_band_window(int n, int m, uint32_t ins, uint32_t del, uint64_t ub) {
+    const int64_t D = (int64_t)m - n, s = (int64_t)ins + del;
+    int64_t hi = ((int64_t)ub + (int64_t)del * D) / s, lo = ((int64_t)ub - (int64_t)ins * D) / s;
+    hi = hi > m ? m : hi;
+    lo = lo > n ? n : lo;
+    sed_band w;
+    w.elo = (int32_t)-lo;
+    w.ehi = (int32_t)hi;
+    return w;
+}
+// Stripe k (rows k ROWS + 1 .. min(n, (k + 1) ROWS)) needs columns [r0 + 1 + elo, r1 + ehi] clipped to [1, m]; its
+// schedule runs whole 64-step chunks clo .. chi (x = clo, y = chi): every lane starts at column 64 clo + 1 from the
+// border state (lane 0's first diagonal, the stripe above's cell at column 64 clo, is the real value where that stripe
+// computed it: it is inside the window when 64 clo = r0 + elo), and lane 63 reaches column 64 chi + 1 (lane t: 64 chi +
+// 64 - t).  Both are nondecreasing in k, clo <= chi <= nchunks - 1, and the last stripe's range holds the sink's chunk.
+// An open window gives 0 .. nchunks - 1.
+__host__ __device__ inline void sed_band_chunks(int n, int m, int ROWS, int nchunks, sed_band w, int k, int *clo,
+                                                int *chi) {
+    const int64_t r0 = (int64_t)k * ROWS, r1 = r0 + ROWS < n ? r0 + ROWS : n;
+    int64_t jlo = r0 + 1 + w.elo, jhi = r1 + w.ehi;
+    jlo = jlo < 1 ? 1 : (jlo > m ? m : jlo);
+    jhi = jhi > m ? m : (jhi < 1 ? 1 : jhi);
+    const int lo = (int)((jlo - 1) >> 6), hi = (int)((jhi + 62) >> 6);
+    *chi = hi < nchunks - 1 ? hi : nchunks - 1;
+    *clo = lo < *chi ? lo : *chi;
+}
+// cells of the pair inside its stripes' chunk ranges: rows x (64 (chi - clo)) columns per stripe (the columns every
+// lane computes, as n m counts them for an unpruned pair; a stripe that runs to its last chunk counts up to m)
+__host__ __device__ inline double sed_band_pair_cells(int n, int m, int R, sed_band w) {
+    const int ROWS = 64 * R, G = 64 / R;
+    const int nstripes = (n + ROWS - 1) / ROWS, SG = (m + 63 + G - 1) / G * G, nchunks = (SG + 63) >> 6;
+    double cells = 0;
+    for (int k = 0; k < nstripes; ++k) {
+        int clo, chi;
+        sed_band_chunks(n, m, ROWS, nchunks, w, k, &clo, &chi);
+        const int rows = (k + 1) * ROWS < n ? ROWS : n - k * ROWS;
+        const int jend = (chi >= nchunks - 1 || 64 * chi > m) ? m : 64 * chi;
+        cells += (double)rows * (double)(jend - 64 * clo);
+    }
+    return cells;
+}
+// the diagonal bound's inputs, for sed_band_kernel: cost[a * 4 + b] = sub(a -> b) as an integer
+struct sed_band_params {
+    uint32_t cost[16];
+    uint32_t ins, del;
+};
+// UB and the window of every wave pair of the launch, into band[pair] (one wave per pair; the forward's first kernel)
+hipError_t sed_launch_band(const sed_launch &L, const sed_band_params &bp);
 // CK batches (L.ck): the traceback that recomputes tiles from the forward kernel's checkpoints
 hipError_t sed_launch_traceback_ck(const sed_launch &L, uint32_t *ops, const sed_i32_params &prm);
 // SPLIT batches with checkpoints: every tile's op codes from the checkpoints, into the per-cell code layout (one wave

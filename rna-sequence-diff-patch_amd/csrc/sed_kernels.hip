@@ -587,7 +587,7 @@ __global__ __launch_bounds__(SPLIT ? 128 : 256) __attribute__((amdgpu_waves_per_
 void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const int2 *__restrict__ tasks,
                   const uint32_t *__restrict__ seqa, const uint32_t *__restrict__ seqb,
                   uint32_t *__restrict__ tb, uint32_t *__restrict__ bnd, sed_result *__restrict__ res,
-                  sed_i32_params prm) {
+                  sed_i32_params prm, const sed_band *__restrict__ band) {
     constexpr int ROWS = 64 * R;
     constexpr int G = Grp<R>::G;
     static_assert(!CK || (R <= 16 && !TB && !LEN), "checkpoints: R <= 16, distance keys");
@@ -629,6 +629,18 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
     const int cap_lane = wsink / R, cap_row = wsink % R;
     uint32_t cap = 0;
     bool ok = true;
+    // band pruning (CK, one wave per pair; sed_internal.h: sed_band_chunks): stripe k runs chunks clo .. chi of its
+    // schedule, from the border state at column 64 clo, and takes the border constant for the top values the stripe
+    // above did not compute (steps past top_hi of the in-place bottom-row buffer, which holds stale words there).
+    // Wave-uniform, in scalar registers; an open window (no band) gives 0 .. nchunks - 1 and every top value.
+    sed_band bw{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
+    if constexpr (CK && !SPLIT) {
+        if (band) {
+            bw.elo = __builtin_amdgcn_readfirstlane(band[pair].elo);
+            bw.ehi = __builtin_amdgcn_readfirstlane(band[pair].ehi);
+        }
+    }
+    int top_hi = 0x7FFFFFFF, clo_prev = 0;  // (of the stripe above)
     // per wave: lane 0's top values of the current 64-step chunk, and a ring of str2 selectors by column
     // (column ci at slots ci & 127 and (ci & 127) + 128; the 64 columns before 0 hold the virtual-column
     // sentinel), from which lane t reads column s - t at step s
@@ -665,6 +677,8 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
             }
         }
         const int row0 = k * ROWS + lane * R;  // 0-based str1 index of this lane's first row
+        int clo = 0, chi = nchunks - 1;
+        if constexpr (CK && !SPLIT) sed_band_chunks(n, m, ROWS, nchunks, bw, k, &clo, &chi);
         uint32_t cv[R], V[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -675,6 +689,20 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         }
         uint32_t top_prev;
         i32_reset<R, LEN, DOT>(V, top_prev);
+        if constexpr (CK && !SPLIT) {
+            // a stripe that starts at column 64 clo + 1 > 1: the diagonal of lane 0's first cell is the cell (r0, 64 clo)
+            // of the stripe above, which lies on the window's edge when 64 clo = r0 + elo, so it is the real value
+            // (its step's word of the bottom-row buffer; every other lane's first diagonal is left of the window).
+            // Only where the stripe above computed that column (clo > its own clo): where both start at the same
+            // chunk the cell is left of the window (e < elo) and the reset's border constant stands.  (The word
+            // there is a virtual-step store of the stripe above, which holds the same constant: a lane's state
+            // stays at the border through its virtual columns, i32_sent.  The guard keeps this load off that.)
+            if (k > 0 && clo > clo_prev) {
+                const int idx = 64 * clo + 62;
+                const uint32_t v = load_sc1(bnd + d.bnd_off + (uint32_t)idx);
+                top_prev = (lane == 0 && idx <= top_hi) ? v : top_prev;
+            }
+        }
         // column-0 state for every lane; virtual columns until the lane's first real one (see above)
         uint32_t bottom = V[R - 1], selv = i32_sent<LEN, DOT>(), outc = 0;
         uint32_t W[4] = {0, 0, 0, 0};
@@ -685,7 +713,10 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         auto load_top = [&](int c) -> uint32_t {
             const int j = 64 * c + lane + 1;
             if (k == 0) return i32_row0<LEN, DOT>();
-            if constexpr (CK) return load_sc1(bnd + d.bnd_off + (uint32_t)(j + 62));
+            if constexpr (CK) {  // (past the stripe above's last chunk: the border, as the columns it never computed)
+                const uint32_t v = load_sc1(bnd + d.bnd_off + (uint32_t)(j + 62));
+                return (SPLIT || j + 62 <= top_hi) ? v : i32_row0<LEN, DOT>();
+            }
             return load_sc1(bnd_in + j + 64);
         };
         auto load_sel = [&](int c) -> uint32_t {
@@ -695,7 +726,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
             if constexpr (DOT) return b == 0 ? prm.dotcol[0] : b == 1 ? prm.dotcol[1] : b == 2 ? prm.dotcol[2] : prm.dotcol[3];
             return i32_sel(b);
         };
-        uint32_t tch = (SPLIT && k > 0) ? 0u : load_top(0), sch = load_sel(0);
+        uint32_t tch = (SPLIT && k > 0) ? 0u : load_top(clo), sch = load_sel(clo);
         if constexpr (SPLIT) {  // stripe 0's constant row in the whole ring; the feeder fills the others'
             if (k == 0) {
 #pragma unroll
@@ -704,8 +735,11 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         } else {
             lch[lane] = tch;
         }
-        ring[lane] = ring[lane + 128] = sch;
-        ring[lane + 64] = ring[lane + 192] = i32_sent<LEN, DOT>();
+        {  // columns 64 clo .. 64 clo + 63 at their slots, the 64 columns before them the sentinel
+            const int h0 = (64 * clo) & 64;
+            ring[h0 + lane] = ring[h0 + lane + 128] = sch;
+            ring[(h0 ^ 64) + lane] = ring[(h0 ^ 64) + lane + 128] = i32_sent<LEN, DOT>();
+        }
         uint32_t *tbk = tb + d.tb_off + (uint64_t)k * (uint64_t)(SG / G) * 256u;
         // CK: column checkpoints of stripe k at ccb[(chunk * (R+1) + v) * 64 + lane], row checkpoints at
         // rcb[group * 64 + (lane / G) * G + step % G] (sed_ck_*_word, the layout sed_traceback_ck_kernel reads)
@@ -723,7 +757,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         // kernels keep the rolled loop for every chunk: split the same way, their hot loop spills.  (Fully
         // unrolled chunks take the compiler > 15 min.)
         const int c_cap = last ? cap_step >> 6 : -1;
-        int s = 0;
+        int s = 64 * clo;
         int ready = 0;  // SPLIT: steps the feeder has published as ready (last read)
         // CK (not SPLIT): the chunks before the sink's run the unrolled group loop, the sink's chunk and any after it the
         // rolled one, as two loops: one loop choosing per chunk merged the paths, and the register allocator moved the
@@ -731,7 +765,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         auto chunk = [&](auto fast_tag, const int c) {
             constexpr bool FASTC = decltype(fast_tag)::value;
             uint32_t tnx = 0, snx = 0;
-            if (c + 1 < nchunks) {
+            if (c < chi) {
                 if (!SPLIT) tnx = load_top(c + 1);
                 snx = load_sel(c + 1);
             }
@@ -815,11 +849,13 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         };
         int cfast = 0;
         if constexpr (CK && !SPLIT) {
-            cfast = c_cap >= 0 ? c_cap : nchunks;
-            for (int c = 0; c < cfast; ++c) chunk(BoolTag<true>{}, c);
+            cfast = c_cap >= 0 ? c_cap : chi + 1;  // (clo <= c_cap <= chi on the last stripe)
+            for (int c = clo; c < cfast; ++c) chunk(BoolTag<true>{}, c);
         }
-        for (int c = cfast; c < nchunks; ++c) chunk(BoolTag<false>{}, c);
+        for (int c = cfast > clo ? cfast : clo; c <= chi; ++c) chunk(BoolTag<false>{}, c);
         if (!last) __builtin_amdgcn_s_waitcnt(0);  // own bottom-row stores done before the next stripe reads them
+        top_hi = 64 * chi + 63;  // the last step whose bottom row this stripe stored
+        clo_prev = clo;
     }
     if (klast == nstripes - 1 && lane == cap_lane) {
         const int2 dl = i32_decode<R, LEN, CK, DOT>(cap, n, m, prm);
@@ -2757,13 +2793,18 @@ template <int R, bool WAVE, bool FULL, int NW>
 __device__ __forceinline__ uint32_t ck_tile_sweep(const CkPairCtx &px, const int lane, const sed_i32_params &prm,
                                                   uint32_t *__restrict__ topb, uint32_t *__restrict__ selb, const int k,
                                                   const int Q, const int c, const int sig_end, uint32_t &one,
-                                                  uint32_t (&W)[NW], uint32_t &vinit) {
+                                                  uint32_t (&W)[NW], uint32_t &vinit, const int bclo = 0,
+                                                  const int bclo_prev = 0, const int btophi = 0x7FFFFFFF) {
     constexpr int NX = SED_CK_NX(NW), SELB = SED_CK_SELB(NW), NH = (NX + 63) / 64;
     constexpr int ROWS = 64 * R, G = Grp<R>::G;  // a tile: G forward lanes (bands) of R rows
     constexpr int LR = R == 4 ? 2 : R == 8 ? 3 : 4;
     constexpr bool VHOLD = CkVHold<R>::value;
     const int n = px.n, m = px.m, SG = px.SG, nchunks = px.nchunks, ngroups = px.ngroups, band = px.band;
     const int J0 = 64 * c - G * Q + 1, rowbase = k * ROWS + 64 * Q;
+    // band pruning: the forward ran stripe k from the border state at column jb = 64 bclo (bclo = 0: column 0 itself),
+    // and the stripe above stored no bottom row past step btophi (both uniform, computed by the caller once per stripe;
+    // the defaults are an open window's)
+    const int jb = 64 * bclo, tophi = Q == 0 ? btophi : 0x7FFFFFFF;
     // ---- boundaries (distance keys -> traceback keys) ----
     // Every load of the tile is issued before the first use (one memory round trip per tile visit): addresses
     // are clamped to valid words and the border cases are selects afterwards.
@@ -2772,7 +2813,7 @@ __device__ __forceinline__ uint32_t ck_tile_sweep(const CkPairCtx &px, const int
     // (uniform 64-bit bases + 32-bit lane offsets: the loads take the scalar-base form and the address
     // arithmetic stays on the scalar unit)
     uint32_t ck0 = 0, ck1 = 0;
-    if (c >= 1) {  // (uniform)
+    if (c > bclo) {  // (uniform)
         const uint32_t *cp = px.ccp + sed_ck_col_word(R, k, nchunks, c - 1, 0, G * Q);
         uint32_t o0 = px.cko0, o1 = px.cko1;
         asm volatile("" : "+v"(o0), "+v"(o1));  // (else the zero-extended offsets are hoisted as 64-bit pairs)
@@ -2806,8 +2847,8 @@ __device__ __forceinline__ uint32_t ck_tile_sweep(const CkPairCtx &px, const int
     const uint32_t clo = (a & 1u) ? prm.costrow[1] : prm.costrow[0];
     const uint32_t chi = (a & 1u) ? prm.costrow[3] : prm.costrow[2];
     const uint32_t cv = (a & 2u) ? chi : clo;
-    uint32_t V = SED_KB, tp = SED_KB;  // c = 0: the column-0 borders
-    if (c >= 1) {
+    uint32_t V = SED_KB, tp = SED_KB;  // c = clo: the borders of column 64 clo
+    if (c > bclo) {
         V = ck_to_tb(ck0, prm);
         tp = ck_to_tb(ck1, prm);
         if (VHOLD && J0 - band - 1 > m) V = 0u;  // (forward garbage past m: key 0 holds under the recurrence)
@@ -2817,11 +2858,15 @@ __device__ __forceinline__ uint32_t ck_tile_sweep(const CkPairCtx &px, const int
     for (int h = 0; h < NH; ++h) {
         const int x = lane + 64 * h;
         if ((FULL || 64 * h <= sig_end + 1) && (64 * (h + 1) <= NX || x < NX)) {
-            const uint32_t v = (above && J0 - G + x >= 1) ? ck_to_tb(rk[h], prm) : SED_KB;
+            // (the stripe above's cell at column jb is real where that stripe started left of it: the diagonal of the
+            // stripe's first cell, as the forward took it)
+            const int tcol = J0 - G + x;
+            const bool tin = tcol > jb || (Q == 0 && bclo > bclo_prev && tcol == jb);
+            const uint32_t v = (above && tin && s0r + x <= tophi) ? ck_to_tb(rk[h], prm) : SED_KB;
             topb[x] = v + 1u;
             const int col = J0 - (G - 1) + x;  // column of lane 0 at step x
             const int ci = min(max(col - 1, 0), m - 1);
-            const uint32_t sv = col < 1 ? SED_SEL_SENT : i32_sel((wb[h] >> ((ci & 15) * 2)) & 3u);
+            const uint32_t sv = col <= jb ? SED_SEL_SENT : i32_sel((wb[h] >> ((ci & 15) * 2)) & 3u);
             if constexpr (VHOLD) {  // band b's copy: the sentinel left of its window (x < G - 1 - b)
 #pragma unroll
                 for (int b = 0; b < G; ++b) selb[b * SELB + 64 + x] = x < G - 1 - b ? SED_SEL_SENT : sv;
@@ -2914,7 +2959,8 @@ __device__ __forceinline__ void ck_traceback_pair(const sed_pair_desc &d, const 
                                                   const uint32_t *__restrict__ seqb, const uint32_t *__restrict__ ck,
                                                   sed_result *__restrict__ res, uint32_t *__restrict__ ops,
                                                   const sed_i32_params &prm, uint32_t *__restrict__ topb,
-                                                  uint32_t *__restrict__ selb) {
+                                                  uint32_t *__restrict__ selb,
+                                                  const sed_band bw = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI}) {
     constexpr int ROWS = 64 * R, G = Grp<R>::G;  // a tile: G forward lanes (bands) of R rows
     static_assert(R == 4 || R == 8 || R == 16, "R in {4, 8, 16}");
     const int n = d.n, m = d.m;
@@ -2939,6 +2985,9 @@ __device__ __forceinline__ void ck_traceback_pair(const sed_pair_desc &d, const 
     int i = n, j = m;
     if (i > 0 && j > 0) {
         const CkPairCtx px = ck_pair_ctx<R>(d, lane, seqa, seqb, ck, 0);
+        // band pruning: the forward computed stripe k from column 64 clo + 1 on, and the stripe above it stored no
+        // bottom row past step tophi; both change only when the walk enters another stripe
+        int kband = -1, clo = 0, clo_prev = 0, tophi = 0x7FFFFFFF;
         uint32_t one = 1u;  // the delete candidate's +1, a VGPR operand of v_add_u32_dpp
         asm volatile("" : "+v"(one));
         int guard = 2 * (n + m) + 8;       // tiles visited; every visit makes progress
@@ -2949,17 +2998,35 @@ __device__ __forceinline__ void ck_traceback_pair(const sed_pair_desc &d, const 
             }
             const int k = (i - 1) / ROWS, t = ((i - 1) % ROWS) / R, Q = t / G;
             const int ce = (j - 1 + t) >> 6;            // the entry cell's chunk
+            if (k != kband) {  // (uniform; once per stripe)
+                int hi_;
+                tophi = 0x7FFFFFFF;
+                clo_prev = 0;
+                if (k >= 1) {
+                    sed_band_chunks(n, m, ROWS, px.nchunks, bw, k - 1, &clo_prev, &hi_);
+                    tophi = 64 * hi_ + 63;
+                }
+                sed_band_chunks(n, m, ROWS, px.nchunks, bw, k, &clo, &hi_);
+                kband = k;
+            }
+            // every optimal path stays inside the window, so a walk that arrives left of it followed keys the forward
+            // never wrote
+            if (j <= 64 * clo) {
+                err = SED_ERR_TB_BAND;
+                break;
+            }
             const int rowbase = k * ROWS + 64 * Q;
             const int re = i - rowbase - 1;             // the entry cell's tile row
             // NW = 12: a window of two chunks (ce - 1, ce) when the entry step x inside its chunk is below re, i.e. when
             // a diagonal path would leave chunk ce through its left edge before the tile's top: the path then crosses
             // the row group in one visit instead of two, 151 against 93 sweep steps per visit but half the visits
             // (22.3 -> 17.1 VALU per emitted op on config 4's pairs, tools/tb_window_model.py)
-            const int c = (NW > 8 && ce >= 1 && ((j - 1 + t) & 63) < re) ? ce - 1 : ce;
+            const int c = (NW > 8 && ce > clo && ((j - 1 + t) & 63) < re) ? ce - 1 : ce;
             const int J0 = 64 * c - G * Q + 1;
             const int sig_end = (j - J0 + G - 1) + re;  // the entry cell's sweep step (<= 16 NW - 2)
             uint32_t W[NW], vinit = 0;
-            const uint32_t ent = ck_tile_sweep<R, WAVE, false, NW>(px, lane, prm, topb, selb, k, Q, c, sig_end, one, W, vinit);
+            const uint32_t ent = ck_tile_sweep<R, WAVE, false, NW>(px, lane, prm, topb, selb, k, Q, c, sig_end, one, W, vinit,
+                                                                   clo, clo_prev, tophi);
             (void)vinit;
 #ifdef SED_TB_DEBUG
             if (visit < 32) {  // debug builds only (pair 0; its script words, 64 spare, then 136 words per visit v)
@@ -3035,7 +3102,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SED_CKTB_WAV
                                                               const uint32_t *__restrict__ seqb,
                                                               const uint32_t *__restrict__ ck,
                                                               sed_result *__restrict__ res,
-                                                              uint32_t *__restrict__ ops, sed_i32_params prm) {
+                                                              uint32_t *__restrict__ ops, sed_i32_params prm,
+                                                              const sed_band *__restrict__ band) {
     if constexpr (SED_CKTB_PRIO > 0) __builtin_amdgcn_s_setprio(SED_CKTB_PRIO);
     const int lane = threadIdx.x;
     const int pair = __builtin_amdgcn_readfirstlane(blockIdx.x);
@@ -3052,7 +3120,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SED_CKTB_WAV
         __syncthreads();
     }
     const uint32_t q0 = (uint32_t)__builtin_amdgcn_readfirstlane(res[pair].len);
-    ck_traceback_pair<R, false, NW>(d, pair, q0, lane, seqa, seqb, ck, res, ops, prm, topb, selb);
+    sed_band bw{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
+    if (band) {
+        bw.elo = __builtin_amdgcn_readfirstlane(band[pair].elo);
+        bw.ehi = __builtin_amdgcn_readfirstlane(band[pair].ehi);
+    }
+    ck_traceback_pair<R, false, NW>(d, pair, q0, lane, seqa, seqb, ck, res, ops, prm, topb, selb, bw);
 }
 
 // ---------------------------------------------------------------------------
@@ -3151,8 +3224,55 @@ __global__ void sed_selftest_kernel(uint32_t *out) {
 }
 
 // ---------------------------------------------------------------------------
+// Band pruning (sed_internal.h: sed_band_window): the cost UB of every wave pair's plain diagonal path and from it the
+// window of diagonals an optimal path can touch, one wave per pair, launched before every forward of a checkpoint
+// batch of the stripe kernel (a batch is run once in real use, so the run pays for its bound).  Each lane sums the
+// substitution costs of its share of the packed words (2 bits per symbol, 16 per word); ~(n + m) / 4 bytes per pair.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__restrict__ pd, int npairs,
+                                                       const uint32_t *__restrict__ seqa,
+                                                       const uint32_t *__restrict__ seqb, sed_band *__restrict__ band,
+                                                       sed_band_params bp) {
+    __shared__ uint32_t tab[16];
+    if (threadIdx.x < 16) tab[threadIdx.x] = bp.cost[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= npairs) return;
+    const sed_pair_desc d = pd[pair];
+    const int n = d.n, m = d.m;
+    if (d.lane || n == 0 || m == 0) {  // not a pair of the stripe kernel
+        if (lane == 0) band[pair] = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
+        return;
+    }
+    const int len = min(n, m), words = (len + 15) >> 4;
+    const uint32_t *pa = seqa + d.a_off, *pb = seqb + d.b_off;
+    uint32_t sum = 0;
+    for (int w = lane; w < words; w += 64) {
+        uint32_t x = pa[w], y = pb[w];
+        const int cnt = min(16, len - 16 * w);
+        for (int u = 0; u < cnt; ++u) {
+            sum += tab[((x & 3u) << 2) | (y & 3u)];
+            x >>= 2;
+            y >>= 2;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) {
+        const uint64_t ub = (uint64_t)sum + (m > n ? (uint64_t)(m - n) * bp.ins : (uint64_t)(n - m) * bp.del);
+        band[pair] = sed_band_window(n, m, bp.ins, bp.del, ub);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Launchers (host side, called from sed_runtime.cpp)
 // ---------------------------------------------------------------------------
+hipError_t sed_launch_band(const sed_launch &L, const sed_band_params &bp) {
+    hipExtLaunchKernelGGL(sed_band_kernel, dim3((L.npairs + 3) / 4), dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd,
+                          L.npairs, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.band, bp);
+    return hipGetLastError();
+}
 template <int R, bool TB, bool LEN = true, bool CK = false, bool DOT = false>
 static hipError_t launch_i32_R(const sed_launch &L, const sed_i32_params &prm) {
     if (L.ntasks > 0) {  // SPLIT: one workgroup per (pair, stripe): the compute wave and its feeder
@@ -3160,15 +3280,22 @@ static hipError_t launch_i32_R(const sed_launch &L, const sed_i32_params &prm) {
             return hipErrorInvalidValue;
         } else {
             SED_LAUNCH((sed_wf_i32_kernel<R, TB, true, LEN, CK, DOT>), dim3(L.ntasks), dim3(128), 0, L, L.pd, L.npairs,
-                       L.tasks, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.tb, L.bnd, L.res, prm);
+                       L.tasks, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.tb, L.bnd, L.res, prm,
+                       (const sed_band *)nullptr);
         }
     } else {
         const int grid = (L.npairs + 3) / 4;
         // SED_OCC_LDS (tuning/A-B only): dynamic LDS bytes per workgroup, which caps the resident waves
         static const int occ_lds = [] { const char *e = getenv("SED_OCC_LDS"); return e ? atoi(e) : 0; }();
-        SED_LAUNCH((sed_wf_i32_kernel<R, TB, false, LEN, CK, DOT>), dim3(grid), dim3(256), occ_lds, L, L.pd, L.npairs,
+        sed_launch Lf = L;
+        if (CK && L.band && L.bandp) {  // band pruning: this run's windows first (the phase's start event rides on it)
+            const hipError_t e = sed_launch_band(L, *L.bandp);
+            if (e != hipSuccess) return e;
+            Lf.ev0 = nullptr;
+        }
+        SED_LAUNCH((sed_wf_i32_kernel<R, TB, false, LEN, CK, DOT>), dim3(grid), dim3(256), occ_lds, Lf, L.pd, L.npairs,
                            L.tasks, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.tb, L.bnd, L.res,
-                           prm);
+                           prm, CK ? (const sed_band *)L.band : nullptr);
     }
     return hipGetLastError();
 }
@@ -3409,10 +3536,17 @@ hipError_t sed_launch_selftest(uint32_t *d_out, hipStream_t stream) {
 hipError_t sed_launch_traceback_ck(const sed_launch &L, uint32_t *ops, const sed_i32_params &prm) {
     const dim3 grid(L.npairs), block(64);
     const uint32_t *a = (const uint32_t *)L.seqa, *b = (const uint32_t *)L.seqb;
+    const sed_band *bd = L.band;
     switch (L.R) {
-    case 4: SED_LAUNCH(sed_traceback_ck_kernel<4>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm); break;
-    case 8: SED_LAUNCH(sed_traceback_ck_kernel<8>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm); break;
-    case 16: SED_LAUNCH(sed_traceback_ck_kernel<16>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm); break;
+    case 4:
+        SED_LAUNCH(sed_traceback_ck_kernel<4>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
+        break;
+    case 8:
+        SED_LAUNCH(sed_traceback_ck_kernel<8>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
+        break;
+    case 16:
+        SED_LAUNCH(sed_traceback_ck_kernel<16>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
+        break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -73,6 +73,8 @@ struct sed_ctx {
     int opt_zc = 0;             // SED_OPT_ZEROCOPY: 0 auto (small batches write results into pinned host memory), 2 never
     int opt_dot = 0;            // SED_OPT_DOT: 0 auto, 2 never (checkpoint batches keep the perm-based distance keys), 3 no wide ladder    // SED_OPT_CHAIN_WAVES: cap on the persistent waves of dynamic CHAIN mode
     int opt_debug_corrupt = 0;  // SED_OPT_DEBUG_CORRUPT: pair + 1 whose sink-tile checkpoint is overwritten
+    int opt_band = 0;           // SED_OPT_BAND: 0 auto (checkpoint batches of the stripe kernel skip the cells no
+                                // optimal path reaches), 2 never
     DevBuf selftest;
     sed_batch *scratch = nullptr;
     // pinned host staging (hipHostMalloc) of small batches: the upload blob, then the results' download
@@ -97,6 +99,14 @@ struct sed_ctx {
 
 struct sed_batch;
 namespace {
+// the cost of the plain diagonal path (band pruning's upper bound on the distance): the host's restatement of
+// sed_band_kernel over unpacked codes
+uint64_t band_diag_bound(const sed_band_params &bp, const uint8_t *a, int n, const uint8_t *b, int m) {
+    uint64_t ub = 0;
+    const int len = std::min(n, m);
+    for (int i = 0; i < len; ++i) ub += bp.cost[(a[i] & 3) * 4 + (b[i] & 3)];
+    return ub + (m > n ? (uint64_t)(m - n) * bp.ins : (uint64_t)(n - m) * bp.del);
+}
 // grow the context's pinned staging to `bytes` (first waiting for a copy still in flight from it)
 hipError_t pin_reserve(sed_ctx *c, size_t bytes) {
     hipError_t e = hipSuccess;
@@ -162,6 +172,13 @@ struct sed_batch {
     uint64_t bnd_zero_gen = 0;
     bool ck = false;           // traceback from checkpoints + recompute (sed_kernels.hip: CK) instead of codes
     bool dot = false;          // CK forward kernel on dot keys (dot_keys below)
+    // band pruning (sed_internal.h: sed_band_window): the forward runs only the chunks an optimal path can reach;
+    // d_band holds every pair's window, rewritten by sed_band_kernel in every run; band_cells = the cells the forward
+    // computes (from the host's own diagonal bounds; = cells when off)
+    bool band = false;
+    DevBuf d_band;
+    sed_band_params bandp{};
+    double band_cells = 0;
     bool lad = false;          // CHAIN kernel with the L field on ladder dot keys (dot_keys ladder mode)
     int nlane = 0, nwave = 0;  // pairs on the lane-per-pair kernel / on the wave kernels
     int nlane_x2 = 0;          // > 0: lane pairs run two per lane (distance only), in this many lanes
@@ -1039,6 +1056,45 @@ int fill_batch(sed_batch *b, const uint8_t *codes_a, const int64_t *off_a, const
     b->ntasks = (int)tasks.size();
     b->ops_words = opw;
     b->cells = cells;
+    // Band pruning: checkpoint batches of the stripe kernel (not CHAIN, not SPLIT), substitution costs >= 0 (the
+    // window's lower bound counts indels only).  SED_BAND=0 in the environment turns it off (A/B through bench.py).
+    // The cells and checkpoint bytes of a run come from the host's restatement of the device's bound.
+    static const int band_env = [] { const char *e = getenv("SED_BAND"); return e ? atoi(e) : 1; }();
+    b->band = b->ck && b->nchains == 0 && c->opt_band != 2 && band_env != 0 && c->K <= 4 && c->ins + c->del > 0;
+    for (int a = 0; a < c->K && b->band; ++a)
+        for (int bb = 0; bb < c->K; ++bb)
+            if (!(c->sub[a * c->K + bb] >= 0)) b->band = false;
+    b->band_cells = cells;
+    if (b->band) {
+        sed_band_params bp{};
+        for (int a = 0; a < 4; ++a)
+            for (int bb = 0; bb < 4; ++bb)
+                bp.cost[a * 4 + bb] = (a < c->K && bb < c->K) ? (uint32_t)c->sub[a * c->K + bb] : 0u;
+        bp.ins = (uint32_t)c->ins;
+        bp.del = (uint32_t)c->del;
+        b->bandp = bp;
+        double bc = 0, ckb = 0;
+        const int G = 64 / R;
+        for (int p = 0; p < npairs; ++p) {
+            const int nn = len_a[p], mm = len_b[p];
+            if (b->pd[p].lane || nn <= 0 || mm <= 0) {
+                bc += (double)nn * mm;
+                continue;
+            }
+            const sed_band w = sed_band_window(nn, mm, bp.ins, bp.del,
+                                               band_diag_bound(bp, codes_a + off_a[p], nn, codes_b + off_b[p], mm));
+            bc += sed_band_pair_cells(nn, mm, R, w);
+            const int nstripes = (nn + ROWS - 1) / ROWS, SG = (mm + 63 + G - 1) / G * G, nchunks = (SG + 63) >> 6;
+            for (int k = 0; k < nstripes; ++k) {  // checkpoints of the chunks the forward runs
+                int clo, chi;
+                sed_band_chunks(nn, mm, ROWS, nchunks, w, k, &clo, &chi);
+                const int steps = std::min(SG, 64 * (chi + 1)) - 64 * clo;
+                ckb += 4.0 * ((double)(chi - clo + 1) * (R + 1) * 64 + (double)(steps / G) * SED_CK_RW);
+            }
+        }
+        b->band_cells = bc;
+        tb_bytes = ckb + 8.0 * npairs;  // (and every pair's window, written and read)
+    }
     b->algo_bytes = in_bytes + (want_tb ? tb_bytes : 0) + 16.0 * npairs;
 
     // ---- pack & upload ----
@@ -1093,7 +1149,9 @@ int fill_batch(sed_batch *b, const uint8_t *codes_a, const int64_t *off_a, const
            total = o_ops + al(4 * std::max<uint64_t>(1, opw));  // (results and scripts adjacent: one download)
     b->small = b->nbuf == 1 && total <= SED_SMALL_BATCH_BYTES;
     b->zc = b->small && !b->tbpar && c->opt_zc != 2;
-    bool okalloc = b->d_bnd.reserve(4 * std::max<uint64_t>(1, bndw)) && b->d_tbmap.reserve(4 * std::max<uint64_t>(1, mapw));
+    bool okalloc = b->d_bnd.reserve(4 * std::max<uint64_t>(1, bndw)) &&
+                   b->d_tbmap.reserve(4 * std::max<uint64_t>(1, mapw)) &&
+                   (!b->band || b->d_band.reserve(sizeof(sed_band) * (size_t)npairs));
     if (b->small) {
         okalloc = okalloc && b->d_small.reserve(total);
     } else {
@@ -1344,6 +1402,7 @@ int run_batch_parts(sed_batch *b, const std::array<hipEvent_t, 4> &lg, sed_launc
         sed_launch Li = L;
         Li.pd = L.pd + first(i);
         Li.res = L.res + first(i);
+        Li.band = L.band ? L.band + first(i) : nullptr;
         Li.npairs = first(i + 1) - first(i);
         Li.stream = stream(i);
         Li.ev0 = i == 0 ? lg[2 * ph] : pl[4 * (i - 1) + 2 * ph];
@@ -1425,6 +1484,8 @@ int run_batch(sed_batch *b) {
     L.tb_ladder = b->mode == SED_MODE_I32 && !b->split_ck;  // (split_ck codes are the plain ops)
     L.tb_wide = b->lad && b->ip.lad == 2;  // (a ladder-dot batch is a CHAIN batch: every wave pair's codes come from the LDOT kernel)
     L.ck = b->ck;
+    L.band = b->band ? (sed_band *)b->d_band.p : nullptr;
+    L.bandp = &b->bandp;
     L.tasks = b->split ? (const int2 *)b->p_tasks : nullptr;
     L.ntasks = b->split ? b->ntasks : 0;
     // buffer k was last read by the traceback of run runs-3 (written by its DP, distance only): wait for it unless it
@@ -1641,6 +1702,8 @@ int fetch_results(sed_batch *b, double *out_dist, uint8_t *out_is_int, int32_t *
         case SED_ERR_TB_GUARD: return c->fail(SED_E_DEVICE, "pair %d: traceback failed: too many tile visits", p);
         case SED_ERR_TB_LENGTH:
             return c->fail(SED_E_DEVICE, "pair %d: traceback failed: script length differs from the sink's", p);
+        case SED_ERR_TB_BAND:
+            return c->fail(SED_E_DEVICE, "pair %d: traceback failed: the walk left the band the forward computed", p);
         default: return c->fail(SED_E_DEVICE, "pair %d: device error code %d", p, (int)hr[p].err);
         }
     }
@@ -1739,6 +1802,10 @@ int sed_set_option(sed_ctx *c, int key, int value) {
     }
     if (key == SED_OPT_CHAIN_WAVES && value >= 0) {
         c->opt_chain_waves = value;
+        return SED_OK;
+    }
+    if (key == SED_OPT_BAND && (value == 0 || value == 2)) {
+        c->opt_band = value;
         return SED_OK;
     }
     if (key == SED_OPT_DEBUG_CORRUPT && value >= 0) {
@@ -1842,6 +1909,52 @@ int sed_dot_factor(const double *sub, double ins, double del, int maxmin, int la
     out[8] = dk.S;  // decode shift (dot keys) or sentinel byte (ladder)
     out[9] = ladder_maxsum > 0 ? unit : dk.M;  // decode multiplier (dot keys) or the L unit (ladder)
     return (int)dk.A;
+}
+
+double sed_batch_band_cells(const sed_batch *b) { return b ? b->band_cells : 0.0; }
+
+int sed_band_bounds(int32_t n, int32_t m, double ins, double del, double ub, int32_t *out) {
+    if (!out || n < 0 || m < 0 || !(ins >= 0) || !(del >= 0) || !(ins + del > 0) || !(ub >= 0) || ins >= 65536 ||
+        del >= 65536 || ub >= 9e15)
+        return SED_E_ARG;
+    const sed_band w = sed_band_window(n, m, (uint32_t)ins, (uint32_t)del, (uint64_t)ub);
+    out[0] = w.elo;
+    out[1] = w.ehi;
+    return SED_OK;
+}
+
+int sed_band_chunk_range(int32_t n, int32_t m, int32_t rows_per_lane, int32_t elo, int32_t ehi, int32_t stripe,
+                         int32_t *out) {
+    const int R = rows_per_lane;
+    if (!out || n < 1 || m < 1 || (R != 4 && R != 8 && R != 16) || stripe < 0 || stripe >= (n + 64 * R - 1) / (64 * R))
+        return SED_E_ARG;
+    const int G = 64 / R, SG = (m + 63 + G - 1) / G * G, nchunks = (SG + 63) >> 6;
+    int clo, chi;
+    sed_band_chunks(n, m, 64 * R, nchunks, sed_band{elo, ehi}, stripe, &clo, &chi);
+    out[0] = clo;
+    out[1] = chi;
+    out[2] = nchunks;
+    return SED_OK;
+}
+
+double sed_band_cells(const double *sub, double ins, double del, const uint8_t *codes_a, int32_t n,
+                      const uint8_t *codes_b, int32_t m, int32_t rows_per_lane) {
+    const int R = rows_per_lane;
+    if (!sub || !codes_a || !codes_b || n < 1 || m < 1 || (R != 4 && R != 8 && R != 16) || !(ins >= 0) || !(del >= 0) ||
+        !(ins + del > 0) || ins >= 65536 || del >= 65536)
+        return -1.0;
+    sed_band_params bp{};
+    for (int i = 0; i < 16; ++i) {
+        if (!(sub[i] >= 0) || sub[i] >= 65536) return -1.0;
+        bp.cost[i] = (uint32_t)sub[i];
+    }
+    bp.ins = (uint32_t)ins;
+    bp.del = (uint32_t)del;
+    for (int i = 0; i < n; ++i)
+        if (codes_a[i] > 3) return -1.0;
+    for (int i = 0; i < m; ++i)
+        if (codes_b[i] > 3) return -1.0;
+    return sed_band_pair_cells(n, m, R, sed_band_window(n, m, bp.ins, bp.del, band_diag_bound(bp, codes_a, n, codes_b, m)));
 }
 
 int sed_batch_dot_keys(const sed_batch *b) {

@@ -54,6 +54,7 @@ SED_OPT_SCALED = 12
 SED_OPT_SEG = 13
 SED_OPT_SPLITCK = 14
 SED_OPT_ZEROCOPY = 15
+SED_OPT_BAND = 16
 MODE_NAMES = {1: "i32", 2: "f64", 3: "f64-typed"}
 
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
@@ -81,6 +82,10 @@ SIGNATURES = [
     ("sed_batch_chains", C.c_int, [C.c_void_p]),
     ("sed_batch_dot_keys", C.c_int, [C.c_void_p]),
     ("sed_dot_factor", C.c_int, [_f64p, C.c_double, C.c_double, C.c_int, C.c_int, _u32p]),
+    ("sed_band_bounds", C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _i32p]),
+    ("sed_band_chunk_range", C.c_int, [C.c_int32] * 6 + [_i32p]),
+    ("sed_band_cells", C.c_double, [_f64p, C.c_double, C.c_double, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32]),
+    ("sed_batch_band_cells", C.c_double, [C.c_void_p]),
     ("sed_batch_packed_pairs", C.c_int, [C.c_void_p]),
     ("sed_batch_bitpar_pairs", C.c_int, [C.c_void_p]),
     ("sed_batch_scaled_pairs", C.c_int, [C.c_void_p]),
@@ -396,6 +401,11 @@ class Batch:
     def dot_keys(self):
         """True when the checkpoint forward kernel runs dot keys (v_dot4 + v_max3 per cell, SED_OPT_DOT)."""
         return (self._lib.sed_batch_dot_keys(self.ptr) & 1) == 1
+
+    @property
+    def band_cells(self):
+        """Cells the forward computes per run: below sum n*m when the batch is band-pruned (SED_OPT_BAND)."""
+        return float(self._lib.sed_batch_band_cells(self.ptr))
 
     @property
     def ladder_dot_keys(self):
@@ -865,3 +875,31 @@ def dot_factor(sub, ins, dele, maxmin=0, ladder_maxsum=0):
         return None
     to_bytes = lambda w: np.frombuffer(np.asarray(w, np.uint32).tobytes(), np.int8).reshape(4, 4).astype(np.int64)
     return A, to_bytes(out[0:4]), to_bytes(out[4:8]), (int(out[8]), int(out[9]))
+
+
+def band_bounds(n, m, ins, dele, ub):
+    """Band pruning (SED_OPT_BAND, no device needed): (e_lo, e_hi), the diagonals e = j - i an optimal path of an
+    n x m pair can touch when some path costs ub."""
+    out = np.zeros(2, np.int32)
+    if load().sed_band_bounds(int(n), int(m), float(ins), float(dele), float(ub), out) != 0:
+        raise SedError("sed_band_bounds: bad arguments")
+    return int(out[0]), int(out[1])
+
+
+def band_chunk_range(n, m, rows_per_lane, e_lo, e_hi, stripe):
+    """(c_lo, c_hi, nchunks): the 64-step chunks stripe `stripe` of an n x m pair runs for the window (e_lo, e_hi)."""
+    out = np.zeros(3, np.int32)
+    if load().sed_band_chunk_range(int(n), int(m), int(rows_per_lane), int(e_lo), int(e_hi), int(stripe), out) != 0:
+        raise SedError("sed_band_chunk_range: bad arguments")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def band_cells(sub, ins, dele, codes_a, codes_b, rows_per_lane=16):
+    """Cells the pruned forward computes for one pair of codes 0..3 under the 4 x 4 table sub, with the plain
+    diagonal's cost as the bound."""
+    a, b = np.ascontiguousarray(codes_a, np.uint8), np.ascontiguousarray(codes_b, np.uint8)
+    r = load().sed_band_cells(np.ascontiguousarray(sub, np.float64).ravel(), float(ins), float(dele), a, len(a), b, len(b),
+                              int(rows_per_lane))
+    if r < 0:
+        raise SedError("sed_band_cells: bad arguments")
+    return float(r)
