@@ -106,6 +106,10 @@ enum {
                                    the device in every run; substitution costs must be >= 0, else off): 0 auto (on),
                                    2 never.  Environment SED_BAND=0 turns it off for the process.  Results are the same
                                    bit for bit. */
+#define SED_OPT_CUT 17          /* distance-only integer batches under a cutoff (sed_batch_set_cutoff), SED_NO_LEN, R = 4/8/16, not
+                                   SPLIT: the wave pairs leave the two-pairs-per-wave and CHAIN routes for the windowed
+                                   stripe kernel: 0 auto (when the window keeps < 2/3 of their cells; pairs already on the
+                                   stripe kernel whenever it skips any), 1 whenever eligible, 2 never (filter only) */
 #define SED_OPT_DEBUG_CORRUPT 9 /* testing only: p + 1 overwrites one checkpoint word of pair p before its traceback,
                                    which must then fail with SED_E_DEVICE naming the pair; 0 off */
 
@@ -205,6 +209,26 @@ int sed_band_chunk_range(int32_t n, int32_t m, int32_t rows_per_lane, int32_t el
 double sed_band_cells(const double *sub, double ins, double del, const uint8_t *codes_a, int32_t n,
                       const uint8_t *codes_b, int32_t m, int32_t rows_per_lane);
 double sed_batch_band_cells(const sed_batch *b);
+/* Bounded search: a cutoff on the distances of a distance-only batch (no SED_WANT_SCRIPT: SED_E_ARG), for the runs that
+ * follow.  Valid on a created batch before any run or between runs (a run in flight is waited for, as a refill does);
+ * calling it again changes the cutoff of later runs on the same resident batch, with no upload of the inputs.
+ * max_dist = +inf turns the cutoff off: every kernel choice and result is then what the batch gives without one.  NaN
+ * or a negative value: SED_E_ARG.  With cutoff T, on every route and in every mode:
+ *   - a pair whose distance D <= T reports exactly what it reports without a cutoff (out_dist, out_is_int, and out_len
+ *     where the batch computes it);
+ *   - a pair with D > T reports out_dist = +inf, out_is_int = 0, out_len = -1;
+ *   - "<=" is exact: in integer mode (sed_batch_mode = SED_MODE_I32, every distance an integer) T is floored and
+ *     clamped to the key range (65535), in the fp64 modes the fp64 values are compared.
+ * Integer SED_NO_LEN batches of wave pairs (R = 4, 8, 16, not SPLIT, substitution costs >= 0, insert + delete > 0) may
+ * then run only the cells a path of cost <= T can reach (the window of SED_OPT_BAND under ub = min(T, diagonal bound),
+ * from the device in every run; a pair whose length difference alone costs more than T runs nothing), see
+ * SED_OPT_CUT; every other route computes as before and only compares.  sed_batch_band_cells reports the cells the
+ * forward computes under the current cutoff (sed_batch_work keeps the nominal sum n*m), sed_batch_chains and
+ * sed_batch_packed_pairs the routes the wave pairs run under it. */
+int sed_batch_set_cutoff(sed_batch *b, double max_dist);
+/* The number of pairs within the cutoff in the last run (waits for it; every pair when that run had no cutoff), without
+ * a download of the distances. */
+int sed_batch_cutoff_hits(sed_batch *b, int32_t *within);
 int sed_batch_traceback_mode(const sed_batch *b);     /* 0 no script, 1 per-cell codes, 2 checkpoints (SED_OPT_TB),
                                                          3 per-cell codes walked stripe-parallel (<= 64 pairs, R = 4),
                                                          4 SPLIT checkpoints recomputed into per-cell codes

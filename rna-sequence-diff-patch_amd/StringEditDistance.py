@@ -691,9 +691,11 @@ def _packed(plan, strs1, strs2):
     return sedgpu.PackedPairs.from_concat(ca, la, cb, lb)
 
 
-def distance_batch(strs1, strs2, userCosts=False, plan=None):
+def distance_batch(strs1, strs2, userCosts=False, plan=None, max_dist=None):
     """[dp[n][m].value for each (str1, str2)] — one GPU launch; same typing and KeyErrors.  plan: batch_plan()'s
-    result for the same arguments (wfsearch builds it once for its cache key)."""
+    result for the same arguments (wfsearch builds it once for its cache key).  max_dist (a batch extension, not in
+    the reference): pairs whose value exceeds it come back as math.inf, and the integer kernels skip the cells no
+    path within it can reach."""
     strs1, strs2 = list(strs1), list(strs2)
     if plan is None:
         plan = batch_plan(strs1, strs2, userCosts)
@@ -701,8 +703,25 @@ def distance_batch(strs1, strs2, userCosts=False, plan=None):
         return []
     ctx = sedgpu.context()
     ctx.set_costs(plan)
-    dist, is_int, _, _ = ctx.run(_packed(plan, strs1, strs2), False, no_len=True)
+    if max_dist is None:
+        dist, is_int, _, _ = ctx.run(_packed(plan, strs1, strs2), False, no_len=True)
+    else:
+        dist, is_int, _, _ = ctx.run_cutoff(_packed(plan, strs1, strs2), max_dist, True)
     return [int(d) if t else float(d) for d, t in zip(dist.tolist(), is_int.tolist())]
+
+
+def distance_deepen(strs1, strs2, k, first, last, userCosts=False, plan=None):
+    """distance_batch under the smallest cutoff of first, 2 first, 4 first, ... (at most last) that at least k pairs
+    are within, on one resident batch: (values, cutoffs tried).  wfsearch.nearest's engine call."""
+    strs1, strs2 = list(strs1), list(strs2)
+    if plan is None:
+        plan = batch_plan(strs1, strs2, userCosts)
+    if not strs1:
+        return [], []
+    ctx = sedgpu.context()
+    ctx.set_costs(plan)
+    dist, is_int, _, _, cuts = ctx.deepen(_packed(plan, strs1, strs2), k, first, last, True)
+    return [int(d) if t else float(d) for d, t in zip(dist.tolist(), is_int.tolist())], cuts
 
 
 def edit_script_batch(strs1, strs2, userCosts=False):

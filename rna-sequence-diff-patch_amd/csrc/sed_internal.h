@@ -282,6 +282,16 @@ struct sed_band_params {
 };
 // UB and the window of every wave pair of the launch, into band[pair] (one wave per pair; the forward's first kernel)
 hipError_t sed_launch_band(const sed_launch &L, const sed_band_params &bp);
+// Cutoff batches (sed_batch_set_cutoff).  tkey = the cutoff on the integer scale.
+// sed_launch_i32_cut: the windowed distance-only stripe kernel (R = 4, 8, 16) over the wave pairs list[0 .. nlist), after
+// their windows of this run (L.band, L.bandp: ub = min(tkey, diagonal bound); an empty window {1, 0} = the pair runs no
+// stripe and reports +inf).  sed_launch_cut_band alone also stores every listed pair's diagonal bound into diag.
+// sed_launch_cut_filter: every result of L.res above `cutoff` becomes {+inf, len -1, not an int}; *hits += pairs within.
+hipError_t sed_launch_cut_band(const sed_launch &L, const int32_t *list, int nlist, uint32_t *diag,
+                               const sed_band_params &bp, uint32_t tkey);
+hipError_t sed_launch_i32_cut(const sed_launch &L, const int32_t *list, int nlist, const sed_i32_params &prm,
+                              uint32_t tkey);
+hipError_t sed_launch_cut_filter(const sed_launch &L, double cutoff, uint32_t *hits);
 // CK batches (L.ck): the traceback that recomputes tiles from the forward kernel's checkpoints
 hipError_t sed_launch_traceback_ck(const sed_launch &L, uint32_t *ops, const sed_i32_params &prm);
 // SPLIT batches with checkpoints: every tile's op codes from the checkpoints, into the per-cell code layout (one wave

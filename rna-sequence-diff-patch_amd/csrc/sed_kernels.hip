@@ -582,7 +582,12 @@ __device__ __forceinline__ void split_feed(const uint64_t *__restrict__ bin64, c
 #ifndef SED_SPLIT_PRIO
 #define SED_SPLIT_PRIO 2
 #endif
-template <int R, bool TB, bool SPLIT, bool LEN = true, bool CK = false, bool DOT = false>
+// CUT (distance-only batches under a cutoff, sed_batch_set_cutoff; not TB, LEN, CK or SPLIT): wave w runs pair
+// list[w] of the cutoff's pair list (passed in `tasks`, npairs = its length) inside the pair's window band[pair]
+// (sed_cut_band_kernel: ub = min(cutoff, diagonal bound)), with the chunk ranges and border rules of the CK forward
+// on this kernel's own bottom-row layout (column j at word j + 64); a pair whose window is empty (elo > ehi: the
+// length difference alone costs more than the cutoff) runs no stripe and reports +inf.
+template <int R, bool TB, bool SPLIT, bool LEN = true, bool CK = false, bool DOT = false, bool CUT = false>
 __global__ __launch_bounds__(SPLIT ? 128 : 256) __attribute__((amdgpu_waves_per_eu(CK ? SED_CK_WAVES : SED_I32_WAVES(R))))
 void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const int2 *__restrict__ tasks,
                   const uint32_t *__restrict__ seqa, const uint32_t *__restrict__ seqb,
@@ -593,6 +598,8 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
     static_assert(!CK || (R <= 16 && !TB && !LEN), "checkpoints: R <= 16, distance keys");
     static_assert(!(CK && SPLIT) || R == 4, "SPLIT checkpoints (sed_ck_codes_kernel): R = 4");
     static_assert(!DOT || CK, "dot keys: checkpoint batches only");
+    static_assert(!CUT || (R <= 16 && !TB && !LEN && !CK && !SPLIT), "cutoff window: distance keys, one wave per pair");
+    constexpr bool WIN = (CK && !SPLIT) || CUT;  // the forward runs a window of chunks per stripe
     if constexpr (SPLIT && SED_SPLIT_PRIO > 0) __builtin_amdgcn_s_setprio(SED_SPLIT_PRIO);
     const int lane = threadIdx.x & 63;
     int pair, kfirst = 0;
@@ -603,9 +610,10 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
     } else {
         pair = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
         if (pair >= npairs) return;
+        if constexpr (CUT) pair = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t *>(tasks)[pair]);
     }
     const sed_pair_desc d = pd[pair];
-    if (d.lane) return;  // short str2: sed_lane.hip
+    if (!CUT && d.lane) return;  // short str2: sed_lane.hip (CUT: the list holds wave pairs only)
     const int n = d.n, m = d.m;
     if (n == 0 || m == 0) {
         if (lane == 0) {
@@ -634,10 +642,21 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
     // above did not compute (steps past top_hi of the in-place bottom-row buffer, which holds stale words there).
     // Wave-uniform, in scalar registers; an open window (no band) gives 0 .. nchunks - 1 and every top value.
     sed_band bw{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
-    if constexpr (CK && !SPLIT) {
+    if constexpr (WIN) {
         if (band) {
             bw.elo = __builtin_amdgcn_readfirstlane(band[pair].elo);
             bw.ehi = __builtin_amdgcn_readfirstlane(band[pair].ehi);
+        }
+    }
+    if constexpr (CUT) {
+        if (bw.elo > bw.ehi) {  // no path within the cutoff (uniform)
+            if (lane == 0) {
+                res[pair].dist = __builtin_huge_val();
+                res[pair].len = -1;
+                res[pair].is_int = 0;
+                res[pair].err = 0;
+            }
+            return;
         }
     }
     int top_hi = 0x7FFFFFFF, clo_prev = 0;  // (of the stripe above)
@@ -678,7 +697,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         }
         const int row0 = k * ROWS + lane * R;  // 0-based str1 index of this lane's first row
         int clo = 0, chi = nchunks - 1;
-        if constexpr (CK && !SPLIT) sed_band_chunks(n, m, ROWS, nchunks, bw, k, &clo, &chi);
+        if constexpr (WIN) sed_band_chunks(n, m, ROWS, nchunks, bw, k, &clo, &chi);
         uint32_t cv[R], V[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -689,7 +708,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         }
         uint32_t top_prev;
         i32_reset<R, LEN, DOT>(V, top_prev);
-        if constexpr (CK && !SPLIT) {
+        if constexpr (WIN) {
             // a stripe that starts at column 64 clo + 1 > 1: the diagonal of lane 0's first cell is the cell (r0, 64 clo)
             // of the stripe above, which lies on the window's edge when 64 clo = r0 + elo, so it is the real value
             // (its step's word of the bottom-row buffer; every other lane's first diagonal is left of the window).
@@ -698,8 +717,8 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
             // there is a virtual-step store of the stripe above, which holds the same constant: a lane's state
             // stays at the border through its virtual columns, i32_sent.  The guard keeps this load off that.)
             if (k > 0 && clo > clo_prev) {
-                const int idx = 64 * clo + 62;
-                const uint32_t v = load_sc1(bnd + d.bnd_off + (uint32_t)idx);
+                const int idx = 64 * clo + 62;  // (its word: the step, or column + 64 in the CUT layout)
+                const uint32_t v = load_sc1(bnd + d.bnd_off + (uint32_t)(idx + (CK ? 0 : 2)));
                 top_prev = (lane == 0 && idx <= top_hi) ? v : top_prev;
             }
         }
@@ -716,6 +735,10 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
             if constexpr (CK) {  // (past the stripe above's last chunk: the border, as the columns it never computed)
                 const uint32_t v = load_sc1(bnd + d.bnd_off + (uint32_t)(j + 62));
                 return (SPLIT || j + 62 <= top_hi) ? v : i32_row0<LEN, DOT>();
+            }
+            if constexpr (CUT) {  // (as above, in this layout)
+                const uint32_t v = load_sc1(bnd_in + j + 64);
+                return j + 62 <= top_hi ? v : i32_row0<LEN, DOT>();
             }
             return load_sc1(bnd_in + j + 64);
         };
@@ -3266,8 +3289,113 @@ __global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__re
 }
 
 // ---------------------------------------------------------------------------
+// Cutoff batches (sed_batch_set_cutoff).  sed_cut_band_kernel: the window of every pair of the cutoff's
+// pair list, one wave per pair, before every windowed forward: ub = min(tkey, the diagonal bound) (tkey = the cutoff
+// on the integer scale), or the empty window {1, 0} when the length difference alone costs more than tkey.  diag (if
+// not null) receives every pair's diagonal bound, which the host reads once for its restatement of the windows.
+// sed_cut_filter_kernel: every pair's result against the cutoff, after the run's last DP kernel: a distance above it
+// becomes {+inf, len -1, not an int}; hits counts the pairs within.  Plain vector stores.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sed_cut_band_kernel(const sed_pair_desc *__restrict__ pd,
+                                                           const int32_t *__restrict__ list, int nlist,
+                                                           const uint32_t *__restrict__ seqa,
+                                                           const uint32_t *__restrict__ seqb, sed_band *__restrict__ band,
+                                                           uint32_t *__restrict__ diag, sed_band_params bp, uint32_t tkey) {
+    __shared__ uint32_t tab[16];
+    if (threadIdx.x < 16) tab[threadIdx.x] = bp.cost[threadIdx.x];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= nlist) return;
+    const int pair = list[w];
+    const sed_pair_desc d = pd[pair];
+    const int n = d.n, m = d.m;
+    if (n == 0 || m == 0) {  // the stripe kernel writes these from the lengths alone
+        if (lane == 0) {
+            band[pair] = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
+            if (diag) diag[pair] = 0xFFFFFFFFu;
+        }
+        return;
+    }
+    const int len = min(n, m), words = (len + 15) >> 4;
+    const uint32_t *pa = seqa + d.a_off, *pb = seqb + d.b_off;
+    uint32_t sum = 0;
+    for (int x = lane; x < words; x += 64) {
+        uint32_t a = pa[x], b = pb[x];
+        const int cnt = min(16, len - 16 * x);
+        for (int u = 0; u < cnt; ++u) {
+            sum += tab[((a & 3u) << 2) | (b & 3u)];
+            a >>= 2;
+            b >>= 2;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) {
+        const uint64_t gap = m > n ? (uint64_t)(m - n) * bp.ins : (uint64_t)(n - m) * bp.del;
+        const uint64_t ub = (uint64_t)sum + gap;
+        if (diag) diag[pair] = (uint32_t)(ub < 0xFFFFFFFFull ? ub : 0xFFFFFFFFull);
+        band[pair] = gap > (uint64_t)tkey ? sed_band{1, 0}
+                                          : sed_band_window(n, m, bp.ins, bp.del, ub < (uint64_t)tkey ? ub : (uint64_t)tkey);
+    }
+}
+
+__global__ __launch_bounds__(256) void sed_cut_filter_kernel(sed_result *__restrict__ res, int npairs, double cutoff,
+                                                             uint32_t *__restrict__ hits) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    bool within = false;
+    if (p < npairs) {
+        const sed_result r = res[p];
+        within = r.err != 0 || r.dist <= cutoff;  // (a failed pair is reported as the failure it is)
+        if (!within) {
+            sed_result o = r;
+            o.dist = __builtin_huge_val();
+            o.len = -1;
+            o.is_int = 0;
+            res[p] = o;
+        }
+    }
+    const uint64_t bal = __ballot(within);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(hits, (uint32_t)__popcll(bal));
+}
+
+// ---------------------------------------------------------------------------
 // Launchers (host side, called from sed_runtime.cpp)
 // ---------------------------------------------------------------------------
+hipError_t sed_launch_cut_band(const sed_launch &L, const int32_t *list, int nlist, uint32_t *diag,
+                               const sed_band_params &bp, uint32_t tkey) {
+    if (nlist <= 0) return hipSuccess;
+    hipExtLaunchKernelGGL(sed_cut_band_kernel, dim3((nlist + 3) / 4), dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd, list,
+                          nlist, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.band, diag, bp, tkey);
+    return hipGetLastError();
+}
+hipError_t sed_launch_i32_cut(const sed_launch &L, const int32_t *list, int nlist, const sed_i32_params &prm,
+                              uint32_t tkey) {
+    if (nlist <= 0 || !L.band || !L.bandp) return hipErrorInvalidValue;
+    const hipError_t e = sed_launch_cut_band(L, list, nlist, nullptr, *L.bandp, tkey);  // (the phase's start event)
+    if (e != hipSuccess) return e;
+    sed_launch Lf = L;
+    Lf.ev0 = nullptr;
+    const dim3 grid((nlist + 3) / 4), block(256);
+    const int2 *lp = reinterpret_cast<const int2 *>(list);  // (the kernel's `tasks` argument: CUT reads it as the list)
+    const uint32_t *a = (const uint32_t *)L.seqa, *b = (const uint32_t *)L.seqb;
+    switch (L.R) {
+#define CASE(RR)                                                                                                        \
+    case RR:                                                                                                            \
+        SED_LAUNCH((sed_wf_i32_kernel<RR, false, false, false, false, false, true>), grid, block, 0, Lf, L.pd, nlist, lp, a, \
+                   b, (uint32_t *)nullptr, L.bnd, L.res, prm, (const sed_band *)L.band);                                \
+        break;
+        CASE(4) CASE(8) CASE(16)
+#undef CASE
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+hipError_t sed_launch_cut_filter(const sed_launch &L, double cutoff, uint32_t *hits) {
+    if (L.npairs <= 0) return hipSuccess;
+    SED_LAUNCH(sed_cut_filter_kernel, dim3((L.npairs + 255) / 256), dim3(256), 0, L, L.res, L.npairs, cutoff, hits);
+    return hipGetLastError();
+}
 hipError_t sed_launch_band(const sed_launch &L, const sed_band_params &bp) {
     hipExtLaunchKernelGGL(sed_band_kernel, dim3((L.npairs + 3) / 4), dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd,
                           L.npairs, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.band, bp);

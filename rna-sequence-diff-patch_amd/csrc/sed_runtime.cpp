@@ -47,6 +47,11 @@ bool is_integral_small(double v, int lim) { return v == std::floor(v) && v >= 0 
 
 }  // namespace
 
+// Cutoff batches: the wave pairs of a batch with x2 or CHAIN pairs move to the windowed stripe kernel when the window
+// keeps less than this share of their cells (sed_batch_set_cutoff)
+#ifndef SED_CUT_SHARE
+#define SED_CUT_SHARE (2.0 / 3.0)
+#endif
 // Batches whose input arrays and results fit this many bytes go up as one blob from pinned staging (fill_batch)
 #define SED_SMALL_BATCH_BYTES (4u << 20)
 
@@ -75,6 +80,8 @@ struct sed_ctx {
     int opt_debug_corrupt = 0;  // SED_OPT_DEBUG_CORRUPT: pair + 1 whose sink-tile checkpoint is overwritten
     int opt_band = 0;           // SED_OPT_BAND: 0 auto (checkpoint batches of the stripe kernel skip the cells no
                                 // optimal path reaches), 2 never
+    int opt_cut = 0;            // SED_OPT_CUT: cutoff batches' wave pairs: 0 auto (the windowed stripe kernel when it
+                                // should pay), 1 whenever eligible, 2 never (filter only)
     DevBuf selftest;
     sed_batch *scratch = nullptr;
     // pinned host staging (hipHostMalloc) of small batches: the upload blob, then the results' download
@@ -179,7 +186,22 @@ struct sed_batch {
     DevBuf d_band;
     sed_band_params bandp{};
     double band_cells = 0;
-    bool lad = false;          // CHAIN kernel with the L field on ladder dot keys (dot_keys ladder mode)
+    // cutoff (sed_batch_set_cutoff): every run ends with sed_cut_filter_kernel (results above cut_cmp
+    // become +inf; cut_cmp = the cutoff floored to the integer scale in integer mode).  cut_win: the wave pairs
+    // (cut_list: every pair not on a lane kernel) leave their routes for the windowed stripe kernel, whose windows
+    // sed_cut_band_kernel writes into d_band in every run.  d_cut = [cut_list | diagonal bounds (npairs) | hits (4)];
+    // cut_diag = the diagonal bounds, read back once for the host's restatement (band_cells) and the routing rule.
+    // cut_bp / cut_costs_ok: the windows' costs and whether they allow pruning, taken at the fill with the kernels' own
+    // parameters (ip), so a later sed_set_costs on the context cannot part the windows from the DP.
+    bool cut_on = false, cut_win = false, cut_ready = false, cut_prune_ok = false, cut_last = false;
+    bool cut_costs_ok = false;
+    sed_band_params cut_bp{};
+    double cutoff = 0, cut_cmp = 0;
+    uint32_t cut_key = 0;
+    std::vector<int32_t> cut_list;
+    std::vector<uint32_t> cut_diag;
+    DevBuf d_cut;
+    bool lad = false;         // CHAIN kernel with the L field on ladder dot keys (dot_keys ladder mode)
     int nlane = 0, nwave = 0;  // pairs on the lane-per-pair kernel / on the wave kernels
     int nlane_x2 = 0;          // > 0: lane pairs run two per lane (distance only), in this many lanes
     bool lane_bitpar = false;  // lane pairs run the bit-parallel unit-cost kernel (distance only)
@@ -233,6 +255,7 @@ struct sed_batch {
         if (h_out) (void)hipHostFree(h_out);
         d_pd.release(); d_seqa.release(); d_seqb.release(); d_bnd.release(); d_ops.release(); d_tbmap.release();
         d_tasks.release(); d_lane.release(); d_chain.release(); d_x2.release(); d_small.release(); d_seg.release();
+        d_band.release(); d_cut.release();
         for (int i = 0; i < 3; ++i) {
             d_tb[i].release();
             d_res[i].release();
@@ -690,6 +713,7 @@ int fill_batch(sed_batch *b, const uint8_t *codes_a, const int64_t *off_a, const
     b->flags = flags;
     b->ran = false;
     b->runs = 0;
+    b->cut_on = b->cut_win = b->cut_ready = b->cut_last = false;  // (a refill starts without a cutoff)
     b->chain_launches[0] = b->chain_launches[1] = b->chain_launches[2] = 0;
     b->nbuf = (flags & SED_PIPELINE) ? 3 : 1;
     b->n.assign(len_a, len_a + npairs);
@@ -1096,6 +1120,18 @@ int fill_batch(sed_batch *b, const uint8_t *codes_a, const int64_t *off_a, const
         tb_bytes = ckb + 8.0 * npairs;  // (and every pair's window, written and read)
     }
     b->algo_bytes = in_bytes + (want_tb ? tb_bytes : 0) + 16.0 * npairs;
+    // a cutoff's windows (sed_batch_set_cutoff): this fill's costs, as the kernels' parameters below
+    b->cut_costs_ok = mode == SED_MODE_I32 && c->K <= 4 && c->ins + c->del > 0;
+    b->cut_bp = sed_band_params{};
+    if (b->cut_costs_ok) {
+        for (int a = 0; a < c->K * c->K; ++a)
+            if (!(c->sub[a] >= 0)) b->cut_costs_ok = false;
+        for (int a = 0; a < 4; ++a)
+            for (int bb = 0; bb < 4; ++bb)
+                b->cut_bp.cost[a * 4 + bb] = (a < c->K && bb < c->K) ? (uint32_t)c->sub[a * c->K + bb] : 0u;
+        b->cut_bp.ins = (uint32_t)c->ins;
+        b->cut_bp.del = (uint32_t)c->del;
+    }
 
     // ---- pack & upload ----
     const uint64_t pad_words = (uint64_t)ROWS / 16 * 2 + 64;
@@ -1501,7 +1537,13 @@ int run_batch(sed_batch *b) {
     // consecutive config-2 DP kernels were ~18 us apart, and for the ~25 us lane kernel (config 5) every
     // avoided packet is measurable.  A phase that launches nothing records its events directly.
     const int nw64 = b->nwave - b->nseg;  // wave pairs of the one-wave-per-pair kernels
-    const int ndp = (b->nwave_x2 > 0) + (nw64 > 0) + (b->nseg > 0) + (b->nlane > 0);
+    // a cutoff: the wave pairs on the windowed stripe kernel instead of their own routes (cut_win), and the filter as
+    // the DP phase's last kernel
+    const bool cut = b->cut_on && !want_tb, win = cut && b->cut_win;
+    const int ndp = (win ? 1 : (b->nwave_x2 > 0) + (nw64 > 0) + (b->nseg > 0)) + (b->nlane > 0) + (cut ? 1 : 0);
+    uint32_t *const hits = cut ? (uint32_t *)b->d_cut.p + b->cut_list.size() + (size_t)b->npairs + k : nullptr;
+    if (cut && (e = hipMemsetAsync(hits, 0, 4, ds)) != hipSuccess) return c->hipfail(e, "reset cutoff hits");
+    b->cut_last = cut;
     int idp = 0;
     auto dp_events = [&]() {
         L.ev0 = idp == 0 ? lg[0] : nullptr;
@@ -1515,12 +1557,20 @@ int run_batch(sed_batch *b) {
     if ((e = next_split_epoch(b, ds, &ip.epoch)) != hipSuccess) return c->hipfail(e, "memset hand-off words");
     const bool len = want_tb || !(b->flags & SED_NO_LEN);
     if (b->nparts > 1 && want_tb) return run_batch_parts(b, lg, L, ip, len);
-    if (b->nwave_x2 > 0) {
+    if (win) {
+        dp_events();
+        sed_launch Lw = L;
+        Lw.band = (sed_band *)b->d_band.p;
+        Lw.bandp = &b->cut_bp;
+        if ((e = sed_launch_i32_cut(Lw, (const int32_t *)b->d_cut.p, (int)b->cut_list.size(), ip, b->cut_key)) != hipSuccess)
+            return c->hipfail(e, "windowed DP kernel launch");
+    }
+    if (!win && b->nwave_x2 > 0) {
         dp_events();
         if ((e = sed_launch_i32x2(L, (const int32_t *)b->p_x2, b->nwave_x2, ip)) != hipSuccess)
             return c->hipfail(e, "packed DP kernel launch");
     }
-    if (nw64 > 0) {
+    if (!win && nw64 > 0) {
         dp_events();
         if (b->mode == SED_MODE_I32 && b->nchains) {
             L.chain_pairs = (const int32_t *)b->p_chain;
@@ -1558,7 +1608,7 @@ int run_batch(sed_batch *b) {
         }
         if (e != hipSuccess) return c->hipfail(e, "DP kernel launch");
     }
-    if (b->nseg > 0) {  // fp64 pairs in 16-lane segments, four per wave
+    if (!win && b->nseg > 0) {  // fp64 pairs in 16-lane segments, four per wave
         dp_events();
         if ((e = sed_launch_f64_seg(L, (const double *)c->gtab.p, b->fp, b->mode == SED_MODE_F64_TYPED,
                                     (const int32_t *)b->p_seg, b->nseg)) != hipSuccess)
@@ -1578,6 +1628,10 @@ int run_batch(sed_batch *b) {
             e = sed_launch_lane_f64(L, (const int32_t *)b->p_lane, b->nlane, (const double *)c->gtab.p, c->ins,
                                     c->del, c->K, b->umask);
         if (e != hipSuccess) return c->hipfail(e, "lane kernel launch");
+    }
+    if (cut) {
+        dp_events();
+        if ((e = sed_launch_cut_filter(L, b->cut_cmp, hits)) != hipSuccess) return c->hipfail(e, "cutoff filter launch");
     }
     if (ndp == 0 && lg[1] && (e = hipEventRecord(lg[1], ds)) != hipSuccess) return c->hipfail(e, "event record");
     L.ev0 = L.ev1 = nullptr;
@@ -1804,6 +1858,10 @@ int sed_set_option(sed_ctx *c, int key, int value) {
         c->opt_chain_waves = value;
         return SED_OK;
     }
+    if (key == SED_OPT_CUT && value >= 0 && value <= 2) {
+        c->opt_cut = value;
+        return SED_OK;
+    }
     if (key == SED_OPT_BAND && (value == 0 || value == 2)) {
         c->opt_band = value;
         return SED_OK;
@@ -1877,7 +1935,7 @@ void sed_batch_destroy(sed_batch *b) {
 int sed_batch_mode(const sed_batch *b) { return b ? b->mode : SED_E_ARG; }
 int sed_batch_rows_per_lane(const sed_batch *b) { return b ? b->R : SED_E_ARG; }
 int sed_batch_lane_pairs(const sed_batch *b) { return b ? b->nlane : SED_E_ARG; }
-int sed_batch_chains(const sed_batch *b) { return b ? b->nchains : SED_E_ARG; }
+int sed_batch_chains(const sed_batch *b) { return b ? (b->cut_on && b->cut_win ? 0 : b->nchains) : SED_E_ARG; }
 int sed_batch_traceback_mode(const sed_batch *b) {
     if (!b || !(b->flags & SED_WANT_SCRIPT)) return 0;
     return b->ck ? 2 : b->split_ck ? 4 : (b->tbpar ? 3 : 1);
@@ -1912,6 +1970,101 @@ int sed_dot_factor(const double *sub, double ins, double del, int maxmin, int la
 }
 
 double sed_batch_band_cells(const sed_batch *b) { return b ? b->band_cells : 0.0; }
+
+int sed_batch_set_cutoff(sed_batch *b, double max_dist) {
+    if (!b) return SED_E_ARG;
+    sed_ctx *c = b->ctx;
+    (void)hipSetDevice(c->device);
+    if (!(max_dist >= 0)) return c->fail(SED_E_ARG, "cutoff must be >= 0 (or +inf for none)");
+    if (b->flags & SED_WANT_SCRIPT) return c->fail(SED_E_ARG, "a script batch takes no cutoff");
+    int rc = sync_batch(b);  // a run in flight reads the windows and the cutoff's pair list
+    if (rc != SED_OK) return rc;
+    if (std::isinf(max_dist)) {
+        b->cut_on = b->cut_win = false;
+        b->band_cells = b->cells;
+        return SED_OK;
+    }
+    hipError_t e;
+    const int np = b->npairs;
+    if (!b->cut_ready) {  // once per fill: the pair list, the windows' buffer and the diagonal bounds (no input upload)
+        b->cut_list.clear();
+        for (int p = 0; p < np; ++p)
+            if (b->pd[p].lane != 1) b->cut_list.push_back(p);
+        int nwork = 0;  // wave pairs with cells
+        for (int32_t p : b->cut_list) nwork += b->n[p] > 0 && b->m[p] > 0;
+        b->cut_prune_ok = b->mode == SED_MODE_I32 && !b->split && (b->flags & SED_NO_LEN) && b->nseg == 0 &&
+                          (b->R == 4 || b->R == 8 || b->R == 16) && b->cut_costs_ok && nwork > 0;
+        const size_t nl = b->cut_list.size();
+        if (!b->d_cut.reserve(4 * (nl + (size_t)np + 4)) || (b->cut_prune_ok && !b->d_band.reserve(sizeof(sed_band) * (size_t)np)))
+            return c->fail(SED_E_OOM, "device allocation failed (cutoff)");
+        b->cut_diag.assign(np, 0xFFFFFFFFu);
+        if (b->cut_prune_ok) {
+            const sed_band_params bp = b->cut_bp;
+            sed_launch L{};
+            L.pd = (const sed_pair_desc *)b->p_pd;
+            L.npairs = np;
+            L.seqa = b->p_seqa;
+            L.seqb = b->p_seqb;
+            L.band = (sed_band *)b->d_band.p;
+            L.stream = c->stream;
+            uint32_t *ddiag = (uint32_t *)b->d_cut.p + nl;
+            if ((e = hipMemcpyAsync(b->d_cut.p, b->cut_list.data(), 4 * nl, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+                return c->hipfail(e, "upload cutoff pair list");
+            if ((e = hipMemsetAsync(ddiag, 0xFF, 4 * (size_t)np, c->stream)) != hipSuccess ||
+                (e = sed_launch_cut_band(L, (const int32_t *)b->d_cut.p, (int)nl, ddiag, bp, 0xFFFFu)) != hipSuccess ||
+                (e = hipMemcpyAsync(b->cut_diag.data(), ddiag, 4 * (size_t)np, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+                (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+                return c->hipfail(e, "diagonal bounds");
+        }
+        b->cut_ready = true;
+    }
+    b->cutoff = max_dist;
+    if (b->mode == SED_MODE_I32) {  // the integer scale: every distance is an integer below 2^16
+        b->cut_cmp = std::floor(std::min(max_dist, 65535.0));
+        b->cut_key = (uint32_t)b->cut_cmp;
+    } else {
+        b->cut_cmp = max_dist;
+        b->cut_key = 0;
+    }
+    b->cut_win = false;
+    b->band_cells = b->cells;
+    if (b->cut_prune_ok && c->opt_cut != 2) {
+        double nominal = 0, bc = 0;
+        for (int32_t p : b->cut_list) {
+            const int nn = b->n[p], mm = b->m[p];
+            if (nn <= 0 || mm <= 0) continue;
+            nominal += (double)nn * mm;
+            const uint64_t gap = mm > nn ? (uint64_t)(mm - nn) * b->cut_bp.ins : (uint64_t)(nn - mm) * b->cut_bp.del;
+            if (gap > b->cut_key) continue;  // runs no stripe
+            bc += sed_band_pair_cells(nn, mm, b->R, sed_band_window(nn, mm, b->cut_bp.ins, b->cut_bp.del,
+                                                                    std::min<uint64_t>(b->cut_key, b->cut_diag[p])));
+        }
+        // x2 runs 4 VALU per 2 cells and CHAIN saves its pairs' ramps; the windowed kernel's cell costs 3 VALU
+        // (SED_CUT_SHARE: DESIGN.md 3.6d); pairs already on the plain stripe kernel gain whatever the window skips
+        const double share = (b->nwave_x2 > 0 || b->nchains > 0) ? SED_CUT_SHARE : 1.0;
+        b->cut_win = c->opt_cut == 1 || bc < share * nominal;
+        if (b->cut_win) b->band_cells = b->cells - nominal + bc;
+    }
+    b->cut_on = true;
+    return SED_OK;
+}
+
+int sed_batch_cutoff_hits(sed_batch *b, int32_t *within) {
+    if (!b || !within) return SED_E_ARG;
+    sed_ctx *c = b->ctx;
+    (void)hipSetDevice(c->device);
+    if (!b->ran) return c->fail(SED_E_STATE, "batch has not been run");
+    int rc = sync_batch(b);
+    if (rc != SED_OK) return rc;
+    uint32_t h = (uint32_t)b->npairs;  // (a run without a cutoff: every pair is within +inf)
+    if (b->cut_last && b->npairs > 0) {
+        const hipError_t e = hipMemcpy(&h, (uint32_t *)b->d_cut.p + b->cut_list.size() + (size_t)b->npairs + b->cur(), 4,
+                                       hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return c->hipfail(e, "download cutoff hits");
+    }
+    *within = (int32_t)h;
+    return SED_OK;
+}
 
 int sed_band_bounds(int32_t n, int32_t m, double ins, double del, double ub, int32_t *out) {
     if (!out || n < 0 || m < 0 || !(ins >= 0) || !(del >= 0) || !(ins + del > 0) || !(ub >= 0) || ins >= 65536 ||
@@ -2006,7 +2159,7 @@ int sed_batch_scaled_pairs(const sed_batch *b) {
 }
 
 int sed_batch_packed_pairs(const sed_batch *b) {
-    return b ? (b->nlane_x2 > 0 ? b->nlane : 0) + 2 * b->nwave_x2 : SED_E_ARG;
+    return b ? (b->nlane_x2 > 0 ? b->nlane : 0) + (b->cut_on && b->cut_win ? 0 : 2 * b->nwave_x2) : SED_E_ARG;
 }
 
 int sed_batch_run(sed_batch *b) {

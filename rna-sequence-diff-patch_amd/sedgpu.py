@@ -55,6 +55,7 @@ SED_OPT_SEG = 13
 SED_OPT_SPLITCK = 14
 SED_OPT_ZEROCOPY = 15
 SED_OPT_BAND = 16
+SED_OPT_CUT = 17
 MODE_NAMES = {1: "i32", 2: "f64", 3: "f64-typed"}
 
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
@@ -86,6 +87,8 @@ SIGNATURES = [
     ("sed_band_chunk_range", C.c_int, [C.c_int32] * 6 + [_i32p]),
     ("sed_band_cells", C.c_double, [_f64p, C.c_double, C.c_double, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32]),
     ("sed_batch_band_cells", C.c_double, [C.c_void_p]),
+    ("sed_batch_set_cutoff", C.c_int, [C.c_void_p, C.c_double]),
+    ("sed_batch_cutoff_hits", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ("sed_batch_packed_pairs", C.c_int, [C.c_void_p]),
     ("sed_batch_bitpar_pairs", C.c_int, [C.c_void_p]),
     ("sed_batch_scaled_pairs", C.c_int, [C.c_void_p]),
@@ -232,6 +235,31 @@ class Context:
                                      dist, is_int, ln, ops_ptr, ops_off_ptr)
         self._check(rc, "sed_run_batch")
         return dist[:np_], is_int[:np_], ln[:np_], ops
+
+    def run_cutoff(self, packed, max_dist, no_len=True):
+        """Distances of packed's pairs under a cutoff, one launch: (dist, is_int, len, hits); pairs beyond max_dist
+        come back as (inf, 0, -1)."""
+        return self.deepen(packed, 0, max_dist, max_dist, no_len)[:4]
+
+    def deepen(self, packed, k, first, last, no_len=True):
+        """One resident batch run under the cutoff `first`, doubled until at least k pairs are within it or it has
+        reached `last` (the deepening loop of wfsearch.nearest; no input is uploaded twice).
+        Returns (dist, is_int, len, hits, cutoffs tried)."""
+        batch = Batch(self, packed, False, no_len=no_len)
+        try:
+            cut, cuts = float(first), []
+            while True:
+                batch.set_cutoff(cut)
+                batch.run()
+                cuts.append(cut)
+                hits = batch.cutoff_hits()
+                if hits >= k or cut >= last:
+                    break
+                cut = min(2.0 * cut, float(last))
+            dist, is_int, ln, _ = batch.results()
+            return dist, is_int, ln, hits, cuts
+        finally:
+            batch.close()
 
     def run_pair(self, codes_a, codes_b, want_script, no_len=False):
         """One pair (codes as bytes): (dist, is_int, len, ops u32[] | None) through sed_run_pair, the per-call path of
@@ -454,6 +482,17 @@ class Batch:
         """SPLIT batches: the (pair, stripe) workgroups of a run, 0 otherwise (SED_OPT_SPLIT)."""
         return self._lib.sed_batch_split_tasks(self.ptr)
 
+    def set_cutoff(self, max_dist):
+        """Bound the distances of the runs that follow (distance-only batches): a pair beyond max_dist comes back as
+        (inf, is_int 0, len -1), the others as without a cutoff; float('inf') turns it off (sed_batch_set_cutoff)."""
+        self.ctx._check(self._lib.sed_batch_set_cutoff(self.ptr, float(max_dist)), "sed_batch_set_cutoff")
+
+    def cutoff_hits(self):
+        """Pairs within the cutoff in the last run (waits for it), without downloading the distances."""
+        h = C.c_int32()
+        self.ctx._check(self._lib.sed_batch_cutoff_hits(self.ptr, C.byref(h)), "sed_batch_cutoff_hits")
+        return h.value
+
     def run(self):
         self.ctx._check(self._lib.sed_batch_run(self.ptr), "sed_batch_run")
 
@@ -628,6 +667,12 @@ class EngineClient:
     def run_pair(self, codes_a, codes_b, want_script, no_len=False):
         return self._call("run_pair", codes_a, codes_b, want_script, no_len)
 
+    def run_cutoff(self, packed, max_dist, no_len=True):
+        return self._call("run_cutoff", packed, max_dist, no_len)
+
+    def deepen(self, packed, k, first, last, no_len=True):
+        return self._call("deepen", packed, k, first, last, no_len)
+
     def full_matrix(self, codes_a, codes_b):
         return self._call("full_matrix", np.asarray(codes_a, np.uint8), np.asarray(codes_b, np.uint8))
 
@@ -687,6 +732,10 @@ def _serve(rx, tx, device, pooled=False):
                 val = ctx.run(*args)
             elif op == "run_pair":
                 val = ctx.run_pair(*args)
+            elif op == "run_cutoff":
+                val = ctx.run_cutoff(*args)
+            elif op == "deepen":
+                val = ctx.deepen(*args)
             elif op == "full_matrix":
                 val = ctx.full_matrix(*args)
             else:

@@ -14,6 +14,7 @@ has the reference's signature and output: a list of (doc['sequence'], score) in
 the return value exactly like the reference.  Other scoring methods (tf/idf vectors, set
 similarities) are not on the engine's path and raise NotImplementedError.
 """
+import math
 from collections import OrderedDict
 
 import StringEditDistance as SED
@@ -51,6 +52,55 @@ def wf_scores(query, seqs, user_cost=False):
 
 def clear_cache():
     _CACHE.clear()
+
+
+def _sequences(seqs_or_collection):
+    """A list of sequences, or a collection's doc['sequence'] in find({}) order."""
+    if hasattr(seqs_or_collection, 'find'):
+        return [doc['sequence'] for doc in seqs_or_collection.find({})]
+    return list(seqs_or_collection)
+
+
+def search_within(query, seqs_or_collection, max_dist, user_cost=False):
+    """[(sequence, 1 / (1 + d))] for the documents whose distance d from query is <= max_dist, in collection order,
+    with one engine launch that skips the cells no path within max_dist can reach.  A batch extension (the
+    reference scores every document); not cached."""
+    seqs = _sequences(seqs_or_collection)
+    if not seqs:
+        return []
+    vals = SED.distance_batch([query] * len(seqs), seqs, user_cost, max_dist=max_dist)
+    return [(s, 1 / (1 + v)) for s, v in zip(seqs, vals) if v != math.inf]
+
+
+def nearest(query, seqs, k, user_cost=False, distance_fn=None):
+    """The k documents of smallest distance from query as [(sequence, 1 / (1 + d))], nearest first, ties in
+    collection order.  One resident batch runs under a cutoff that starts at the k-th smallest length-difference
+    lower bound (at least insert + delete) and doubles until k documents are within it or it has reached the largest
+    n delete + m insert; the far documents are never computed in full.  Those k are the true top k: every document
+    outside the last cutoff T has d > T, and T is >= each of theirs.
+    distance_fn(queries, seqs, max_dist) -> [d or math.inf] replaces the engine (CPU tests).  Not cached."""
+    seqs = _sequences(seqs)
+    k = min(int(k), len(seqs))
+    if k <= 0:
+        return []
+    queries = [query] * len(seqs)
+    plan = SED.batch_plan(queries, seqs, user_cost)
+    ins, dele, n = plan.ins, plan.dele, len(query)
+    bounds = sorted(ins * max(len(s) - n, 0) + dele * max(n - len(s), 0) for s in seqs)
+    last = max(max(n * dele + len(s) * ins for s in seqs), 0)
+    first = max(bounds[k - 1], ins + dele)
+    first = min(first if first > 0 else 1, last)
+    if distance_fn is None:
+        vals, _ = SED.distance_deepen(queries, seqs, k, first, last, user_cost, plan=plan)
+    else:
+        cut = first
+        while True:
+            vals = list(distance_fn(queries, seqs, cut))
+            if sum(v != math.inf for v in vals) >= k or cut >= last:
+                break
+            cut = min(2 * cut, last)
+    order = sorted((v, i) for i, v in enumerate(vals) if v != math.inf)[:k]
+    return [(seqs[i], 1 / (1 + v)) for v, i in order]
 
 
 def search_collection(query, vector_type, collection, method, return_dict=None, callback=None):
