@@ -71,20 +71,20 @@ __device__ __forceinline__ void zero_script_tails_wave(uint32_t *__restrict__ op
 }
 #endif  // __HIPCC__
 
-// Integer kernel constants (offset-key space, see sed_kernels.hip):
+// Integer kernel constants (offset-key space, see sed_i32_keys.h):
 //   costrow[a]   byte b = (cost(a -> b) - insert - delete - 1) & 0xFF  (32-bit keys)
 //   costrow16[a] byte b = (cost(a -> b) - insert - delete) & 0xFF      (16-bit packed distance keys)
 //   kins = (insert << 16) + 4, kdel = (delete << 16) + 5: the lane kernels' key increments (op included;
 //   their offsets per column / row are kins and kdel - 1).  The wave kernels derive their own from ins/del.
-#define SED_KB 0xFFFFFFFCu  // bias of the 32-bit distance-only offset keys (sed_kernels.hip)
+#define SED_KB 0xFFFFFFFCu  // bias of the 32-bit distance-only offset keys (sed_i32_keys.h)
 #define SED_KB_DOT 0u       // border of the dot keys (every border cell is X = U = 0)
 struct sed_i32_params {
     uint32_t costrow[4];
     uint32_t costrow16[4];
     uint32_t kins, kdel;
     uint32_t ins, del;
-    uint32_t epoch;  // SPLIT hand-off words' tag: 1..32767 per run (sed_kernels.hip: store_tagged)
-    // Dot keys (checkpoint batches of the stripe kernel, sed_kernels.hip: i32_step DOT): the update addend
+    uint32_t epoch;  // SPLIT hand-off words' tag: 1..32767 per run (sed_dev.h: store_tagged)
+    // Dot keys (checkpoint batches of the stripe kernel, sed_i32_keys.h: i32_step DOT): the update addend
     // A*kappa(a, b) + 1, kappa = insert + delete - cost(a -> b), as a signed byte dot product
     // dot4(dotrow[a], dotcol[b]); keys W = A*X + U (X = sum of kappa on the path, U = its updates), maximised.
     // Decode: X = (k * dotM) >> dotS (= floor(k*kmax / (A*kmax + 1)); dotM includes kmax, dotS >= 32, so the
@@ -94,7 +94,7 @@ struct sed_i32_params {
     uint32_t dotrow[4], dotcol[4];
     // Ladder dot keys (CHAIN kernel with the L field): V = D*ladA + 8L over the ladder (lad = 1) or D*ladA + 16L over
     // the wide ladder (lad = 2), the update addend of a d = -1 row -(ladA*kappa + 7) (+ 15) = dot4(ladrow[a],
-    // ladcol[b]) (sed_kernels.hip: i32_step LDOT)
+    // ladcol[b]) (sed_i32_keys.h: i32_step LDOT)
     uint32_t lad, ladA, ladsent;
     uint32_t ladrow[4], ladcol[4];
 };
@@ -103,7 +103,7 @@ struct sed_f64_params {
     double ins, del;
     int32_t ins_int, del_int;
     int32_t K;
-    uint32_t epoch;  // SPLIT hand-off words' tag, as sed_i32_params::epoch (sed_kernels.hip: sed_wf_f64_split_kernel)
+    uint32_t epoch;  // SPLIT hand-off words' tag, as sed_i32_params::epoch (sed_f64.hip: sed_wf_f64_split_kernel)
 };
 
 // Full-matrix output (dp proxy materialisation): D[i*(m+1)+j], M = edge mask (1 ins, 2 del, 4 upd) | int << 3.
@@ -128,7 +128,7 @@ struct sed_launch {
     sed_result *res;
     int R;
     hipStream_t stream;
-    bool tb_ladder;     // traceback codes of the integer kernels carry the row's ladder rung (sed_kernels.hip)
+    bool tb_ladder;     // traceback codes of the integer kernels carry the row's ladder rung (sed_i32_keys.h)
     bool tb_wide;       // ... of the wide ladder (ladder dot keys, LadderW: the CHAIN kernel's LDOT batches)
     bool ck;            // integer R = 16 wave kernel: tb holds checkpoints, the traceback recomputes tiles
     // band pruning (checkpoint batches of the stripe kernel): band[pair] = the window of diagonals the forward computes

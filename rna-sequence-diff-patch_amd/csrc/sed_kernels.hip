@@ -16,7 +16,7 @@
 // row) and every lane its str2 selector from small per-wave LDS rings, read as
 // broadcasts; lane 63's bottom row is collected by DPP wave_shl:1 and stored as
 // the next stripe's top row (per 64-step chunk in one wave, per 16-step group
-// through tagged words between SPLIT workgroups, below).
+// through tagged words between SPLIT workgroups, sed_dev.h).
 //
 // Integer kernels (the exact fast path).  When every cost is
 // an integral positive Python float (or the int 0 of a match), the reference's
@@ -24,7 +24,7 @@
 //    (distance, path length, op)   lexicographically minimal
 // is one unsigned v_min3_u32 over packed keys.  Three key formats, all kept in
 // an offset space where the insert candidate needs no add and every border is a
-// constant (details at "Integer (packed-key) kernels" below):
+// constant (details in sed_i32_keys.h):
 //  - ladder keys V = D << 16 + L << 3 + op (per-cell traceback codes): v_perm,
 //    v_add, v_min3, v_and_or (clears the op), v_alignbit (packs the 2-bit op)
 //    = 5 VALU per cell, plus a delete add on 3 of 16 rows;
@@ -38,445 +38,20 @@
 // fp64 kernel (the general path): fp64 candidates added exactly as the
 // reference does, equality ties, L tie-break on an integer key, and an
 // optional int/float typing bit.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <type_traits>
+//
+// Where things live:
+//   sed_dev.h       cross-lane moves, min / packed helpers, code-group stores, the SPLIT hand-off's tagged words
+//   sed_i32_keys.h  the integer key machinery (i32_step, i32_group, ladders, decode, forward -> traceback keys)
+//   sed_ck_tile.h   the checkpoint tile sweep and walk (shared by sed_cktb.hip and sed_ck_codes_kernel)
+//   sed_kernels.hip (this file) the integer wave-per-pair kernels and the tracebacks over per-cell codes, in this order:
+//                   integer stripe / SPLIT / cutoff, two pairs per wave, CHAIN, tracebacks (lane, window, stripe-
+//                   parallel), sed_ck_codes_kernel, self-test, band and cutoff windows; then their launchers
+//   sed_f64.hip     the fp64 wave kernel (whole wave and 16-lane segments), fp64 SPLIT and their launchers
+//   sed_cktb.hip    the checkpoint traceback and its launcher, built with its own code-generation options
+//   sed_lane.hip    lane-per-pair kernels for short str2
 #include <hip/hip_ext.h>
-#include "sed_internal.h"
-
-#define DPP_WAVE_SHL1 0x130  // lane i <- lane i+1, lane 63 keeps `old`
-#define DPP_WAVE_ROL1 0x134  // lane i <- lane i+1, lane 63 <- lane 0
-#define DPP_WAVE_SHR1 0x138  // lane i <- lane i-1, lane 0 keeps `old`
-
-__device__ __forceinline__ uint32_t dpp_shr1(uint32_t old, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, DPP_WAVE_SHR1, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t dpp_shl1(uint32_t old, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, DPP_WAVE_SHL1, 0xf, 0xf, false);
-}
-__device__ __forceinline__ uint32_t dpp_rol1(uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)src, (int)src, DPP_WAVE_ROL1, 0xf, 0xf, false);
-}
-// lane i <- lane i-1's src + addv, lane 0 keeps `old`: one v_add_u32_dpp (the s_nop covers the DPP read of
-// a VGPR written by the previous VALU instruction)
-__device__ __forceinline__ uint32_t dpp_shr1_add(uint32_t old, uint32_t src, uint32_t addv) {
-    asm("s_nop 1\n\tv_add_u32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(old) : "v"(src), "v"(addv));
-    return old;
-}
-__device__ __forceinline__ double dpp_shr1_f64(double old, double src) {
-    const uint64_t o = __double_as_longlong(old), s = __double_as_longlong(src);
-    const uint32_t lo = dpp_shr1((uint32_t)o, (uint32_t)s);
-    const uint32_t hi = dpp_shr1((uint32_t)(o >> 32), (uint32_t)(s >> 32));
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double dpp_shl1_f64(double old, double src) {
-    const uint64_t o = __double_as_longlong(old), s = __double_as_longlong(src);
-    const uint32_t lo = dpp_shl1((uint32_t)o, (uint32_t)s);
-    const uint32_t hi = dpp_shl1((uint32_t)(o >> 32), (uint32_t)(s >> 32));
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double dpp_rol1_f64(double src) {
-    const uint64_t s = __double_as_longlong(src);
-    const uint32_t lo = dpp_rol1((uint32_t)s), hi = dpp_rol1((uint32_t)(s >> 32));
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-
-// The same moves inside segments of SW lanes (SW = 64: the whole wave; SW = 16: each DPP row, so a wave runs four
-// independent segments, the fp64 kernel's short pairs): shr = lane i <- lane i-1 (the segment's lane 0 keeps `old`,
-// row_shr:1), shl = lane i <- lane i+1 (the segment's last lane keeps `old`, row_shl:1), rol = lane i <- lane i+1
-// mod SW (row_ror:15).
-#define DPP_ROW_SHL1 0x101
-#define DPP_ROW_SHR1 0x111
-#define DPP_ROW_ROR15 0x12F
-template <int SW> __device__ __forceinline__ uint32_t seg_shr1(uint32_t old, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, SW == 64 ? DPP_WAVE_SHR1 : DPP_ROW_SHR1, 0xf, 0xf,
-                                                 false);
-}
-template <int SW> __device__ __forceinline__ uint32_t seg_shl1(uint32_t old, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, SW == 64 ? DPP_WAVE_SHL1 : DPP_ROW_SHL1, 0xf, 0xf,
-                                                 false);
-}
-template <int SW> __device__ __forceinline__ uint32_t seg_rol1(uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)src, (int)src, SW == 64 ? DPP_WAVE_ROL1 : DPP_ROW_ROR15, 0xf, 0xf,
-                                                 false);
-}
-template <int SW> __device__ __forceinline__ double seg_shr1_f64(double old, double src) {
-    const uint64_t o = __double_as_longlong(old), s = __double_as_longlong(src);
-    const uint32_t lo = seg_shr1<SW>((uint32_t)o, (uint32_t)s), hi = seg_shr1<SW>((uint32_t)(o >> 32), (uint32_t)(s >> 32));
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-template <int SW> __device__ __forceinline__ double seg_shl1_f64(double old, double src) {
-    const uint64_t o = __double_as_longlong(old), s = __double_as_longlong(src);
-    const uint32_t lo = seg_shl1<SW>((uint32_t)o, (uint32_t)s), hi = seg_shl1<SW>((uint32_t)(o >> 32), (uint32_t)(s >> 32));
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-template <int SW> __device__ __forceinline__ double seg_rol1_f64(double src) {
-    const uint64_t s = __double_as_longlong(src);
-    const uint32_t lo = seg_rol1<SW>((uint32_t)s), hi = seg_rol1<SW>((uint32_t)(s >> 32));
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { return min(min(a, b), c); }
-__device__ __forceinline__ uint32_t umax3(uint32_t a, uint32_t b, uint32_t c) { return max(max(a, b), c); }
-// the dot keys' update candidate: diag + dot4(row vector, column vector) over signed bytes (v_dot4_i32_i8)
-// (the VOP3P form with its own destination: the builtin picks v_dot4c_i32_i8, which accumulates in place and made
-// the register allocator copy every diagonal first, 186 instead of 111 v_mov per 256 cells).  The hardware needs
-// wait states between a v_dot4 and a VALU op reading its result, which the compiler cannot see through the asm
-// (tools/ubench/dot_sem.hip: the next op reads a stale value), so the asm is volatile (issued in program order)
-// and the caller keeps every consumer 4 dots behind its producer (dot_fence).
-__device__ __forceinline__ uint32_t dot_add(uint32_t rowv, uint32_t colv, uint32_t diag) {
-    uint32_t r;
-    asm volatile("v_dot4_i32_i8 %0, %1, %2, %3" : "=v"(r) : "v"(rowv), "v"(colv), "v"(diag));
-    return r;
-}
-// dots issued ahead of the max / min chain (>= 4: tools/ubench/dot_sem.hip shows the next op reading stale data;
-// the fence then leaves 3 or more instructions between a dot and its reader).  A/B on config 4's forward kernel
-// (tools/ab.sh, profiles/r02_dot/ab_ahead.jsonl): 4 -> 9.24-9.33 ms, 6 same, 8 -> 9.16-9.23 ms, 12 9.29, 16 9.18.
-#ifndef SED_DOT_AHEAD
-#define SED_DOT_AHEAD 8
-#endif
-// an empty volatile asm on a dot result, placed after the dots that must separate it from its consumer: the
-// consumer cannot be scheduled above it.  (The compiler treats the asm as a write of x and puts an s_nop 0 between
-// it and the max reading x, 50 per 64-cell group.  Fencing one row earlier drops that to 29 but lets the compiler
-// pair up dependent maxes back to back: config 4's forward 9.19 -> 9.49 ms, so the fence stays next to its max.)
-__device__ __forceinline__ void dot_fence(uint32_t &x) { asm volatile("" : "+v"(x)); }
-// An opaque v_min3_u32: over three selects (tie keys of the fp64 kernel) the compiler rewrites
-// min(min(a, b), c) into select-of-min chains that cost one op more per cell.
-__device__ __forceinline__ uint32_t umin3_op(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// relaxed agent-scope load = global_load sc1: bypasses this CU's L1 so a
-// stripe reads the bottom row its own wave stored during the previous stripe.
-__device__ __forceinline__ uint32_t load_sc1(const uint32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t load_sc1_u64(const uint64_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Traceback codes are stored per "group" of G = 64/R steps: G steps x R rows x 2 bits
-// = 16 bytes per lane, one dwordx4 store; the wave writes 1 KiB contiguous.
-template <int R> struct Grp { static constexpr int G = 64 / R; };
-
-__device__ __forceinline__ void store_tb(uint32_t *p, const uint32_t (&w)[4]) {
-    *reinterpret_cast<uint4 *>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-}
-// G (a multiple of 4) consecutive words, 16-byte aligned
-template <int G> __device__ __forceinline__ void store_words(uint32_t *p, const uint32_t (&w)[G]) {
-#pragma unroll
-    for (int k = 0; k < G; k += 4) *reinterpret_cast<uint4 *>(p + k) = make_uint4(w[k], w[k + 1], w[k + 2], w[k + 3]);
-}
-
-// ---------------------------------------------------------------------------
-// Integer (packed-key) kernels.  The reference's decision per cell is the
-// lexicographic minimum of (distance, path length, op) over its candidates, i.e.
-// one unsigned min over the keys
-//     V = D << 16 + L << 3 + op        (op 0 insert, 1 delete, 2 update)
-// with candidates V_left + Ki, V_up + Kd + 1, V_diag + (cost << 16) + 10, where
-// Ki = (insert << 16) + 8 and Kd = (delete << 16) + 8.  The L field may run past
-// its 13 bits: the three candidates of cell (i, j) have L in [max(i,j), i+j],
-// so 8 * |L difference| <= 8 * min(n, m) < 2^16 and any distance difference
-// still dominates (the host keeps min(n, m) < 8192); at the sink L is read
-// modulo 8192 inside that window.
-//
-// Offset keys.  Subtracting the same amount from the three candidates of a cell
-// keeps their order, so cells are stored as
-//     W(i, j) = V(i, j) - i*Kd - j*Ki + B + c(i)        (B = SED_KB3)
-// where i*Kd + j*Ki bounds V from above (the all-delete-then-insert path) and
-// the host checks that it stays below B, so W never wraps.  c(i) in 0..5 is a
-// per-row residue ("ladder") that steps down by one from row to row and jumps
-// back up on a few rows (Ladder<R> below, periodic in i with a period dividing
-// R, so every lane row has a compile-time rung).  With d = c(i) - c(i-1):
-//     insert candidate = W_left,
-//     delete candidate = W_up + (d + 1)          (no add on the d = -1 rows),
-//     update candidate = W_diag + ((cost - delete - insert) << 16) - 6 + d.
-// The update constant is one v_perm_b32 of a per-row byte vector (cost - delete
-// - insert - 1; the bytes below it 0xFF / (d - 6) from the inline constant d - 6;
-// the host requires cost <= insert + delete).  mm = min3 is a clean value (low 3
-// bits = c(i)) plus the winning op, which never leaves the 8-block because
-// c(i) + 2 <= 7, so clearing the op is one v_and_or: (mm & ~7) | c(i).  A cell
-// therefore costs v_perm, v_add, v_min3, v_and_or, v_alignbit = 5 VALU, plus the
-// delete add on 3 of 16 rows.  The traceback codes are mm's low 2 bits
-// (c(i) + op) & 3; the traceback kernels subtract the rung of the row they are on.
-// Every border is a constant: W(0, j) = B, W(i, 0) = B + c(i).
-//
-// Distance keys (!LEN): V = D << 16 - U without an op field, W = V -
-// i*(delete << 16) - j*(insert << 16) + SED_KB, update constant ((cost - delete -
-// insert) << 16) - 1: an update also subtracts 1 from the low half, which never
-// borrows (fewer than 2^16 updates on any path), so D = (V + 0xFFFF) >> 16 and
-// U = (D << 16) - V.  At equal D the smaller key has more updates, i.e. the
-// shorter path (L = i + j - U), so the min is the (D, L) minimum; only the op
-// tie-break is missing, which the CK traceback recomputes.  That is v_perm,
-// v_add, v_min3 = 3 VALU per cell; every border is SED_KB.
-// Lanes run unmasked all the time, and a lane past column m computes columns
-// that nothing reads.
-// ---------------------------------------------------------------------------
-#define SED_KB3 0xFFFFFE00u  // bias of the ladder keys (= 0 mod 8, 512 below 2^32 for the ramp sentinel)
-
-// The ladder: rung c(i) of row i by i mod P, 4 bits per rung; runs of 5,4,3,2,1,0 as long as the
-// period allows (P = 16: jumps at i = 1, 7, 11 (mod 16); P = 8: at 1, 7; P = 4: at 1).
-template <int R> struct Ladder {
-    static constexpr int P = R >= 16 ? 16 : R;
-    static constexpr uint64_t pat = P == 16 ? 0x1234501230123450ull : (P == 8 ? 0x10123450ull : 0x1230ull);
-    static constexpr int rung(int i) { return (int)((pat >> (4 * (i & (P - 1)))) & 0xF); }
-};
-// The wide ladder of the ladder dot keys (LDOT = 2, the CHAIN kernel): rung + op in the low 4 bits (V = D*A + 16L + op,
-// the host keeps 16 min(n, m) + 15 < A and A a multiple of 16), rungs up to 13, so the rung runs down through a whole period
-// with one jump (P = 8: rows 1..7 on rungs 7..1; P = 16: 13..0 and two jumps): 1 jump row in 8 instead of 2, each a
-// delete add and an update add fewer.  Same P, so the tracebacks read it through their runtime pattern alone.
-template <int R> struct LadderW {
-    static constexpr int P = R >= 16 ? 16 : R;
-    static constexpr uint64_t pat = P == 16 ? 0x10123456789ABCD0ull : (P == 8 ? 0x12345670ull : 0x1230ull);
-    static constexpr int rung(int i) { return (int)((pat >> (4 * (i & (P - 1)))) & 0xF); }
-};
-
-// One column step of a lane's R rows.  tv = {top, sel} of this step's column
-// for lane 0 (the stripe's top row and str2 symbol): every lane reads the same
-// LDS word, only lane 0 keeps it (the DPP move's `old` operand).  Lane rows are
-// i = (multiple of P) + r + 1, so row r sits on rung Ladder::rung(r + 1).
-// SELL: the lane's own selector arrives in tv.y (read from the wave's LDS selector ring, see
-// sed_wf_i32_kernel), instead of flowing from lane 0 through a DPP move (one DPP + one copy per step).
-// TOPC: lane 0's top is the row-0 constant, which its top_prev already holds (single-stripe pairs: the CHAIN
-// kernel), so the DPP move writes over top_prev in place instead of over a copy of tv.x.
-template <int R, bool TB, bool LEN, bool COLLECT = true, bool SELL = false, bool TOPC = false, bool DOT = false,
-          int LDOT = 0>
-__device__ __forceinline__ void i32_step(uint32_t (&V)[R], const uint32_t (&cv)[R], uint32_t &top_prev,
-                                         uint32_t &bottom, uint32_t &selv, const uint2 tv, uint32_t &outc,
-                                         uint32_t (&W)[4], const int u, const uint32_t jv = 0u) {
-    using Lad = Ladder<R>;
-    if constexpr (SELL) selv = tv.y;
-    else selv = dpp_shr1(tv.y, selv);  // perm selector of this column's str2 symbol
-    constexpr int d0 = Lad::rung(1) - Lad::rung(0);
-    // row 0's update candidate from top_prev, before the DPP move overwrites top_prev in place (TOPC): the
-    // empty asm makes the move's `old` depend on it, so top_prev needs no copy
-    if constexpr (LEN && LDOT) {
-        // ladder keys with the update addend as one v_dot4 (ladder dot keys, sed_runtime.cpp): the addend of a row
-        // whose rung steps down by one (d = -1) is -(A*kappa + 7) over the 3-bit ladder (LDOT = 1: V = D*A + 8L) or
-        // -(A*kappa + 15) over the wide one (LDOT = 2: V = D*A + 16L, LadderW) = the dot of the row's and the column's
-        // byte vectors (column vectors negated by the host); a row with another step adds d + 1 to it, which is where
-        // the perm took its inline constant d - 6.  Candidates run 4 rows ahead of the min chain (dot_add).  Per cell:
-        // v_dot4, v_min3, v_and_or, v_alignbit = 4 VALU (5 with the perm), plus two adds on a jump row.
-        using Lad = std::conditional_t<LDOT == 2, LadderW<R>, Ladder<R>>;
-        constexpr uint32_t LOW = LDOT == 2 ? 15u : 7u;  // the rung + op field
-        // the wide ladder's jump is row 0 of every lane (i = 1 mod P): its delete and update inputs, the cell above
-        // the band and the diagonal, both take d + 1 = J0, which the DPP move from lane t - 1 adds itself (one
-        // v_add_u32_dpp with jv = J0 instead of v_mov_b32_dpp), so top_prev carries it too (i32_reset: tpb)
-        constexpr bool BIAS = LDOT == 2;
-        constexpr uint32_t J0 = (uint32_t)(Lad::rung(1) - Lad::rung(0) + 1);
-        constexpr int AH = R < 4 ? R : 4;
-        uint32_t cand[R];
-        cand[0] = dot_add(cv[0], selv, top_prev);
-#pragma unroll
-        for (int r = 1; r < AH; ++r) cand[r] = dot_add(cv[r], selv, V[r - 1]);
-        const uint32_t topv = BIAS ? dpp_shr1_add(TOPC ? top_prev : tv.x + J0, bottom, jv)
-                                   : dpp_shr1(TOPC ? top_prev : tv.x, bottom);
-        uint32_t up = topv;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (r + AH < R) cand[r + AH] = dot_add(cv[r + AH], selv, V[r + AH - 1]);
-            dot_fence(cand[r]);
-            const int c = Lad::rung(r + 1), d = c - Lad::rung(r);  // compile-time after unrolling
-            const bool plain = d == -1 || (BIAS && r == 0);          // (BIAS: row 0's inputs carry d + 1)
-            const uint32_t upd = plain ? cand[r] : cand[r] + (uint32_t)(d + 1);
-            const uint32_t mm = umin3(V[r], plain ? up : up + (uint32_t)(d + 1), upd);
-            if constexpr (TB) {
-                const int k = u * R + r;
-                W[k >> 4] = __builtin_amdgcn_alignbit(mm, W[k >> 4], 2);
-            }
-            up = (mm & ~LOW) | (uint32_t)c;
-            V[r] = up;
-        }
-        top_prev = topv;
-        bottom = V[R - 1];
-        if constexpr (COLLECT) outc = dpp_shl1(bottom, outc);
-        return;
-    }
-    if constexpr (DOT) {  // dot keys: maximise, the update addend is one v_dot4 of signed bytes
-        // candidates run 4 rows ahead of the max chain (the dot's result hazard, dot_add): row r + 4's diagonal is
-        // still the old value of row r + 3 when row r is updated
-        constexpr int AH = R < SED_DOT_AHEAD ? R : SED_DOT_AHEAD;
-        uint32_t cand[R];
-        cand[0] = dot_add(cv[0], selv, top_prev);
-#pragma unroll
-        for (int r = 1; r < AH; ++r) cand[r] = dot_add(cv[r], selv, V[r - 1]);
-        const uint32_t topv = dpp_shr1(TOPC ? top_prev : tv.x, bottom);
-        uint32_t up = topv;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (r + AH < R) cand[r + AH] = dot_add(cv[r + AH], selv, V[r + AH - 1]);
-            dot_fence(cand[r]);  // row r's candidate was issued AH dots ago
-            up = umax3(V[r], up, cand[r]);
-            V[r] = up;
-        }
-        top_prev = topv;
-        bottom = V[R - 1];
-        if constexpr (COLLECT) outc = dpp_shl1(bottom, outc);
-        return;
-    }
-    uint32_t dg0 = top_prev + __builtin_amdgcn_perm(cv[0], LEN ? (uint32_t)(d0 - 6) : 0xFFFFFFFFu, selv);
-    if constexpr (TOPC) asm("" : "+v"(top_prev) : "v"(dg0));
-    const uint32_t topv = dpp_shr1(TOPC ? top_prev : tv.x, bottom);  // cell above the band, this column
-    uint32_t up = topv, diag = top_prev;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t left = V[r];
-        uint32_t mm;
-        if constexpr (LEN) {
-            const int c = Lad::rung(r + 1), d = c - Lad::rung(r);  // compile-time after unrolling
-            // insert (op 0) = left, delete (op 1) = up + d + 1, update (op 2) = diag + offset constant
-            // (perm bytes 1:0 from the inline constant d - 6)
-            mm = umin3(left, d == -1 ? up : up + (uint32_t)(d + 1),
-                       r == 0 ? dg0 : diag + __builtin_amdgcn_perm(cv[r], (uint32_t)(d - 6), selv));
-            if constexpr (TB) {
-                const int k = u * R + r;
-                W[k >> 4] = __builtin_amdgcn_alignbit(mm, W[k >> 4], 2);
-            }
-            up = (mm & ~7u) | (uint32_t)c;
-        } else {
-            mm = umin3(left, up, r == 0 ? dg0 : diag + __builtin_amdgcn_perm(cv[r], 0xFFFFFFFFu, selv));
-            up = mm;
-        }
-        diag = left;
-        V[r] = up;
-    }
-    top_prev = topv;
-    bottom = V[R - 1];
-    if constexpr (COLLECT) outc = dpp_shl1(bottom, outc);  // lane 63's bottom row (CK: the row checkpoints)
-}
-
-// Column-0 state of rows row0+1 .. row0+R (row0 = multiple of P) and of row0, the diagonal of the
-// first column.
-template <int R, bool LEN, bool DOT = false, bool WIDE = false>
-__device__ __forceinline__ void i32_reset(uint32_t (&V)[R], uint32_t &top_prev) {
-    // (WIDE: top_prev carries row 0's jump, i32_step LDOT = 2)
-    top_prev = LEN ? SED_KB3 + (WIDE ? (uint32_t)(LadderW<R>::rung(1) - LadderW<R>::rung(0) + 1) : 0u)
-                   : DOT ? SED_KB_DOT : SED_KB;
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-        V[r] = LEN ? SED_KB3 + (uint32_t)(WIDE ? LadderW<R>::rung(r + 1) : Ladder<R>::rung(r + 1)) : DOT ? SED_KB_DOT : SED_KB;
-}
-// row 0 (D = j*insert, L = j) in offset keys
-template <bool LEN, bool DOT = false> __device__ __forceinline__ uint32_t i32_row0() {
-    return LEN ? SED_KB3 : DOT ? SED_KB_DOT : SED_KB;
-}
-
-// The sink cell (n, m) back to V space; returns {D, L} (without LEN, L = n + m - U when WANT_L, else -1).
-// Dot key k = A*X + U -> {X, U}: X = floor(k*kmax / (A*kmax + 1)) by a multiply-shift (the host checks k*kmax
-// < 2^29 and picks dotM, dotS so the product is exact), U = k - A*X.
-__device__ __forceinline__ uint2 dot_split(uint32_t w, const sed_i32_params &prm) {
-    const uint32_t k = w - SED_KB_DOT;
-    const uint32_t X = __umulhi(k, prm.dotM) >> (prm.dotS - 32u);  // dotM carries kmax (one v_mul_hi, full-rate rest)
-    return make_uint2(X, k - __umul24(prm.dotA, X));
-}
-template <int R, bool LEN, bool WANT_L = false, bool DOT = false, int LDOT = 0>
-__device__ __forceinline__ int2 i32_decode(uint32_t w, int n, int m, const sed_i32_params &prm) {
-    if constexpr (LEN && LDOT) {  // V = D*A + uL: one division per pair
-        // u = 8: the host keeps 8 (n + m) + 7 < A; u = 16 (the wide ladder): 16 min(n, m) + 15 < A, and L is read inside
-        // its window [max(n, m), n + m] (the candidates of a cell differ in L by at most min(n, m), so that bound keeps
-        // their order)
-        constexpr uint32_t U = LDOT == 2 ? 16u : 8u;
-        const uint32_t rg = (uint32_t)(LDOT == 2 ? LadderW<R>::rung(n) : Ladder<R>::rung(n));
-        const uint32_t v = w - SED_KB3 - rg + (uint32_t)n * (prm.del * prm.ladA + U) + (uint32_t)m * (prm.ins * prm.ladA + U);
-        const uint32_t lo = LDOT == 2 ? U * (uint32_t)max(n, m) : 0u;
-        const uint32_t D = (v - lo) / prm.ladA;
-        return make_int2((int)D, (int)((v - D * prm.ladA) / U));
-    } else if constexpr (DOT) {  // D = n*delete + m*insert - X, L = n + m - U
-        const uint2 xu = dot_split(w, prm);
-        return make_int2((int)((uint32_t)n * prm.del + (uint32_t)m * prm.ins - xu.x), n + m - (int)xu.y);
-    } else if constexpr (LEN) {
-        const uint32_t v = w - SED_KB3 - (uint32_t)Ladder<R>::rung(n) + (uint32_t)n * ((prm.del << 16) + 8u) +
-                           (uint32_t)m * ((prm.ins << 16) + 8u);
-        const uint32_t lo = (uint32_t)max(n, m);
-        const uint32_t L = lo + ((((v >> 3) & 0x1FFFu) - lo) & 0x1FFFu);  // L in [max(n,m), n+m]
-        return make_int2((int)((v - 8u * L) >> 16), (int)L);
-    } else {
-        const uint32_t v = w - SED_KB + (((uint32_t)n * prm.del + (uint32_t)m * prm.ins) << 16);
-        const uint32_t D = (v + 0xFFFFu) >> 16;
-        return make_int2((int)D, WANT_L ? n + m - (int)((D << 16) - v) : -1);
-    }
-}
-
-// Distance key (!LEN) of a cell -> the traceback key of the same (D, L) (clean, op 0).  Traceback keys
-// (sed_traceback_ck_kernel) are T = V - i*((delete << 16) + 4) - j*((insert << 16) + 4) + SED_KB over
-// V = D << 16 | L << 2 | op: the insert candidate is the left cell, the delete candidate the cell above
-// + 1, the update candidate the diagonal + ((cost - delete - insert) << 16) - 2, and the winner's low 2
-// bits are the op itself.  With U = (SED_KB - w) & 0xFFFF (updates on the path) both keys share
-// (D - i*delete - j*insert) << 16, and T = w - 3U; independent of the cell's position.
-__device__ __forceinline__ uint32_t i32_dist_to_tb(uint32_t w) {
-    const uint32_t U = (SED_KB - w) & 0xFFFFu;
-    return w - 3u * U;
-}
-// either forward key format -> traceback key: T = SED_KB - (X << 16) - 4U (X = i*delete + j*insert - D)
-__device__ __forceinline__ uint32_t ck_to_tb(uint32_t w, const sed_i32_params &prm) {
-    if (prm.dot) {  // = SED_KB - 4k + 4A X - (X << 16)
-        const uint32_t k = w - SED_KB_DOT;
-        const uint32_t X = __umulhi(k, prm.dotM) >> (prm.dotS - 32u);
-        return SED_KB - 4u * k + __umul24(4u * prm.dotA, X) - (X << 16);
-    }
-    return i32_dist_to_tb(w);
-}
-
-// Ramp for free.  Every lane starts a stripe at its column-0 state and lane t begins real work
-// at step t.  Before that it runs "virtual" columns, which leave its state unchanged: their str2
-// selector is a sentinel, so with every neighbour at its column-0 value the insert candidate
-// (the border itself) is the minimum and keeps the border:
-//   ladder keys: insert B + c(i), delete B + c(i) + 1, update B + c(i-1) + 255 (SED_SEL_SENT3:
-//   update constant 0xFF >= any jump d);
-//   distance keys (and the 16-bit packed ones): insert = delete = border, update border + 0.
-// The lane's first real column then sees exactly D[row][0], D[row-1][0] and the cell above.
-#define SED_SEL_SENT 0x0C0C0C0Cu
-#define SED_SEL_SENT3 0x0C0C0C0Du
-template <bool LEN, bool DOT = false> __device__ __forceinline__ uint32_t i32_sent() {
-    return LEN ? SED_SEL_SENT3 : DOT ? 0u : SED_SEL_SENT;  // dot keys: the zero column vector adds 0
-}
-// perm selector of str2 symbol b: byte3 <- 0xFF, byte2 <- cost byte b, bytes 1:0 <- the constant
-__device__ __forceinline__ uint32_t i32_sel(uint32_t b) { return 0x0D000100u | ((4u + b) << 16); }
-
-template <bool B> struct BoolTag { static constexpr bool value = B; };
-
-// CAP: the group that produces the sink cell (captured on its lane); every extra variant is
-// another merge point where the register allocator may insert copies of the whole state.
-// The stripe kernel's group: lane 0's top values from the chunk's LDS slots (ltop, broadcast reads),
-// each lane's str2 selectors from the wave's LDS selector ring at its own column (lsel: this group's
-// first step for this lane, doubled ring so the G reads never wrap).
-// PF (SED_CK_TVPF, the CK forward's unrolled chunk loop): the group's first {top, selector} pair arrives in tvpf, read
-// at the previous group's start, and this group reads the next group's first pair with its own, so its first step's
-// dots start without waiting on an LDS round trip (the last group of a chunk reads one entry past it, unused).
-template <int R, bool TB, bool LEN, bool CAP, bool CK = false, bool DOT = false, bool COLLECT = !CK, bool PF = false>
-__device__ __forceinline__ void i32_group(uint32_t (&V)[R], const uint32_t (&cv)[R], uint32_t &top_prev,
-                                          uint32_t &bottom, uint32_t &selv, const uint32_t *__restrict__ ltop,
-                                          const uint32_t *__restrict__ lsel, uint32_t &outc, uint32_t (&W)[4],
-                                          const int s0, const int lane, const int cap_step, const int cap_lane,
-                                          const int cap_row, uint32_t &cap, uint32_t (&rcv)[Grp<R>::G],
-                                          uint2 *tvpf = nullptr) {
-    constexpr int G = Grp<R>::G;
-    uint2 tv[G];
-    const uint32_t *lp = ltop + (s0 & 63);  // G divides 64: a group never wraps the chunk
-    if constexpr (PF) {
-        tv[0] = *tvpf;
-#pragma unroll
-        for (int u = 1; u < G; ++u) tv[u] = make_uint2(lp[u], lsel[u]);
-        *tvpf = make_uint2(lp[G], lsel[G]);
-    } else {
-#pragma unroll
-        for (int u = 0; u < G; ++u) tv[u] = make_uint2(lp[u], lsel[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-        const int s = s0 + u;
-        i32_step<R, TB, LEN, COLLECT, true, false, DOT>(V, cv, top_prev, bottom, selv, tv[u], outc, W, u);
-        if constexpr (CK) rcv[u] = V[R - 1];  // the band's bottom row, step s (row checkpoints)
-        if constexpr (CAP) {
-            const bool hit = (s == cap_step) && (lane == cap_lane);
-#pragma unroll
-            for (int r = 0; r < R; ++r) cap = (hit && r == cap_row) ? V[r] : cap;
-        }
-    }
-}
+#include <stdlib.h>
+#include "sed_ck_tile.h"
 
 // Minimum waves per SIMD the register allocator must leave room for, per R: the budget at which
 // the hot loop does not spill (R=16: 96 VGPRs / 5 waves; the 80-VGPR budget of 6 waves spills the
@@ -491,28 +66,11 @@ template <int R> struct I32Waves { static constexpr int value = R >= 32 ? 4 : (R
 #ifndef SED_CK_GUNROLL
 #define SED_CK_GUNROLL 2  // groups per iteration of the CK chunk loop
 #endif
-#ifndef SED_CK_TVPF
-#define SED_CK_TVPF 0  // CK forward: each group's first LDS pair read a group ahead (i32_group PF; A/B)
-#endif
 #ifdef SED_I32_WAVES_PER_EU
 #define SED_I32_WAVES(R) SED_I32_WAVES_PER_EU
 #else
 #define SED_I32_WAVES(R) I32Waves<R>::value
 #endif
-// Inter-workgroup hand-off of stripe bottom rows (SPLIT mode), per 16-step group and self-validating: every
-// bottom-row cell travels as one 64-bit word {tag, value}, stored with a relaxed agent-scope 64-bit atomic
-// (single-copy atomic, so a reader sees the tag and the value of one store together), tag = the run's epoch
-// (1..32767, prm.epoch) | poison << 31.  The consumer's feeder wave (split_feed) polls the words and re-polls any
-// whose tag is not this run's.  No counter, fence or s_waitcnt on the producer side:
-// with the per-chunk counter hand-off (stores, s_waitcnt, release fence, counter; the consumer prefetching a
-// chunk ahead) each stripe ran 3 chunks (192 steps) behind the one above.
-// The previous run's words carry another epoch; the host zeroes the buffer on a batch's first run and when the
-// epoch wraps.  A stripe that gave up waiting publishes with the poison bit, so its consumer stops waiting too,
-// and the last stripe reports err.
-#define SED_PROG_POISON 0x80000000u
-__device__ __forceinline__ void store_tagged(uint64_t *p, uint32_t tag, uint32_t v) {
-    __hip_atomic_store(p, ((uint64_t)tag << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // SPLIT: the ring of lane 0's top values (one per step) and the hand-off feeder.  Each stripe below the first runs
 // as two waves: the compute wave, which never waits on a global load (any such wait with its own stores in flight is
@@ -523,13 +81,6 @@ __device__ __forceinline__ void store_tagged(uint64_t *p, uint32_t tag, uint32_t
 // A poisoned word upstream, or no progress for ~2^22 polls, poisons flag[0] (bit 31) with every step ready, so the
 // compute wave never waits again and the last stripe reports err.
 #define SED_SPLIT_RING 256
-// the flags are relaxed workgroup-scope atomics: a volatile LDS access is followed by s_waitcnt vmcnt(0) lgkmcnt(0)
-__device__ __forceinline__ uint32_t lds_flag_get(uint32_t *f) {
-    return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_flag_set(uint32_t *f, uint32_t v) {
-    __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 template <int G>
 __device__ __forceinline__ void split_feed(const uint64_t *__restrict__ bin64, const int m, const int SG,
                                            const uint32_t epoch, uint32_t *ring, uint32_t *flag,
@@ -567,7 +118,7 @@ __device__ __forceinline__ void split_feed(const uint64_t *__restrict__ bin64, c
 // SPLIT = true : one 128-thread workgroup per stripe (the compute wave and its
 //                feeder, split_feed), all stripes of a pair run concurrently,
 //                each a few groups behind the stripe above it (single long
-//                pairs: config 2, the GUI; hand-off above).
+//                pairs: config 2, the GUI; hand-off: sed_dev.h).
 // CK (not SPLIT): instead of per-cell codes, tb receives checkpoints for the recompute traceback
 // (sed_traceback_ck_kernel; layout in sed_internal.h): per stripe, at every chunk end each lane's R row values
 // and its top_prev ("column checkpoints", [chunk][R+1][64 lanes]), and every step the bottom row of the lanes
@@ -576,12 +127,6 @@ __device__ __forceinline__ void split_feed(const uint64_t *__restrict__ bin64, c
 // (D, L), which is all the checkpoints need; the traceback recomputes the op tie-break.
 // The CK kernel (distance keys, no codes) would fit 80 VGPRs (6 waves per SIMD, spills per chunk only) but
 // ran slower: 12.45 against 12.11 ms at 5 waves (profiles/r02/ab_ck_waves.txt).
-// issue priority of SPLIT's stripe waves (SED_SPLIT_PRIO): a single pair's stripe chain is latency-bound, and the
-// previous run's traceback kernels may share its SIMDs.  Config 2 at 100 steps: 0.2974-0.3008 against 0.2984-0.3039
-// ms per step at 0, 3 interleaved rounds (profiles/r05/s17)
-#ifndef SED_SPLIT_PRIO
-#define SED_SPLIT_PRIO 2
-#endif
 // CUT (distance-only batches under a cutoff, sed_batch_set_cutoff; not TB, LEN, CK or SPLIT): wave w runs pair
 // list[w] of the cutoff's pair list (passed in `tasks`, npairs = its length) inside the pair's window band[pair]
 // (sed_cut_band_kernel: ub = min(cutoff, diagonal bound)), with the chunk ranges and border rules of the CK forward
@@ -722,7 +267,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
                 top_prev = (lane == 0 && idx <= top_hi) ? v : top_prev;
             }
         }
-        // column-0 state for every lane; virtual columns until the lane's first real one (see above)
+        // column-0 state for every lane; virtual columns until the lane's first real one (sed_i32_keys.h: ramp for free)
         uint32_t bottom = V[R - 1], selv = i32_sent<LEN, DOT>(), outc = 0;
         uint32_t W[4] = {0, 0, 0, 0};
 
@@ -806,13 +351,14 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
                 }
             };
             if constexpr (FASTC) {
-                uint2 tvpf = make_uint2(lch[0], lsel[0]);  // (SED_CK_TVPF: the first group's first pair)
+                // (lch is the first capture this lambda names: the closure's members follow the order of first use, and
+                // with another order every variant of the kernel, the rolled ones too, allocates its registers differently)
+                const uint32_t *ltop = lch;
 #pragma unroll SED_CK_GUNROLL
                 for (int g = 0; g < 64 / G; ++g) {
                     const int s0 = 64 * c + g * G;  // (s0 & 63 folds to g * G)
-                    i32_group<R, TB, LEN, false, CK, DOT, !CK, (bool)SED_CK_TVPF>(V, cv, top_prev, bottom, selv, lch,
-                                                     lsel + g * G, outc, W, s0, lane, cap_step, cap_lane, cap_row, cap,
-                                                     rcv, &tvpf);
+                    i32_group<R, TB, LEN, false, CK, DOT, !CK>(V, cv, top_prev, bottom, selv, ltop, lsel + g * G, outc, W, s0,
+                                                               lane, cap_step, cap_lane, cap_row, cap, rcv);
                     if (s0 < SG) stores(s0);
                 }
                 s = 64 * (c + 1);  // lane 63's bottom cells of the whole chunk are in outc (!CK)
@@ -902,14 +448,6 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
 // stripes and rows, and the wave runs max(m) columns, the shorter pair's extra columns being
 // don't-care.  Each pair's sink is captured at its own step.
 // ---------------------------------------------------------------------------
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b));
-}
-__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t,
-                              __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
 // 16-bit offset key of the sink back to D: D = W - 0xFFFF + n*delete + m*insert (mod 2^16)
 __device__ __forceinline__ uint32_t x2_decode(uint32_t half, int n, int m, const sed_i32_params &prm) {
     return (half + 1u + (uint32_t)n * prm.del + (uint32_t)m * prm.ins) & 0xFFFFu;
@@ -1369,593 +907,6 @@ sed_wf_i32_chain_kernel(const sed_pair_desc *__restrict__ pd, const int32_t *__r
 }
 
 // ---------------------------------------------------------------------------
-// fp64 kernel (general costs).  State per row: D (fp64), Lk = L << 2,
-// optional int-typing bit T (TYPED).  Cost table in LDS:
-//   tab[a*K + b] = {cost value, is-int flag}
-// ---------------------------------------------------------------------------
-// Path-length keys of the fp64 kernel in U-space: LK = SED_F64_LB - 4U (U = updates on the canonical path to the
-// cell, so L = i + j - U) with the op in the low 2 bits of a candidate.  At a cell every candidate's L is the cell's
-// i + j - U, so comparing B - 4U orders candidates exactly as L does, and the borders are all B: the insert
-// candidate is LK_left (op 0), the delete candidate LK_up + 1, the update candidate LK_diag - 4 + 2.  (L << 2 keys
-// took an add per candidate, +4, +5, +6: 21.25 against 20.25 VALU per cell on the R = 8 group loop's unmasked path.)
-#define SED_F64_LB 0x80000000u
-struct f64_cell_in {
-    double d;
-    uint32_t lk;
-    uint32_t t;
-};
-
-// PF: the caller has moved this step's column symbol (bsel) and read its table entries (epf) a step ahead (the
-// SPLIT kernel's lone waves, whose LDS reads would otherwise stall every step)
-template <int R, bool TB, bool TYPED, bool MASKED, bool FULL, int SW = 64, bool PF = false>
-__device__ __forceinline__ void f64_step(double (&D)[R], uint32_t (&LK)[R], uint32_t (&T)[R],
-                                         const uint32_t (&rowbase)[R], const double2 *__restrict__ tab,
-                                         double &dtop_prev, uint32_t &ltop_prev, uint32_t &ttop_prev,
-                                         double &dbot, uint32_t &lbot, uint32_t &tbot, uint32_t &bsel,
-                                         const double dtin, const uint32_t ltin, const uint32_t ttin,
-                                         const uint32_t stin, uint32_t (&W)[4], const int u,
-                                         const double cins, const double cdel, const uint32_t tins,
-                                         const uint32_t tdel, const bool active, const sed_full_out &fo,
-                                         const int i0, const int j, const double2 *epf = nullptr) {
-    // the segment's first lane takes this step's top-row cell and column symbol (dtin .. stin, broadcast LDS reads of
-    // the chunk), the others the lane above's bottom cell and previous symbol
-    const double dtop = seg_shr1_f64<SW>(dtin, dbot);
-    const uint32_t ltop = seg_shr1<SW>(ltin, lbot);
-    uint32_t ttop = 0;
-    if constexpr (TYPED) ttop = seg_shr1<SW>(ttin, tbot);
-    if constexpr (!PF) bsel = seg_shr1<SW>(stin, bsel);
-    double dup = dtop, ddiag = dtop_prev;
-    uint32_t lup = ltop, ldiag = ltop_prev, tup = ttop, tdiag = ttop_prev;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const double2 e = PF ? epf[r] : tab[rowbase[r] + bsel];  // x = cost, y = int flag (as double bits)
-        const double dl = D[r];
-        const double ca = dl + cins;
-        const double cb = dup + cdel;
-        const double cc = ddiag + e.x;
-        const double mn = fmin(ca, fmin(cb, cc));
-        const bool ea = (ca == mn), eb = (cb == mn), ec = (cc == mn);
-        const uint32_t ka = ea ? LK[r] : 0xFFFFFFFFu;  // (U-space keys: the insert candidate needs no add)
-        const uint32_t kb = eb ? lup + 1u : 0xFFFFFFFFu;
-        const uint32_t kc = ec ? ldiag - 2u : 0xFFFFFFFFu;
-        const uint32_t km = umin3_op(ka, kb, kc);
-        const uint32_t ln = km & ~3u;
-        uint32_t tn = 0;
-        if constexpr (TYPED) {
-            const uint32_t tc = (uint32_t)__double_as_longlong(e.y);
-            tn = ea ? (T[r] & tins) : (eb ? (tup & tdel) : (tdiag & tc));
-        }
-        if constexpr (TB) {
-            const int c = u * R + r;
-            W[c >> 4] = __builtin_amdgcn_alignbit(km, W[c >> 4], 2);
-        }
-        if constexpr (FULL) {  // full-matrix materialisation (dp proxy, GUI path): value, edge mask, typing
-            if (active && i0 + r <= fo.n) {
-                const uint64_t o = (uint64_t)(i0 + r) * (uint64_t)(fo.m + 1) + (uint64_t)j;
-                const uint32_t t = TYPED ? tn : (uint32_t)(mn == 0.0);
-                fo.D[o] = mn;
-                fo.M[o] = (uint8_t)((ea ? 1u : 0u) | (eb ? 2u : 0u) | (ec ? 4u : 0u) | (t << 3));
-            }
-        }
-        ddiag = dl;
-        ldiag = LK[r];
-        if constexpr (TYPED) tdiag = T[r];
-        dup = mn;
-        lup = ln;
-        if constexpr (TYPED) tup = tn;
-        if constexpr (MASKED) {
-            D[r] = active ? mn : dl;
-            LK[r] = active ? ln : LK[r];
-            if constexpr (TYPED) T[r] = active ? tn : T[r];
-        } else {
-            D[r] = mn;
-            LK[r] = ln;
-            if constexpr (TYPED) T[r] = tn;
-        }
-    }
-    if constexpr (MASKED) {
-        dtop_prev = active ? dtop : dtop_prev;
-        ltop_prev = active ? ltop : ltop_prev;
-        if constexpr (TYPED) ttop_prev = active ? ttop : ttop_prev;
-    } else {
-        dtop_prev = dtop;
-        ltop_prev = ltop;
-        if constexpr (TYPED) ttop_prev = ttop;
-    }
-    dbot = D[R - 1];
-    lbot = LK[R - 1];
-    if constexpr (TYPED) tbot = T[R - 1];
-}
-
-// Per wave: the current chunk's top row (cell values, L keys, typing) and str2 symbols, which the segment's first lane
-// reads one per step, and the segment's last lane's bottom cells of the chunk, which it writes one per step (the
-// next stripe's top row, stored to global memory at the chunk's end).  These replace DPP rotations of the chunk
-// values and a DPP collection of the bottom cells: 8-11 VALU per step.
-struct f64_chunk_lds {
-    double d[64], od[64];
-    uint32_t l[64], t[64], s[64], ol[64], ot[64];
-};
-
-// SW = 64: one wave per pair (pairs with d.seg set are skipped: they run in segments).  SW = 16 (short pairs of
-// large batches): each DPP row of 16 lanes runs its own pair (items idx[0 .. nidx), four per wave, the
-// host sorts them so a wave's four pairs have similar shapes): stripes of 16 R rows, 16-step chunks, a 15-step ramp
-// instead of 63, and every lane move a row DPP (seg_*), so the four segments never exchange data.  The loop bounds
-// are then per lane (uniform within a segment), and a segment whose pair is done sits out with its lanes masked.
-// issue priority of the fp64 DP's waves (SED_F64_PRIO): pipelined fp64 script batches run the traceback of run k
-// beside the DP of run k+1, which now issues first.  iupac 4.83-4.85 against 4.87-4.89 ms per step at 0, timing within
-// noise, 3 interleaved rounds (profiles/r05/s17)
-#ifndef SED_F64_PRIO
-#define SED_F64_PRIO 1
-#endif
-template <int R, bool TB, bool TYPED, bool FULL, int SW = 64>
-__global__ __launch_bounds__(256) void sed_wf_f64_kernel(const sed_pair_desc *__restrict__ pd, int npairs,
-                                                         const uint8_t *__restrict__ seqa,
-                                                         const uint8_t *__restrict__ seqb,
-                                                         uint32_t *__restrict__ tb, uint32_t *__restrict__ bnd,
-                                                         sed_result *__restrict__ res,
-                                                         const double *__restrict__ gtab, sed_f64_params prm,
-                                                         sed_full_out fo, const int32_t *__restrict__ idx) {
-    if constexpr (SED_F64_PRIO > 0) __builtin_amdgcn_s_setprio(SED_F64_PRIO);
-    static_assert(SW == 64 || (SW == 16 && !FULL), "segments of 16 lanes: no full-matrix output");
-    constexpr int ROWS = SW * R;
-    constexpr int G = Grp<R>::G;
-    static_assert(SW % G == 0, "a group of G steps never crosses a chunk");
-    __shared__ double2 tab[SED_MAX_K * SED_MAX_K];
-    __shared__ f64_chunk_lds chx[4];
-    const int K = prm.K;
-    for (int e = threadIdx.x; e < K * K; e += blockDim.x)
-        tab[e] = make_double2(gtab[2 * e], gtab[2 * e + 1]);
-    __syncthreads();
-
-    const int lane = SW == 64 ? (threadIdx.x & 63) : (threadIdx.x & (SW - 1));  // lane within the segment
-    int pair;
-    if constexpr (SW == 64) {
-        pair = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-        if (pair >= npairs) return;
-    } else {
-        const int item = (blockIdx.x * 256 + threadIdx.x) / SW;
-        if (item >= npairs) return;  // (npairs = the item count)
-        pair = idx[item];
-    }
-    const sed_pair_desc d = pd[pair];
-    if (d.lane || (SW == 64 && d.pad[1])) return;  // short str2, distance only: sed_lane.hip; segments: the SW = 16 launch
-    const int n = d.n, m = d.m;
-    if constexpr (FULL) {  // border cells: row 0 (insert edges) and column 0 (delete edges)
-        for (int j = lane; j <= m; j += 64) {
-            const double v = (double)j * prm.ins;
-            const uint32_t t = (j == 0) ? 1u : (TYPED ? (uint32_t)prm.ins_int : (uint32_t)(v == 0.0));
-            fo.D[j] = v;
-            fo.M[j] = (uint8_t)((j == 0 ? 0u : 1u) | (t << 3));
-        }
-        for (int i = 1 + lane; i <= n; i += 64) {
-            const double v = (double)i * prm.del;
-            const uint32_t t = TYPED ? (uint32_t)prm.del_int : (uint32_t)(v == 0.0);
-            fo.D[(uint64_t)i * (m + 1)] = v;
-            fo.M[(uint64_t)i * (m + 1)] = (uint8_t)(2u | (t << 3));
-        }
-    }
-    if (n == 0 || m == 0) {
-        if (lane == 0) {
-            res[pair].dist = (n == 0) ? (double)m * prm.ins : (double)n * prm.del;
-            res[pair].len = n + m;
-            res[pair].is_int = (n == 0 && m == 0) ? 1 : (n == 0 ? prm.ins_int : prm.del_int);
-            res[pair].err = 0;
-        }
-        return;
-    }
-    const int nstripes = (n + ROWS - 1) / ROWS;
-    const int SG = (m + SW - 1 + G - 1) / G * G;
-    const int nchunks = (SG + SW - 1) / SW;
-    // bottom-row buffer of a pair: [D as u64 | L as u32 | T as u32] planes; column j at index j + SW
-    const uint64_t bwords = (uint64_t)(nchunks + 2) * SW;
-    uint64_t *bndD = reinterpret_cast<uint64_t *>(bnd + d.bnd_off);
-    uint32_t *bndL = bnd + d.bnd_off + 2 * bwords;
-    uint32_t *bndT = bndL + bwords;
-    const uint8_t *pa = seqa + d.a_off;
-    const uint8_t *pb = seqb + d.b_off;
-    const uint32_t tins = (uint32_t)prm.ins_int, tdel = (uint32_t)prm.del_int;
-
-    for (int k = 0; k < nstripes; ++k) {
-        const int row0 = k * ROWS + lane * R;
-        double D[R];
-        uint32_t LK[R], T[R], rowbase[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int ri = row0 + r;
-            const uint32_t a = (ri < n) ? pa[ri] : 0u;
-            rowbase[r] = a * (uint32_t)K;
-            D[r] = (double)(ri + 1) * prm.del;
-            LK[r] = SED_F64_LB;
-            T[r] = tdel;
-        }
-        double dtop_prev = (double)row0 * prm.del;
-        uint32_t ltop_prev = SED_F64_LB;
-        uint32_t ttop_prev = (row0 == 0) ? 1u : tdel;
-        double dbot = 0.0;
-        uint32_t lbot = 0, tbot = 0, bsel = 0;
-        uint32_t W[4] = {0, 0, 0, 0};
-
-        auto load_d = [&](int c) -> double {
-            const int j = SW * c + lane + 1;
-            if (k == 0) return (double)j * prm.ins;
-            return __longlong_as_double((long long)load_sc1_u64(bndD + j + SW));
-        };
-        auto load_l = [&](int c) -> uint32_t {
-            const int j = SW * c + lane + 1;
-            if (k == 0) return SED_F64_LB;
-            return load_sc1(bndL + j + SW);
-        };
-        auto load_t = [&](int c) -> uint32_t {
-            if (k == 0) return tins;
-            return load_sc1(bndT + SW * c + lane + SW + 1);
-        };
-        auto load_sel = [&](int c) -> uint32_t {
-            const int ci = SW * c + lane;
-            return (ci < m) ? (uint32_t)pb[ci] : 0u;
-        };
-        double dch = load_d(0);
-        uint32_t lch = load_l(0), tch = TYPED ? load_t(0) : 0u, sch = load_sel(0);
-        f64_chunk_lds &cx = chx[threadIdx.x >> 6];
-        const int sb = (threadIdx.x & 63) - lane;  // the segment's first slot
-        const bool lastlane = lane == SW - 1;
-        uint32_t *tbk = tb + d.tb_off + (uint64_t)k * (uint64_t)(SG / G) * (SW * 4u);
-        const bool last = (k == nstripes - 1);
-        int s = 0;
-        for (int c = 0; c < nchunks; ++c) {
-            double dnx = 0.0;
-            uint32_t lnx = 0, tnx = 0, snx = 0;
-            if (c + 1 < nchunks) {
-                dnx = load_d(c + 1);
-                lnx = load_l(c + 1);
-                if (TYPED) tnx = load_t(c + 1);
-                snx = load_sel(c + 1);
-            }
-            // this chunk's top row and symbols (after the previous chunk's last reads: a wave's LDS accesses run in
-            // order)
-            cx.d[sb + lane] = dch;
-            cx.l[sb + lane] = lch;
-            if (TYPED) cx.t[sb + lane] = tch;
-            cx.s[sb + lane] = sch;
-            // (A separate loop for chunks of unmasked steps, as in the integer kernels, measured slower: iupac DP
-            // 4.89 against 4.81 ms, timing 4.60 against 4.47 ms; profiles/r03/f64_plain_dropped.)
-            for (int g = 0; g < SW / G && s < SG; ++g, s += G) {
-                const bool full = (s >= SW - 1) && (s + G - 1 < m);
-                const int cu0 = sb + g * G;
-#pragma unroll
-                for (int u = 0; u < G; ++u) {
-                    const int j = s + u - lane + 1;
-                    const bool active = (j >= 1) && (j <= m);
-                    const double dtin = cx.d[cu0 + u];
-                    const uint32_t ltin = cx.l[cu0 + u], ttin = TYPED ? cx.t[cu0 + u] : 0u, stin = cx.s[cu0 + u];
-                    if (full)
-                        f64_step<R, TB, TYPED, false, FULL, SW>(D, LK, T, rowbase, tab, dtop_prev, ltop_prev, ttop_prev,
-                                                                dbot, lbot, tbot, bsel, dtin, ltin, ttin, stin, W, u,
-                                                                prm.ins, prm.del, tins, tdel, active, fo, row0 + 1, j);
-                    else
-                        f64_step<R, TB, TYPED, true, FULL, SW>(D, LK, T, rowbase, tab, dtop_prev, ltop_prev, ttop_prev,
-                                                               dbot, lbot, tbot, bsel, dtin, ltin, ttin, stin, W, u,
-                                                               prm.ins, prm.del, tins, tdel, active, fo, row0 + 1, j);
-                    if (!last && lastlane) {  // the next stripe's top row
-                        cx.od[cu0 + u] = dbot;
-                        cx.ol[cu0 + u] = lbot;
-                        if (TYPED) cx.ot[cu0 + u] = tbot;
-                    }
-                }
-                if constexpr (TB) store_tb(tbk + ((uint64_t)(s / G) * SW + lane) * 4u, W);
-            }
-            // slot i holds the segment's last lane's bottom cell of the chunk's step SW c + i, i.e. column
-            // SW (c - 1) + 2 + i at index SW c + 2 + i (a short last chunk: only its steps' slots)
-            if (!last && lane < s - SW * c) {
-                bndD[SW * c + 2 + lane] = (uint64_t)__double_as_longlong(cx.od[sb + lane]);
-                bndL[SW * c + 2 + lane] = cx.ol[sb + lane];
-                if (TYPED) bndT[SW * c + 2 + lane] = cx.ot[sb + lane];
-            }
-            dch = dnx;
-            lch = lnx;
-            tch = tnx;
-            sch = snx;
-        }
-        if (!last) __builtin_amdgcn_s_waitcnt(0);
-        else {
-            const int w = (n - 1) % ROWS;
-            if (lane == w / R) {
-                const int rf = w % R;
-                double dv = 0.0;
-                uint32_t lv = 0, tv = 0;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    dv = (r == rf) ? D[r] : dv;
-                    lv = (r == rf) ? LK[r] : lv;
-                    tv = (r == rf) ? T[r] : tv;
-                }
-                res[pair].dist = dv;
-                res[pair].len = n + m - (int32_t)((SED_F64_LB - lv) >> 2);
-                res[pair].is_int = TYPED ? (uint8_t)tv : (uint8_t)(dv == 0.0);
-                res[pair].err = 0;
-            }
-        }
-    }
-}
-
-// SPLIT fp64 (few long pairs: timing.py's one-call loop, GUI calls over IUPAC symbols).  A lone fp64 wave issues
-// ~20 dependent VALU per cell on one SIMD (a 2000^2 pair took 3.5 ms), so, as in the integer SPLIT kernel, each
-// stripe of 64 R rows (R = 2 by default, 4 on request) is a 128-thread workgroup of its own: all stripes of a pair
-// run at once, each ~63 steps (its lanes' systolic depth) plus a 16-step block and the hand-off's latency behind the
-// stripe above.  The hand-off is the integer kernel's tagged words: lane 63's bottom cell of column j
-// travels as three relaxed agent-scope 64-bit stores {tag, D low}, {tag, D high}, {tag, L key | T} (the L key is a
-// multiple of 4, so its bit 0 carries the typing bit), each single-copy atomic and validated on its own, tag = the
-// run's epoch | poison << 31.  The feeder wave (f64_split_feed) polls the stripe above's words, writes the steps'
-// top-row cells and str2 symbols into an LDS ring and publishes how many steps are ready; stripe 0's feeder writes
-// the row-0 border.  The compute wave is sed_wf_f64_kernel's stripe loop (SW = 64) reading the ring, with each step's
-// column symbol and table entries read a step ahead (f64_step PF).  Codes, their layout and the result are the
-// one-wave kernel's, so the tracebacks read them unchanged.
-#define SED_F64_RING 256
-template <int G> struct f64_split_lds {
-    double d[SED_F64_RING];
-    uint32_t l[SED_F64_RING], t[SED_F64_RING], s[SED_F64_RING];
-    double od[G][64];  // every lane's bottom cell of the group's steps (lane 63's are handed off)
-    uint32_t ol[G][64], ot[G][64];
-};
-// the three hand-off planes of stripe k: words [plane][column + 64], (nchunks + 2) * 64 per plane
-__device__ __forceinline__ uint64_t *f64_split_words(uint32_t *bnd, const sed_pair_desc &d, int k, uint32_t plane_words) {
-    return reinterpret_cast<uint64_t *>(bnd + d.bnd_off) + (uint64_t)k * 3u * plane_words;
-}
-template <int G>
-__device__ void f64_split_feed(const uint64_t *__restrict__ hin, const uint32_t plane_words, const bool top, const int m,
-                               const int SG, const uint32_t epoch, const uint8_t *__restrict__ pb, const double ins,
-                               const uint32_t tins, f64_split_lds<G> &rg, uint32_t *flag, const int lane) {
-    uint32_t poison = 0, idle = 0;
-    int have = 0;  // steps whose top-row cells are in the ring
-    while (have < SG) {
-        if (have + 64 > (int)lds_flag_get(flag + 1) + SED_F64_RING) {  // ring full: the compute wave is behind
-            __builtin_amdgcn_s_sleep(2);
-            continue;
-        }
-        const int t = have + lane, col = t + 1;
-        const bool need = !top && t < SG && col <= m;  // columns past m are never stored nor waited for
-        uint64_t w0 = 0, w1 = 0, w2 = 0;
-        if (need) {
-            w0 = load_sc1_u64(hin + (uint32_t)(col + 64));
-            w1 = load_sc1_u64(hin + plane_words + (uint32_t)(col + 64));
-            w2 = load_sc1_u64(hin + 2u * plane_words + (uint32_t)(col + 64));
-        }
-        const uint32_t g0 = (uint32_t)(w0 >> 32), g1 = (uint32_t)(w1 >> 32), g2 = (uint32_t)(w2 >> 32);
-        const bool good = !need || (((g0 & ~SED_PROG_POISON) == epoch) && ((g1 & ~SED_PROG_POISON) == epoch) &&
-                                    ((g2 & ~SED_PROG_POISON) == epoch));
-        const uint64_t bad = __ballot(!good);
-        const int nv = min(bad ? (int)__builtin_ctzll(bad) : 64, SG - have);  // the valid prefix
-        if (__any(lane < nv && need && ((g0 | g1 | g2) & SED_PROG_POISON))) poison = SED_PROG_POISON;
-        if (nv > 0) {
-            if (lane < nv) {
-                const int slot = t & (SED_F64_RING - 1);
-                if (top) {  // row 0: D = j * insert, L key B, typing of insert
-                    rg.d[slot] = (double)col * ins;
-                    rg.l[slot] = SED_F64_LB;
-                    rg.t[slot] = tins;
-                } else {
-                    rg.d[slot] = __longlong_as_double((long long)(((w1 & 0xFFFFFFFFull) << 32) | (w0 & 0xFFFFFFFFull)));
-                    rg.l[slot] = (uint32_t)w2 & ~3u;
-                    rg.t[slot] = (uint32_t)w2 & 1u;
-                }
-                rg.s[slot] = t < m ? (uint32_t)pb[t] : 0u;
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the values before the count
-            have += nv;
-            idle = 0;
-        } else if (++idle > (1u << 22)) {  // the stripe above stopped: give up, let the compute wave drain
-            poison = SED_PROG_POISON;
-            have = SG;
-        } else {
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (lane == 0 && (nv > 0 || poison)) lds_flag_set(flag, (uint32_t)have | poison);
-    }
-}
-
-template <int R, bool TB, bool TYPED, bool FULL>
-__global__ __launch_bounds__(128) void sed_wf_f64_split_kernel(const sed_pair_desc *__restrict__ pd,
-                                                               const int2 *__restrict__ tasks,
-                                                               const uint8_t *__restrict__ seqa,
-                                                               const uint8_t *__restrict__ seqb,
-                                                               uint32_t *__restrict__ tb, uint32_t *__restrict__ bnd,
-                                                               sed_result *__restrict__ res,
-                                                               const double *__restrict__ gtab, sed_f64_params prm,
-                                                               sed_full_out fo) {
-    if constexpr (SED_SPLIT_PRIO > 0) __builtin_amdgcn_s_setprio(SED_SPLIT_PRIO);
-    static_assert(!(FULL && TB), "full-matrix output: distance kernel");
-    constexpr int ROWS = 64 * R;
-    constexpr int G = Grp<R>::G;
-    __shared__ double2 tab[SED_MAX_K * SED_MAX_K];
-    __shared__ f64_split_lds<Grp<R>::G> rg;
-    __shared__ uint32_t split_flag[2];
-    const int K = prm.K;
-    for (int e = threadIdx.x; e < K * K; e += blockDim.x) tab[e] = make_double2(gtab[2 * e], gtab[2 * e + 1]);
-    if (threadIdx.x < 2) split_flag[threadIdx.x] = 0u;
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int2 task = tasks[blockIdx.x];
-    const int pair = __builtin_amdgcn_readfirstlane(task.x), k = __builtin_amdgcn_readfirstlane(task.y);
-    const sed_pair_desc d = pd[pair];
-    const int n = d.n, m = d.m;
-    if constexpr (FULL) {  // border cells (stripe 0's compute wave): row 0 (insert edges) and column 0 (delete edges)
-        if (k == 0 && threadIdx.x < 64) {
-            for (int j = lane; j <= m; j += 64) {
-                const double v = (double)j * prm.ins;
-                const uint32_t t = (j == 0) ? 1u : (TYPED ? (uint32_t)prm.ins_int : (uint32_t)(v == 0.0));
-                fo.D[j] = v;
-                fo.M[j] = (uint8_t)((j == 0 ? 0u : 1u) | (t << 3));
-            }
-            for (int i = 1 + lane; i <= n; i += 64) {
-                const double v = (double)i * prm.del;
-                const uint32_t t = TYPED ? (uint32_t)prm.del_int : (uint32_t)(v == 0.0);
-                fo.D[(uint64_t)i * (m + 1)] = v;
-                fo.M[(uint64_t)i * (m + 1)] = (uint8_t)(2u | (t << 3));
-            }
-        }
-    }
-    if (n == 0 || m == 0) {
-        if (threadIdx.x == 0) {
-            res[pair].dist = (n == 0) ? (double)m * prm.ins : (double)n * prm.del;
-            res[pair].len = n + m;
-            res[pair].is_int = (n == 0 && m == 0) ? 1 : (n == 0 ? prm.ins_int : prm.del_int);
-            res[pair].err = 0;
-        }
-        return;
-    }
-    const int nstripes = (n + ROWS - 1) / ROWS;
-    const int SG = (m + 63 + G - 1) / G * G;
-    const int nchunks = (SG + 63) >> 6;
-    const uint32_t plane_words = (uint32_t)(nchunks + 2) * 64u;
-    const uint8_t *pa = seqa + d.a_off;
-    const uint8_t *pb = seqb + d.b_off;
-    const uint32_t tins = (uint32_t)prm.ins_int, tdel = (uint32_t)prm.del_int;
-    if (threadIdx.x >= 64) {  // the feeder wave
-        f64_split_feed<G>(k > 0 ? f64_split_words(bnd, d, k - 1, plane_words) : nullptr, plane_words, k == 0, m, SG,
-                       prm.epoch, pb, prm.ins, tins, rg, split_flag, lane);
-        return;
-    }
-    uint64_t *hout = f64_split_words(bnd, d, k, plane_words);
-    const int row0 = k * ROWS + lane * R;
-    double D[R];
-    uint32_t LK[R], T[R], rowbase[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int ri = row0 + r;
-        const uint32_t a = (ri < n) ? pa[ri] : 0u;
-        rowbase[r] = a * (uint32_t)K;
-        D[r] = (double)(ri + 1) * prm.del;
-        LK[r] = SED_F64_LB;
-        T[r] = tdel;
-    }
-    double dtop_prev = (double)row0 * prm.del;
-    uint32_t ltop_prev = SED_F64_LB;
-    uint32_t ttop_prev = (row0 == 0) ? 1u : tdel;
-    double dbot = 0.0;
-    uint32_t lbot = 0, tbot = 0, bsel = 0;
-    uint32_t W[4] = {0, 0, 0, 0};
-    uint32_t *tbk = TB ? tb + d.tb_off + (uint64_t)k * (uint64_t)(SG / G) * 256u : nullptr;
-    const bool last = (k == nstripes - 1);
-    const uint32_t tag = prm.epoch;
-    bool ok = true;
-    int ready = 0;  // steps the feeder has published as ready (last read)
-    constexpr int HB = G < 16 ? G : 16;  // steps per block of ring reads, waits and hand-offs
-    // until the ring holds the top-row cells of steps < upto (LDS only)
-    auto wait_ready = [&](int upto) {
-        upto = min(upto, SG);  // (the feeder publishes SG steps in all)
-        if (ready < upto) {
-            uint32_t f = lds_flag_get(split_flag), spins = 0;
-            while (ok && (int)(f & ~SED_PROG_POISON) < upto) {
-                if (++spins > (1u << 24)) ok = false;
-                __builtin_amdgcn_s_sleep(1);
-                f = lds_flag_get(split_flag);
-            }
-            if (f & SED_PROG_POISON) ok = false;
-            ready = (int)(f & ~SED_PROG_POISON);
-            asm volatile("" ::: "memory");
-        }
-    };
-    // lane u < HB hands off column s0 + u - 62 (lane 63's cell of step s0 + u, staged at rg.od[u0 + u]), then the
-    // block's ring slots are free again
-    auto handoff = [&](const int s0, const int u0) {
-        if (!last && lane < HB) {
-            const int col = s0 + lane - 62;
-            if (col >= 1 && col <= m) {
-                const uint32_t tg = tag | (ok ? 0u : SED_PROG_POISON);
-                const uint64_t bits = (uint64_t)__double_as_longlong(rg.od[u0 + lane][63]);
-                const uint32_t lt = rg.ol[u0 + lane][63] | (TYPED ? rg.ot[u0 + lane][63] : 0u);
-                store_tagged(hout + (uint32_t)(col + 64), tg, (uint32_t)bits);
-                store_tagged(hout + plane_words + (uint32_t)(col + 64), tg, (uint32_t)(bits >> 32));
-                store_tagged(hout + 2u * plane_words + (uint32_t)(col + 64), tg, lt);
-            }
-        }
-        asm volatile("" ::: "memory");
-        if (lane == 0) lds_flag_set(split_flag + 1, (uint32_t)(s0 + HB));
-    };
-    for (int s = 0; s < SG; s += G) {
-        // a block needs its own steps and the next block's first symbol (the table reads a step ahead)
-        wait_ready(s + (HB < G ? HB + 1 : HB));
-        // the group's steps as one straight-line block per variant (a lone wave is latency-bound: a branch per step
-        // kept the compiler from overlapping one step's table reads with the previous step's arithmetic)
-        // The group's top-row cells and symbols are read from the ring at its start, and each step's column symbol
-        // and table entries are fetched one step ahead (PF).
-        // (ring entries in blocks of 16 steps: the R = 2 group's 32 would take ~160 VGPRs at once; each block waits
-        // for its own steps and hands its bottom cells off, so the stripe below trails by 16 steps, not 32)
-        auto group = [&](auto masked_tag) {
-            constexpr bool MASKED = decltype(masked_tag)::value;
-            double2 en[R];
-            uint32_t bn = dpp_shr1(rg.s[s & (SED_F64_RING - 1)], bsel);
-#pragma unroll
-            for (int r = 0; r < R; ++r) en[r] = tab[rowbase[r] + bn];
-#pragma unroll
-            for (int h = 0; h < G; h += HB) {
-                if (h > 0) wait_ready(s + h + (h + HB < G ? HB + 1 : HB));
-                double dg[HB];
-                uint32_t lg[HB], tg[HB], sg[HB + 1];
-#pragma unroll
-                for (int v = 0; v <= HB; ++v) {
-                    const int slot = (s + h + v) & (SED_F64_RING - 1);
-                    if (v < HB) {
-                        dg[v] = rg.d[slot];
-                        lg[v] = rg.l[slot];
-                        tg[v] = TYPED ? rg.t[slot] : 0u;
-                    }
-                    if (v > 0) sg[v] = rg.s[slot];  // (sg[0]: in bn already)
-                }
-#pragma unroll
-                for (int v = 0; v < HB; ++v) {
-                    const int u = h + v;
-                    const int j = s + u - lane + 1;
-                    const bool active = (j >= 1) && (j <= m);
-                    double2 e[R];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) e[r] = en[r];
-                    bsel = bn;
-                    if (u + 1 < G) {
-                        bn = dpp_shr1(sg[v + 1], bsel);
-#pragma unroll
-                        for (int r = 0; r < R; ++r) en[r] = tab[rowbase[r] + bn];
-                    }
-                    f64_step<R, TB, TYPED, MASKED, FULL, 64, true>(D, LK, T, rowbase, tab, dtop_prev, ltop_prev,
-                                                                   ttop_prev, dbot, lbot, tbot, bsel, dg[v], lg[v],
-                                                                   tg[v], 0u, W, u, prm.ins, prm.del, tins, tdel,
-                                                                   active, fo, row0 + 1, j, e);
-                    // every lane's bottom cell, lane 63's read back below: a write under lane == 63 put a branch
-                    // (exec skip) between every two steps
-                    rg.od[u][lane] = dbot;
-                    rg.ol[u][lane] = lbot;
-                    if (TYPED) rg.ot[u][lane] = tbot;
-                    __builtin_amdgcn_sched_barrier(0);  // (the next step's table reads stay a step ahead of their use)
-                }
-                handoff(s + h, h);
-            }
-        };
-        if ((s >= 63) && (s + G - 1 < m))
-            group(BoolTag<false>{});
-        else
-            group(BoolTag<true>{});
-        if constexpr (TB) store_tb(tbk + ((uint64_t)(s / G) * 64u + lane) * 4u, W);
-    }
-    if (last) {
-        const int w = (n - 1) % ROWS;
-        if (lane == w / R) {
-            const int rf = w % R;
-            double dv = 0.0;
-            uint32_t lv = 0, tv = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                dv = (r == rf) ? D[r] : dv;
-                lv = (r == rf) ? LK[r] : lv;
-                tv = (r == rf) ? T[r] : tv;
-            }
-            res[pair].dist = dv;
-            res[pair].len = n + m - (int32_t)((SED_F64_LB - lv) >> 2);
-            res[pair].is_int = TYPED ? (uint8_t)tv : (uint8_t)(dv == 0.0);
-            res[pair].err = ok ? 0 : SED_ERR_SPLIT_TIMEOUT;  // a timed-out wait anywhere up the chain poisons the pair
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // Traceback: one lane per pair walks the 2-bit choices from (n, m) to (0, 0)
 // and writes the op codes origin->sink, 16 per word.  Position bookkeeping is
 // incremental (stripe k, lane t, row r, step s) with power-of-two R, and the
@@ -2173,13 +1124,15 @@ __global__ __launch_bounds__(64) void sed_traceback_window_kernel(const sed_pair
 // ---------------------------------------------------------------------------
 // Stripe-parallel traceback for few pairs (per-cell codes; config 2, the GUI: one 4096^2 pair, SPLIT at
 // R = 4, 16 stripes).  The window walk above is one dependent chain of ~4200 steps.  Instead:
-//   map kernel: one lane per (stripe k in 1 .. K-2, column x): walk the codes from cell (last row of stripe
-//     k, x) until the path steps into stripe k-1; record that column and the ops taken.  One more lane walks
-//     the sink's stripe from the sink.  A path through a cell continues the same way whatever led to it (each
-//     code is the cell's canonical op), so these maps compose;
-//   emit kernel: one wave per (pair, stripe): compose the maps from the sink down to its stripe (its entry
-//     column and the script positions of its segment), then walk that segment with the window walk, storing
-//     script words with atomicOr (the two words a segment shares with its neighbours; the buffer is zeroed).
+//   band map kernel: one lane per (64-row band g, column x): walk the codes from cell (last row of band g, x)
+//     until the path steps into band g-1; record that column and the ops taken.  A path through a cell continues
+//     the same way whatever led to it (each code is the cell's canonical op), so these maps compose;
+//   compose kernel: one thread per (stripe k in 1 .. K-2, column x) chains the stripe's R bands into a stripe
+//     map entry, and one more thread the sink's stripe from the sink;
+//   band emit kernel: one wave per (pair, band): compose the stripe maps from the sink down to its stripe and
+//     that stripe's band maps down to its band (its entry column and the script positions of its segment), then
+//     walk that segment with the window walk, storing script words with atomicOr (the two words a segment shares
+//     with its neighbours; the buffer is zeroed).
 // ---------------------------------------------------------------------------
 template <int R> struct CodeCursor {  // per-lane reader of one pair's per-cell codes, one 16-byte block cached
     static constexpr int G = Grp<R>::G, LR = R == 2 ? 1 : R == 4 ? 2 : R == 8 ? 3 : R == 16 ? 4 : 5, LG = 6 - LR;
@@ -2204,16 +1157,21 @@ template <int R> struct CodeCursor {  // per-lane reader of one pair's per-cell 
     }
 };
 
-// map[pd.map_off + 2 * (k * (m + 1) + x)] = {exit column, ops} for stripes 1 .. K-2; the sink's stripe at x = 0.
-// A workgroup takes 256 consecutive columns x0 .. x0+255 of one stripe.  Paths near the diagonal stay in the
-// stripe's 64R rows and within SED_TBMAP_LEFT (R = 2: SED_TBMAP_LEFT_R2) columns left of x0: the code groups of those steps are one
-// contiguous run of 1 KiB groups (layout [group][64 lanes][16 B]), copied to LDS once, so a step reads LDS
-// instead of waiting on a global load (a wave's lanes need new blocks at different steps: with global loads
-// nearly every step waited on one).  A path that leaves the staged steps (cells far from the diagonal insert
-// first, since ties prefer insert, and can run along the row for thousands of columns) stops: its entry is
-// marked unknown (exit 0xFFFFFFFF) and the emit kernel walks that stripe itself if the real path needs it.
-// The last workgroup of a pair walks the sink's stripe from the sink.  Every workgroup also zeroes its share
-// of the pair's script words, which the emit kernel's segments OR into (lane-kernel pairs wrote theirs already).
+// The map of a pair, at pd.map_off, in {exit column, ops} entries of two words: the stripe map, entry k * (m + 1) + x
+// for stripes 1 .. K-2 and the sink's stripe at x = 0 (K (m + 1) entries), then the band maps, entry
+// (g - 1) * (m + 1) + x for bands 1 .. nbt-1 (band g: rows 64g + 1 .. 64g + 64; stripe 0's upper bands too, for the
+// band emit): the exit column at row 64g, walked from the band's last row, or from row n in the last band.
+// A band map workgroup takes 256 consecutive columns x0 .. x0+255 of one band.  Paths near the diagonal stay within
+// SED_TBMAP_LEFT (R = 2: SED_TBMAP_LEFT_R2) columns left of x0: the band's 64/R forward lanes of the code groups of
+// those steps (layout [group][64 lanes][16 B]) are copied to LDS once, so a step reads LDS instead of waiting on a
+// global load (a wave's lanes need new blocks at different steps: with global loads nearly every step waited on
+// one).  A path that leaves the staged steps (cells far from the diagonal insert first, since ties prefer insert,
+// and can run along the row for thousands of columns) stops: its entry is marked unknown (exit 0xFFFFFFFF) and the
+// emit kernel walks that band itself if the real path needs it.  Every workgroup also zeroes its share of the
+// pair's script words, which the emit kernel's segments OR into (lane-kernel pairs wrote theirs already).
+// One lane per band, not per stripe: a whole stripe is a chain of up to ~700 dependent LDS steps at about one wave
+// per SIMD (config 2: 104 us); the bands are R times the lanes at 1/R the chain and 1/R the LDS per workgroup, so
+// many workgroups share a CU.
 #ifndef SED_TBMAP_LEFT
 #define SED_TBMAP_LEFT 512
 #endif
@@ -2226,9 +1184,6 @@ template <int R> struct CodeCursor {  // per-lane reader of one pair's per-cell 
 #ifndef SED_TBMAP_LEFT_R2
 #define SED_TBMAP_LEFT_R2 128
 #endif
-#ifndef SED_TBMAP_BANDS  // 1: band maps + compose (sed_tb_bandmap_kernel), 0: one lane per stripe (A/B)
-#define SED_TBMAP_BANDS 1
-#endif
 #ifndef SED_TBMAP_RUN
 #define SED_TBMAP_RUN 96
 #endif
@@ -2240,107 +1195,6 @@ template <int R> struct CodeCursor {  // per-lane reader of one pair's per-cell 
 #ifndef SED_TBMAP_CAP
 #define SED_TBMAP_CAP 64
 #endif
-template <int R>
-__global__ __launch_bounds__(256) void sed_tb_stripemap_kernel(const sed_pair_desc *__restrict__ pd,
-                                                               const uint32_t *__restrict__ tb,
-                                                               uint32_t *__restrict__ map,
-                                                               uint32_t *__restrict__ ops, const uint64_t pat) {
-    constexpr int ROWS = 64 * R, G = Grp<R>::G, LG = CodeCursor<R>::LG, LR = CodeCursor<R>::LR;
-    constexpr int P = Ladder<R>::P;
-    constexpr int LEFT = R == 2 ? SED_TBMAP_LEFT_R2 : SED_TBMAP_LEFT;
-    constexpr int NSG = (LEFT + 256 + 64 + 2 * G) / G + 1;  // staged step groups
-    constexpr int NIT = (NSG * 64 + 255) / 256;  // staging trips of the 256 threads
-    __shared__ uint4 stage[NIT * 256];
-    const __attribute__((address_space(3))) uint32_t *stage32 =
-        (const __attribute__((address_space(3))) uint32_t *)(stage);
-    const int p = blockIdx.y;
-    const sed_pair_desc d = pd[p];
-    const int n = d.n, m = d.m;
-    if (d.lane) return;
-    const int tid = threadIdx.x, idx = blockIdx.x * 256 + tid;
-    if (idx < (n + m + 15) / 16) ops[d.ops_off + idx] = 0u;
-    if (n == 0 || m == 0) return;
-    const int K = (n + ROWS - 1) / ROWS;
-    if (K < 3) return;  // walked whole by the emit kernel
-    const int nx = m + 1, nxc = (nx + 255) / 256;
-    const int blk = blockIdx.x;
-    if (blk > (K - 2) * nxc) return;
-    const int SG = (m + 63 + G - 1) / G * G;
-    const uint64_t stripe_words = (uint64_t)(SG / G) * 256u;
-    int k, i, j, slot, x0;
-    bool live;
-    if (blk == (K - 2) * nxc) {  // the sink's stripe, from the sink: the last lane of a block ending at m
-        k = K - 1;
-        x0 = max(0, m - 255);
-        i = n;
-        j = m;
-        slot = k * nx;
-        live = tid == m - x0;
-    } else {
-        k = 1 + blk / nxc;
-        x0 = (blk % nxc) * 256;
-        j = x0 + tid;
-        i = (k + 1) * ROWS;
-        slot = k * nx + j;
-        live = j <= m;
-    }
-    // stage the groups of steps s = j' - 1 + t, j' in [x0 - LEFT, x0 + 255], t in [0, 63]
-    const uint32_t *tbk = tb + d.tb_off + (uint64_t)k * stripe_words;
-    const int s_lo = max(0, x0 - LEFT - 1), s_hi = min(SG - 1, x0 + 255 + 63);
-    const int sg_lo = s_lo >> LG, nsg = min(NSG, (s_hi >> LG) - sg_lo + 1);
-    const uint4 *src = reinterpret_cast<const uint4 *>(tbk) + (uint64_t)sg_lo * 64u;
-    {  // fixed trip count, unguarded stores (clamped loads fill the tail): every load is in flight before the first
-       // wait (guarded stores split the blocks, and the copy ran load, wait, store per trip)
-        uint4 v[NIT];
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) {
-            const int e = tid + 256 * u;
-            v[u] = src[e < nsg * 64 ? e : 0];
-        }
-#pragma unroll
-        for (int u = 0; u < NIT; ++u) stage[tid + 256 * u] = v[u];
-    }
-    __syncthreads();
-    if (!live) return;
-    const int top = k * ROWS;  // row top belongs to stripe k - 1
-    uint32_t cnt = 0, run = 0;  // run: consecutive inserts
-    for (;;) {  // one exit per step (separate exits became nested exec-mask regions); reason decided after
-        const int rr = i - 1, t = (rr >> LR) & 63, r = rr & (R - 1);
-        const int s = j - 1 + t;
-        const uint32_t c = ((uint32_t)(s & (G - 1)) << LR) | (uint32_t)r;
-        // one unconditional ds_read_b32 per step (an LDS-qualified pointer: a generic one became a flat load, and
-        // a uint4 read was split into two branch-guarded halves)
-        const uint32_t rel = (uint32_t)((s >> LG) - sg_lo);
-        const bool inside = rel < (uint32_t)nsg;
-        const uint32_t word = stage32[(inside ? rel : 0u) * 256u + (uint32_t)t * 4u + (c >> 4)];
-        if (!((i > top) & (j > 0) & inside & (run <= SED_TBMAP_RUN))) break;
-        const uint32_t op = ((word >> (2u * (c & 15u))) - (uint32_t)(pat >> (4 * (i & (P - 1))))) & 3u;
-        ++cnt;
-        run = op == 0u ? run + 1u : 0u;
-        i -= (int)(op != 0u);
-        j -= (int)(op != 1u);
-    }
-    if (i > top) {
-        if (j == 0) {  // the column-0 border: deletes up to the stripe above
-            cnt += (uint32_t)(i - top);
-        } else {  // left of the staged steps, or a long run of inserts (a cell far from the diagonal): unknown,
-            j = -1;  // walked by the emit kernel if the real path needs it; the run limit bounds such walks
-            cnt = 0;
-        }
-    }
-    uint32_t *mp = map + (uint32_t)d.map_off + 2u * (uint32_t)slot;
-    mp[0] = (uint32_t)j;  // 0xFFFFFFFF: unknown
-    mp[1] = cnt;
-}
-
-// Band maps (round 5, SED_TBMAP_BANDS = 1, the default): the map kernel above gives one lane a whole stripe, a
-// chain of up to ~700 dependent LDS steps at about one wave per SIMD (config 2: 104 us).  Here a lane walks one
-// 64-row band (band g: rows 64g + 1 .. 64g + 64, from its last row, or from the sink in the sink's band) for every
-// band 1 .. nbt-1 (stripe 0's upper bands too, for the banded emit) and every column: 4x (R = 4) the lanes at 1/4 the
-// chain, each workgroup staging only its band's 64/R forward lanes of the code groups (1/4 the LDS, so many
-// workgroups per CU).  band map entry bm[(g - 1) * (m + 1) + x] = {exit column at row 64g, ops}, or unknown; it
-// follows the stripe map's K (m + 1) entries.  sed_tb_bandcompose_kernel then chains a stripe's NB bands into the
-// stripe map, and the emit kernel composes both.
 template <int R>
 __global__ __launch_bounds__(256) void sed_tb_bandmap_kernel(const sed_pair_desc *__restrict__ pd,
                                                              const uint32_t *__restrict__ tb,
@@ -2377,7 +1231,8 @@ __global__ __launch_bounds__(256) void sed_tb_bandmap_kernel(const sed_pair_desc
     const int s_lo = max(0, x0 - LEFT - 1), s_hi = min(SG - 1, x0 + 255 + 63);
     const int sg_lo = s_lo >> LG, nsg = min(NSG, (s_hi >> LG) - sg_lo + 1);
     const uint4 *src = reinterpret_cast<const uint4 *>(tbk) + (uint64_t)sg_lo * 64u + t0;
-    {  // as in the stripe map kernel: every load in flight before the first wait
+    {  // fixed trip count, unguarded stores (clamped loads fill the tail): every load is in flight before the first
+       // wait (guarded stores split the blocks, and the copy ran load, wait, store per trip)
         uint4 v[NIT];
 #pragma unroll
         for (int u = 0; u < NIT; ++u) {
@@ -2392,10 +1247,12 @@ __global__ __launch_bounds__(256) void sed_tb_bandmap_kernel(const sed_pair_desc
     const int top = 64 * g;  // row top belongs to band g - 1
     uint32_t cnt = 0, run = 0;  // run: consecutive inserts
     const uint32_t cap = SED_TBMAP_CAP ? (uint32_t)SED_TBMAP_CAP + 64u * (uint32_t)((m + n - 1) / n) : 0xFFFFFFFFu;
-    for (;;) {  // the stripe map kernel's loop on the band's staged lanes
+    for (;;) {  // one exit per step (separate exits became nested exec-mask regions); reason decided after
         const int rr = i - 1, t = (rr >> LR) & 63, r = rr & (R - 1);
         const int s = j - 1 + t;
         const uint32_t c = ((uint32_t)(s & (G - 1)) << LR) | (uint32_t)r;
+        // one unconditional ds_read_b32 per step (an LDS-qualified pointer: a generic one became a flat load, and
+        // a uint4 read was split into two branch-guarded halves)
         const uint32_t rel = (uint32_t)((s >> LG) - sg_lo);
         const bool inside = rel < (uint32_t)nsg;
         // (t - t0) & (NL - 1): the read after the exit row (t outside the band) stays inside the staged lanes
@@ -2410,8 +1267,8 @@ __global__ __launch_bounds__(256) void sed_tb_bandmap_kernel(const sed_pair_desc
     if (i > top) {
         if (j == 0) {  // the column-0 border: deletes up to the band above
             cnt += (uint32_t)(i - top);
-        } else {  // unknown (see the stripe map kernel)
-            j = -1;
+        } else {  // left of the staged steps, a long run of inserts (a cell far from the diagonal) or past the step
+            j = -1;  // limit: unknown, walked by the emit kernel if the real path needs it
             cnt = 0;
         }
     }
@@ -2421,8 +1278,8 @@ __global__ __launch_bounds__(256) void sed_tb_bandmap_kernel(const sed_pair_desc
 }
 
 // The stripe map from the band maps: one thread per (stripe k in 1 .. K-2, column x), chaining the stripe's NB
-// bands from its last row, and one for the sink's stripe, from the sink (stored at x = 0, as the stripe map kernel
-// does).  Unknown if any band on the chain is.
+// bands from its last row, and one for the sink's stripe, from the sink (stored at x = 0).  Unknown if any band on
+// the chain is.
 template <int R>
 __global__ __launch_bounds__(256) void sed_tb_bandcompose_kernel(const sed_pair_desc *__restrict__ pd,
                                                                  uint32_t *__restrict__ map) {
@@ -2466,7 +1323,7 @@ __global__ __launch_bounds__(256) void sed_tb_bandcompose_kernel(const sed_pair_
     mp[2u * slot + 1u] = cnt;
 }
 
-// The exit column and op count of stripe k's segment from cell (i, j), walked here (entries the map kernel left
+// The exit column and op count of stripe k's segment from cell (i, j), walked here (entries the maps left
 // unknown); wave-uniform, codes read one word per step
 template <int R>
 __device__ __forceinline__ uint2 ck_count_walk(const sed_pair_desc &d, const uint32_t *__restrict__ tb, const uint64_t pat,
@@ -2493,70 +1350,11 @@ __device__ __forceinline__ uint2 ck_count_walk(const sed_pair_desc &d, const uin
     return make_uint2((uint32_t)j, cnt);
 }
 
-// One wave per (pair, stripe): its segment of the canonical path, from the composed maps (see above; entries the map left unknown are walked here)
-template <int R>
-__global__ __launch_bounds__(64) void sed_tb_stripeemit_kernel(const sed_pair_desc *__restrict__ pd,
-                                                               const uint32_t *__restrict__ tb,
-                                                               sed_result *__restrict__ res,
-                                                               uint32_t *__restrict__ ops,
-                                                               const uint32_t *__restrict__ map, const uint64_t pat) {
-    constexpr int ROWS = 64 * R;
-    const int lane = threadIdx.x;
-    const int pair = __builtin_amdgcn_readfirstlane(blockIdx.x), kme = __builtin_amdgcn_readfirstlane(blockIdx.y);
-    const sed_pair_desc d = pd[pair];
-    if (d.lane) return;
-    const int n = d.n, m = d.m;
-    const int K = n > 0 ? (n + ROWS - 1) / ROWS : 1;
-    const int Keff = (K >= 3 && m > 0) ? K : 1;  // pairs of one or two stripes: one segment, the whole walk
-    if (kme >= Keff) return;
-    const uint32_t L = (uint32_t)__builtin_amdgcn_readfirstlane(res[pair].len);
-    int i0 = n, j0 = m;
-    uint32_t qhi = L, cnt = L;  // cnt: the ops of this segment
-    if (Keff > 1) {
-        const uint32_t nx = (uint32_t)m + 1u;
-        const uint32_t *mp = map + (uint32_t)d.map_off;
-        uint32_t x = mp[2u * ((uint32_t)(K - 1) * nx)];
-        cnt = mp[2u * ((uint32_t)(K - 1) * nx) + 1u];
-        if (x == 0xFFFFFFFFu) {  // the sink's walk left its staged columns
-            const uint2 w = ck_count_walk<R>(d, tb, pat, K - 1, n, m);
-            x = w.x;
-            cnt = w.y;
-        }
-        for (int kk = K - 2; kk >= kme; --kk) {  // down to this stripe: its entry column and script positions
-            qhi -= cnt;
-            const uint32_t e = 2u * ((uint32_t)kk * nx + x);
-            if (kk > 0) {
-                i0 = (kk + 1) * ROWS;
-                j0 = (int)x;
-                uint32_t xn = mp[e];
-                cnt = mp[e + 1u];
-                if (xn == 0xFFFFFFFFu) {
-                    const uint2 w = ck_count_walk<R>(d, tb, pat, kk, i0, j0);
-                    xn = w.x;
-                    cnt = w.y;
-                }
-                x = xn;
-            } else {  // stripe 0: to the origin, whatever is left
-                cnt = qhi;
-                i0 = ROWS;
-                j0 = (int)x;
-            }
-        }
-    }
-    const int istop = (Keff == 1 || kme == 0) ? 0 : kme * ROWS;
-    uint32_t bad = 0;
-    const uint32_t q = window_walk<R, true>(d, i0, j0, istop, qhi, lane, tb, ops + d.ops_off, pat, bad);
-    if ((bad || q != qhi - cnt) && lane == 0) res[pair].err = SED_ERR_TB_LENGTH;
-}
-
-// Banded emit (round 6, SED_TB_BANDEMIT = 1, the default): one wave per (pair, 64-row band) instead of per stripe, so
-// a wave walks one band's segment of the path (~1/R of a stripe's).  The wave composes the stripe maps from the sink
-// down to its band's stripe, then that stripe's band maps down to its band (entries the maps left unknown are walked
-// here, ck_count_walk), and walks its segment to the band's top row (band 0: to the origin) with the window walk,
-// ORing its script words into the zeroed buffer as the stripe emit does.
-#ifndef SED_TB_BANDEMIT
-#define SED_TB_BANDEMIT 1
-#endif
+// The emit: one wave per (pair, 64-row band) walks its band's segment of the canonical path (a wave per stripe
+// walked R times as far).  The wave composes the stripe maps from the sink down to its band's stripe, then that
+// stripe's band maps down to its band (entries the maps left unknown are walked here, ck_count_walk), and walks its
+// segment to the band's top row (band 0: to the origin) with the window walk, ORing its script words into the zeroed
+// buffer.
 template <int R>
 __global__ __launch_bounds__(64) void sed_tb_bandemit_kernel(const sed_pair_desc *__restrict__ pd,
                                                              const uint32_t *__restrict__ tb,
@@ -2625,532 +1423,6 @@ __global__ __launch_bounds__(64) void sed_tb_bandemit_kernel(const sed_pair_desc
     if ((bad || q != qhi - cnt) && lane == 0) res[pair].err = SED_ERR_TB_LENGTH;
 }
 
-
-// ---------------------------------------------------------------------------
-// Traceback from checkpoints (CK: script batches of the stripe and CHAIN kernels with R = 4, 8 or 16 rows
-// per lane, G = 64/R).  One wave per pair walks the canonical path back from (n, m) tile by tile.  A tile
-// is 64 rows (forward lanes GQ .. GQ+G-1 of a stripe, the tile's G bands of R rows) x the 64 columns those
-// lanes processed in one chunk c, a staircase: band t = GQ + b covers columns 64c - t + 1 .. 64c - t + 64.
-// Entering a tile, the wave recomputes it from
-//   - the column checkpoints of chunk c-1 (each band's R row values at column 64c - t, and the value
-//     above the band at that column), or the column-0 borders for c = 0;
-//   - the row above the tile: the row checkpoints of lane GQ-1 (or lane 63 of the stripe above, or
-//     row 0), read through LDS by lane 0;
-// with one lane per row (row r at sweep step sigma is at column J0 - (G-1) + sigma - r, J0 = 64c - GQ + 1;
-// the cell above arrives through the DPP chain from lane r - 1, the str2 selector from LDS).  The forward kernel
-// stores distance keys (D, L without the op); every checkpoint value is converted on load to the
-// traceback key of the same (D, L) (i32_dist_to_tb), whose min carries the canonical op in its low two
-// bits: 6 VALU per cell (v_add_u32_dpp for the cell above + 1, perm, add, min3, and, alignbit).  Lanes of
-// band b hold their checkpoint until their first column (step r - b + G - 1: one v_cndmask on a scalar
-// mask) and read code 3 there (outside the band's window, OR-ed in per word); the first row of bands
-// 1..G-1 takes its first diagonal from the checkpoint; columns < 1 get the sentinel selector, so they keep
-// the column-0 border.  The sweep stops after the 16-step word holding the entry cell's step (the path only
-// goes up and left), and the entry cell's key must carry the path length still to emit: a mismatch (a
-// corrupted checkpoint, SED_OPT_DEBUG_CORRUPT) sets res.err instead of writing a wrong script.  Codes stay
-// in registers, 16 steps per word.  The walk is scalar: one v_readlane per step and the state packed as
-// S = row + (step << 7), 10 SALU per step (a step moves S by 128 / 129 / 257 for insert / delete /
-// update; one masked compare catches leaving the word, the tile (bit 6 = above it) and the window (code
-// 3)), one unrolled copy per code word since the step only decreases.
-// ---------------------------------------------------------------------------
-// S decrement per code: insert 128, delete 129, update 257 (S = row | step << 7); the marker 3 (left of the
-// band's window) moves S by 0x8000, out of every word, and is taken back at the exit.  Only the low 16 bits of S
-// are kept: a move subtracts the next code's field << 16 as well.
-#define SED_TB_MOVES (128ull | (129ull << 16) | (257ull << 32) | (0x8000ull << 48))
-#define SED_TB_WORD 0xF840u  // S bits that change when the walk leaves a 16-step word or the tile (bit 6: above it)
-// The walk of one tile from state S; returns the state of the first cell it did not take (outside the
-// tile: above it, left of its band's window, or at column 0 for C0), low 16 bits.  One loop per code word with a
-// single exit test: the next state's word bits (S & SED_TB_WORD) must still be the word's tag.
-template <bool C0, int NW>  // C0: chunk-0 tile, whose window reaches the column-0 border: stop at j = 0
-__device__ __forceinline__ uint32_t ck_walk(const uint32_t (&W)[NW], uint32_t S, uint32_t &q, uint64_t &acc,
-                                            uint32_t &err, uint32_t *__restrict__ out, int jcol) {
-    static_assert(NW <= 15, "the step field (S bits 7..14) and the word tags need a free bit 15");
-#pragma unroll
-    for (int w = NW - 1; w >= 0; --w) {
-        const uint32_t tag = (uint32_t)w << 11;
-        if ((S & SED_TB_WORD) == tag) {
-            // Every op moves the walk at least one step left, so one word yields at most 16 ops.  Inside the loop
-            // the state is carried as T = S - tag (same low 11 bits: lane and shift), so leaving the word, the tile or
-            // the window is (T & SED_TB_WORD) != 0, one s_and that sets SCC; the codes collect in a 32-bit lo
-            // (s_lshl2_add_u32), which holds all of them, and go onto the 64-bit acc (the last 32 ops) after the
-            // loop, where the script word completed in it, if any, is stored.  A step is one v_readlane and 10 SALU.
-            const uint32_t qs = q;
-            uint32_t T = S - tag, lo = 0, code;
-            do {
-                // s_lshr takes the low 5 bits of T >> 6: 2 * (step & 15), bit 6 being clear inside the tile
-                code = ((uint32_t)__builtin_amdgcn_readlane((int)W[w], (int)T) >> ((T >> 6) & 31u)) & 3u;
-                if (C0 && jcol == 0) code = 3u;
-                // the marker too: taken back below (asm: the compiler emits s_lshl + s_or; the op writes SCC)
-                asm("s_lshl2_add_u32 %0, %1, %2" : "=s"(lo) : "s"(lo), "s"(code) : "scc");
-                if constexpr (C0) jcol -= (int)((5u >> code) & 1u);
-                T -= (uint32_t)(SED_TB_MOVES >> (code << 4));
-                --q;
-            } while ((T & SED_TB_WORD) == 0u);
-            S = T + tag;
-            const bool marker = code == 3u;
-            // opaque: otherwise the compiler keeps the previous lo and q alive through the loop for the undo
-            asm volatile("" : "+s"(lo), "+s"(q));
-            if (marker) {  // not an op: the walk stays at the cell before it
-                lo >>= 2;
-                ++q;
-            }
-            // lo started at 0 and holds exactly this word's ops (at most 16)
-            const uint32_t nw = qs - q;
-            acc = (acc << (2u * nw)) | lo;
-            // the script word [p, p + 16) completed in this word, if any: [q, qs) holds at most 16 positions, so at most
-            // one p = 16k with q <= p < qs
-            const uint32_t p = (q + 15u) & ~15u;
-            if ((int32_t)nw < 0) err = SED_ERR_TB_LENGTH;  // ran past the sink's L (q wrapped; the tile bounds the walk)
-            else if (p < qs) out[p >> 4] = (uint32_t)(acc >> (2u * (p - q)));
-            if (marker) return (S + 0x8000u) & 0xFFFFu;
-        }
-    }
-    return S & 0xFFFFu;
-}
-
-// SED_CK_VHOLD (default on; -DSED_CK_VHOLD=0 restores the select): at R = 16 lanes left of their window hold
-// their key without a select (per-band selector copies carry the sentinel, and each band's first row takes a
-// compensated delete addend until its band starts).  6 VALU per swept cell instead of 7; profiles/r03/vhold:
-// traceback 3.78 against 3.91 ms beside the forward parts, step within noise
-#ifndef SED_CK_VHOLD
-#define SED_CK_VHOLD 1
-#endif
-// NW code words per lane cover sweep steps 0 .. 16 NW - 1: 8 for one chunk's tile (127 steps), 12 for a wide window
-// of two chunks (191 steps); topb holds 16 NW + 4 words, each band's selector copy 64 more
-#define SED_CK_NX(NW) (16 * (NW) + 4)
-#define SED_CK_SELB(NW) (64 + SED_CK_NX(NW))
-template <int R> struct CkVHold { static constexpr bool value = SED_CK_VHOLD && R == 16; };
-// lanes 0 .. n-1 have reached their window at sweep step sig (sig0(r) = r - r/R + G - 1 is nondecreasing)
-template <int R> constexpr int ck_active_lanes(int sig) {
-    constexpr int G = 64 / R;
-    int n = 0;
-    for (int r = 0; r < 64; ++r)
-        if (r - r / R + G - 1 <= sig) n = r + 1;
-    return n;
-}
-// lanes >= act keep v, the others take vn: the mask is built on the scalar unit inside the asm, so the
-// compiler can neither hoist the 60-odd constant masks (they spill) nor turn them into a VALU compare
-__device__ __forceinline__ uint32_t ck_hold(uint32_t vn, uint32_t v, const int act) {
-    uint32_t r;
-    uint64_t m;
-    // (s_lshl_b64 writes SCC: without the clobber a compare's SCC could be read across the asm)
-    asm("s_lshl_b64 %1, -1, %4\n\tv_cndmask_b32 %0, %2, %3, %1" : "=v"(r), "=&s"(m) : "v"(vn), "v"(v), "i"(act) : "scc");
-    return r;
-}
-
-// band b >= 1 of a tile starts (its first row takes the checkpoint's top_prev as diagonal) at sweep step
-// (R - 1) b + G - 1; returns b, or 0 when `sig` starts no band
-template <int R> constexpr int ck_band_start(int sig) {
-    constexpr int G = 64 / R;
-    for (int b = 1; b < G; ++b)
-        if (sig == (R - 1) * b + G - 1) return b;
-    return 0;
-}
-
-// f(integral_constant<int, I>) for I = B .. E-1, expanded at compile time
-template <int B, int E, class F> __device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
-// a word at a 32-bit byte offset from a uniform base: the scalar-base (saddr) load form, no 64-bit lane address
-__device__ __forceinline__ uint32_t ld_byte_off(const uint32_t *__restrict__ base, const uint32_t off) {
-    return *(const uint32_t *)((const char *)base + off);
-}
-
-// LDS ordering inside the traceback: a workgroup barrier for the one-wave traceback kernel; WAVE: a wave-local
-// wait, for a traceback run by a wave of a larger workgroup (LDS accesses of one wave execute in order; the
-// clobber keeps the compiler from moving them across).  Fusing the traceback into the CK forward kernel this way
-// (each wave walks its pair after its forward pass) measured 13.9-14.0 ms per config-4 step against 13.87 ms
-// for the separate kernel (profiles/r02/abfuse), so the traceback stays a kernel of its own.
-template <bool WAVE> __device__ __forceinline__ void ck_sync() {
-    if constexpr (WAVE) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else __syncthreads();
-}
-
-// topb[x] (132 words): the row above the tile at lane 0's column of step x, plus 1 (lane 0's delete candidate);
-// selb[64 + x] (196 words): str2 selector of lane 0's column at step x; lane r reads selb[64 + sigma - r] itself
-// (its column at step sigma), so no selector travels through the DPP chain.  q0: the sink's L.
-// Per-pair constants of the checkpoint tiles.  ckoff: word offset of the checkpoints past d.tb_off (SPLIT batches keep
-// them after the pair's per-cell code region, sed_ck_codes_kernel).
-struct CkPairCtx {
-    int n, m, SG, nchunks, ngroups, band;
-    const uint32_t *ccp, *rcp, *pa, *pb;
-    uint32_t cko0, cko1, hm[4];
-};
-template <int R>
-__device__ __forceinline__ CkPairCtx ck_pair_ctx(const sed_pair_desc &d, const int lane, const uint32_t *__restrict__ seqa,
-                                                 const uint32_t *__restrict__ seqb, const uint32_t *__restrict__ ck,
-                                                 const uint64_t ckoff) {
-    constexpr int ROWS = 64 * R, G = Grp<R>::G;
-    constexpr int LR = R == 4 ? 2 : R == 8 ? 3 : 4;
-    CkPairCtx px;
-    px.n = d.n;
-    px.m = d.m;
-    const int nstripes = (d.n + ROWS - 1) / ROWS;
-    px.SG = (d.m + 63 + G - 1) / G * G;
-    px.nchunks = (px.SG + 63) >> 6;
-    px.ngroups = px.SG / G;
-    px.ccp = ck + d.tb_off + ckoff;
-    px.rcp = px.ccp + sed_ck_col_words(R, nstripes, px.nchunks);
-    px.pa = seqa + d.a_off;
-    px.pb = seqb + d.b_off;
-    px.band = lane >> LR;
-    px.cko0 = ((uint32_t)(lane & (R - 1)) * 64u + (uint32_t)px.band) * 4u;
-    px.cko1 = (uint32_t)(R * 64 + px.band) * 4u;
-    const int sig0 = lane - px.band + G - 1;  // first real sweep step of this lane (<= 63)
-    // code 3 (outside the window) for the steps before sig0, OR-ed into words 0..3 once they are complete
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int h = min(max(sig0 - 16 * w, 0), 16);
-        px.hm[w] = h >= 16 ? ~0u : (1u << (2 * h)) - 1u;
-    }
-    return px;
-}
-
-// One tile visit: tile (stripe k, band group Q, chunk c) recomputed from its checkpoints up to sweep step sig_end (FULL:
-// all 128 steps), the codes in W (lane r's code of step sigma in W[sigma >> 4], bits 2 (sigma & 15)); returns the lanes'
-// keys after the last step (the entry keys).
-template <int R, bool WAVE, bool FULL, int NW>
-__device__ __forceinline__ uint32_t ck_tile_sweep(const CkPairCtx &px, const int lane, const sed_i32_params &prm,
-                                                  uint32_t *__restrict__ topb, uint32_t *__restrict__ selb, const int k,
-                                                  const int Q, const int c, const int sig_end, uint32_t &one,
-                                                  uint32_t (&W)[NW], uint32_t &vinit, const int bclo = 0,
-                                                  const int bclo_prev = 0, const int btophi = 0x7FFFFFFF) {
-    constexpr int NX = SED_CK_NX(NW), SELB = SED_CK_SELB(NW), NH = (NX + 63) / 64;
-    constexpr int ROWS = 64 * R, G = Grp<R>::G;  // a tile: G forward lanes (bands) of R rows
-    constexpr int LR = R == 4 ? 2 : R == 8 ? 3 : 4;
-    constexpr bool VHOLD = CkVHold<R>::value;
-    const int n = px.n, m = px.m, SG = px.SG, nchunks = px.nchunks, ngroups = px.ngroups, band = px.band;
-    const int J0 = 64 * c - G * Q + 1, rowbase = k * ROWS + 64 * Q;
-    // band pruning: the forward ran stripe k from the border state at column jb = 64 bclo (bclo = 0: column 0 itself),
-    // and the stripe above stored no bottom row past step btophi (both uniform, computed by the caller once per stripe;
-    // the defaults are an open window's)
-    const int jb = 64 * bclo, tophi = Q == 0 ? btophi : 0x7FFFFFFF;
-    // ---- boundaries (distance keys -> traceback keys) ----
-    // Every load of the tile is issued before the first use (one memory round trip per tile visit): addresses
-    // are clamped to valid words and the border cases are selects afterwards.
-    const int ir = min(rowbase + lane, n - 1);  // 0-based str1 index of this lane's row (clamped)
-    const uint32_t wa = px.pa[ir >> 4];
-    // (uniform 64-bit bases + 32-bit lane offsets: the loads take the scalar-base form and the address
-    // arithmetic stays on the scalar unit)
-    uint32_t ck0 = 0, ck1 = 0;
-    if (c > bclo) {  // (uniform)
-        const uint32_t *cp = px.ccp + sed_ck_col_word(R, k, nchunks, c - 1, 0, G * Q);
-        uint32_t o0 = px.cko0, o1 = px.cko1;
-        asm volatile("" : "+v"(o0), "+v"(o1));  // (else the zero-extended offsets are hoisted as 64-bit pairs)
-        ck0 = ld_byte_off(cp, o0);
-        ck1 = ld_byte_off(cp, o1);
-    }
-    // the row above the tile at column J0 - G + x (x = lane, lane + 64, lane + 128 < 132): row checkpoints of
-    // forward lane G*Q - 1 (or lane 63 of the stripe above); steps clamped: past SG the columns are beyond m and
-    // never read by the walk; columns < 1 are the column-0 border (a CHAIN wave's lanes still hold the
-    // previous pair there)
-    const bool above = Q >= 1 || k >= 1;  // (uniform) else row 0: the border
-    const int kr = Q >= 1 ? k : k - 1, tr = Q >= 1 ? G * Q - 1 : 63, s0r = Q >= 1 ? 64 * c - G - 1 : 64 * c + 63 - G;
-    uint32_t rk[NH], wb[NH];
-    const uint32_t *rbase = px.rcp + sed_ck_row_word(R, max(kr, 0), ngroups, 0, tr);  // (uniform; read when above)
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-        const int x = lane + 64 * h;
-        rk[h] = 0u;
-        // (a visit reads the top row and selectors of steps <= sig_end + 1 only: the blocks past it are skipped, a
-        // uniform branch; the entry word's reads past sig_end see unused words)
-        if ((FULL || 64 * h <= sig_end + 1) && (64 * (h + 1) <= NX || x < NX)) {
-            if (above) {
-                const uint32_t s = (uint32_t)min(max(s0r + x, 0), SG - 1);
-                rk[h] = ld_byte_off(rbase, ((s >> (6 - LR)) * (uint32_t)SED_CK_RW + (s & (uint32_t)(G - 1))) * 4u);
-            }
-            const int ci = min(max(J0 - (G - 1) + x - 1, 0), m - 1);
-            wb[h] = px.pb[ci >> 4];
-        }
-    }
-    const uint32_t a = (wa >> ((ir & 15) * 2)) & 3u;
-    const uint32_t clo = (a & 1u) ? prm.costrow[1] : prm.costrow[0];
-    const uint32_t chi = (a & 1u) ? prm.costrow[3] : prm.costrow[2];
-    const uint32_t cv = (a & 2u) ? chi : clo;
-    uint32_t V = SED_KB, tp = SED_KB;  // c = clo: the borders of column 64 clo
-    if (c > bclo) {
-        V = ck_to_tb(ck0, prm);
-        tp = ck_to_tb(ck1, prm);
-        if (VHOLD && J0 - band - 1 > m) V = 0u;  // (forward garbage past m: key 0 holds under the recurrence)
-    }
-    tp += 1u;  // diagonals carry the +1 of the delete candidate they were taken from
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-        const int x = lane + 64 * h;
-        if ((FULL || 64 * h <= sig_end + 1) && (64 * (h + 1) <= NX || x < NX)) {
-            // (the stripe above's cell at column jb is real where that stripe started left of it: the diagonal of the
-            // stripe's first cell, as the forward took it)
-            const int tcol = J0 - G + x;
-            const bool tin = tcol > jb || (Q == 0 && bclo > bclo_prev && tcol == jb);
-            const uint32_t v = (above && tin && s0r + x <= tophi) ? ck_to_tb(rk[h], prm) : SED_KB;
-            topb[x] = v + 1u;
-            const int col = J0 - (G - 1) + x;  // column of lane 0 at step x
-            const int ci = min(max(col - 1, 0), m - 1);
-            const uint32_t sv = col <= jb ? SED_SEL_SENT : i32_sel((wb[h] >> ((ci & 15) * 2)) & 3u);
-            if constexpr (VHOLD) {  // band b's copy: the sentinel left of its window (x < G - 1 - b)
-#pragma unroll
-                for (int b = 0; b < G; ++b) selb[b * SELB + 64 + x] = x < G - 1 - b ? SED_SEL_SENT : sv;
-            } else {
-                selb[64 + x] = sv;
-            }
-        }
-    }
-    ck_sync<WAVE>();
-    // ---- sweep: lane r at step sigma computes (row rowbase + r + 1, column J0 - (G-1) + sigma - r) ----
-    // Whole 16-step words (a branch per step would keep the LDS reads from running ahead), except the
-    // word holding the entry step, which stops at it: the lanes' keys are then the entry keys.  The cell above and the diagonal
-    // carry the delete candidate's +1 (one v_add_u32_dpp: lane r - 1's key + 1, or topb for lane 0), so
-    // the update constant is one less.  Lanes still left of their window (sigma < sig0: lanes
-    // ck_active_lanes(sigma) .. 63, a compile-time count) keep their checkpoint through one v_cndmask on a
-    // scalar mask; their codes become 3 through hm.  Steps 0 .. G-2 hold every lane and are skipped.
-    W[0] = 0u;  // steps 0 .. G-2 are skipped: their bits are OR-ed to 3 from a defined word
-    if constexpr (VHOLD) {  // a band's first row: V - V_above + 1 until the band starts
-        // (through the asm DPP add: with the builtin, the compiler folded V - dpp(V) into one
-        // v_subrev_u32_dpp ... bound_ctrl:1, which returned V_above - V on the device)
-        uint32_t zero = 0u;
-        asm volatile("" : "+v"(zero));
-        const uint32_t vabove = dpp_shr1_add(0u, V, zero);
-        one = ((lane & (R - 1)) == 0 && lane > 0) ? V - vabove + 1u : 1u;
-    }
-#ifdef SED_TB_DEBUG
-    vinit = V;
-#endif
-    uint32_t tprev = dpp_shr1_add(topb[G - 1], V, one);  // diagonal of step G-1 (+1)
-    // the top row's reads through one opaque base register and immediate offsets (else every constant address became a
-    // VGPR of its own: 28 preloaded at the kernel's start, one more v_mov per two steps of an entry word)
-    const uint32_t *topr = topb;
-    {
-        uint32_t z = 0u;
-        asm volatile("" : "+v"(z));
-        topr += z;
-    }
-    const uint32_t *selp = selb + (VHOLD ? band * SELB : 0) + 64 - lane;  // lane r's selector at step sigma
-    const int w_end = FULL ? NW - 1 : sig_end >> 4;  // FULL: every word, whole
-    auto step = [&](const int sig, uint32_t &wv, const uint32_t topin, const uint32_t selv) {
-        if (sig < G - 1) return;  // every lane holds
-        const int bs = ck_band_start<R>(sig);  // folds to a constant in the unrolled sweep
-        if (VHOLD && bs > 0) one = lane == R * bs ? 1u : one;  // the band starts: its first row's real delete
-        const uint32_t topv = dpp_shr1_add(topin, V, one);
-        // (selv: steps before the lane's first column read don't-care)
-        uint32_t diag = tprev;
-        if (bs > 0) diag = lane == R * bs ? tp : diag;
-        const uint32_t mm = umin3(V, topv, diag + __builtin_amdgcn_perm(cv, 0xFFFFFFFDu, selv));
-        const uint32_t vn = mm & ~3u;
-        if constexpr (VHOLD) {
-            V = vn;
-        } else {
-            const int act = ck_active_lanes<R>(sig);  // lanes 0 .. act-1 are inside their window
-            V = act >= 64 ? vn : ck_hold(vn, V, act);
-        }
-        wv = __builtin_amdgcn_alignbit(mm, wv, 2);
-        tprev = topv;
-    };
-    // (the words expand through static_for: a #pragma unroll over 12 words gives up, and the steps' constants with it)
-    static_for<0, NW>([&](auto wc) {
-        constexpr int w = decltype(wc)::value;
-        if (w > w_end) return;  // the path never needs later steps
-        if (!FULL && w == w_end) {  // up to the entry step exactly: the lanes then hold the entry keys
-            // the word's LDS inputs first (the compiler sinks them into the steps anyway; pinning them ahead of the exits
-            // with an asm use measured the same, profiles/r06/ck_wide)
-            uint32_t tw[16], sw[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                tw[u] = topr[16 * w + u + 1];
-                sw[u] = selp[16 * w + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                if (16 * w + u > sig_end) break;
-                step(16 * w + u, W[w], tw[u], sw[u]);
-            }
-            W[w] >>= 2u * (15u - ((uint32_t)sig_end & 15u));  // step u's code to bits 2u, 2u+1
-        } else {
-#pragma unroll
-            for (int u = 0; u < 16; ++u) step(16 * w + u, W[w], topr[16 * w + u + 1], selp[16 * w + u]);
-        }
-        if (w < 4) W[w] |= px.hm[w];
-    });
-    return V;
-}
-
-template <int R, bool WAVE, int NW>
-__device__ __forceinline__ void ck_traceback_pair(const sed_pair_desc &d, const int pair, const uint32_t q0,
-                                                  const int lane, const uint32_t *__restrict__ seqa,
-                                                  const uint32_t *__restrict__ seqb, const uint32_t *__restrict__ ck,
-                                                  sed_result *__restrict__ res, uint32_t *__restrict__ ops,
-                                                  const sed_i32_params &prm, uint32_t *__restrict__ topb,
-                                                  uint32_t *__restrict__ selb,
-                                                  const sed_band bw = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI}) {
-    constexpr int ROWS = 64 * R, G = Grp<R>::G;  // a tile: G forward lanes (bands) of R rows
-    static_assert(R == 4 || R == 8 || R == 16, "R in {4, 8, 16}");
-    const int n = d.n, m = d.m;
-#ifdef SED_TB_DEBUG
-    int visit = 0;  // debug dumps: 136 words per tile visit (entry keys, initial keys, coordinates)
-#endif
-    uint32_t *out = ops + d.ops_off;
-#ifndef SED_TB_DEBUG
-    zero_script_tail(out, (int)q0, n, m, lane, 64);  // (before the walk, as sed_traceback_kernel)
-#endif
-    uint32_t q = q0, err = 0;
-    uint64_t acc = 0;  // the last 32 ops, the latest (position q) in bits 1:0
-    auto emit = [&](uint32_t op) {  // sink -> origin (trailing border runs)
-        if (q == 0) {
-            err = SED_ERR_TB_LENGTH;
-            return;
-        }
-        acc = (acc << 2) | op;
-        if ((--q & 15u) == 0) out[q >> 4] = (uint32_t)acc;
-    };
-    const uint32_t Kd = (prm.del << 16) + 4u, Ki = (prm.ins << 16) + 4u;
-    int i = n, j = m;
-    if (i > 0 && j > 0) {
-        const CkPairCtx px = ck_pair_ctx<R>(d, lane, seqa, seqb, ck, 0);
-        // band pruning: the forward computed stripe k from column 64 clo + 1 on, and the stripe above it stored no
-        // bottom row past step tophi; both change only when the walk enters another stripe
-        int kband = -1, clo = 0, clo_prev = 0, tophi = 0x7FFFFFFF;
-        uint32_t one = 1u;  // the delete candidate's +1, a VGPR operand of v_add_u32_dpp
-        asm volatile("" : "+v"(one));
-        int guard = 2 * (n + m) + 8;       // tiles visited; every visit makes progress
-        while (i > 0 && j > 0) {
-            if (--guard <= 0) {
-                err = SED_ERR_TB_GUARD;
-                break;
-            }
-            const int k = (i - 1) / ROWS, t = ((i - 1) % ROWS) / R, Q = t / G;
-            const int ce = (j - 1 + t) >> 6;            // the entry cell's chunk
-            if (k != kband) {  // (uniform; once per stripe)
-                int hi_;
-                tophi = 0x7FFFFFFF;
-                clo_prev = 0;
-                if (k >= 1) {
-                    sed_band_chunks(n, m, ROWS, px.nchunks, bw, k - 1, &clo_prev, &hi_);
-                    tophi = 64 * hi_ + 63;
-                }
-                sed_band_chunks(n, m, ROWS, px.nchunks, bw, k, &clo, &hi_);
-                kband = k;
-            }
-            // every optimal path stays inside the window, so a walk that arrives left of it followed keys the forward
-            // never wrote
-            if (j <= 64 * clo) {
-                err = SED_ERR_TB_BAND;
-                break;
-            }
-            const int rowbase = k * ROWS + 64 * Q;
-            const int re = i - rowbase - 1;             // the entry cell's tile row
-            // NW = 12: a window of two chunks (ce - 1, ce) when the entry step x inside its chunk is below re, i.e. when
-            // a diagonal path would leave chunk ce through its left edge before the tile's top: the path then crosses
-            // the row group in one visit instead of two, 151 against 93 sweep steps per visit but half the visits
-            // (22.3 -> 17.1 VALU per emitted op on config 4's pairs, tools/tb_window_model.py)
-            const int c = (NW > 8 && ce > clo && ((j - 1 + t) & 63) < re) ? ce - 1 : ce;
-            const int J0 = 64 * c - G * Q + 1;
-            const int sig_end = (j - J0 + G - 1) + re;  // the entry cell's sweep step (<= 16 NW - 2)
-            uint32_t W[NW], vinit = 0;
-            const uint32_t ent = ck_tile_sweep<R, WAVE, false, NW>(px, lane, prm, topb, selb, k, Q, c, sig_end, one, W, vinit,
-                                                                   clo, clo_prev, tophi);
-            (void)vinit;
-#ifdef SED_TB_DEBUG
-            if (visit < 32) {  // debug builds only (pair 0; its script words, 64 spare, then 136 words per visit v)
-                uint32_t *dv = out + ((n + m + 15) >> 4) + 64 + 136 * visit;
-                dv[lane] = ent;
-                dv[64 + lane] = vinit;
-                if (lane == 0) {
-                    dv[128] = (uint32_t)i; dv[129] = (uint32_t)j; dv[130] = (uint32_t)c; dv[131] = (uint32_t)Q;
-                    dv[132] = (uint32_t)k; dv[133] = (uint32_t)sig_end; dv[134] = (uint32_t)re; dv[135] = q;
-                }
-            }
-            ++visit;
-#endif
-            // ---- the entry cell's key must carry the ops still to emit (L of a canonical-path cell) ----
-            {
-                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)ent, re) - SED_KB + (uint32_t)i * Kd +
-                                   (uint32_t)j * Ki;
-                if (((v >> 2) & 0x3FFFu) != q) {
-                    err = SED_ERR_TB_CHECK;
-                    break;
-                }
-            }
-            // ---- walk inside the tile ----
-            const uint32_t qin = q;
-            const uint32_t S0 = (uint32_t)re | ((uint32_t)sig_end << 7);
-            const uint32_t S = c == 0 ? ck_walk<true, NW>(W, S0, q, acc, err, out, j)
-                                      : ck_walk<false, NW>(W, S0, q, acc, err, out, j);
-            if (err) break;
-            if (q == qin) {  // no progress: give up rather than spin
-                err = SED_ERR_TB_STALL;
-                break;
-            }
-            const int sg = (int)((S + 64u) >> 7), r = (int)((S + 64u) & 127u) - 64;
-            i = rowbase + r + 1;
-            j = J0 - (G - 1) + sg - r;
-            ck_sync<WAVE>();  // topb / selb are rewritten for the next tile
-        }
-    }
-    if (!err) {
-        while (j > 0) { emit(0u); --j; }
-        while (i > 0) { emit(1u); --i; }
-        if (q != 0) err = SED_ERR_TB_LENGTH;
-    }
-#ifdef SED_TB_DEBUG
-    if (lane == 0) out[((n + m + 15) >> 4) + 63] = err | ((uint32_t)visit << 8);  // (debug: no error, the dumps stay)
-#else
-    if (err && lane == 0) res[pair].err = (uint8_t)err;
-#endif
-}
-
-// waves per SIMD the checkpoint traceback is compiled for (A/B: SED_CKTB_WAVES; 1 = the compiler's choice: 128 VGPRs and
-// 4 waves with the two-chunk windows, whose c4 traceback span was 3.2-3.3 against 2.06 ms at 5 waves / 96 VGPRs, no
-// spills; profiles/r06/ck_wide), and its
-// waves' issue priority against the other part's forward waves on the same SIMD (SED_CKTB_PRIO, s_setprio).  At
-// priority 1 the traceback's waves issue ahead of the forward's when both are ready, so a part's traceback ends
-// sooner beside the other part's forward and the step's tracebacks-only tail shrinks from ~0.5 to ~0.13 ms: c4
-// 9.74-9.79 against 9.91-9.98 ms at 0, 3 interleaved rounds (profiles/r05/s15; 3 is no different from 1).  With the
-// two-chunk windows: 0 9.70-9.74 against 9.55-9.60 ms; 2 and 3 within noise of 1 over 4 rounds (profiles/r06/ckprio)
-#ifndef SED_CKTB_WAVES
-#define SED_CKTB_WAVES 5
-#endif
-#ifndef SED_CKTB_PRIO
-#define SED_CKTB_PRIO 1
-#endif
-// code words per lane of the checkpoint traceback's sweep: 12 = two-chunk windows where they pay (ck_traceback_pair), 8 =
-// one chunk per visit
-#ifndef SED_CKTB_NW
-#define SED_CKTB_NW 12
-#endif
-template <int R>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SED_CKTB_WAVES))) void sed_traceback_ck_kernel(const sed_pair_desc *__restrict__ pd, int npairs,
-                                                              const uint32_t *__restrict__ seqa,
-                                                              const uint32_t *__restrict__ seqb,
-                                                              const uint32_t *__restrict__ ck,
-                                                              sed_result *__restrict__ res,
-                                                              uint32_t *__restrict__ ops, sed_i32_params prm,
-                                                              const sed_band *__restrict__ band) {
-    if constexpr (SED_CKTB_PRIO > 0) __builtin_amdgcn_s_setprio(SED_CKTB_PRIO);
-    const int lane = threadIdx.x;
-    const int pair = __builtin_amdgcn_readfirstlane(blockIdx.x);
-    if (pair >= npairs) return;
-    const sed_pair_desc d = pd[pair];
-    if (d.lane) return;  // scripted by sed_lane.hip
-#ifdef SED_TB_DEBUG
-    if (pair != 0) return;
-#endif
-    constexpr int NSEL = CkVHold<R>::value ? Grp<R>::G : 1, NW = SED_CKTB_NW;
-    __shared__ uint32_t topb[SED_CK_NX(NW)], selb[NSEL * SED_CK_SELB(NW)];
-    if constexpr (NSEL > 1) {
-        for (int x = lane; x < NSEL * SED_CK_SELB(NW); x += 64) selb[x] = SED_SEL_SENT;  // (entries below 64: before column 1)
-        __syncthreads();
-    }
-    const uint32_t q0 = (uint32_t)__builtin_amdgcn_readfirstlane(res[pair].len);
-    sed_band bw{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
-    if (band) {
-        bw.elo = __builtin_amdgcn_readfirstlane(band[pair].elo);
-        bw.ehi = __builtin_amdgcn_readfirstlane(band[pair].ehi);
-    }
-    ck_traceback_pair<R, false, NW>(d, pair, q0, lane, seqa, seqb, ck, res, ops, prm, topb, selb, bw);
-}
-
 // ---------------------------------------------------------------------------
 // SPLIT batches with checkpoints (config 2, GUI pairs; sed_runtime.cpp: split_ck).  The SPLIT forward kernel runs the
 // distance (or dot) keys, 2-3 VALU per cell instead of the ladder keys' 5.2, and stores checkpoints after the pair's
@@ -3160,6 +1432,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SED_CKTB_WAV
 // the stripe-parallel traceback walks (as plain ops: the ladder keys' per-row code offsets are not applied, L.tb_ladder).
 // Every tile is written, those below row n too, so the walks only ever read codes of a DP.  R = 4 (G = 16): tile lane r = 4 b + rr is forward lane G Q + b's row rr; its
 // codes of the chunk's forward steps 64 c .. 64 c + 63 sit at sweep steps G - 1 + 3 b + rr onwards.
+// (In this unit, beside the forward kernel whose checkpoints it reads: built in another unit, the compiler generates
+// different code for the checkpoint forward kernels, tools/kernel_resources.py.)
 __device__ __forceinline__ uint32_t ck_codes_transpose(uint32_t y) {
     // 4 x 4 transpose of 2-bit elements, byte = row: (row rr, element u) -> (row u, element rr)
     uint32_t t = ((y >> 6) ^ y) & 0x00CC00CCu;
@@ -3220,7 +1494,6 @@ __global__ __launch_bounds__(64) void sed_ck_codes_kernel(const sed_pair_desc *_
     *reinterpret_cast<uint4 *>(gp) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-#ifndef SED_CKTB_TU  // (sed_cktb.hip compiles this file for the checkpoint traceback's launcher alone)
 // ---------------------------------------------------------------------------
 // Self-test of the cross-lane primitives the kernels rely on.
 // ---------------------------------------------------------------------------
@@ -3246,30 +1519,18 @@ __global__ void sed_selftest_kernel(uint32_t *out) {
     atomicOr(out, fail);
 }
 
-// ---------------------------------------------------------------------------
-// Band pruning (sed_internal.h: sed_band_window): the cost UB of every wave pair's plain diagonal path and from it the
-// window of diagonals an optimal path can touch, one wave per pair, launched before every forward of a checkpoint
-// batch of the stripe kernel (a batch is run once in real use, so the run pays for its bound).  Each lane sums the
-// substitution costs of its share of the packed words (2 bits per symbol, 16 per word); ~(n + m) / 4 bytes per pair.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__restrict__ pd, int npairs,
-                                                       const uint32_t *__restrict__ seqa,
-                                                       const uint32_t *__restrict__ seqb, sed_band *__restrict__ band,
-                                                       sed_band_params bp) {
-    __shared__ uint32_t tab[16];
+// The block's LDS copy of the 4 x 4 cost table, ready on return.  It holds the block's barrier, so a kernel calls it
+// ahead of its early exits; that is why it is not part of diag_cost_sum.
+__device__ __forceinline__ void diag_cost_table(uint32_t *tab, const sed_band_params &bp) {
     if (threadIdx.x < 16) tab[threadIdx.x] = bp.cost[threadIdx.x];
     __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (pair >= npairs) return;
-    const sed_pair_desc d = pd[pair];
-    const int n = d.n, m = d.m;
-    if (d.lane || n == 0 || m == 0) {  // not a pair of the stripe kernel
-        if (lane == 0) band[pair] = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
-        return;
-    }
-    const int len = min(n, m), words = (len + 15) >> 4;
-    const uint32_t *pa = seqa + d.a_off, *pb = seqb + d.b_off;
+}
+// The cost of a wave pair's plain diagonal path over its first len = min(n, m) symbols, in every lane of the wave:
+// each lane sums its share of the packed words through tab (diag_cost_table), then the wave adds the lanes up.  The
+// host restates it as band_diag_bound (sed_runtime.cpp).
+__device__ __forceinline__ uint32_t diag_cost_sum(const uint32_t *tab, const uint32_t *pa, const uint32_t *pb,
+                                                  const int len, const int lane) {
+    const int words = (len + 15) >> 4;
     uint32_t sum = 0;
     for (int w = lane; w < words; w += 64) {
         uint32_t x = pa[w], y = pb[w];
@@ -3282,6 +1543,31 @@ __global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__re
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    return sum;
+}
+
+// ---------------------------------------------------------------------------
+// Band pruning (sed_internal.h: sed_band_window): the cost UB of every wave pair's plain diagonal path and from it the
+// window of diagonals an optimal path can touch, one wave per pair, launched before every forward of a checkpoint
+// batch of the stripe kernel (a batch is run once in real use, so the run pays for its bound).  ~(n + m) / 4 bytes per pair
+// (2 bits per symbol, 16 per word).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__restrict__ pd, int npairs,
+                                                       const uint32_t *__restrict__ seqa,
+                                                       const uint32_t *__restrict__ seqb, sed_band *__restrict__ band,
+                                                       sed_band_params bp) {
+    __shared__ uint32_t tab[16];
+    diag_cost_table(tab, bp);
+    const int lane = threadIdx.x & 63;
+    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= npairs) return;
+    const sed_pair_desc d = pd[pair];
+    const int n = d.n, m = d.m;
+    if (d.lane || n == 0 || m == 0) {  // not a pair of the stripe kernel
+        if (lane == 0) band[pair] = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
+        return;
+    }
+    const uint32_t sum = diag_cost_sum(tab, seqa + d.a_off, seqb + d.b_off, min(n, m), lane);
     if (lane == 0) {
         const uint64_t ub = (uint64_t)sum + (m > n ? (uint64_t)(m - n) * bp.ins : (uint64_t)(n - m) * bp.del);
         band[pair] = sed_band_window(n, m, bp.ins, bp.del, ub);
@@ -3302,8 +1588,7 @@ __global__ __launch_bounds__(256) void sed_cut_band_kernel(const sed_pair_desc *
                                                            const uint32_t *__restrict__ seqb, sed_band *__restrict__ band,
                                                            uint32_t *__restrict__ diag, sed_band_params bp, uint32_t tkey) {
     __shared__ uint32_t tab[16];
-    if (threadIdx.x < 16) tab[threadIdx.x] = bp.cost[threadIdx.x];
-    __syncthreads();
+    diag_cost_table(tab, bp);
     const int lane = threadIdx.x & 63;
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= nlist) return;
@@ -3317,20 +1602,7 @@ __global__ __launch_bounds__(256) void sed_cut_band_kernel(const sed_pair_desc *
         }
         return;
     }
-    const int len = min(n, m), words = (len + 15) >> 4;
-    const uint32_t *pa = seqa + d.a_off, *pb = seqb + d.b_off;
-    uint32_t sum = 0;
-    for (int x = lane; x < words; x += 64) {
-        uint32_t a = pa[x], b = pb[x];
-        const int cnt = min(16, len - 16 * x);
-        for (int u = 0; u < cnt; ++u) {
-            sum += tab[((a & 3u) << 2) | (b & 3u)];
-            a >>= 2;
-            b >>= 2;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const uint32_t sum = diag_cost_sum(tab, seqa + d.a_off, seqb + d.b_off, min(n, m), lane);
     if (lane == 0) {
         const uint64_t gap = m > n ? (uint64_t)(m - n) * bp.ins : (uint64_t)(n - m) * bp.del;
         const uint64_t ub = (uint64_t)sum + gap;
@@ -3510,76 +1782,6 @@ hipError_t sed_launch_i32(const sed_launch &L, const sed_i32_params &prm, bool l
     }
 }
 
-template <int R, bool TB, bool TYPED, bool FULL = false, int SW = 64>
-static hipError_t launch_f64_R(const sed_launch &L, const double *gtab, const sed_f64_params &prm,
-                               const sed_full_out &fo = sed_full_out{}, const int32_t *idx = nullptr, int nidx = 0) {
-    const int items = SW == 64 ? L.npairs : nidx;
-    const int grid = (items * SW + 255) / 256;
-    if (items <= 0) return hipSuccess;
-    SED_LAUNCH((sed_wf_f64_kernel<R, TB, TYPED, FULL, SW>), dim3(grid), dim3(256), 0, L, L.pd, items,
-                       (const uint8_t *)L.seqa, (const uint8_t *)L.seqb, L.tb, L.bnd, L.res, gtab, prm, fo, idx);
-    return hipGetLastError();
-}
-
-// SPLIT (L.ntasks > 0): one 128-thread workgroup per (pair, stripe) task, R = 2 (the default) or 4
-template <bool TB, bool TYPED, bool FULL = false>
-static hipError_t launch_f64_split(const sed_launch &L, const double *gtab, const sed_f64_params &prm,
-                                   const sed_full_out &fo = sed_full_out{}) {
-    if (L.R == 2)
-        SED_LAUNCH((sed_wf_f64_split_kernel<2, TB, TYPED, FULL>), dim3(L.ntasks), dim3(128), 0, L, L.pd, L.tasks,
-                   (const uint8_t *)L.seqa, (const uint8_t *)L.seqb, L.tb, L.bnd, L.res, gtab, prm, fo);
-    else if (L.R == 4)
-        SED_LAUNCH((sed_wf_f64_split_kernel<4, TB, TYPED, FULL>), dim3(L.ntasks), dim3(128), 0, L, L.pd, L.tasks,
-               (const uint8_t *)L.seqa, (const uint8_t *)L.seqb, L.tb, L.bnd, L.res, gtab, prm, fo);
-    return hipGetLastError();
-}
-
-hipError_t sed_launch_f64_full(const sed_launch &L, const double *gtab, const sed_f64_params &prm, bool typed,
-                               const sed_full_out &fo) {
-    if (L.tb || (L.ntasks > 0 ? (L.R != 2 && L.R != 4) : L.R != 4)) return hipErrorInvalidValue;
-    if (L.ntasks > 0)
-        return typed ? launch_f64_split<false, true, true>(L, gtab, prm, fo)
-                     : launch_f64_split<false, false, true>(L, gtab, prm, fo);
-    return typed ? launch_f64_R<4, false, true, true>(L, gtab, prm, fo)
-                 : launch_f64_R<4, false, false, true>(L, gtab, prm, fo);
-}
-
-hipError_t sed_launch_f64(const sed_launch &L, const double *gtab, const sed_f64_params &prm, bool typed) {
-    const bool tb = L.tb != nullptr;
-    if (L.ntasks > 0) {
-        if (L.R != 2 && L.R != 4) return hipErrorInvalidValue;
-        if (typed) return tb ? launch_f64_split<true, true>(L, gtab, prm) : launch_f64_split<false, true>(L, gtab, prm);
-        return tb ? launch_f64_split<true, false>(L, gtab, prm) : launch_f64_split<false, false>(L, gtab, prm);
-    }
-    switch (L.R) {
-#define CASE(RR)                                                                                    \
-    case RR:                                                                                        \
-        if (typed) return tb ? launch_f64_R<RR, true, true>(L, gtab, prm)                           \
-                             : launch_f64_R<RR, false, true>(L, gtab, prm);                         \
-        return tb ? launch_f64_R<RR, true, false>(L, gtab, prm) : launch_f64_R<RR, false, false>(L, gtab, prm);
-        CASE(4) CASE(8)  // (R = 16: 206 VGPRs, 2 waves per SIMD, iupac 5.22-5.25 against 5.04-5.06 ms at R = 8)
-#undef CASE
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t sed_launch_f64_seg(const sed_launch &L, const double *gtab, const sed_f64_params &prm, bool typed,
-                              const int32_t *idx, int nidx) {
-    const bool tb = L.tb != nullptr;
-    const sed_full_out none{};
-    switch (L.R) {
-#define CASE(RR)                                                                                               \
-    case RR:                                                                                                   \
-        if (typed) return tb ? launch_f64_R<RR, true, true, false, 16>(L, gtab, prm, none, idx, nidx)          \
-                             : launch_f64_R<RR, false, true, false, 16>(L, gtab, prm, none, idx, nidx);        \
-        return tb ? launch_f64_R<RR, true, false, false, 16>(L, gtab, prm, none, idx, nidx)                    \
-                  : launch_f64_R<RR, false, false, false, 16>(L, gtab, prm, none, idx, nidx);
-        CASE(4) CASE(8)
-#undef CASE
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t sed_launch_traceback_seg(const sed_launch &L, uint32_t *ops, const int32_t *idx, int nidx) {
     if (nidx <= 0) return hipSuccess;
     const int grid = (nidx + 63) / 64;
@@ -3626,25 +1828,16 @@ hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops) {
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax) {
     // items: map workgroups x 256 of the largest pair, and at least every pair's script words; >= one block
     // (the compose grid: (K-2)(m+1)+1 threads per pair, at most items / 256 / R + 1 blocks, sed_runtime.cpp)
-    const bool bandemit = SED_TBMAP_BANDS && SED_TB_BANDEMIT;
-    const dim3 gmap((max(items, 1) + 255) / 256, L.npairs), gemit(L.npairs, max(kmax, 1) * (bandemit ? L.R : 1)),
+    const dim3 gmap((max(items, 1) + 255) / 256, L.npairs), gemit(L.npairs, max(kmax, 1) * L.R),
         gcomp((max(items, 1) + 255) / 256 / max(L.R, 1) + 1, L.npairs);
     switch (L.R) {
 #define CASE(RR)                                                                                                 \
     case RR: {                                                                                                   \
         const uint64_t pat = L.tb_ladder ? (L.tb_wide ? LadderW<RR>::pat : Ladder<RR>::pat) : 0ull;                                               \
-        if (SED_TBMAP_BANDS) {                                                                                   \
-            hipExtLaunchKernelGGL((sed_tb_bandmap_kernel<RR>), gmap, dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd, L.tb, map, ops, pat); \
-            hipLaunchKernelGGL((sed_tb_bandcompose_kernel<RR>), gcomp, dim3(256), 0, L.stream, L.pd, map);          \
-        } else {                                                                                                 \
-            hipExtLaunchKernelGGL((sed_tb_stripemap_kernel<RR>), gmap, dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd, L.tb, map, ops, pat); \
-        }                                                                                                        \
-        if (bandemit)                                                                                            \
-            hipExtLaunchKernelGGL((sed_tb_bandemit_kernel<RR>), gemit, dim3(64), 0, L.stream, nullptr, L.ev1, 0, L.pd, L.tb, L.res, ops, \
-                                  map, pat);                                                                     \
-        else                                                                                                     \
-            hipExtLaunchKernelGGL((sed_tb_stripeemit_kernel<RR>), gemit, dim3(64), 0, L.stream, nullptr, L.ev1, 0, L.pd, L.tb, L.res, ops, \
-                                  map, pat);                                                                     \
+        hipExtLaunchKernelGGL((sed_tb_bandmap_kernel<RR>), gmap, dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd, L.tb, map, ops, pat); \
+        hipLaunchKernelGGL((sed_tb_bandcompose_kernel<RR>), gcomp, dim3(256), 0, L.stream, L.pd, map);          \
+        hipExtLaunchKernelGGL((sed_tb_bandemit_kernel<RR>), gemit, dim3(64), 0, L.stream, nullptr, L.ev1, 0, L.pd, L.tb, L.res, ops, \
+                              map, pat);                                                                 \
         break;                                                                                                   \
     }
         CASE(2) CASE(4)
@@ -3658,25 +1851,3 @@ hipError_t sed_launch_selftest(uint32_t *d_out, hipStream_t stream) {
     hipLaunchKernelGGL(sed_selftest_kernel, dim3(1), dim3(64), 0, stream, d_out);
     return hipGetLastError();
 }
-#else
-// the checkpoint traceback, in its own translation unit (sed_cktb.hip: built with private arrays kept out of vector
-// registers, so a visit's code words stay separate registers)
-hipError_t sed_launch_traceback_ck(const sed_launch &L, uint32_t *ops, const sed_i32_params &prm) {
-    const dim3 grid(L.npairs), block(64);
-    const uint32_t *a = (const uint32_t *)L.seqa, *b = (const uint32_t *)L.seqb;
-    const sed_band *bd = L.band;
-    switch (L.R) {
-    case 4:
-        SED_LAUNCH(sed_traceback_ck_kernel<4>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
-        break;
-    case 8:
-        SED_LAUNCH(sed_traceback_ck_kernel<8>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
-        break;
-    case 16:
-        SED_LAUNCH(sed_traceback_ck_kernel<16>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif

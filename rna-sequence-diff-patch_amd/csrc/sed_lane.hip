@@ -7,7 +7,7 @@
 // row by row (StringEditDistance.py:185-222 order) with the whole DP row in VGPRs: no DPP, no
 // LDS, no inter-lane traffic; 64 pairs per wave, >= 4 waves per SIMD for 250k pairs.
 //
-// Cell keys are the offset keys of sed_kernels.hip (W = V - i*(kdel - 1) - j*kins + B over
+// Cell keys are the offset keys of sed_i32_keys.h (W = V - i*(kdel - 1) - j*kins + B over
 // V = D << 16 | L << 2 | op), so results (distance, L = script length, canonical op) are
 // identical to the wave kernel's:
 //   LEN:  candidates left, up + 1, diag + perm(costrow, -2, sel) -> v_min3 -> & ~3   (5 VALU)
@@ -16,12 +16,9 @@
 // row-major, and the same lane walks it back from (n, m) to write the canonical script.
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
+#include "sed_dev.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) {
-    return min(min(a, b), c);  // folds to v_min3_u32
-}
 
 template <bool LEN, bool TB>
 __global__ __launch_bounds__(256) void sed_lane_i32_kernel(const sed_pair_desc *__restrict__ pd,
@@ -141,14 +138,6 @@ __global__ __launch_bounds__(256) void sed_lane_i32_kernel(const sed_pair_desc *
 // (W = D - i*delete - j*insert + 0xFFFF; the host checks n*delete + 32*insert <= 0xFFFF and that
 // every substitution is cheaper than delete + insert), so packed 16-bit ops do two cells at once:
 //   perm (P's and Q's update constants in one word) + v_pk_add_u16 + 2 v_pk_min_u16 = 4 VALU / 2 cells.
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));  // v_pk_*_u16 operands
-__device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b));
-}
-__device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b) {
-    return __builtin_bit_cast(uint32_t,
-                              __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
 
 __global__ __launch_bounds__(256) void sed_lane_i32x2_kernel(const sed_pair_desc *__restrict__ pd,
                                                              const int32_t *__restrict__ idx, int nlanes,

@@ -560,7 +560,7 @@ def test_offset_key_eligibility_edges(gpu, case):
 
 
 def test_ladder_rows_and_long_paths(gpu, tables):
-    """Ladder keys (sed_kernels.hip): every rung of the 16-row ladder at the sink (n = 1..48), stripes of
+    """Ladder keys (sed_i32_keys.h): every rung of the 16-row ladder at the sink (n = 1..48), stripes of
     R = 4/8/16, and script lengths past 8192 (L read modulo 8192 inside [max(n,m), n+m])."""
     rng = np.random.default_rng(4242)
     pairs = [("".join(rng.choice(list("ACGU"), size=n)), "".join(rng.choice(list("ACGU"), size=int(m))))

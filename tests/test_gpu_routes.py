@@ -470,7 +470,7 @@ def _same(out, ref, ops_off):
 
 @pytest.mark.parametrize("R,pipeline", [(4, False), (4, True), (16, False)])
 def test_split_handoff_repeated_runs(gpu, tables, R, pipeline):
-    """SPLIT's stripes hand their bottom rows over as 64-bit {epoch tag, value} words (sed_kernels.hip): words of
+    """SPLIT's stripes hand their bottom rows over as 64-bit {epoch tag, value} words (sed_dev.h): words of
     an earlier run carry another epoch and must never be taken for this run's.  One batch run 40 times (results
     after each run), and the one-shot path (its scratch batch refilled per call, epoch restarting at 1), must
     match the oracle every time; the 4096^2 pair is config 2's shape."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static check of the v_dot4 result hazard in libsed.so's gfx950 code object.
 
-The dot-key kernels issue the VOP3P v_dot4_i32_i8 as inline asm (sed_kernels.hip: dot_add), so the compiler's
+The dot-key kernels issue the VOP3P v_dot4_i32_i8 as inline asm (sed_i32_keys.h: dot_add), so the compiler's
 hazard recognizer cannot insert the wait states a VALU reader of its result needs: the very next instruction
 reads a stale value (tools/ubench/dot_dist.hip, profiles/r03/ubench_dot_dist.txt).  Correctness rests on the
 asm ordering (volatile dots issued SED_DOT_AHEAD / 4 rows ahead, dot_fence next to each reader).  This check

@@ -1,5 +1,12 @@
 """Per-kernel register, LDS and scratch use of libsed.so's gfx950 code objects (the AMDGPU metadata notes):
-name, VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes per lane, and the waves per SIMD the VGPR count allows."""
+name, VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes per lane, and the waves per SIMD the VGPR count allows; then
+the kernel's fingerprint: its instruction count and a short hash of its disassembled instruction stream (mnemonics
+and operands as llvm-objdump -d prints them, without addresses and encodings).  Lines are sorted by demangled name,
+so two libraries compare with plain diff:
+
+    python tools/kernel_resources.py [libsed.so [name substring]]
+"""
+import hashlib
 import os
 import re
 import subprocess
@@ -52,6 +59,19 @@ def kernels(text):
     return [r for r in rows if "name" in r and not r["name"].endswith(".kd")]
 
 
+def fingerprints(lib_path):
+    """{kernel symbol: (instruction count, 12 hex digits of the SHA-256 of its instruction lines)}"""
+    with tempfile.TemporaryDirectory() as wd:
+        texts = dot_hazard.disassemble(lib_path, wd)
+    streams = {}
+    for text in texts:
+        for fn, mn, ops in dot_hazard.parse(text):
+            if mn == "...":  # llvm-objdump's mark for a run of zero padding after a code object's last kernel
+                continue
+            streams.setdefault(fn, []).append("%s %s\n" % (mn, ", ".join(ops)))
+    return {fn: (len(lines), hashlib.sha256("".join(lines).encode()).hexdigest()[:12]) for fn, lines in streams.items()}
+
+
 if __name__ == "__main__":
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
         __file__))), "rna-sequence-diff-patch_amd", "libsed.so")
@@ -60,11 +80,13 @@ if __name__ == "__main__":
     filt = os.path.join(LLVM, "llvm-cxxfilt")
     names = subprocess.check_output([filt] if os.path.exists(filt) else ["c++filt"], input="\n".join(
         r["name"] for r in rows), text=True).splitlines() if rows else []
-    for r, nm in zip(rows, names):
+    prints = fingerprints(lib)
+    for nm, r in sorted(zip(names, rows), key=lambda t: t[0]):
         if pat not in nm:
             continue
+        ninst, digest = prints[r["name"]]
         v = r.get("vgpr", 0) + r.get("agpr", 0)
         waves = min(8, 512 // max(8, (v + 7) // 8 * 8)) if v else 8
-        print("%-90s vgpr %3d agpr %3d sgpr %3d lds %6d scratch %4d spill v%d s%d waves/SIMD %d" % (
+        print("%-90s vgpr %3d agpr %3d sgpr %3d lds %6d scratch %4d spill v%d s%d waves/SIMD %d insts %5d hash %s" % (
             nm[:90], r.get("vgpr", 0), r.get("agpr", 0), r.get("sgpr", 0), r.get("lds", 0), r.get("scratch", 0),
-            r.get("vspill", 0), r.get("sspill", 0), waves))
+            r.get("vspill", 0), r.get("sspill", 0), waves, ninst, digest))

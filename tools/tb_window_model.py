@@ -1,4 +1,4 @@
-"""Model of the checkpoint traceback's tile visits (sed_kernels.hip: ck_traceback_pair) on config 4's pairs: the oracle's
+"""Model of the checkpoint traceback's tile visits (sed_cktb.hip: ck_traceback_pair) on config 4's pairs: the oracle's
 canonical path of synthetic 4096 x 4096 pairs (user_costs.json, bench.py's generator) is walked through the kernel's
 visit geometry (stripes of 64 R rows, row groups of 64 rows, chunks of 64 forward steps; R = 16) and each visit is
 priced at 6 VALU per sweep step (the step: DPP add, perm, add, min3, and, alignbit) plus a fixed per-visit setup.

@@ -1,6 +1,6 @@
 // The c4 forward's step (R = 16 rows per lane, dot keys: 16 v_dot4 + 16 dependent v_max3 + the DPP move of the cell
 // above) at full occupancy, against the same work as two independent 8-row chains per step (round 6).
-//   chains 1: the kernel's step (sed_kernels.hip i32_step DOT): row r's max needs row r-1's, and row 0 needs the previous
+//   chains 1: the kernel's step (sed_i32_keys.h i32_step DOT): row r's max needs row r-1's, and row 0 needs the previous
 //             step's row 15 of the lane before (DPP), a 17-deep chain per step.
 //   chains 2: rows 0-7 at column j and rows 8-15 one column behind (j-1): the lower chain's cell above is the upper
 //             chain's row 7 of the previous step, so each step holds two 8-deep chains (+ the DPP) that can interleave.
