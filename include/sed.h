@@ -191,6 +191,24 @@ int sed_batch_split_tasks(const sed_batch *b);        /* SPLIT: workgroups (pair
  * byte, out[9] = decode multiplier / ladder L unit.  Returns A (> 0), 0 when the table has no such factorisation,
  * or SED_E_ARG. */
 int sed_dot_factor(const double *sub, double ins, double del, int maxmin, int ladder_maxsum, uint32_t *out);
+/* The planner, without a device (tests, diagnostics): what sed_batch_create would decide for these costs (as
+ * sed_set_costs takes them), options and pairs (as sed_batch_create takes them), with no context and no HIP call.
+ * options = noptions (key, value) pairs: the SED_OPT_* keys with the values sed_set_option takes, and the
+ * SED_PLAN_ENV_* keys below, which stand for the process environment the runtime reads once (any value).
+ * out[0 .. nout) receives, in this order, what the getters of the created batch would return:
+ *   0 sed_batch_mode, 1 _rows_per_lane, 2 _lane_pairs, 3 _chains, 4 _traceback_mode, 5 _dot_keys, 6 _bitpar_pairs,
+ *   7 _segment_pairs, 8 _split_tasks, 9 _scaled_pairs, 10 _packed_pairs, 11 _dp_launches, 12 _band_cells,
+ *   13 and 14 sed_batch_work's cells and algo_bytes.
+ * Returns SED_OK or the SED_E_* code batch creation would fail with (SED_E_ARG also for a bad option). */
+#define SED_PLAN_ENV_TBPAR 101     /* SED_TBPAR: 0 / 1 overrides the stripe-parallel traceback's rule; unset = -1 */
+#define SED_PLAN_ENV_BAND 102      /* SED_BAND: 0 turns band pruning off; unset = 1 */
+#define SED_PLAN_ENV_ALT_DP 103    /* SED_ALT_DP: 0 keeps every DP on the context's stream; unset = 1 */
+#define SED_PLAN_ENV_CK_HALVES 104 /* SED_CK_HALVES: parts of a checkpoint batch, 1..4; unset = -1 (2 parts) */
+int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                    int del_is_int, const int32_t *options, int noptions,
+                    const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
+                    const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b,
+                    int32_t npairs, uint32_t flags, double *out, int nout);
 int sed_batch_dot_keys(const sed_batch *b);           /* bit 0: the checkpoint forward kernel runs dot keys, bit 1: the
                                                          CHAIN kernel runs ladder dot keys (SED_OPT_DOT), bit 2: over
                                                          the wide ladder (L unit 16) */

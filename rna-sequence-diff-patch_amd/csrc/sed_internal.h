@@ -182,7 +182,7 @@ hipError_t sed_launch_lane_f64(const sed_launch &L, const int32_t *idx, int nidx
 // are exact, so an integer DP of the scaled costs gives D * S exactly (sed_lane.hip: sed_lane_scaled_kernel).
 // row[a] = the 8 bytes (cost(a -> b) * S - ins - del - 1) & 0xFF for b = 0..7 (b = 0..3 in row[a][0]); ins / del
 // scaled; pairs with pd.pad[0] run bit-parallel as in sed_lane_f64_kernel (umap: the 2-bit unit-subset code of every
-// code < 8 at bits 2c).  Byte-coded sequences start 16-byte aligned (fill_batch).
+// code < 8 at bits 2c).  Byte-coded sequences start 16-byte aligned (sed_plan.cpp: plan_layout).
 struct sed_scaled_params {
     uint32_t row[8][2];
     uint32_t ins, del;
@@ -193,6 +193,20 @@ hipError_t sed_launch_lane_scaled(const sed_launch &L, const int32_t *idx, int n
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);
+// A pair's schedule on the wave kernels (SW = 64 lanes a pair, or 16 in the fp64 segments), R rows per lane: nstripes
+// stripes of SW R rows, each SG steps (m + SW - 1 rounded up to whole traceback groups of G = 64/R steps) in nchunks
+// chunks of SW steps.
+struct sed_geom {
+    int nstripes, SG, nchunks;
+};
+__host__ __device__ inline sed_geom sed_stripe_geom(int n, int m, int R, int SW) {
+    const int64_t G = 64 / R, rows = (int64_t)SW * R;
+    sed_geom g;
+    g.nstripes = (int)((n + rows - 1) / rows);
+    g.SG = (int)((m + SW - 1 + G - 1) / G * G);
+    g.nchunks = (g.SG + SW - 1) / SW;
+    return g;
+}
 // Checkpoint layout of the CK forward kernels (R = 4, 8 or 16 rows per lane, G = 64/R steps per group):
 //   column checkpoints, per stripe [nchunks][R + 1][64 lanes]: each lane's R row values and its top_prev
 //   at every 64-step chunk end;
@@ -211,7 +225,7 @@ __host__ __device__ inline uint64_t sed_ck_col_words(int R, int nstripes, int nc
 // served a two-pairs-per-wave traceback of 32-row tiles, measured and dropped in round 3: the forward kernel took
 // 9.87 instead of 9.18-9.32 ms and that traceback 2.43 instead of 2.20 ms (profiles/r03/ab_tb_tiles.jsonl).
 #ifndef SED_CK_HALVES_DEFAULT
-#define SED_CK_HALVES_DEFAULT 2  // checkpoint batches: parts on as many streams, >= 1024 wave pairs each (sed_runtime.cpp)
+#define SED_CK_HALVES_DEFAULT 2  // checkpoint batches: parts on as many streams, >= 1024 wave pairs each (sed_plan.cpp)
 #endif
 #ifndef SED_CK_TILE
 #define SED_CK_TILE 64
@@ -263,8 +277,7 @@ __host__ __device__ inline void sed_band_chunks(int n, int m, int ROWS, int nchu
 // cells of the pair inside its stripes' chunk ranges: rows x (64 (chi - clo)) columns per stripe (the columns every
 // lane computes, as n m counts them for an unpruned pair; a stripe that runs to its last chunk counts up to m)
 __host__ __device__ inline double sed_band_pair_cells(int n, int m, int R, sed_band w) {
-    const int ROWS = 64 * R, G = 64 / R;
-    const int nstripes = (n + ROWS - 1) / ROWS, SG = (m + 63 + G - 1) / G * G, nchunks = (SG + 63) >> 6;
+    const int ROWS = 64 * R, nstripes = sed_stripe_geom(n, m, R, 64).nstripes, nchunks = sed_stripe_geom(n, m, R, 64).nchunks;
     double cells = 0;
     for (int k = 0; k < nstripes; ++k) {
         int clo, chi;

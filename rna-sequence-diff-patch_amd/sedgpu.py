@@ -56,6 +56,11 @@ SED_OPT_SPLITCK = 14
 SED_OPT_ZEROCOPY = 15
 SED_OPT_BAND = 16
 SED_OPT_CUT = 17
+# sed_plan_routes only: the environment knobs the runtime reads once per process, as options of a plan
+SED_PLAN_ENV_TBPAR = 101
+SED_PLAN_ENV_BAND = 102
+SED_PLAN_ENV_ALT_DP = 103
+SED_PLAN_ENV_CK_HALVES = 104
 MODE_NAMES = {1: "i32", 2: "f64", 3: "f64-typed"}
 
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
@@ -82,6 +87,8 @@ SIGNATURES = [
     ("sed_batch_lane_pairs", C.c_int, [C.c_void_p]),
     ("sed_batch_chains", C.c_int, [C.c_void_p]),
     ("sed_batch_dot_keys", C.c_int, [C.c_void_p]),
+    ("sed_plan_routes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                  _u8p, _i64p, _i32p, _u8p, _i64p, _i32p, C.c_int32, C.c_uint32, _f64p, C.c_int]),
     ("sed_dot_factor", C.c_int, [_f64p, C.c_double, C.c_double, C.c_int, C.c_int, _u32p]),
     ("sed_band_bounds", C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _i32p]),
     ("sed_band_chunk_range", C.c_int, [C.c_int32] * 6 + [_i32p]),
@@ -924,6 +931,31 @@ def dot_factor(sub, ins, dele, maxmin=0, ladder_maxsum=0):
         return None
     to_bytes = lambda w: np.frombuffer(np.asarray(w, np.uint32).tobytes(), np.int8).reshape(4, 4).astype(np.int64)
     return A, to_bytes(out[0:4]), to_bytes(out[4:8]), (int(out[8]), int(out[9]))
+
+
+PLAN_ROUTE_FIELDS = ("mode", "rows_per_lane", "lane_pairs", "chains", "traceback_mode", "dot_keys", "bitpar_pairs",
+                     "segment_pairs", "split_tasks", "scaled_pairs", "packed_pairs", "dp_launches", "band_cells", "cells",
+                     "algo_bytes")
+
+
+def plan_routes(costs, options, packed, flags):
+    """The planner without a device (sed_plan_routes): what a Batch of `packed` created under these costs and options
+    would report, as {field: number} over PLAN_ROUTE_FIELDS (counts as ints).  costs = (K, sub, sub_int, ins, ins_int,
+    dele, del_int) as sed_set_costs takes them; options = {SED_OPT_* or SED_PLAN_ENV_*: value}.  Raises SedError
+    carrying the SED_E_* code (.code) batch creation would fail with."""
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    out = np.zeros(len(PLAN_ROUTE_FIELDS), np.float64)
+    rc = load().sed_plan_routes(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
+                                np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
+                                int(del_int), opts, len(options), packed.codes_a, packed.off_a, packed.len_a,
+                                packed.codes_b, packed.off_b, packed.len_b, packed.npairs, flags, out, len(out))
+    if rc != 0:
+        err = SedError("sed_plan_routes failed (%d)" % rc)
+        err.code = rc
+        raise err
+    return {k: (float(v) if k in ("band_cells", "cells", "algo_bytes") else int(v))
+            for k, v in zip(PLAN_ROUTE_FIELDS, out)}
 
 
 def band_bounds(n, m, ins, dele, ub):

@@ -1,4 +1,4 @@
-"""CPU: the signed-byte factorisations behind the dot keys (sed_runtime.cpp: dot_keys, via sed_dot_factor).
+"""CPU: the signed-byte factorisations behind the dot keys (sed_plan.cpp: dot_keys, via sed_dot_factor).
 The checkpoint forward kernel adds dot4(row(a), col(b)) = A*kappa(a, b) + 1 to the diagonal and maximises; the
 CHAIN kernel's ladder keys add -(A*kappa + u - 1) (u = 16 on the wide ladder, else 8).  Checked here for both shipped tables: exact products, byte ranges,
 the ordering bound A > min(n, m) (kmax - kmin) / kmin, the decode multiply-shift, and the ineligible cases."""

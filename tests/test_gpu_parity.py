@@ -533,7 +533,7 @@ def _int_table(ins, dele, sub):
 
 @pytest.mark.parametrize("case", ["sum", "over", "wide", "tight"])
 def test_offset_key_eligibility_edges(gpu, case):
-    """The offset-key kernels need cost <= insert + delete <= 255 (sed_runtime.cpp: i32_eligible) and the
+    """The offset-key kernels need cost <= insert + delete <= 255 (sed_plan.cpp: i32_eligible) and the
     16-bit packed distance keys cost < insert + delete.  At the edges: substitutions costing exactly
     insert + delete stay on the integer kernel (packing off), costlier ones or insert + delete > 255 fall
     back to fp64; every route bit-exact against the oracle (script, length, distance-only packed/unpacked)."""
@@ -824,7 +824,7 @@ def test_fp64_split_forced_over_segments_and_r2_fallback(gpu, tables):
 
 @pytest.mark.parametrize("script", [True, False])
 def test_fp64_split_gate(gpu, tables, script):
-    """The automatic fp64 SPLIT route of <= 256 pairs is gated on its cost model (sed_runtime.cpp: f64_split_pays):
+    """The automatic fp64 SPLIT route of <= 256 pairs is gated on its cost model (sed_plan.cpp: f64_split_pays):
     128 long narrow pairs (2000 x 100, 16 stripes each, whose chains hold the resident workgroups mostly waiting on the
     stripe lag) run one wave per pair; 16 pairs of 1000^2 run SPLIT.  Identical results on both routes, the oracle's
     on a sample."""

@@ -9,6 +9,7 @@ import pytest
 
 from conftest import padding_errors
 import oracle
+import plan_route_cases
 import sedcost
 import sedgpu
 
@@ -357,7 +358,7 @@ def test_headline_config4_route(gpu, tables):
     A, B = [A[i] for i in order], [B[i] for i in order]
     la = np.array([len(x) for x in A], np.float64)
     lb = np.array([len(x) for x in B], np.float64)
-    assert (la * lb).sum() >= 512 * (la + lb).sum()  # the automatic checkpoint rule (sed_runtime.cpp: b->ck)
+    assert (la * lb).sum() >= 512 * (la + lb).sum()  # the automatic checkpoint rule (sed_plan.cpp: plan_traceback)
     assert np.minimum(la, lb).max() < 4320 and (np.minimum(la, lb) > 4096).sum() == 6
     plan = _plan(tables[True])
     gpu.set_costs(plan)
@@ -696,7 +697,7 @@ def test_checkpoint_two_residency_rounds_every_pair(gpu, tables):
     A, B = _ragged(5800, 5600, 1000, 1500, 1000, 1500)
     la = np.array([len(x) for x in A], np.float64)
     lb = np.array([len(x) for x in B], np.float64)
-    assert (la * lb).sum() >= 512 * (la + lb).sum()  # the automatic checkpoint rule (sed_runtime.cpp: b->ck)
+    assert (la * lb).sum() >= 512 * (la + lb).sum()  # the automatic checkpoint rule (sed_plan.cpp: plan_traceback)
     plan = _plan(tables[True])
     gpu.set_costs(plan)
     packed = sedgpu.PackedPairs(A, B)
@@ -707,3 +708,34 @@ def test_checkpoint_two_residency_rounds_every_pair(gpu, tables):
     finally:
         b.close()
     _check_all(plan, packed, d, ii, ln, ops)
+
+
+@pytest.mark.parametrize("name", plan_route_cases.GPU_NAMES)
+def test_getters_agree_with_the_device_free_planner(gpu, name):
+    """A created batch (nothing runs) reports through every sed_batch_* getter what sed_plan_routes computes for the
+    same costs, options and pairs without a device: one fill per family of routes (tests/plan_route_cases.py)."""
+    case = plan_route_cases.Case(name)
+    K, sub, sub_int, ins, ins_int, dele, del_int = case.costs
+    gpu.invalidate_costs()  # (set below past the Context's cache)
+    assert gpu._lib.sed_set_costs(gpu.ptr, K, sub, sub_int, ins, ins_int, dele, del_int) == 0
+    want = sedgpu.plan_routes(case.costs, case.options, case.packed, case.flags)
+    for k, v in case.options.items():
+        gpu.set_option(k, v)
+    try:
+        b = sedgpu.Batch(gpu, case.packed, bool(case.flags & sedgpu.SED_WANT_SCRIPT),
+                         pipeline=bool(case.flags & sedgpu.SED_PIPELINE), no_len=bool(case.flags & sedgpu.SED_NO_LEN))
+        try:
+            lib = gpu._lib
+            cells, algo_bytes = b.work()
+            got = {"mode": lib.sed_batch_mode(b.ptr), "rows_per_lane": b.rows_per_lane, "lane_pairs": b.lane_pairs,
+                   "chains": b.chains, "traceback_mode": b.traceback_mode, "dot_keys": lib.sed_batch_dot_keys(b.ptr),
+                   "bitpar_pairs": b.bitpar_pairs, "segment_pairs": b.segment_pairs, "split_tasks": b.split_tasks,
+                   "scaled_pairs": b.scaled_pairs, "packed_pairs": b.packed_pairs, "dp_launches": b.dp_launches,
+                   "band_cells": b.band_cells, "cells": cells, "algo_bytes": algo_bytes}
+        finally:
+            b.close()
+    finally:
+        for k in case.options:
+            gpu.set_option(k, 0)
+        gpu.invalidate_costs()
+    assert got == want

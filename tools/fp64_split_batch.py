@@ -1,5 +1,5 @@
-"""fp64 batches of many long pairs: the automatic route (SPLIT for <= 256 pairs with wave pairs, sed_runtime.cpp
-fill_batch) against SPLIT forced (SED_OPT_SPLIT = 1) and one wave per pair (= 2).  Random IUPAC pairs of equal length
+"""fp64 batches of many long pairs: the automatic route (SPLIT for <= 256 pairs with wave pairs, sed_plan.cpp
+plan_mode) against SPLIT forced (SED_OPT_SPLIT = 1) and one wave per pair (= 2).  Random IUPAC pairs of equal length
 under costs.json, P pairs per batch, scripts and distances with length (many-pair fp64 batches, e.g.
 wf_scores with user costs against a few hundred long documents).  Prints one line per (P, length, flags) with the
 median engine time of 5 calls and SPLIT's task count.
