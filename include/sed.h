@@ -110,6 +110,10 @@ enum {
                                    SPLIT: the wave pairs leave the two-pairs-per-wave and CHAIN routes for the windowed
                                    stripe kernel: 0 auto (when the window keeps < 2/3 of their cells; pairs already on the
                                    stripe kernel whenever it skips any), 1 whenever eligible, 2 never (filter only) */
+#define SED_OPT_FIT_CHUNK 18    /* fit search (sed_fit_search): owned text columns per lane: 0 auto, else the chunk length
+                                   (tests and A/Bs; a value >= every text's length + 1 is one lane per text).  An
+                                   option of sed_fit_search / sed_fit_plan only: sed_plan_routes, which plans batches,
+                                   refuses it */
 #define SED_OPT_DEBUG_CORRUPT 9 /* testing only: p + 1 overwrites one checkpoint word of pair p before its traceback,
                                    which must then fail with SED_E_DEVICE naming the pair; 0 off */
 
@@ -289,6 +293,40 @@ int sed_batch_export(sed_batch *b, uint64_t d_dist, uint64_t d_len, uint64_t d_o
 /* Algorithmic counts of one run: DP cells (sum n*m, nominal: pruned cells count too) and HBM bytes (inputs +
  * traceback + outputs; with band pruning the checkpoints of the chunks that run). */
 int sed_batch_work(const sed_batch *b, double *cells, double *algo_bytes);
+
+/* Fit search (an extension; the reference has no such function): the best approximate occurrence of a short pattern
+ * in each text, blocking, under the costs of sed_set_costs.
+ * Pair q: pattern p = codes_p[off_p[q] .. +len_p[q]) of length P, 1 <= P <= 32, text t = codes_t[off_t[q] .. +len_t[q])
+ * of length n >= 0; pairs may share patterns and texts through the offsets (Q queries x D documents with one copy of
+ * each).  G(s, e) = the distance wagnerFisher(p, t[s:e]) gives (str1 = the pattern, str2 = the substring, the direction
+ * of wf_score(query, doc)).  The hit of a pair is (dist, start, end):
+ *   dist  = min over 0 <= s <= e <= n of G(s, e)  (the empty substring is allowed, so dist <= P * delete);
+ *   end   = the smallest e for which some s gives dist;
+ *   start = the largest s with G(s, end) = dist   (the tightest window ending earliest).
+ * It is the sink scan of the DP with borders D[0][j] = 0, D[i][0] = i * delete and the reference's recurrence, every
+ * cell carrying (D, -s) as one lexicographic key: the first strict minimum of row P over j.
+ * Cost models served (anything else: SED_E_RANGE, the text says which condition failed; there is no fallback):
+ *   at most 8 symbols (K <= 8); some S = 2^k, k <= 8, makes insert, delete and every substitution cost an integer in
+ *   0..255 with (insert + delete) * S <= 255 and P * delete * S <= 65535; a lane's text columns fit 16 bits (a text runs
+ *   in chunks of at most 65535 - W columns, W = P + floor(P * delete / insert); with insert = 0 a text runs as one
+ *   chunk, n <= 65534).  For such tables every fp64 sum of the reference is exact, so out_dist = D / S equals the sink
+ *   value of wagnerFisher(p, t[start:end]) as a number.  No is_int is reported: callers who need the typed value or
+ *   the script run the window through sed_run_batch.
+ * Errors: SED_E_ARG (NULL, negative length, a code >= K), SED_E_STATE (no costs set, or a pair in flight after
+ * sed_pair_submit), SED_E_RANGE as above.  SED_OPT_FIT_CHUNK sets the chunk length. */
+int sed_fit_search(sed_ctx *ctx,
+                   const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                   const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
+                   int32_t npairs, double *out_dist, int32_t *out_start, int32_t *out_end);
+/* What sed_fit_search would decide, without a device: the code it would return for these costs (as sed_set_costs takes
+ * them), options (as sed_plan_routes takes them) and lengths, and out[0 .. nout) = 0 the scale S, 1 W (-1 when
+ * insert = 0), 2 the chunk length (0 = one lane per text), 3 lanes, 4 cells computed (P x columns, warm-up included),
+ * 5 nominal cells (sum P * n). */
+int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                 double del, int del_is_int, const int32_t *options, int noptions,
+                 const int32_t *len_p, const int32_t *len_t, int32_t npairs, double *out, int nout);
+/* Device time of the last sed_fit_search's kernel, from HIP events (ms); SED_E_STATE before the first search. */
+int sed_fit_last_time(const sed_ctx *ctx, float *kernel_ms);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

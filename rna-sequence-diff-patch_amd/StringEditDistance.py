@@ -724,6 +724,23 @@ def distance_deepen(strs1, strs2, k, first, last, userCosts=False, plan=None):
     return [int(d) if t else float(d) for d, t in zip(dist.tolist(), is_int.tolist())], cuts
 
 
+def fit_batch(patterns, texts, userCosts=False):
+    """[(dist, start, end)] for each (pattern, text): the smallest wagnerFisher(pattern, text[start:end]) value over
+    all substrings of the text (the empty one included), for the occurrence that ends earliest and, among those, starts
+    latest — one GPU launch (sedgpu.Context.fit).  Patterns have 1..32 symbols; the engine serves dyadic cost tables
+    over at most 8 symbols and raises SedError otherwise (include/sed.h: sed_fit_search).  dist is a float (no int
+    typing: run the window through wagnerFisher for the reference's typed value).  Same KeyErrors as the reference
+    would raise for (pattern, text)."""
+    patterns, texts = list(patterns), list(texts)
+    plan = batch_plan(patterns, texts, userCosts)
+    if not patterns:
+        return []
+    ctx = sedgpu.context()
+    ctx.set_costs(plan)
+    dist, start, end = ctx.fit(_packed(plan, patterns, texts))
+    return list(zip(dist.tolist(), start.tolist(), end.tolist()))
+
+
 def edit_script_batch(strs1, strs2, userCosts=False):
     """[(value, generate_es(create_paths(dp)[0], s1, s2))] for each pair — one GPU launch."""
     strs1, strs2 = list(strs1), list(strs2)

@@ -190,6 +190,25 @@ struct sed_scaled_params {
     uint32_t umask, umap;
 };
 hipError_t sed_launch_lane_scaled(const sed_launch &L, const int32_t *idx, int nidx, const sed_scaled_params &sp);
+// Fit search (sed_fit.hip: sed_fit_kernel; include/sed.h: sed_fit_search).  One lane per (pair, chunk): it owns the
+// text columns [c0, c0 + cnt) of its pair and starts `lead` columns before c0 at the border column, which is symbol
+// 4 tw of the packed text buffer (every text starts 4-byte aligned and lead is rounded up so the lane does too); it
+// runs nsteps columns after the border column.  pat = the pair's pattern record (32 byte codes, the pattern
+// right-aligned, code 8 in front).  row[a] = the 8 bytes kappa(a -> b) = insert + delete - min(cost(a -> b), insert +
+// delete) on the integer scale, b = 0..3 in row[a][0].  out[pair] = min over the pair's lanes of
+// D << 48 | end << 16 | (end - start), preset to all ones.
+struct sed_fit_lane {
+    uint32_t tw;
+    int32_t pair, pat, plen;
+    int32_t nsteps, lead, cnt, c0;
+};
+struct sed_fit_params {
+    uint32_t row[8][2];
+    uint32_t ins, del;
+};
+#define SED_FIT_BLOCK 64
+hipError_t sed_launch_fit(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_lane *lanes, int nlanes,
+                          const void *pats, const void *text, unsigned long long *out, const sed_fit_params &fp);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

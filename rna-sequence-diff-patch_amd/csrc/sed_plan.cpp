@@ -1071,6 +1071,7 @@ const OptSpec opt_table[] = {
     {SED_OPT_CHAIN_WAVES, &sed_opts::chain_waves, 0, INT_MAX},
     {SED_OPT_CUT, &sed_opts::cut, 0, 2},
     {SED_OPT_BAND, &sed_opts::band, V(0, 2), 0},
+    {SED_OPT_FIT_CHUNK, &sed_opts::fit_chunk, 0, INT_MAX},
     {SED_OPT_DEBUG_CORRUPT, &sed_opts::debug_corrupt, 0, INT_MAX},
     {SED_OPT_CHAIN, &sed_opts::chain, 0, 1024},
     {SED_OPT_ROWS_PER_LANE, &sed_opts::R, V(0, 1, 2) | V(4, 8, 16) | V(32), 0},
@@ -1107,6 +1108,94 @@ bool sed_simple_typing(const sed_costs &c) {
         if (c.sub_int[e] ? c.sub[e] != 0 : !(c.sub[e] > 0)) return false;
     }
     return true;
+}
+
+// ---- fit search ----
+// The device the auto chunk rule sizes for: 256 CUs x 4 SIMDs, 64 lanes a wave.  One lane per text is kept when that
+// alone gives every SIMD SED_FIT_ENOUGH_WAVES waves; else the chunk is the length that gives SED_FIT_TARGET_WAVES, but
+// never below W (a lane's warm-up is W columns, so warm-up stays at most half of its work).
+#define SED_FIT_SIMDS 1024
+#define SED_FIT_ENOUGH_WAVES 2
+#define SED_FIT_TARGET_WAVES 4
+#define SED_FIT_MAX_SPAN 65535  // columns of one lane, border column included: the 16-bit start field
+
+int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                       sed_fit_plan_t *plan, std::string *err) {
+    if (npairs < 0 || (npairs > 0 && (!len_p || !len_t))) return fail(err, SED_E_ARG, "bad fit arguments");
+    if (c.K > 8) return fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
+    int pmax = 0;
+    for (int p = 0; p < npairs; ++p) {
+        if (len_t[p] < 0) return fail(err, SED_E_ARG, "pair %d: negative text length", p);
+        if (len_p[p] < 1 || len_p[p] > SED_LANE_MAXM)
+            return fail(err, SED_E_RANGE, "fit search: pair %d: pattern length %d outside 1..%d", p, len_p[p], SED_LANE_MAXM);
+        pmax = std::max(pmax, len_p[p]);
+    }
+    // the smallest S = 2^k, k <= 8, that makes every cost an integer in 0..255
+    int k = 0;
+    for (;; ++k) {
+        if (k > 8)
+            return fail(err, SED_E_RANGE, "fit search: the costs are not all multiples of 2^-k in 0..255 * 2^-k for any k <= 8");
+        const double S = std::ldexp(1.0, k);
+        auto integral = [&](double v) { const double x = v * S; return x == std::floor(x) && x >= 0 && x < 1e9; };
+        auto byte = [&](double v) { return integral(v) && v * S <= 255; };
+        bool ok = byte(c.ins) && integral(c.del);  // (delete's range is reported below, with P)
+        for (int e = 0; e < c.K * c.K && ok; ++e) ok = byte(c.sub[e]);
+        if (ok) break;
+    }
+    const double S = std::ldexp(1.0, k);
+    const double insS = c.ins * S, delS = c.del * S;
+    if ((double)pmax * delS > 65535.0)
+        return fail(err, SED_E_RANGE, "fit search: P * delete * S = %d * %g exceeds 65535", pmax, delS);
+    if (delS > 255.0) return fail(err, SED_E_RANGE, "fit search: delete * S = %g exceeds 255", delS);
+    if (insS + delS > 255.0)
+        return fail(err, SED_E_RANGE, "fit search: (insert + delete) * S = %g exceeds 255 (the update addend's byte)", insS + delS);
+    const uint32_t ins = (uint32_t)insS, del = (uint32_t)delS;
+    plan->scale_log2 = k;
+    plan->fp = sed_fit_params{};
+    plan->fp.ins = ins;
+    plan->fp.del = del;
+    for (int a = 0; a < c.K; ++a)
+        for (int b = 0; b < c.K; ++b) {
+            const uint32_t v = std::min((uint32_t)(c.sub[a * c.K + b] * S), ins + del);
+            plan->fp.row[a][b >> 2] |= (ins + del - v) << (8 * (b & 3));
+        }
+    plan->W = ins ? pmax + (int64_t)pmax * del / ins : -1;
+    // the chunk length
+    double cols = 0;
+    for (int p = 0; p < npairs; ++p) cols += (double)len_t[p] + 1;
+    int64_t chunk = 0;
+    if (ins && o.fit_chunk > 0)
+        chunk = o.fit_chunk;
+    else if (ins && npairs > 0 && npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * 64) {
+        chunk = (int64_t)std::ceil(cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * 64));
+        chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
+    }
+    if (ins && o.fit_chunk == 0)  // texts too long for one lane's start field are always split
+        for (int p = 0; p < npairs; ++p)
+            if ((int64_t)len_t[p] + 1 > SED_FIT_MAX_SPAN && (chunk == 0 || chunk + plan->W + 3 > SED_FIT_MAX_SPAN))
+                chunk = SED_FIT_MAX_SPAN - plan->W - 3;
+    plan->chunk = 0;
+    plan->first.assign((size_t)npairs + 1, 0);
+    plan->cells = plan->nominal = 0;
+    bool split = false;
+    for (int p = 0; p < npairs; ++p) {
+        const int64_t ncol = (int64_t)len_t[p] + 1;
+        const int64_t nl = chunk > 0 ? (ncol + chunk - 1) / chunk : 1;
+        split = split || nl > 1;
+        if ((nl > 1 ? chunk + plan->W + 3 : ncol) > SED_FIT_MAX_SPAN)
+            return fail(err, SED_E_RANGE, "fit search: pair %d: a lane would span more than %d text columns%s", p,
+                        SED_FIT_MAX_SPAN, ins ? "" : " (insert = 0: a text runs as one chunk)");
+        plan->first[p + 1] = plan->first[p] + nl;
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t c0 = l * chunk, c1 = nl > 1 ? std::min(ncol, c0 + chunk) : ncol;
+            plan->cells += (double)len_p[p] * (double)(c1 - 1 - (c0 - sed_fit_lead(plan->W, c0)));
+        }
+        plan->nominal += (double)len_p[p] * (double)len_t[p];
+    }
+    plan->lanes = plan->first[npairs];
+    if (plan->lanes > INT_MAX) return fail(err, SED_E_RANGE, "fit search: %lld lanes", (long long)plan->lanes);
+    plan->chunk = split || o.fit_chunk > 0 ? (int32_t)std::min<int64_t>(chunk, INT_MAX) : 0;
+    return SED_OK;
 }
 
 sed_band_params sed_band_params_from(const sed_costs &c) {
@@ -1182,8 +1271,8 @@ int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins
     c.ins_int = ins_is_int ? 1 : 0;
     c.del_int = del_is_int ? 1 : 0;
     sed_opts o;
-    for (int i = 0; i < noptions; ++i)
-        if (!sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    for (int i = 0; i < noptions; ++i)  // (SED_OPT_FIT_CHUNK is no option of a batch: sed_fit_plan takes it)
+        if (options[2 * i] == SED_OPT_FIT_CHUNK || !sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
     sed_plan p;
     const int rc = sed_plan_batch(c, o, codes_a, off_a, len_a, codes_b, off_b, len_b, npairs, flags, &p, nullptr);
     if (rc != SED_OK) return rc;
@@ -1191,6 +1280,32 @@ int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins
                         (double)sed_plan_traceback_mode(p), (double)sed_plan_dot_keys(p), (double)sed_plan_bitpar_pairs(p),
                         (double)p.nseg, (double)sed_plan_split_tasks(p), (double)sed_plan_scaled_pairs(p),
                         (double)sed_plan_packed_pairs(p, false), (double)p.nparts, p.band_cells, p.cells, p.algo_bytes};
+    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}
+
+int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                 const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                 double *out, int nout) {
+    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options) || nout < 0 || (nout && !out)) return SED_E_ARG;
+    if (!std::isfinite(ins) || !std::isfinite(del)) return SED_E_ARG;
+    for (int e = 0; e < K * K; ++e)
+        if (!std::isfinite(sub[e])) return SED_E_ARG;
+    sed_costs c;
+    c.K = K;
+    c.sub.assign(sub, sub + K * K);
+    if (sub_int) c.sub_int.assign(sub_int, sub_int + K * K);
+    c.ins = ins;
+    c.del = del;
+    c.ins_int = ins_is_int ? 1 : 0;
+    c.del_int = del_is_int ? 1 : 0;
+    sed_opts o;
+    for (int i = 0; i < noptions; ++i)
+        if (!sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = sed_fit_plan_batch(c, o, len_p, len_t, npairs, &p, nullptr);
+    if (rc != SED_OK) return rc;
+    const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal};
     for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
     return SED_OK;
 }

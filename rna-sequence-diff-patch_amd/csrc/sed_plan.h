@@ -34,6 +34,7 @@ struct sed_opts {
                             // optimal path reaches), 2 never
     int cut = 0;            // SED_OPT_CUT: cutoff batches' wave pairs: 0 auto (the windowed stripe kernel when it
                             // should pay), 1 whenever eligible, 2 never (filter only)
+    int fit_chunk = 0;      // SED_OPT_FIT_CHUNK: fit search, owned text columns per lane: 0 auto, else the chunk length
     int env_tbpar = -1;     // SED_TBPAR: 0/1 overrides the stripe-parallel traceback's rule (A/B), -1 unset
     int env_band = 1;       // SED_BAND: 0 turns band pruning off (A/B through bench.py)
     int env_alt_dp = 1;     // SED_ALT_DP: 0 keeps every DP on the context's stream (A/B)
@@ -119,6 +120,26 @@ int sed_plan_batch(const sed_costs &c, const sed_opts &o, const uint8_t *codes_a
 void sed_pack_sequences(const sed_plan &plan, const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
                         const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b, std::vector<uint32_t> &ha,
                         std::vector<uint32_t> &hb);
+
+// Fit search (include/sed.h: sed_fit_search): what it decides from the cost model, the options and the pairs' lengths.
+// Pair p's lanes are first[p] .. first[p + 1); lane k of a pair owns text columns [k chunk, min((k + 1) chunk, n + 1))
+// (chunk = 0: the pair's one lane owns them all) and starts sed_fit_lead(W, c0) columns before its first.
+struct sed_fit_plan_t {
+    int scale_log2 = 0;      // S = 2^scale_log2
+    int64_t W = 0;           // P + floor(P delete / insert) over the batch's longest pattern; -1 when insert = 0
+    int32_t chunk = 0;       // owned columns per lane; 0 = one lane per text
+    int64_t lanes = 0;
+    double cells = 0, nominal = 0;  // P x columns computed (warm-up included), and sum P n
+    std::vector<int64_t> first;
+    sed_fit_params fp{};
+};
+int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                       sed_fit_plan_t *plan, std::string *err);
+// columns a lane that owns [c0, ...) starts before c0: min(c0, W) rounded up so that c0 - lead is a multiple of 4
+inline int32_t sed_fit_lead(int64_t W, int64_t c0) {
+    const int64_t jb = c0 <= W ? 0 : (c0 - W) & ~(int64_t)3;
+    return (int32_t)(c0 - jb);
+}
 
 bool sed_simple_typing(const sed_costs &c);  // a cell's value is an int exactly when it equals 0
 sed_band_params sed_band_params_from(const sed_costs &c);

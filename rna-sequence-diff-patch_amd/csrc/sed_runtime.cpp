@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -82,6 +83,10 @@ struct sed_ctx {
     size_t pin_cap = 0;
     bool pin_busy = false;  // a copy from / to `pin` may still be in flight on `stream`
     bool pair_pending = false;  // sed_pair_submit enqueued the scratch batch; sed_pair_wait has not fetched it
+    // fit search (sed_fit_search): its device arrays and the events around its kernel, kept across calls
+    DevBuf fit_text, fit_pat, fit_lanes, fit_out;
+    hipEvent_t fit_ev[2] = {nullptr, nullptr};
+    bool fit_timed = false;
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -800,6 +805,9 @@ void sed_destroy(sed_ctx *c) {
     if (c->pin) (void)hipHostFree(c->pin);
     c->gtab.release();
     c->selftest.release();
+    c->fit_text.release(); c->fit_pat.release(); c->fit_lanes.release(); c->fit_out.release();
+    for (hipEvent_t e : c->fit_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1250,6 +1258,112 @@ int sed_pair_wait(sed_ctx *c, double *out_dist, uint8_t *out_is_int, int32_t *ou
     const bool script = (c->scratch->plan.flags & SED_WANT_SCRIPT) != 0;
     return fetch_results(c->scratch, out_dist, out_is_int, out_len ? out_len : &len, script ? out_ops : nullptr,
                          script && out_ops ? &off : nullptr);
+}
+
+// Fit search.  The planner decides scale, window and lanes from the lengths (sed_plan.cpp: sed_fit_plan_batch); here the
+// distinct patterns become 32-byte records (right-aligned, code 8 in front) and the distinct texts one buffer in which
+// each starts 4-byte aligned, so pairs that share a pattern or a text through their offsets share its copy.
+int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p, const uint8_t *codes_t,
+                   const int64_t *off_t, const int32_t *len_t, int32_t npairs, double *out_dist, int32_t *out_start,
+                   int32_t *out_end) {
+    if (!c) return SED_E_ARG;
+    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
+    if (npairs < 0 || (npairs > 0 && (!codes_p || !off_p || !len_p || !codes_t || !off_t || !len_t || !out_dist ||
+                                      !out_start || !out_end)))
+        return c->fail(SED_E_ARG, "bad fit arguments");
+    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
+    (void)hipSetDevice(c->device);
+    sed_fit_plan_t plan;
+    int rc = sed_fit_plan_batch(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err);
+    if (rc != SED_OK || npairs == 0) return rc;
+    const int K = c->costs.K;
+    struct Span {
+        int64_t off;
+        int32_t len;
+        bool operator==(const Span &o) const { return off == o.off && len == o.len; }
+    };
+    struct SpanHash {
+        size_t operator()(const Span &s) const { return std::hash<int64_t>()(s.off * 0x9E3779B97F4A7C15ll + s.len); }
+    };
+    std::unordered_map<Span, int64_t, SpanHash> pat_of, text_of;
+    std::vector<uint8_t> pats, text;
+    std::vector<sed_fit_lane> lanes((size_t)plan.lanes);
+    for (int p = 0; p < npairs; ++p) {
+        if (off_p[p] < 0 || off_t[p] < 0) return c->fail(SED_E_ARG, "pair %d: negative offset", p);
+        const int P = len_p[p], n = len_t[p];
+        auto pi = pat_of.find(Span{off_p[p], P});
+        if (pi == pat_of.end()) {
+            pi = pat_of.emplace(Span{off_p[p], P}, (int64_t)(pats.size() / SED_LANE_MAXM)).first;
+            pats.resize(pats.size() + SED_LANE_MAXM, 8);
+            uint8_t *rec = pats.data() + pats.size() - P;
+            for (int i = 0; i < P; ++i) {
+                rec[i] = codes_p[off_p[p] + i];
+                if (rec[i] >= K) return c->fail(SED_E_ARG, "pair %d: pattern code %d outside the alphabet (K=%d)", p, rec[i], K);
+            }
+        }
+        auto ti = text_of.find(Span{off_t[p], n});
+        if (ti == text_of.end()) {
+            ti = text_of.emplace(Span{off_t[p], n}, (int64_t)(text.size() / 4)).first;
+            const size_t at = text.size();
+            text.resize(at + (((size_t)n + 3) & ~(size_t)3), 0);
+            uint8_t top = 0;
+            for (int j = 0; j < n; ++j) top |= (text[at + j] = codes_t[off_t[p] + j]) >= K ? 0x80 : 0;
+            if (top) return c->fail(SED_E_ARG, "pair %d: a text code is outside the alphabet (K=%d)", p, K);
+            if (text.size() / 4 > 0xFFFFFFF0u) return c->fail(SED_E_RANGE, "fit search: more than 16 GB of text");
+        }
+        const int64_t ncol = (int64_t)n + 1, nl = plan.first[p + 1] - plan.first[p];
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t c0 = l * plan.chunk, c1 = nl > 1 ? std::min(ncol, c0 + plan.chunk) : ncol;
+            const int32_t lead = sed_fit_lead(plan.W, c0);
+            sed_fit_lane &ln = lanes[(size_t)(plan.first[p] + l)];
+            ln.tw = (uint32_t)(ti->second + (c0 - lead) / 4);
+            ln.pair = p;
+            ln.pat = (int32_t)pi->second;
+            ln.plen = P;
+            ln.nsteps = (int32_t)(c1 - 1 - (c0 - lead));
+            ln.lead = lead;
+            ln.cnt = (int32_t)(c1 - c0);
+            ln.c0 = (int32_t)c0;
+        }
+    }
+    text.resize(text.size() + 16, 0);  // (a lane reads one word past its last)
+    if (!c->fit_text.reserve(text.size()) || !c->fit_pat.reserve(pats.size()) ||
+        !c->fit_lanes.reserve(lanes.size() * sizeof(sed_fit_lane)) || !c->fit_out.reserve(8 * (size_t)npairs))
+        return c->fail(SED_E_OOM, "device allocation failed (fit search, %zu text bytes)", text.size());
+    hipError_t e = hipSuccess;
+    for (hipEvent_t &ev : c->fit_ev)
+        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
+    c->fit_timed = false;
+    std::vector<uint64_t> keys((size_t)npairs);
+    if ((e = hipMemcpyAsync(c->fit_text.p, text.data(), text.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(c->fit_pat.p, pats.data(), pats.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(c->fit_lanes.p, lanes.data(), lanes.size() * sizeof(sed_fit_lane), hipMemcpyHostToDevice,
+                            c->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->fit_out.p, 0xFF, 8 * (size_t)npairs, c->stream)) != hipSuccess)
+        return c->hipfail(e, "upload (fit search)");
+    if ((e = sed_launch_fit(c->stream, c->fit_ev[0], c->fit_ev[1], (const sed_fit_lane *)c->fit_lanes.p, (int)lanes.size(),
+                            c->fit_pat.p, c->fit_text.p, (unsigned long long *)c->fit_out.p, plan.fp)) != hipSuccess)
+        return c->hipfail(e, "fit kernel launch");
+    if ((e = hipMemcpyAsync(keys.data(), c->fit_out.p, 8 * (size_t)npairs, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+        return c->hipfail(e, "download (fit search)");
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit kernel execution");
+    c->fit_timed = true;
+    const double inv = std::ldexp(1.0, -plan.scale_log2);
+    for (int p = 0; p < npairs; ++p) {
+        const uint64_t k = keys[p];
+        const int64_t end = (int64_t)((k >> 16) & 0xFFFFFFFFu), len = (int64_t)(k & 0xFFFFu);
+        if (k == ~0ull || end > len_t[p] || len > end) return c->fail(SED_E_DEVICE, "pair %d: no fit result from the device", p);
+        out_dist[p] = (double)(k >> 48) * inv;
+        out_end[p] = (int32_t)end;
+        out_start[p] = (int32_t)(end - len);
+    }
+    return SED_OK;
+}
+
+int sed_fit_last_time(const sed_ctx *c, float *kernel_ms) {
+    if (!c || !kernel_ms) return SED_E_ARG;
+    if (!c->fit_timed) return SED_E_STATE;
+    return hipEventElapsedTime(kernel_ms, c->fit_ev[0], c->fit_ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
 }
 
 int sed_full_matrix(sed_ctx *c, const uint8_t *codes_a, int32_t n, const uint8_t *codes_b, int32_t m, double *D,

@@ -56,6 +56,7 @@ SED_OPT_SPLITCK = 14
 SED_OPT_ZEROCOPY = 15
 SED_OPT_BAND = 16
 SED_OPT_CUT = 17
+SED_OPT_FIT_CHUNK = 18
 # sed_plan_routes only: the environment knobs the runtime reads once per process, as options of a plan
 SED_PLAN_ENV_TBPAR = 101
 SED_PLAN_ENV_BAND = 102
@@ -119,6 +120,10 @@ SIGNATURES = [
     ("sed_batch_device_results", C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint64)] * 5),
     ("sed_batch_export", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]),
     ("sed_batch_work", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("sed_fit_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
+    ("sed_fit_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                               _i32p, _i32p, C.c_int32, _f64p, C.c_int]),
+    ("sed_fit_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -267,6 +272,25 @@ class Context:
             return dist, is_int, ln, hits, cuts
         finally:
             batch.close()
+
+    def fit(self, packed):
+        """Fit search (sed_fit_search): packed = PackedPairs with the patterns (1..32 symbols) as side a and the texts
+        as side b.  Returns (dist f64[], start i32[], end i32[]): for each pair the smallest distance of the pattern to
+        any substring text[start:end], the occurrence ending earliest and, among those, the shortest."""
+        np_ = packed.npairs
+        dist = np.zeros(max(np_, 1), np.float64)
+        start = np.zeros(max(np_, 1), np.int32)
+        end = np.zeros(max(np_, 1), np.int32)
+        rc = self._lib.sed_fit_search(self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.codes_b,
+                                      packed.off_b, packed.len_b, np_, dist, start, end)
+        self._check(rc, "sed_fit_search")
+        return dist[:np_], start[:np_], end[:np_]
+
+    def fit_last_ms(self):
+        """Device time of the last fit()'s kernel (ms, HIP events)."""
+        ms = C.c_float()
+        self._check(self._lib.sed_fit_last_time(self.ptr, C.byref(ms)), "sed_fit_last_time")
+        return ms.value
 
     def run_pair(self, codes_a, codes_b, want_script, no_len=False):
         """One pair (codes as bytes): (dist, is_int, len, ops u32[] | None) through sed_run_pair, the per-call path of
@@ -680,6 +704,9 @@ class EngineClient:
     def deepen(self, packed, k, first, last, no_len=True):
         return self._call("deepen", packed, k, first, last, no_len)
 
+    def fit(self, packed):
+        return self._call("fit", packed)
+
     def full_matrix(self, codes_a, codes_b):
         return self._call("full_matrix", np.asarray(codes_a, np.uint8), np.asarray(codes_b, np.uint8))
 
@@ -743,6 +770,8 @@ def _serve(rx, tx, device, pooled=False):
                 val = ctx.run_cutoff(*args)
             elif op == "deepen":
                 val = ctx.deepen(*args)
+            elif op == "fit":
+                val = ctx.fit(*args)
             elif op == "full_matrix":
                 val = ctx.full_matrix(*args)
             else:
@@ -956,6 +985,28 @@ def plan_routes(costs, options, packed, flags):
         raise err
     return {k: (float(v) if k in ("band_cells", "cells", "algo_bytes") else int(v))
             for k, v in zip(PLAN_ROUTE_FIELDS, out)}
+
+
+FIT_PLAN_FIELDS = ("scale", "W", "chunk", "lanes", "cells", "nominal_cells")
+
+
+def fit_plan(costs, options, len_p, len_t):
+    """What Context.fit would decide, without a device (sed_fit_plan): {field: number} over FIT_PLAN_FIELDS.  costs and
+    options as plan_routes takes them; len_p / len_t = the pairs' pattern and text lengths.  Raises SedError carrying
+    the SED_E_* code (.code) the search would fail with."""
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
+    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
+    out = np.zeros(len(FIT_PLAN_FIELDS), np.float64)
+    rc = load().sed_fit_plan(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
+                             np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
+                             int(del_int), opts, len(options), lp, lt, len(len_p), out, len(out))
+    if rc != 0:
+        err = SedError("sed_fit_plan failed (%d)" % rc)
+        err.code = rc
+        raise err
+    return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
 
 
 def band_bounds(n, m, ins, dele, ub):

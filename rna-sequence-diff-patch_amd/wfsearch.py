@@ -103,6 +103,25 @@ def nearest(query, seqs, k, user_cost=False, distance_fn=None):
     return [(seqs[i], 1 / (1 + v)) for v, i in order]
 
 
+def fit_search(query, seqs_or_collection, user_cost=False, max_dist=None, scripts=False, fit_fn=None):
+    """Where in each document does query occur, approximately: [(sequence, 1 / (1 + dist), start, end)] in collection
+    order, dist = the smallest distance from query to any substring sequence[start:end] (the one ending earliest, then
+    the shortest; StringEditDistance.fit_batch), one engine launch for the collection.  max_dist keeps only the hits
+    with dist <= max_dist.  scripts=True appends the edit script of (query, sequence[start:end]) to each kept hit, from
+    one edit_script_batch call; patching(es, query) then gives the matched substring.
+    fit_fn(patterns, texts, user_cost) -> [(dist, start, end)] replaces the engine (CPU tests).  Not cached."""
+    seqs = _sequences(seqs_or_collection)
+    if not seqs:
+        return []
+    hits = (fit_fn or SED.fit_batch)([query] * len(seqs), seqs, user_cost)
+    kept = [(s, d, a, b) for s, (d, a, b) in zip(seqs, hits) if max_dist is None or d <= max_dist]
+    out = [(s, 1 / (1 + d), a, b) for s, d, a, b in kept]
+    if scripts and kept:
+        es = SED.edit_script_batch([query] * len(kept), [s[a:b] for s, _, a, b in kept], user_cost)
+        out = [hit + (e,) for hit, (_, e) in zip(out, es)]
+    return out
+
+
 def search_collection(query, vector_type, collection, method, return_dict=None, callback=None):
     """IRMethods.search_collection for method == wf_score (IRMethods.py:443-477)."""
     if getattr(method, '__name__', None) != 'wf_score':
