@@ -325,6 +325,21 @@ int sed_fit_search(sed_ctx *ctx,
 int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
                  double del, int del_is_int, const int32_t *options, int noptions,
                  const int32_t *len_p, const int32_t *len_t, int32_t npairs, double *out, int nout);
+/* The lane records sed_fit_search would run for the same arguments, without a device (for tests and tools): one lane
+ * per (pair, chunk of text columns), pair by pair in chunk order, lanes as sed_fit_plan counts them.
+ * out_lanes = eight 32-bit words per lane, room for max_lanes lanes (SED_E_ARG when there are more):
+ *   0 tw      the lane's border column, in 4-symbol words from the start of the pair's own text (the search adds the
+ *             word at which its copy of the text starts)
+ *   1 pair    2 pat  0 here (the search sets the pattern's record)    3 plen  the pattern's length P
+ *   4 nsteps  text columns the lane runs after its border column (the kernel rounds it up to a multiple of 4)
+ *   5 lead    columns before c0 that only warm the lane up          6 cnt   columns it owns, [c0, c0 + cnt)
+ *   7 c0      its first owned column (column j = the DP column after j text symbols; column 0 is the border)
+ * out_params = 18 words: the update addends insert + delete - min(cost(a -> b), insert + delete) on the integer scale,
+ * one byte each, b = 0..3 in word 2a and b = 4..7 in word 2a + 1 for a = 0..7, then insert * S and delete * S. */
+int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                  double del, int del_is_int, const int32_t *options, int noptions,
+                  const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                  int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params);
 /* Device time of the last sed_fit_search's kernel, from HIP events (ms); SED_E_STATE before the first search. */
 int sed_fit_last_time(const sed_ctx *ctx, float *kernel_ms);
 

@@ -33,6 +33,8 @@ def load():
         lib.sed_oracle_pair.restype = C.c_int
         lib.sed_oracle_batch.argtypes = [P, P, P, P, P, P, C.c_int, C.POINTER(_Costs), P, P, P, P, P, C.c_int]
         lib.sed_oracle_batch.restype = C.c_int
+        lib.sed_oracle_fit.argtypes = [P, P, P, P, P, P, C.c_int, C.POINTER(_Costs), P, P, P, C.c_int]
+        lib.sed_oracle_fit.restype = C.c_int
         lib.sed_synth_codes.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_int, P]
         lib.sed_synth_codes.restype = None
         _lib = lib
@@ -101,6 +103,20 @@ def batch(costs, codes_a, off_a, len_a, codes_b, off_b, len_b, npairs, want_ops=
     if rc:
         raise MemoryError("oracle allocation failed")
     return dist[:npairs], is_int[:npairs], ln[:npairs], ops, ops_off
+
+
+def fit(costs, codes_p, off_p, len_p, codes_t, off_t, len_t, npairs, nthreads=1):
+    """Fit search from its definition (sed_oracle_fit): (dist f64[], start i32[], end i32[]) of every pair's pattern
+    (side p) in its text (side t), in the packed-pair layout batch() takes."""
+    lib = load()
+    dist = np.zeros(max(npairs, 1), np.float64)
+    start = np.zeros(max(npairs, 1), np.int32)
+    end = np.zeros(max(npairs, 1), np.int32)
+    rc = lib.sed_oracle_fit(_ptr(codes_p), _ptr(off_p), _ptr(len_p), _ptr(codes_t), _ptr(off_t), _ptr(len_t), npairs,
+                            C.byref(costs.c), _ptr(dist), _ptr(start), _ptr(end), nthreads)
+    if rc:
+        raise MemoryError("oracle allocation failed")
+    return dist[:npairs], start[:npairs], end[:npairs]
 
 
 def synth_codes(base, pair_id, stream, length):

@@ -160,6 +160,84 @@ int sed_oracle_batch(const uint8_t *codes_a, const int64_t *off_a, const int32_t
     return err;
 }
 
+/* ---- fit search (include/sed.h: sed_fit_search), restated from its definition ----
+ * Rows are the pattern p (length P >= 0), columns the text t (length n >= 0).  D[0][j] = 0 with start j,
+ * D[i][0] = i * delete with start 0, and every other cell is the lexicographic minimum of (D, -start) over
+ * insert (left), delete (up) and update (diagonal), each ONE fp64 add.  The hit is the first strict minimum of the
+ * last row: (dist, start, end).  One column of P + 1 cells is kept: O(P) memory, any P, any K, no scaling.
+ * Returns 0, or -1 on allocation failure. */
+typedef struct { double d; int32_t s; } fit_cell;
+
+static int fit_less(double d, int32_t s, const fit_cell *c) { return d < c->d || (d == c->d && s > c->s); }
+
+int sed_oracle_fit_pair(const uint8_t *p, int P, const uint8_t *t, int n, const sed_oracle_costs *c,
+                        double *dist, int32_t *start, int32_t *end)
+{
+    fit_cell *col = (fit_cell *)malloc(sizeof(fit_cell) * (size_t)(P + 1));
+    if (!col) return -1;
+    for (int i = 0; i <= P; ++i) { col[i].d = (double)i * c->del; col[i].s = 0; }
+    double bd = col[P].d;
+    int32_t bs = col[P].s, be = 0;
+    for (int j = 1; j <= n; ++j) {
+        const uint8_t bj = t[j - 1];
+        fit_cell diag = col[0];                 /* column j - 1, row i - 1 */
+        col[0].d = 0.0; col[0].s = j;
+        for (int i = 1; i <= P; ++i) {
+            const fit_cell left = col[i];       /* column j - 1, row i */
+            fit_cell v;
+            v.d = left.d + c->ins; v.s = left.s;
+            const double up = col[i - 1].d + c->del;
+            if (fit_less(up, col[i - 1].s, &v)) { v.d = up; v.s = col[i - 1].s; }
+            const double dg = diag.d + c->sub[(size_t)p[i - 1] * c->K + bj];
+            if (fit_less(dg, diag.s, &v)) { v.d = dg; v.s = diag.s; }
+            col[i] = v;
+            diag = left;
+        }
+        if (col[P].d < bd) { bd = col[P].d; bs = col[P].s; be = j; }
+    }
+    *dist = bd; *start = bs; *end = be;
+    free(col);
+    return 0;
+}
+
+typedef struct {
+    const uint8_t *codes_p, *codes_t;
+    const int64_t *off_p, *off_t;
+    const int32_t *len_p, *len_t;
+    int npairs, nthreads, tid;
+    const sed_oracle_costs *c;
+    double *dist; int32_t *start, *end;
+    int err;
+} fit_job;
+
+static void *fit_worker(void *q)
+{
+    fit_job *jb = (fit_job *)q;
+    for (int k = jb->tid; k < jb->npairs; k += jb->nthreads)
+        if (sed_oracle_fit_pair(jb->codes_p + jb->off_p[k], jb->len_p[k], jb->codes_t + jb->off_t[k], jb->len_t[k],
+                                jb->c, &jb->dist[k], &jb->start[k], &jb->end[k])) { jb->err = -1; return NULL; }
+    return NULL;
+}
+
+int sed_oracle_fit(const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                   const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
+                   int npairs, const sed_oracle_costs *c, double *dist, int32_t *start, int32_t *end, int nthreads)
+{
+    if (nthreads < 1) nthreads = 1;
+    fit_job *jobs = (fit_job *)calloc(nthreads, sizeof(fit_job));
+    pthread_t *th = (pthread_t *)calloc(nthreads, sizeof(pthread_t));
+    if (!jobs || !th) { free(jobs); free(th); return -1; }
+    for (int t = 0; t < nthreads; ++t) {
+        fit_job j = {codes_p, codes_t, off_p, off_t, len_p, len_t, npairs, nthreads, t, c, dist, start, end, 0};
+        jobs[t] = j;
+        pthread_create(&th[t], NULL, fit_worker, &jobs[t]);
+    }
+    int err = 0;
+    for (int t = 0; t < nthreads; ++t) { pthread_join(th[t], NULL); err |= jobs[t].err; }
+    free(jobs); free(th);
+    return err;
+}
+
 /* ---- the splitmix64 synthetic generator (same definition as synth.py) ---- */
 static uint64_t mix64(uint64_t z)
 {

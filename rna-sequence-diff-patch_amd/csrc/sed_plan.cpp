@@ -1198,6 +1198,27 @@ int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len
     return SED_OK;
 }
 
+void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                         std::vector<sed_fit_lane> &lanes) {
+    lanes.assign((size_t)plan.lanes, sed_fit_lane{});
+    for (int p = 0; p < npairs; ++p) {
+        const int64_t ncol = (int64_t)len_t[p] + 1, nl = plan.first[p + 1] - plan.first[p];
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t c0 = l * plan.chunk, c1 = nl > 1 ? std::min(ncol, c0 + plan.chunk) : ncol;
+            const int32_t lead = sed_fit_lead(plan.W, c0);
+            sed_fit_lane &ln = lanes[(size_t)(plan.first[p] + l)];
+            ln.tw = (uint32_t)((c0 - lead) / 4);
+            ln.pair = p;
+            ln.pat = 0;
+            ln.plen = len_p[p];
+            ln.nsteps = (int32_t)(c1 - 1 - (c0 - lead));
+            ln.lead = lead;
+            ln.cnt = (int32_t)(c1 - c0);
+            ln.c0 = (int32_t)c0;
+        }
+    }
+}
+
 sed_band_params sed_band_params_from(const sed_costs &c) {
     sed_band_params bp{};
     for (int a = 0; a < 4; ++a)
@@ -1284,10 +1305,11 @@ int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins
     return SED_OK;
 }
 
-int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
-                 const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
-                 double *out, int nout) {
-    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options) || nout < 0 || (nout && !out)) return SED_E_ARG;
+// sed_fit_plan's and sed_fit_lanes' common half: the plan of the C arguments
+static int fit_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                       int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
+                       int32_t npairs, sed_fit_plan_t *p) {
+    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options)) return SED_E_ARG;
     if (!std::isfinite(ins) || !std::isfinite(del)) return SED_E_ARG;
     for (int e = 0; e < K * K; ++e)
         if (!std::isfinite(sub[e])) return SED_E_ARG;
@@ -1302,11 +1324,39 @@ int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, i
     sed_opts o;
     for (int i = 0; i < noptions; ++i)
         if (!sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    return sed_fit_plan_batch(c, o, len_p, len_t, npairs, p, nullptr);
+}
+
+int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                 const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                 double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
     sed_fit_plan_t p;
-    const int rc = sed_fit_plan_batch(c, o, len_p, len_t, npairs, &p, nullptr);
+    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
     if (rc != SED_OK) return rc;
     const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal};
     for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}
+
+int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                  const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                  int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    if (max_lanes < 0 || (max_lanes && !out_lanes) || !out_params) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
+    if (rc != SED_OK) return rc;
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    std::vector<sed_fit_lane> lanes;
+    sed_fit_build_lanes(p, len_p, len_t, npairs, lanes);
+    static_assert(sizeof(sed_fit_lane) == 8 * sizeof(int32_t), "a lane record is eight 32-bit words");
+    if (!lanes.empty()) std::memcpy(out_lanes, lanes.data(), lanes.size() * sizeof(sed_fit_lane));
+    for (int a = 0; a < 8; ++a) {
+        out_params[2 * a] = p.fp.row[a][0];
+        out_params[2 * a + 1] = p.fp.row[a][1];
+    }
+    out_params[16] = p.fp.ins;
+    out_params[17] = p.fp.del;
     return SED_OK;
 }
 

@@ -141,6 +141,12 @@ inline int32_t sed_fit_lead(int64_t W, int64_t c0) {
     return (int32_t)(c0 - jb);
 }
 
+// The lane records of a planned batch (sed_internal.h: sed_fit_lane), lanes[plan.first[p] + k] = lane k of pair p, from
+// the plan and the lengths alone: tw counts 4-symbol words from the pair's own text start and pat is 0.  The runtime
+// adds the base word of each text's copy and sets the pattern record (sed_runtime.cpp: sed_fit_search).
+void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                         std::vector<sed_fit_lane> &lanes);
+
 bool sed_simple_typing(const sed_costs &c);  // a cell's value is an int exactly when it equals 0
 sed_band_params sed_band_params_from(const sed_costs &c);
 // the cost of the plain diagonal path (band pruning's upper bound on the distance): the host's restatement of

@@ -1260,7 +1260,8 @@ int sed_pair_wait(sed_ctx *c, double *out_dist, uint8_t *out_is_int, int32_t *ou
                          script && out_ops ? &off : nullptr);
 }
 
-// Fit search.  The planner decides scale, window and lanes from the lengths (sed_plan.cpp: sed_fit_plan_batch); here the
+// Fit search.  The planner decides scale, window and lanes from the lengths and builds the lane records
+// (sed_plan.cpp: sed_fit_plan_batch, sed_fit_build_lanes); here the
 // distinct patterns become 32-byte records (right-aligned, code 8 in front) and the distinct texts one buffer in which
 // each starts 4-byte aligned, so pairs that share a pattern or a text through their offsets share its copy.
 int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p, const uint8_t *codes_t,
@@ -1287,7 +1288,8 @@ int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, con
     };
     std::unordered_map<Span, int64_t, SpanHash> pat_of, text_of;
     std::vector<uint8_t> pats, text;
-    std::vector<sed_fit_lane> lanes((size_t)plan.lanes);
+    std::vector<sed_fit_lane> lanes;
+    sed_fit_build_lanes(plan, len_p, len_t, npairs, lanes);
     for (int p = 0; p < npairs; ++p) {
         if (off_p[p] < 0 || off_t[p] < 0) return c->fail(SED_E_ARG, "pair %d: negative offset", p);
         const int P = len_p[p], n = len_t[p];
@@ -1311,19 +1313,9 @@ int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, con
             if (top) return c->fail(SED_E_ARG, "pair %d: a text code is outside the alphabet (K=%d)", p, K);
             if (text.size() / 4 > 0xFFFFFFF0u) return c->fail(SED_E_RANGE, "fit search: more than 16 GB of text");
         }
-        const int64_t ncol = (int64_t)n + 1, nl = plan.first[p + 1] - plan.first[p];
-        for (int64_t l = 0; l < nl; ++l) {
-            const int64_t c0 = l * plan.chunk, c1 = nl > 1 ? std::min(ncol, c0 + plan.chunk) : ncol;
-            const int32_t lead = sed_fit_lead(plan.W, c0);
-            sed_fit_lane &ln = lanes[(size_t)(plan.first[p] + l)];
-            ln.tw = (uint32_t)(ti->second + (c0 - lead) / 4);
-            ln.pair = p;
-            ln.pat = (int32_t)pi->second;
-            ln.plen = P;
-            ln.nsteps = (int32_t)(c1 - 1 - (c0 - lead));
-            ln.lead = lead;
-            ln.cnt = (int32_t)(c1 - c0);
-            ln.c0 = (int32_t)c0;
+        for (int64_t l = plan.first[p]; l < plan.first[p + 1]; ++l) {  // the planner's records, at this text's copy
+            lanes[(size_t)l].tw += (uint32_t)ti->second;
+            lanes[(size_t)l].pat = (int32_t)pi->second;
         }
     }
     text.resize(text.size() + 16, 0);  // (a lane reads one word past its last)

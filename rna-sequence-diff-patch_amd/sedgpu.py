@@ -123,6 +123,8 @@ SIGNATURES = [
     ("sed_fit_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
     ("sed_fit_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                _i32p, _i32p, C.c_int32, _f64p, C.c_int]),
+    ("sed_fit_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                _i32p, _i32p, C.c_int32, _i32p, C.c_int64, _u32p]),
     ("sed_fit_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
@@ -1007,6 +1009,32 @@ def fit_plan(costs, options, len_p, len_t):
         err.code = rc
         raise err
     return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
+
+
+FIT_LANE_FIELDS = ("tw", "pair", "pat", "plen", "nsteps", "lead", "cnt", "c0")
+
+
+def fit_lanes(costs, options, len_p, len_t):
+    """The lane records Context.fit would run, without a device (sed_fit_lanes): (lanes, params).  lanes = {field:
+    int64[nlanes]} over FIT_LANE_FIELDS, tw in 4-symbol words from the pair's own text start; params = {"row":
+    u32[8][2] update addend bytes, "ins", "del": the scaled insert and delete}.  Arguments and errors as fit_plan."""
+    nl = fit_plan(costs, options, len_p, len_t)["lanes"]
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
+    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    par = np.zeros(18, np.uint32)
+    rc = load().sed_fit_lanes(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
+                              np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
+                              int(del_int), opts, len(options), lp, lt, len(len_p), rec.ravel(), nl, par)
+    if rc != 0:
+        err = SedError("sed_fit_lanes failed (%d)" % rc)
+        err.code = rc
+        raise err
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
 
 
 def band_bounds(n, m, ins, dele, ub):

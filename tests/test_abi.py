@@ -21,6 +21,7 @@ def declared():
 def test_library_exports_every_declared_symbol():
     names = declared()
     assert len(names) >= 20
+    assert {"sed_fit_search", "sed_fit_plan", "sed_fit_lanes", "sed_fit_last_time"} <= set(names)
     lib = ctypes.CDLL(sedgpu.LIB_PATH)
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing

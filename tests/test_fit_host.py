@@ -106,6 +106,31 @@ def test_lane_count_under_a_chunk_override():
     assert one["cells"] == one["nominal_cells"]  # one lane per text: no warm-up
 
 
+def test_lane_records_tile_every_text():
+    """sed_fit_lanes: a pair's lanes own [0, n + 1) without gap or overlap, start min(c0, W) columns early rounded to
+    a 4-symbol word of the text, and run to their last owned column."""
+    rng = np.random.default_rng(11)
+    lt = rng.integers(0, 900, size=40).tolist() + [0, 1, 63, 64, 65]
+    lp = rng.integers(1, 33, size=len(lt)).tolist()
+    costs = costs_of(load_golden("user_costs.json"), "ACGU")
+    for c in (0, 1, 7, 64, 200, 5000):
+        opts = {sedgpu.SED_OPT_FIT_CHUNK: c}
+        plan = sedgpu.fit_plan(costs, opts, lp, lt)
+        lanes, par = sedgpu.fit_lanes(costs, opts, lp, lt)
+        assert len(lanes["pair"]) == plan["lanes"] and (par["ins"], par["del"]) == (2, 3)
+        W = plan["W"]
+        for q, n in enumerate(lt):
+            at = np.flatnonzero(lanes["pair"] == q)
+            c0, cnt, lead = lanes["c0"][at], lanes["cnt"][at], lanes["lead"][at]
+            assert c0[0] == 0 and (c0[1:] == c0[:-1] + cnt[:-1]).all() and c0[-1] + cnt[-1] == n + 1
+            assert (lanes["plen"][at] == lp[q]).all() and not lanes["pat"][at].any()
+            assert (4 * lanes["tw"][at] == c0 - lead).all() and (lanes["nsteps"][at] == lead + cnt - 1).all()
+            assert ((lead >= np.minimum(c0, W)) & (lead < np.minimum(c0, W) + 4) & (lead <= c0)).all()
+    with pytest.raises(sedgpu.SedError) as ex:
+        sedgpu.fit_lanes(unit_costs(9, 1, 1), {}, [5], [10])
+    assert ex.value.code == E_RANGE
+
+
 def test_insert_zero_runs_one_lane_per_pair():
     lt = [0, 5, 3000, 40000]
     for opts in ({}, {sedgpu.SED_OPT_FIT_CHUNK: 16}):
@@ -137,7 +162,8 @@ def _brute(costs, p, t):
     return float(best), start, end
 
 
-def test_definition_against_brute_force():
+def _brute_cases():
+    """The 120 small cases of test_definition_against_brute_force: (it, sub, insert, delete, pattern, text)."""
     rng = np.random.default_rng(2024)
     for it in range(120):
         K = int(rng.integers(2, 5))
@@ -149,8 +175,72 @@ def test_definition_against_brute_force():
         if it % 3 == 0 and len(t) >= len(p):  # a planted copy
             at = int(rng.integers(0, len(t) - len(p) + 1))
             t[at:at + len(p)] = p
+        yield it, sub, ins, dele, p, t
+
+
+def test_definition_against_brute_force():
+    for it, sub, ins, dele, p, t in _brute_cases():
+        K = len(sub)
         costs = oracle.Costs(sub, np.zeros((K, K), np.uint8), ins, 0, dele, 0)
         assert fit_definition(sub.tolist(), ins, dele, p.tolist(), t.tolist()) == _brute(costs, p, t), (it, p, t)
+
+
+def oracle_fit(sub, ins, dele, pats, texts, nthreads=1):
+    """oracle.fit over lists of code arrays: [(dist, start, end)]."""
+    K = len(sub)
+    costs = oracle.Costs(sub, np.zeros((K, K), np.uint8), ins, 0, dele, 0)
+    pk = sedgpu.PackedPairs(pats, texts)
+    d, s, e = oracle.fit(costs, pk.codes_a, pk.off_a, pk.len_a, pk.codes_b, pk.off_b, pk.len_b, pk.npairs, nthreads)
+    return list(zip(d.tolist(), s.tolist(), e.tolist()))
+
+
+def test_oracle_fit_on_the_brute_force_cases():
+    """The compiled oracle equals the pure-Python definition and the brute force over every substring, exactly."""
+    for it, sub, ins, dele, p, t in _brute_cases():
+        K = len(sub)
+        costs = oracle.Costs(sub, np.zeros((K, K), np.uint8), ins, 0, dele, 0)
+        got = oracle_fit(sub, ins, dele, [p], [t])[0]
+        assert got == fit_definition(sub.tolist(), ins, dele, p.tolist(), t.tolist()), (it, p, t)
+        assert got == _brute(costs, p, t), (it, p, t)
+
+
+def test_oracle_fit_against_the_definition_on_random_pairs():
+    """3000 pairs in 60 cost models: K 2..8, P 1..40 (past the kernel's 32 on purpose), texts 0..200, costs multiples of
+    1/4 with insert = 0, delete = 0, nonzero diagonals and substitutions dearer than insert + delete among them.  Every
+    sum of such costs is exact in fp64, so equality is exact.  Two oracle threads: the batch driver's split."""
+    rng = np.random.default_rng(4040)
+    seen = {"ins0": 0, "del0": 0, "diag": 0, "dear": 0, "P>32": 0}
+    for model in range(60):
+        K = 2 + model % 7
+        ins = 0.0 if model % 6 == 0 else float(rng.integers(1, 9)) / 4
+        dele = 0.0 if model % 6 == 1 else float(rng.integers(1, 13)) / 4
+        sub = rng.integers(0, 4 * int(ins + dele + 2) + 1, size=(K, K)) / 4.0  # up to about insert + delete + 2
+        if model % 3:
+            sub[np.eye(K) > 0] = 0
+        seen["ins0"] += ins == 0
+        seen["del0"] += dele == 0
+        seen["diag"] += bool(np.diag(sub).any())
+        seen["dear"] += bool((sub > ins + dele).any())
+        pats, texts = [], []
+        for it in range(50):
+            P = (1, 32, 33, 40)[it] if it < 4 else int(rng.integers(1, 41))
+            n = (0, 1, 200)[it] if it < 3 else int(rng.integers(0, 201))
+            p = rng.integers(0, K, size=P).astype(np.uint8)
+            t = rng.integers(0, K, size=n).astype(np.uint8)
+            if it % 2 and n >= P:  # a planted copy, some of them with a symbol changed
+                at = int(rng.integers(0, n - P + 1))
+                t[at:at + P] = p
+                if it % 4 == 1:
+                    t[at + int(rng.integers(0, P))] = rng.integers(0, K)
+            seen["P>32"] += P > 32
+            pats.append(p)
+            texts.append(t)
+        got = oracle_fit(sub, ins, dele, pats, texts, nthreads=2)
+        subl = sub.tolist()
+        want = [fit_definition(subl, ins, dele, p.tolist(), t.tolist()) for p, t in zip(pats, texts)]
+        bad = [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
+        assert not bad, (model, bad[:3])
+    assert all(v >= 5 for v in seen.values()), seen
 
 
 def test_fit_search_module(wfsearch):

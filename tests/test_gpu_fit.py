@@ -1,5 +1,7 @@
 """GPU: fit search (sed_fit_search) against the pure-Python restatement of its definition
-(tests/test_fit_host.py: fit_definition); for every hit the C oracle must also give G(start, end) = dist."""
+(tests/test_fit_host.py: fit_definition); for every hit the C oracle must also give G(start, end) = dist.  The tests of
+the numeric envelope (second half) take the compiled restatement, oracle.fit, which is pinned to the same definition on
+the CPU (tests/test_fit_host.py), so that long texts and large batches stay quick."""
 import importlib
 import os
 import types
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_golden
+import fit_envelope
 import oracle
 import sedcost
 import sedgpu
@@ -219,3 +222,189 @@ def test_fit_search_with_scripts(gpu, monkeypatch):
         assert cost == want[0]
     assert hits[0][1] == 1.0  # the exact copy
     assert wfsearch.fit_search(query, docs, user_cost=True, max_dist=0) == [hits[0][:4]]
+
+
+# ---- the numeric envelope: every pair against the compiled definition, oracle.fit, exactly ----
+
+def _packed(pats, texts, filler=0):
+    """PackedPairs of the pairs, then `filler` more pairs of one 1-symbol pattern and one empty text, shared through
+    their offsets."""
+    pk = sedgpu.PackedPairs(pats, texts)
+    if not filler:
+        return pk
+    n = pk.npairs
+    return types.SimpleNamespace(
+        npairs=n + filler, codes_a=pk.codes_a, codes_b=pk.codes_b,  # (the spare last byte of each is the filler's)
+        off_a=np.concatenate([pk.off_a[:n], np.full(filler, len(pk.codes_a) - 1, np.int64)]),
+        len_a=np.concatenate([pk.len_a[:n], np.ones(filler, np.int32)]),
+        off_b=np.concatenate([pk.off_b[:n], np.full(filler, len(pk.codes_b) - 1, np.int64)]),
+        len_b=np.concatenate([pk.len_b[:n], np.zeros(filler, np.int32)]))
+
+
+def _check_oracle(gpu, plan, pats, texts, filler=0):
+    """Run the pairs and compare every hit with oracle.fit, and every hit's distance with the oracle's G(start, end)."""
+    gpu.set_costs(plan)
+    pk = _packed(pats, texts, filler)
+    dist, start, end = gpu.fit(pk)
+    costs = oracle.Costs.from_plan(plan)
+    wd, ws, we = oracle.fit(costs, pk.codes_a, pk.off_a, pk.len_a, pk.codes_b, pk.off_b, pk.len_b, pk.npairs, 8)
+    bad = np.flatnonzero((dist != wd) | (start != ws) | (end != we))
+    assert not len(bad), [(int(i), (dist[i], start[i], end[i]), (wd[i], ws[i], we[i])) for i in bad[:5]]
+    n = len(pats)
+    assert ((0 <= start) & (start <= end)).all() and (end[:n] <= [len(t) for t in texts]).all() and not end[n:].any()
+    win = _packed(pats, [t[s:e] for t, s, e in zip(texts, start.tolist(), end.tolist())], filler)
+    g = oracle.batch(costs, win.codes_a, win.off_a, win.len_a, win.codes_b, win.off_b, win.len_b, win.npairs, nthreads=8)[0]
+    assert np.array_equal(g, dist)
+    return list(zip(dist[:n].tolist(), start[:n].tolist(), end[:n].tolist()))
+
+
+def _chunked(gpu, chunk, fn):
+    try:
+        gpu.set_option(sedgpu.SED_OPT_FIT_CHUNK, chunk)
+        return fn()
+    finally:
+        gpu.set_option(sedgpu.SED_OPT_FIT_CHUNK, 0)
+
+
+@pytest.mark.parametrize("name", [n for n, _ in fit_envelope.cost_limit_tables()])
+def test_cost_limits(gpu, name):
+    """Scaled costs on the limits of the byte addend, the 16-bit distance field and the clamp: P in {1, 31, 32}, texts
+    of 600..1500 (4 to 11 rebases a lane) with planted mutated copies, under the automatic chunk and a chunk of 255."""
+    plan = dict(fit_envelope.cost_limit_tables())[name]
+    rng = np.random.default_rng(600 + len(name))
+    pats, texts = [], []
+    for P in (1, 31, 32):
+        for n in (600, 1001, 1500, int(rng.integers(600, 1501))):
+            p = rng.integers(0, plan.K, size=P).astype(np.uint8)
+            pats.append(p)
+            texts.append(fit_envelope.planted_text(rng, plan.K, p, n))
+    auto = _check_oracle(gpu, plan, pats, texts)
+    assert _chunked(gpu, 255, lambda: _check_oracle(gpu, plan, pats, texts)) == auto
+
+
+def test_widest_window(gpu):
+    """insert 1, delete 254, P = 32: W = 8160.  One text of 30 000 under the automatic chunk and under a chunk of W."""
+    plan = dict(fit_envelope.cost_limit_tables())["i1_d254"]
+    rng = np.random.default_rng(8160)
+    p = rng.integers(0, plan.K, size=32).astype(np.uint8)
+    t = fit_envelope.planted_text(rng, plan.K, p, 30000, copies=8)
+    got = sedgpu.fit_plan(plan.costs(), {}, [32], [30000])
+    assert got["W"] == 8160 and got["lanes"] > 1
+    auto = _check_oracle(gpu, plan, [p], [t])
+    assert _chunked(gpu, 8160, lambda: _check_oracle(gpu, plan, [p], [t])) == auto
+
+
+def _unit(K=4, sub=2.0):
+    return np.where(np.eye(K) > 0, 0.0, sub)
+
+
+def test_zero_insert(gpu):
+    """insert = 0 runs one lane per text whatever the chunk option says: texts of 0, 1, around one rebase, and 65 534
+    symbols, the longest lane there is."""
+    plan = fit_envelope.Plan(_unit(), 0, 1.5)
+    rng = np.random.default_rng(65534)
+    pats, texts = [], []
+    for n in (0, 1, 127, 128, 129, 65534):
+        for P in (1, 31, 32):
+            p = rng.integers(0, 4, size=P).astype(np.uint8)
+            pats.append(p)
+            texts.append(fit_envelope.planted_text(rng, 4, p[:n], n) if n else np.zeros(0, np.uint8))
+    lens = ([len(p) for p in pats], [len(t) for t in texts])
+    for opts in ({}, {sedgpu.SED_OPT_FIT_CHUNK: 64}):
+        assert sedgpu.fit_plan(plan.costs(), opts, *lens)["lanes"] == len(pats)
+    auto = _check_oracle(gpu, plan, pats, texts)
+    assert _chunked(gpu, 64, lambda: _check_oracle(gpu, plan, pats, texts)) == auto
+
+
+def test_span_refusal(gpu):
+    plan = fit_envelope.Plan(_unit(), 0, 1.5)
+    rng = np.random.default_rng(65535)
+    p = rng.integers(0, 4, size=7).astype(np.uint8)
+    gpu.set_costs(plan)
+    with pytest.raises(sedgpu.SedError, match=r"\(-4\).*span"):
+        gpu.fit(sedgpu.PackedPairs([p], [rng.integers(0, 4, size=65535).astype(np.uint8)]))
+    _check_oracle(gpu, plan, [p] * 2, [fit_envelope.planted_text(rng, 4, p, 500), rng.integers(0, 4, size=65534).astype(np.uint8)])
+
+
+def test_zero_delete(gpu):
+    """delete = 0: deleting the whole pattern is free, so every hit is (0, 0, 0)."""
+    rng = np.random.default_rng(255)
+    for plan in (fit_envelope.Plan(_unit(), 1.25, 0), dict(fit_envelope.cost_limit_tables())["i255_d0"]):
+        pats, texts = _fuzz_pairs(rng, plan.K, 60)
+        got = _check_oracle(gpu, plan, pats, texts)
+        assert got == [(0.0, 0, 0)] * len(pats)
+
+
+@pytest.mark.parametrize("K", [6, 7, 8])
+def test_all_eight_symbols(gpu, K):
+    """Symbols 4..7 select the second addend word (chi): a table whose rows differ in every column."""
+    rng = np.random.default_rng(800 + K)
+    plan = fit_envelope.eight_symbol_table(K)
+    pats, texts = _fuzz_pairs(rng, K, 200)
+    assert set(np.concatenate(pats).tolist()) == set(range(K)) == set(np.concatenate(texts).tolist())
+    _check_oracle(gpu, plan, pats, texts)
+
+
+def test_long_texts(gpu):
+    """Texts of 65 534 (the largest unsplit lane), 65 535 (the first that must split), 65 536, 70 001 and 200 000
+    symbols in a batch large enough that the automatic rule keeps one lane per text, so only the span limit splits
+    them: exact and 3-edit copies end one column before, at and one after every forced seam and at the end of the
+    200 000 text, where end needs more than 16 bits."""
+    plan = fit_envelope.Plan(_unit(), 1, 4)
+    rng = np.random.default_rng(200000)
+    filler = 1 << 17
+    lens = (65534, 65535, 65536, 70001, 200000)
+    got = sedgpu.fit_plan(plan.costs(), {}, [32] * len(lens) + [1] * filler, list(lens) + [0] * filler)
+    chunk = got["chunk"]
+    # (the chunk is the batch's: 65 534 runs as one lane only in a batch without longer texts, below)
+    assert got["W"] == 160 and chunk == 65535 - 160 - 3 and got["lanes"] == filler + 2 + 2 + 2 + 2 + 4
+    p = rng.integers(0, 4, size=32).astype(np.uint8)
+    pats, texts = [], []
+    for n in lens:
+        ends = [e for seam in range(chunk, n + 1, chunk) for e in (seam - 1, seam, seam + 1)]
+        ends += [n] if n < 70000 else [n - 1, n]
+        for end in ends:
+            for edits in (0, 3):
+                t = rng.integers(0, 4, size=n).astype(np.uint8)
+                m = p if edits == 0 else _mutate(rng, p, 4, 3)
+                t[end - len(m):end] = m
+                pats.append(p)
+                texts.append(t)
+    hits = _check_oracle(gpu, plan, pats, texts, filler)
+    assert sum(d == 0 for d, _, _ in hits) >= len(hits) // 2  # (the exact copies were found)
+    assert max(e for _, _, e in hits) > 0x20000
+    gpu.set_costs(plan)
+    try:
+        gpu.set_option(sedgpu.SED_OPT_FIT_CHUNK, 1 << 20)
+        with pytest.raises(sedgpu.SedError, match=r"\(-4\).*span"):
+            gpu.fit(_packed(pats, texts, filler))
+    finally:
+        gpu.set_option(sedgpu.SED_OPT_FIT_CHUNK, 0)
+    assert _check_oracle(gpu, plan, pats[-2:], texts[-2:]) == hits[-2:]
+    alone = sedgpu.fit_plan(plan.costs(), {}, [32, 32] + [1] * filler, [65534, 65534] + [0] * filler)
+    assert alone["chunk"] == 0 and alone["lanes"] == filler + 2  # one lane of 65 535 columns each
+    assert _check_oracle(gpu, plan, pats[:2], texts[:2], filler) == hits[:2]
+
+
+def test_auto_chunk_above_window(gpu):
+    """512 texts of 20 000, unit costs, P <= 8: the automatic rule picks a chunk longer than W."""
+    plan = fit_envelope.Plan(_unit(sub=1.0), 1, 1)
+    rng = np.random.default_rng(512)
+    pats = [rng.integers(0, 4, size=int(rng.integers(1, 9))).astype(np.uint8) for _ in range(512)]
+    texts = [rng.integers(0, 4, size=20000).astype(np.uint8) for _ in range(512)]
+    got = sedgpu.fit_plan(plan.costs(), {}, [len(p) for p in pats], [20000] * 512)
+    assert got["chunk"] > got["W"] > 0 and got["lanes"] > 512
+    _check_oracle(gpu, plan, pats, texts)
+
+
+def test_buffer_reuse(gpu):
+    """A large search, a one-pair search, the large one again, on one context: the device buffers are kept across
+    calls, and each search must read only its own."""
+    plan = _golden_plan("user_costs.json", "ACGU")
+    rng = np.random.default_rng(77)
+    pats = [rng.integers(0, 4, size=int(rng.integers(1, 33))).astype(np.uint8) for _ in range(300)]
+    texts = [fit_envelope.planted_text(rng, 4, p, int(rng.integers(2000, 4000))) for p in pats]
+    big = _check_oracle(gpu, plan, pats, texts)
+    one = _check_oracle(gpu, plan, [pats[-1]], [texts[-1][:50]])
+    assert _check_oracle(gpu, plan, pats, texts) == big
+    assert _check_oracle(gpu, plan, [pats[-1]], [texts[-1][:50]]) == one
