@@ -104,8 +104,11 @@ enum {
                                    the forward skips the 64-step chunks of every stripe that no optimal path can reach,
                                    by the cost of the plain diagonal path as an upper bound on the distance (computed on
                                    the device in every run; substitution costs must be >= 0, else off): 0 auto (on),
-                                   2 never.  Environment SED_BAND=0 turns it off for the process.  Results are the same
-                                   bit for bit. */
+                                   2 never, 3 the static windows only.  By default every stripe below a pair's first
+                                   narrows its range further from the row the stripe above left behind (refined windows:
+                                   a smaller upper bound from the diagonal cell, and each computed cell's slack under it).
+                                   Environment SED_BAND=0 turns pruning off for the process, SED_BAND=static selects the
+                                   static windows.  Results are the same bit for bit. */
 #define SED_OPT_CUT 17          /* distance-only integer batches under a cutoff (sed_batch_set_cutoff), SED_NO_LEN, R = 4/8/16, not
                                    SPLIT: the wave pairs leave the two-pairs-per-wave and CHAIN routes for the windowed
                                    stripe kernel: 0 auto (when the window keeps < 2/3 of their cells; pairs already on the
@@ -205,7 +208,8 @@ int sed_dot_factor(const double *sub, double ins, double del, int maxmin, int la
  *   13 and 14 sed_batch_work's cells and algo_bytes.
  * Returns SED_OK or the SED_E_* code batch creation would fail with (SED_E_ARG also for a bad option). */
 #define SED_PLAN_ENV_TBPAR 101     /* SED_TBPAR: 0 / 1 overrides the stripe-parallel traceback's rule; unset = -1 */
-#define SED_PLAN_ENV_BAND 102      /* SED_BAND: 0 turns band pruning off; unset = 1 */
+#define SED_PLAN_ENV_BAND 102      /* SED_BAND: 0 turns band pruning off, 3 (SED_BAND=static) keeps the static windows;
+                                      unset = 1 */
 #define SED_PLAN_ENV_ALT_DP 103    /* SED_ALT_DP: 0 keeps every DP on the context's stream; unset = 1 */
 #define SED_PLAN_ENV_CK_HALVES 104 /* SED_CK_HALVES: parts of a checkpoint batch, 1..4; unset = -1 (2 parts) */
 int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
@@ -224,7 +228,20 @@ int sed_batch_dot_keys(const sed_batch *b);           /* bit 0: the checkpoint f
  *   that window, out[2] = the chunks of an unpruned stripe.  A stripe starts at column 64 out[0] + 1.
  * sed_band_cells: the cells the forward computes for one pair of codes 0..3 under the 4 x 4 table sub (a -> b,
  *   row-major), with ub = the cost of the plain diagonal path; negative on bad arguments.
- * sed_batch_band_cells: the same summed over the batch's pairs (= sum n*m when the batch is not pruned). */
+ * sed_batch_band_cells: the same summed over the batch's pairs (= sum n*m when the batch is not pruned).  It restates the
+ *   static windows on the host, so for a batch with refined windows it is an upper estimate.
+ * sed_band_refine_row: the refinement of one stripe, as the forward kernel does it.  drow[j] = the cost of some path to
+ *   cell (stripe * 64 rows_per_lane, j) for j = 0..m (only the columns the stripe above computed, 64 clo_prev + 1 ..
+ *   min(m, 64 chi_prev + 1), are read); ub_prev = the bound so far, suf = the plain diagonal's cost from (r0, r0) to the
+ *   sink, negative where r0 > min(n, m).  out[0..1] = the stripe's chunk range, out[2] = the new bound, out[3] = 1 when a
+ *   cell survived (else the static range of the new bound).
+ * sed_batch_band_chunks_run: after a finished run of a band-pruned batch, the 64-step chunks its forward ran, summed
+ *   over the stripes of its wave pairs from the ranges the kernel stored; *total (if not null) = the chunks of the same
+ *   stripes unpruned.  Negative when the batch is not band-pruned or has not run. */
+int sed_band_refine_row(int32_t n, int32_t m, int32_t rows_per_lane, double ins, double del, int32_t stripe,
+                        double ub_prev, double suf, const int32_t *drow, int32_t clo_prev, int32_t chi_prev,
+                        int32_t *out);
+double sed_batch_band_chunks_run(sed_batch *b, double *total);
 int sed_band_bounds(int32_t n, int32_t m, double ins, double del, double ub, int32_t *out);
 int sed_band_chunk_range(int32_t n, int32_t m, int32_t rows_per_lane, int32_t elo, int32_t ehi, int32_t stripe,
                          int32_t *out);

@@ -16,7 +16,8 @@ __device__ __forceinline__ void ck_traceback_pair(const sed_pair_desc &d, const 
                                                   sed_result *__restrict__ res, uint32_t *__restrict__ ops,
                                                   const sed_i32_params &prm, uint32_t *__restrict__ topb,
                                                   uint32_t *__restrict__ selb,
-                                                  const sed_band bw = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI}) {
+                                                  const sed_band bw = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI},
+                                                  const int2 *__restrict__ win = nullptr) {
     constexpr int ROWS = 64 * R, G = Grp<R>::G;  // a tile: G forward lanes (bands) of R rows
     static_assert(R == 4 || R == 8 || R == 16, "R in {4, 8, 16}");
     const int n = d.n, m = d.m;
@@ -58,11 +59,20 @@ __device__ __forceinline__ void ck_traceback_pair(const sed_pair_desc &d, const 
                 int hi_;
                 tophi = 0x7FFFFFFF;
                 clo_prev = 0;
-                if (k >= 1) {
-                    sed_band_chunks(n, m, ROWS, px.nchunks, bw, k - 1, &clo_prev, &hi_);
-                    tophi = 64 * hi_ + 63;
+                if (win) {  // refined windows: the ranges the forward of this run stored, stripe by stripe
+                    if (k >= 1) {
+                        const int2 wp = win[k - 1];
+                        clo_prev = __builtin_amdgcn_readfirstlane(wp.x);
+                        tophi = 64 * __builtin_amdgcn_readfirstlane(wp.y) + 63;
+                    }
+                    clo = __builtin_amdgcn_readfirstlane(win[k].x);
+                } else {
+                    if (k >= 1) {
+                        sed_band_chunks(n, m, ROWS, px.nchunks, bw, k - 1, &clo_prev, &hi_);
+                        tophi = 64 * hi_ + 63;
+                    }
+                    sed_band_chunks(n, m, ROWS, px.nchunks, bw, k, &clo, &hi_);
                 }
-                sed_band_chunks(n, m, ROWS, px.nchunks, bw, k, &clo, &hi_);
                 kband = k;
             }
             // every optimal path stays inside the window, so a walk that arrives left of it followed keys the forward
@@ -159,7 +169,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SED_CKTB_WAV
                                                               const uint32_t *__restrict__ ck,
                                                               sed_result *__restrict__ res,
                                                               uint32_t *__restrict__ ops, sed_i32_params prm,
-                                                              const sed_band *__restrict__ band) {
+                                                              const sed_band *__restrict__ band,
+                                                              const int2 *__restrict__ win, int wstride) {
     if constexpr (SED_CKTB_PRIO > 0) __builtin_amdgcn_s_setprio(SED_CKTB_PRIO);
     const int lane = threadIdx.x;
     const int pair = __builtin_amdgcn_readfirstlane(blockIdx.x);
@@ -181,22 +192,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SED_CKTB_WAV
         bw.elo = __builtin_amdgcn_readfirstlane(band[pair].elo);
         bw.ehi = __builtin_amdgcn_readfirstlane(band[pair].ehi);
     }
-    ck_traceback_pair<R, false, NW>(d, pair, q0, lane, seqa, seqb, ck, res, ops, prm, topb, selb, bw);
+    ck_traceback_pair<R, false, NW>(d, pair, q0, lane, seqa, seqb, ck, res, ops, prm, topb, selb, bw,
+                                    win ? win + (size_t)pair * wstride : nullptr);
 }
 
 hipError_t sed_launch_traceback_ck(const sed_launch &L, uint32_t *ops, const sed_i32_params &prm) {
     const dim3 grid(L.npairs), block(64);
     const uint32_t *a = (const uint32_t *)L.seqa, *b = (const uint32_t *)L.seqb;
     const sed_band *bd = L.band;
+    const int2 *win = L.band && L.bsuf ? L.bwin : nullptr;  // (refined windows only: the static ones are restated)
+    const int ws = L.bstripes;
     switch (L.R) {
     case 4:
-        SED_LAUNCH(sed_traceback_ck_kernel<4>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
+        SED_LAUNCH(sed_traceback_ck_kernel<4>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd, win, ws);
         break;
     case 8:
-        SED_LAUNCH(sed_traceback_ck_kernel<8>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
+        SED_LAUNCH(sed_traceback_ck_kernel<8>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd, win, ws);
         break;
     case 16:
-        SED_LAUNCH(sed_traceback_ck_kernel<16>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd);
+        SED_LAUNCH(sed_traceback_ck_kernel<16>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd, win, ws);
         break;
     default: return hipErrorInvalidValue;
     }

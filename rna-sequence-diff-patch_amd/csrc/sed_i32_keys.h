@@ -259,6 +259,14 @@ __device__ __forceinline__ int2 i32_decode(uint32_t w, int n, int m, const sed_i
     }
 }
 
+// The distance alone of cell (i, j) from its checkpoint-forward key (dot or distance keys), as the sink decode above
+template <bool DOT>
+__device__ __forceinline__ uint32_t ck_key_dist(uint32_t w, int i, int j, const sed_i32_params &prm) {
+    const uint32_t base = (uint32_t)i * prm.del + (uint32_t)j * prm.ins;
+    if constexpr (DOT) return base - dot_split(w, prm).x;
+    return (w - SED_KB + (base << 16) + 0xFFFFu) >> 16;
+}
+
 // Distance key (!LEN) of a cell -> the traceback key of the same (D, L) (clean, op 0).  Traceback keys
 // (sed_traceback_ck_kernel) are T = V - i*((delete << 16) + 4) - j*((insert << 16) + 4) + SED_KB over
 // V = D << 16 | L << 2 | op: the insert candidate is the left cell, the delete candidate the cell above

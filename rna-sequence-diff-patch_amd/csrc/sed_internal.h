@@ -34,6 +34,7 @@ struct sed_result {
 #define SED_ERR_TB_GUARD 4       // traceback: more tile visits than any path can need
 #define SED_ERR_TB_LENGTH 5      // traceback: the walk's op count differs from the sink's L
 #define SED_ERR_TB_BAND 6        // CK traceback: the walk left the band the forward computed (band pruning)
+#define SED_ERR_FWD_BAND 7       // CK forward: no cell of a stripe's boundary row passed the refinement's slack test
 
 #ifdef __HIPCC__  // (device helpers: the runtime, compiled by g++, does not see them)
 // Script padding.  A pair's script region holds ceil((n+m)/16) words; its ops fill ceil(len/16) of them.  Every walk
@@ -135,6 +136,13 @@ struct sed_launch {
     // and the traceback assumes, written by sed_band_kernel before every forward with bandp's costs; nullptr = off
     struct sed_band *band;
     const struct sed_band_params *bandp;
+    // the windows per stripe: bwin[pair * bstripes + k] = {clo, chi}, the chunks the forward ran of stripe k (it writes
+    // them whenever bwin is set; sed_batch_band_chunks_run sums them).  Refined windows (bsuf set): sed_band_kernel
+    // writes bsuf[pair * bstripes + k] = suf(k ROWS), the forward narrows every stripe below the first from the row
+    // above it (sed_refine_cell) and the traceback reads bwin instead of restating the static range.
+    int2 *bwin;
+    uint32_t *bsuf;
+    int bstripes;
     // timing events carried by the launches themselves (hipExtLaunchKernelGGL: timestamps on the dispatch
     // packet, no marker packet between kernels): the launcher's first kernel records ev0 at its start, its last
     // kernel ev1 at its end; nullptr = none
@@ -293,6 +301,65 @@ __host__ __device__ inline void sed_band_chunks(int n, int m, int ROWS, int nchu
     *chi = hi < nchunks - 1 ? hi : nchunks - 1;
     *clo = lo < *chi ? lo : *chi;
 }
+// Refined windows ("Refinement"): before stripe k >= 1 the forward holds row r0 = k ROWS of the stripe
+// above, every value a real path's cost.  With UB_k = min(UB_{k-1}, D(r0, r0) + suf(r0)) (suf = the plain diagonal's
+// cost from (r0, r0) to the sink), a cell (r0, j), e0 = j - r0, with
+//   slack = UB_k - D(r0, j) - rem,   rem = insert (Dl - e0)+ + delete (e0 - Dl)+,   Dl = m - n
+// below 0 lies on no optimal path.  A path through a surviving cell that later touches diagonal e costs at least
+// D + insert ((e - e0)+ + (Dl - e)+) + delete ((e0 - e)+ + (e - Dl)+): moving towards Dl is paid for by rem already,
+// every step beyond [min(e0, Dl), max(e0, Dl)] costs insert + delete more.  So it stays within
+//   min(e0, Dl) - slack / (insert + delete)  <=  e  <=  max(e0, Dl) + slack / (insert + delete)      (integer floor).
+// sed_refine_cell folds one cell into the running extremes, kept times s = insert + delete so that no cell divides:
+// lo = min(s min(e0, Dl) - slack), hi = max(s max(e0, Dl) + slack); lo > hi = no cell survived.  The planner keeps
+// s (n + m) below 2^30 for every pair of a refined batch, so everything fits 32 bits.
+#define SED_REFINE_LO_INIT 0x7FFFFFFF
+#define SED_REFINE_HI_INIT (-0x7FFFFFFF - 1)
+#define SED_REFINE_NO_SUF 0xFFFFFFFFu  // suf(r0) of a stripe boundary below the diagonal's end (r0 > min(n, m))
+__host__ __device__ inline void sed_refine_cell(int n, int m, uint32_t ins, uint32_t del, int r0, int j, uint32_t D,
+                                                uint32_t ub, int32_t *lo, int32_t *hi) {
+    const int32_t dl = m - n, e0 = j - r0, s = (int32_t)(ins + del);
+    const int32_t rem = e0 < dl ? (int32_t)ins * (dl - e0) : (int32_t)del * (e0 - dl);
+    const int32_t slack = (int32_t)ub - (int32_t)D - rem;
+    if (slack < 0) return;
+    const int32_t a = s * (e0 < dl ? e0 : dl) - slack, b = s * (e0 < dl ? dl : e0) + slack;
+    *lo = a < *lo ? a : *lo;
+    *hi = b > *hi ? b : *hi;
+}
+// Stripe k's chunk range from the extremes over row r0's computed cells: the offsets [ceil(lo / s), floor(hi / s)]
+// inside the static window of UB_k, mapped to chunks as sed_band_chunks does, then raised to the range of the stripe
+// above (the kernels rely on both ends being nondecreasing: top_hi, the clo > clo_prev diagonal load, the in-place
+// bottom-row buffer; a path is monotone, so neither clamp drops a cell an optimal path reaches).  False when no cell
+// survived: the stripe then keeps the static range of UB_k (a correct forward always has a survivor, the cell of
+// row r0 on an optimal path).  The refined offsets hold Dl, so the last stripe's range holds the sink's chunk.
+__host__ __device__ inline bool sed_refine_chunks(int n, int m, int ROWS, int nchunks, uint32_t ins, uint32_t del,
+                                                  uint32_t ub, int32_t lo, int32_t hi, int k, int clo_prev, int chi_prev,
+                                                  int *clo, int *chi) {
+    // (sed_band_window in 32 bits: ub and delete |Dl| stay below 2^30 under the planner's bound, both numerators >= 0)
+    const int32_t s = (int32_t)(ins + del), dl = m - n;
+    const uint32_t whi = (uint32_t)((int32_t)ub + (int32_t)del * dl) / (uint32_t)s;
+    const uint32_t wlo = (uint32_t)((int32_t)ub - (int32_t)ins * dl) / (uint32_t)s;
+    sed_band w;
+    w.ehi = (int32_t)(whi > (uint32_t)m ? (uint32_t)m : whi);
+    w.elo = -(int32_t)(wlo > (uint32_t)n ? (uint32_t)n : wlo);
+    const bool any = lo <= hi;
+    if (any) {
+        const uint32_t us = (uint32_t)s;
+        const int32_t elo = lo >= 0 ? (int32_t)(((uint32_t)lo + us - 1u) / us) : -(int32_t)((uint32_t)(-lo) / us);  // ceil
+        const int32_t ehi = hi >= 0 ? (int32_t)((uint32_t)hi / us) : -(int32_t)(((uint32_t)(-hi) + us - 1u) / us);  // floor
+        w.elo = elo > w.elo ? elo : w.elo;
+        w.ehi = ehi < w.ehi ? ehi : w.ehi;
+    }
+    sed_band_chunks(n, m, ROWS, nchunks, w, k, clo, chi);
+    *clo = *clo > clo_prev ? *clo : clo_prev;
+    *chi = *chi > chi_prev ? *chi : chi_prev;
+    return any;
+}
+// the per-stripe windows as the kernels take them (sed_launch: bwin, bsuf, bstripes); all null = none
+struct sed_stripe_wins {
+    int2 *win;
+    const uint32_t *suf;
+    int stride;
+};
 // cells of the pair inside its stripes' chunk ranges: rows x (64 (chi - clo)) columns per stripe (the columns every
 // lane computes, as n m counts them for an unpruned pair; a stripe that runs to its last chunk counts up to m)
 __host__ __device__ inline double sed_band_pair_cells(int n, int m, int R, sed_band w) {
@@ -312,7 +379,8 @@ struct sed_band_params {
     uint32_t cost[16];
     uint32_t ins, del;
 };
-// UB and the window of every wave pair of the launch, into band[pair] (one wave per pair; the forward's first kernel)
+// UB and the window of every wave pair of the launch, into band[pair] (one wave per pair; the forward's first kernel);
+// with L.bsuf also the diagonal's suffix cost at every stripe boundary
 hipError_t sed_launch_band(const sed_launch &L, const sed_band_params &bp);
 // Cutoff batches (sed_batch_set_cutoff).  tkey = the cutoff on the integer scale.
 // sed_launch_i32_cut: the windowed distance-only stripe kernel (R = 4, 8, 16) over the wave pairs list[0 .. nlist), after

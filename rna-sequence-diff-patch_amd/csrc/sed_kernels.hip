@@ -137,7 +137,7 @@ __global__ __launch_bounds__(SPLIT ? 128 : 256) __attribute__((amdgpu_waves_per_
 void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const int2 *__restrict__ tasks,
                   const uint32_t *__restrict__ seqa, const uint32_t *__restrict__ seqb,
                   uint32_t *__restrict__ tb, uint32_t *__restrict__ bnd, sed_result *__restrict__ res,
-                  sed_i32_params prm, const sed_band *__restrict__ band) {
+                  sed_i32_params prm, const sed_band *__restrict__ band, sed_stripe_wins sw) {
     constexpr int ROWS = 64 * R;
     constexpr int G = Grp<R>::G;
     static_assert(!CK || (R <= 16 && !TB && !LEN), "checkpoints: R <= 16, distance keys");
@@ -205,6 +205,11 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         }
     }
     int top_hi = 0x7FFFFFFF, clo_prev = 0;  // (of the stripe above)
+    // refined windows: the running upper bound (UB_0 = suf(0), the whole diagonal) and the forward's own error
+    uint32_t ub_run = 0, rerr = 0;
+    if constexpr (CK && !SPLIT) {
+        if (sw.suf) ub_run = (uint32_t)__builtin_amdgcn_readfirstlane((int)sw.suf[(size_t)pair * sw.stride]);
+    }
     // per wave: lane 0's top values of the current 64-step chunk, and a ring of str2 selectors by column
     // (column ci at slots ci & 127 and (ci & 127) + 128; the 64 columns before 0 hold the virtual-column
     // sentinel), from which lane t reads column s - t at step s
@@ -243,6 +248,41 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         const int row0 = k * ROWS + lane * R;  // 0-based str1 index of this lane's first row
         int clo = 0, chi = nchunks - 1;
         if constexpr (WIN) sed_band_chunks(n, m, ROWS, nchunks, bw, k, &clo, &chi);
+        if constexpr (CK && !SPLIT) {
+            // refined windows (sed_internal.h: sed_refine_cell): the stripe above left row r0 = k ROWS complete in the
+            // bottom-row buffer (column j at word j + 62, columns 64 clo_prev + 1 .. its last, its stores waited for at
+            // its end), every value a real path's cost.  The wave scans it 64 columns at a time, takes the extremes
+            // across its lanes and keeps the chunk range uniform; the chunk loops below do not change.
+            if (sw.suf && k > 0) {
+                const int r0 = k * ROWS, chi_prev = top_hi >> 6;
+                const int j0 = 64 * clo_prev + 1, j1 = min(m, 64 * chi_prev + 1);
+                const uint32_t *row = bnd + d.bnd_off + 62;
+                const uint32_t suf = sw.suf[(size_t)pair * sw.stride + k];
+                if (suf != SED_REFINE_NO_SUF && r0 >= j0 && r0 <= j1) {  // (uniform) the diagonal cell and the rest of its path
+                    const uint32_t dd = ck_key_dist<DOT>(load_sc1(row + r0), r0, r0, prm) + suf;
+                    ub_run = min(ub_run, (uint32_t)__builtin_amdgcn_readfirstlane((int)dd));
+                }
+                int32_t lo = SED_REFINE_LO_INIT, hi = SED_REFINE_HI_INIT;
+                for (int jb = j0; jb <= j1; jb += 64) {
+                    const int j = jb + lane;
+                    if (j <= j1)
+                        sed_refine_cell(n, m, prm.ins, prm.del, r0, j, ck_key_dist<DOT>(load_sc1(row + j), r0, j, prm), ub_run,
+                                        &lo, &hi);
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    lo = min(lo, __shfl_xor(lo, o));
+                    hi = max(hi, __shfl_xor(hi, o));
+                }
+                lo = __builtin_amdgcn_readfirstlane(lo);
+                hi = __builtin_amdgcn_readfirstlane(hi);
+                if (!sed_refine_chunks(n, m, ROWS, nchunks, prm.ins, prm.del, ub_run, lo, hi, k, clo_prev, chi_prev, &clo, &chi))
+                    rerr = SED_ERR_FWD_BAND;
+                clo = __builtin_amdgcn_readfirstlane(clo);
+                chi = __builtin_amdgcn_readfirstlane(chi);
+            }
+            if (sw.win && lane == 0) sw.win[(size_t)pair * sw.stride + k] = make_int2(clo, chi);
+        }
         uint32_t cv[R], V[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -431,7 +471,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         res[pair].dist = (double)dl.x;
         res[pair].len = dl.y;
         res[pair].is_int = (dl.x == 0);
-        res[pair].err = ok ? 0 : SED_ERR_SPLIT_TIMEOUT;  // SPLIT: a timed-out wait anywhere up the stripe chain poisons the pair
+        res[pair].err = ok ? rerr : SED_ERR_SPLIT_TIMEOUT;  // SPLIT: a timed-out wait anywhere up the stripe chain poisons the pair
     }
 }
 
@@ -1555,7 +1595,8 @@ __device__ __forceinline__ uint32_t diag_cost_sum(const uint32_t *tab, const uin
 __global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__restrict__ pd, int npairs,
                                                        const uint32_t *__restrict__ seqa,
                                                        const uint32_t *__restrict__ seqb, sed_band *__restrict__ band,
-                                                       sed_band_params bp) {
+                                                       sed_band_params bp, uint32_t *__restrict__ suf, int stride,
+                                                       int ROWS) {
     __shared__ uint32_t tab[16];
     diag_cost_table(tab, bp);
     const int lane = threadIdx.x & 63;
@@ -1567,11 +1608,36 @@ __global__ __launch_bounds__(256) void sed_band_kernel(const sed_pair_desc *__re
         if (lane == 0) band[pair] = sed_band{SED_BAND_OPEN_LO, SED_BAND_OPEN_HI};
         return;
     }
-    const uint32_t sum = diag_cost_sum(tab, seqa + d.a_off, seqb + d.b_off, min(n, m), lane);
-    if (lane == 0) {
-        const uint64_t ub = (uint64_t)sum + (m > n ? (uint64_t)(m - n) * bp.ins : (uint64_t)(n - m) * bp.del);
-        band[pair] = sed_band_window(n, m, bp.ins, bp.del, ub);
+    const uint32_t gap = m > n ? (uint32_t)(m - n) * bp.ins : (uint32_t)(n - m) * bp.del;
+    uint32_t sum = 0;
+    if (suf) {
+        // refined windows: also suf(k ROWS), the diagonal's cost from every stripe boundary to the sink, one word per
+        // stripe of the pair.  ROWS is a multiple of 16, so a packed word belongs to one stripe: from the last stripe
+        // up, the lanes sum their words of the stripe and the wave adds them to the running suffix (each word is still
+        // read once).  suf(0) is UB itself.
+        const int len = min(n, m), words = (len + 15) >> 4, wps = ROWS >> 4;
+        const uint32_t *pa = seqa + d.a_off, *pb = seqb + d.b_off;
+        uint32_t *out = suf + (size_t)pair * stride;
+        for (int k = (n + ROWS - 1) / ROWS - 1; k >= 0; --k) {
+            uint32_t part = 0;
+            for (int w = k * wps + lane; w < min(words, (k + 1) * wps); w += 64) {
+                uint32_t x = pa[w], y = pb[w];
+                const int cnt = min(16, len - 16 * w);
+                for (int u = 0; u < cnt; ++u) {
+                    part += tab[((x & 3u) << 2) | (y & 3u)];
+                    x >>= 2;
+                    y >>= 2;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+            sum += part;
+            if (lane == 0) out[k] = k * ROWS <= len ? sum + gap : SED_REFINE_NO_SUF;
+        }
+    } else {
+        sum = diag_cost_sum(tab, seqa + d.a_off, seqb + d.b_off, min(n, m), lane);
     }
+    if (lane == 0) band[pair] = sed_band_window(n, m, bp.ins, bp.del, (uint64_t)sum + gap);
 }
 
 // ---------------------------------------------------------------------------
@@ -1655,7 +1721,7 @@ hipError_t sed_launch_i32_cut(const sed_launch &L, const int32_t *list, int nlis
 #define CASE(RR)                                                                                                        \
     case RR:                                                                                                            \
         SED_LAUNCH((sed_wf_i32_kernel<RR, false, false, false, false, false, true>), grid, block, 0, Lf, L.pd, nlist, lp, a, \
-                   b, (uint32_t *)nullptr, L.bnd, L.res, prm, (const sed_band *)L.band);                                \
+                   b, (uint32_t *)nullptr, L.bnd, L.res, prm, (const sed_band *)L.band, sed_stripe_wins{});             \
         break;
         CASE(4) CASE(8) CASE(16)
 #undef CASE
@@ -1670,7 +1736,8 @@ hipError_t sed_launch_cut_filter(const sed_launch &L, double cutoff, uint32_t *h
 }
 hipError_t sed_launch_band(const sed_launch &L, const sed_band_params &bp) {
     hipExtLaunchKernelGGL(sed_band_kernel, dim3((L.npairs + 3) / 4), dim3(256), 0, L.stream, L.ev0, nullptr, 0, L.pd,
-                          L.npairs, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.band, bp);
+                          L.npairs, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.band, bp, L.bsuf, L.bstripes,
+                          64 * L.R);
     return hipGetLastError();
 }
 template <int R, bool TB, bool LEN = true, bool CK = false, bool DOT = false>
@@ -1681,7 +1748,7 @@ static hipError_t launch_i32_R(const sed_launch &L, const sed_i32_params &prm) {
         } else {
             SED_LAUNCH((sed_wf_i32_kernel<R, TB, true, LEN, CK, DOT>), dim3(L.ntasks), dim3(128), 0, L, L.pd, L.npairs,
                        L.tasks, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.tb, L.bnd, L.res, prm,
-                       (const sed_band *)nullptr);
+                       (const sed_band *)nullptr, sed_stripe_wins{});
         }
     } else {
         const int grid = (L.npairs + 3) / 4;
@@ -1695,7 +1762,8 @@ static hipError_t launch_i32_R(const sed_launch &L, const sed_i32_params &prm) {
         }
         SED_LAUNCH((sed_wf_i32_kernel<R, TB, false, LEN, CK, DOT>), dim3(grid), dim3(256), occ_lds, Lf, L.pd, L.npairs,
                            L.tasks, (const uint32_t *)L.seqa, (const uint32_t *)L.seqb, L.tb, L.bnd, L.res,
-                           prm, CK ? (const sed_band *)L.band : nullptr);
+                           prm, CK ? (const sed_band *)L.band : nullptr,
+                           CK && L.band ? sed_stripe_wins{L.bwin, L.bsuf, L.bstripes} : sed_stripe_wins{});
     }
     return hipGetLastError();
 }

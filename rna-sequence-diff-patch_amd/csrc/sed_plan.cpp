@@ -864,8 +864,19 @@ void plan_band(Planning &P) {
         if (!(c.sub[e] >= 0)) costs_ok = false;
     b.band = b.ck && b.nchains == 0 && P.o.band != 2 && P.o.env_band != 0 && costs_ok;
     b.band_cells = b.cells;
+    b.band_refine = false;
+    b.band_stripes = 0;
     if (b.band) {
         const sed_band_params bp = b.bandp = sed_band_params_from(c);
+        // refined windows unless switched to the static ones; their 32-bit arithmetic needs (insert + delete) (n + m)
+        // below 2^30 for every wave pair (sed_internal.h: sed_refine_cell)
+        b.band_refine = P.o.band != 3 && P.o.env_band != 3;
+        for (int p = 0; p < npairs; ++p) {
+            const int64_t nn = P.len_a[p], mm = P.len_b[p];
+            if (b.pd[p].lane || nn <= 0 || mm <= 0) continue;
+            b.band_stripes = std::max(b.band_stripes, sed_stripe_geom((int)nn, (int)mm, R, 64).nstripes);
+            if (((int64_t)bp.ins + bp.del) * (nn + mm) >= (1ll << 30)) b.band_refine = false;
+        }
         double bc = 0, ckb = 0;
         const int G = 64 / R;
         for (int p = 0; p < npairs; ++p) {
@@ -1070,7 +1081,7 @@ const OptSpec opt_table[] = {
     {SED_OPT_DOT, &sed_opts::dot, V(0, 2, 3), 0},
     {SED_OPT_CHAIN_WAVES, &sed_opts::chain_waves, 0, INT_MAX},
     {SED_OPT_CUT, &sed_opts::cut, 0, 2},
-    {SED_OPT_BAND, &sed_opts::band, V(0, 2), 0},
+    {SED_OPT_BAND, &sed_opts::band, V(0, 2, 3), 0},
     {SED_OPT_FIT_CHUNK, &sed_opts::fit_chunk, 0, INT_MAX},
     {SED_OPT_DEBUG_CORRUPT, &sed_opts::debug_corrupt, 0, INT_MAX},
     {SED_OPT_CHAIN, &sed_opts::chain, 0, 1024},
@@ -1395,6 +1406,32 @@ int sed_band_bounds(int32_t n, int32_t m, double ins, double del, double ub, int
     const sed_band w = sed_band_window(n, m, (uint32_t)ins, (uint32_t)del, (uint64_t)ub);
     out[0] = w.elo;
     out[1] = w.ehi;
+    return SED_OK;
+}
+
+int sed_band_refine_row(int32_t n, int32_t m, int32_t rows_per_lane, double ins, double del, int32_t stripe,
+                        double ub_prev, double suf, const int32_t *drow, int32_t clo_prev, int32_t chi_prev,
+                        int32_t *out) {
+    const int R = rows_per_lane;
+    if (!out || !drow || n < 1 || m < 1 || (R != 4 && R != 8 && R != 16) || stripe < 1 ||
+        stripe >= sed_stripe_geom(n, m, R, 64).nstripes || !(ins >= 0) || !(del >= 0) || !(ins + del > 0) ||
+        (ins + del) * ((double)n + m) >= (double)(1 << 30) || !(ub_prev >= 0) || ub_prev >= (double)(1u << 31) ||
+        suf >= (double)(1u << 31))
+        return SED_E_ARG;
+    const int ROWS = 64 * R, nchunks = sed_stripe_geom(n, m, R, 64).nchunks, r0 = stripe * ROWS;
+    if (clo_prev < 0 || chi_prev < clo_prev || chi_prev >= nchunks) return SED_E_ARG;
+    const uint32_t ui = (uint32_t)ins, ud = (uint32_t)del;
+    const int j0 = 64 * clo_prev + 1, j1 = std::min(m, 64 * chi_prev + 1);  // the columns the stripe above computed
+    uint32_t ub = (uint32_t)ub_prev;
+    if (suf >= 0 && r0 >= j0 && r0 <= j1) ub = std::min(ub, (uint32_t)drow[r0] + (uint32_t)suf);
+    int32_t lo = SED_REFINE_LO_INIT, hi = SED_REFINE_HI_INIT;
+    for (int j = j0; j <= j1; ++j) sed_refine_cell(n, m, ui, ud, r0, j, (uint32_t)drow[j], ub, &lo, &hi);
+    int clo, chi;
+    const bool any = sed_refine_chunks(n, m, ROWS, nchunks, ui, ud, ub, lo, hi, stripe, clo_prev, chi_prev, &clo, &chi);
+    out[0] = clo;
+    out[1] = chi;
+    out[2] = (int32_t)ub;
+    out[3] = any ? 1 : 0;
     return SED_OK;
 }
 

@@ -31,12 +31,13 @@ struct sed_opts {
     int dot = 0;            // SED_OPT_DOT: 0 auto, 2 never (checkpoint batches keep the perm-based distance keys), 3 no wide ladder
     int debug_corrupt = 0;  // SED_OPT_DEBUG_CORRUPT: pair + 1 whose sink-tile checkpoint is overwritten
     int band = 0;           // SED_OPT_BAND: 0 auto (checkpoint batches of the stripe kernel skip the cells no
-                            // optimal path reaches), 2 never
+                            // optimal path reaches, every stripe's range refined from the row above it), 2 never,
+                            // 3 the static windows only
     int cut = 0;            // SED_OPT_CUT: cutoff batches' wave pairs: 0 auto (the windowed stripe kernel when it
                             // should pay), 1 whenever eligible, 2 never (filter only)
     int fit_chunk = 0;      // SED_OPT_FIT_CHUNK: fit search, owned text columns per lane: 0 auto, else the chunk length
     int env_tbpar = -1;     // SED_TBPAR: 0/1 overrides the stripe-parallel traceback's rule (A/B), -1 unset
-    int env_band = 1;       // SED_BAND: 0 turns band pruning off (A/B through bench.py)
+    int env_band = 1;       // SED_BAND: 0 turns band pruning off, 3 ("static") keeps the static windows (A/B through bench.py)
     int env_alt_dp = 1;     // SED_ALT_DP: 0 keeps every DP on the context's stream (A/B)
     int env_ck_halves = -1; // SED_CK_HALVES: parts per checkpoint batch, -1 unset (SED_CK_HALVES_DEFAULT)
 };
@@ -68,6 +69,10 @@ struct sed_plan {
     // band pruning (sed_internal.h: sed_band_window): the forward runs only the chunks an optimal path can reach;
     // band_cells = the cells the forward computes (from the host's own diagonal bounds; = cells when off)
     bool band = false;
+    // refined windows (sed_internal.h: sed_refine_cell): band_stripes = the most stripes of any wave pair, the stride of
+    // the per-stripe regions [suffix costs (npairs x band_stripes words) | windows (npairs x band_stripes x 2)]
+    bool band_refine = false;
+    int band_stripes = 0;
     sed_band_params bandp{};
     double band_cells = 0;
     // a cutoff's windows (sed_batch_set_cutoff): their costs and whether they allow pruning, taken at the fill with the

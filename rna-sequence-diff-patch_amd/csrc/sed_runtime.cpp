@@ -53,6 +53,8 @@ const sed_opts &env_opts() {
         auto knob = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
         o.env_tbpar = knob("SED_TBPAR", -1);
         o.env_band = knob("SED_BAND", 1);
+        if (const char *e = getenv("SED_BAND"))
+            if (!strcmp(e, "static")) o.env_band = 3;  // band pruning with the static windows only
         o.env_alt_dp = knob("SED_ALT_DP", 1);
         o.env_ck_halves = knob("SED_CK_HALVES", -1);
         return o;
@@ -152,6 +154,10 @@ struct sed_batch {
     uint64_t bnd_zero_gen = 0;
     // band pruning: d_band holds every pair's window, rewritten by sed_band_kernel in every run
     DevBuf d_band;
+    // the per-stripe regions of a band-pruned batch (sed_plan: band_stripes): [suffix costs | windows], and the host's
+    // copy of the windows for sed_batch_band_chunks_run
+    DevBuf d_bwin;
+    std::vector<int32_t> h_bwin;
     // cutoff (sed_batch_set_cutoff): every run ends with sed_cut_filter_kernel (results above cut_cmp
     // become +inf; cut_cmp = the cutoff floored to the integer scale in integer mode).  cut_win: the wave pairs
     // (cut_list: every pair not on a lane kernel) leave their routes for the windowed stripe kernel, whose windows
@@ -200,7 +206,7 @@ struct sed_batch {
         if (h_out) (void)hipHostFree(h_out);
         d_pd.release(); d_seqa.release(); d_seqb.release(); d_bnd.release(); d_ops.release(); d_tbmap.release();
         d_tasks.release(); d_lane.release(); d_chain.release(); d_x2.release(); d_small.release(); d_seg.release();
-        d_band.release(); d_cut.release();
+        d_band.release(); d_cut.release(); d_bwin.release();
         for (int i = 0; i < 3; ++i) {
             d_tb[i].release();
             d_res[i].release();
@@ -300,7 +306,8 @@ int reserve_batch(sed_batch *b) {
     const bool want_tb = (p.flags & SED_WANT_SCRIPT) != 0;
     bool ok = b->d_bnd.reserve(4 * std::max<uint64_t>(1, p.bnd_words)) &&
               b->d_tbmap.reserve(4 * std::max<uint64_t>(1, p.map_words)) &&
-              (!p.band || b->d_band.reserve(sizeof(sed_band) * (size_t)p.npairs));
+              (!p.band || (b->d_band.reserve(sizeof(sed_band) * (size_t)p.npairs) &&
+                           b->d_bwin.reserve(12 * std::max<size_t>(1, (size_t)p.npairs * p.band_stripes))));
     if (p.small) {
         ok = ok && b->d_small.reserve(p.blob_bytes);
     } else {
@@ -471,6 +478,8 @@ int run_batch_parts(sed_batch *b, const std::array<hipEvent_t, 4> &lg, sed_launc
         Li.pd = L.pd + first(i);
         Li.res = L.res + first(i);
         Li.band = L.band ? L.band + first(i) : nullptr;
+        Li.bwin = L.bwin ? L.bwin + (size_t)first(i) * L.bstripes : nullptr;
+        Li.bsuf = L.bsuf ? L.bsuf + (size_t)first(i) * L.bstripes : nullptr;
         Li.npairs = first(i + 1) - first(i);
         Li.stream = stream(i);
         Li.ev0 = i == 0 ? lg[2 * ph] : pl[4 * (i - 1) + 2 * ph];
@@ -542,6 +551,12 @@ int run_batch(sed_batch *b) {
     L.ck = b->plan.ck;
     L.band = b->plan.band ? (sed_band *)b->d_band.p : nullptr;
     L.bandp = &b->plan.bandp;
+    if (L.band && b->plan.band_stripes > 0) {
+        const size_t per = (size_t)b->plan.npairs * b->plan.band_stripes;
+        L.bstripes = b->plan.band_stripes;
+        L.bsuf = b->plan.band_refine ? (uint32_t *)b->d_bwin.p : nullptr;
+        L.bwin = (int2 *)((uint32_t *)b->d_bwin.p + per);
+    }
     L.tasks = b->plan.split ? (const int2 *)b->p_tasks : nullptr;
     L.ntasks = b->plan.split ? b->plan.ntasks : 0;
     // buffer k was last read by the traceback of run runs-3 (written by its DP, distance only): wait for it unless it
@@ -761,6 +776,8 @@ int fetch_results(sed_batch *b, double *out_dist, uint8_t *out_is_int, int32_t *
             return c->fail(SED_E_DEVICE, "pair %d: traceback failed: script length differs from the sink's", p);
         case SED_ERR_TB_BAND:
             return c->fail(SED_E_DEVICE, "pair %d: traceback failed: the walk left the band the forward computed", p);
+        case SED_ERR_FWD_BAND:
+            return c->fail(SED_E_DEVICE, "pair %d: forward failed: no cell of a stripe's boundary row fits the bound", p);
         default: return c->fail(SED_E_DEVICE, "pair %d: device error code %d", p, (int)hr[p].err);
         }
     }
@@ -876,6 +893,32 @@ int sed_batch_chains(const sed_batch *b) { return b ? sed_plan_chains(b->plan, b
 int sed_batch_traceback_mode(const sed_batch *b) { return b ? sed_plan_traceback_mode(b->plan) : 0; }
 
 double sed_batch_band_cells(const sed_batch *b) { return b ? b->band_cells : 0.0; }
+
+double sed_batch_band_chunks_run(sed_batch *b, double *total) {
+    if (!b || !b->plan.band || !b->ran || b->plan.band_stripes <= 0) return -1.0;
+    sed_ctx *c = b->ctx;
+    (void)hipSetDevice(c->device);
+    if (sync_batch(b) != SED_OK) return -1.0;
+    const size_t per = (size_t)b->plan.npairs * b->plan.band_stripes;
+    b->h_bwin.resize(2 * per);
+    if (hipMemcpy(b->h_bwin.data(), (const uint32_t *)b->d_bwin.p + per, 8 * per, hipMemcpyDeviceToHost) != hipSuccess) {
+        c->fail(SED_E_DEVICE, "download the stripes' windows");
+        return -1.0;
+    }
+    double run = 0, all = 0;
+    for (int p = 0; p < b->plan.npairs; ++p) {
+        const sed_pair_desc &d = b->plan.pd[p];
+        if (d.lane || d.n <= 0 || d.m <= 0) continue;
+        const sed_geom g = sed_stripe_geom(d.n, d.m, b->plan.R, 64);
+        for (int k = 0; k < g.nstripes; ++k) {
+            const int32_t *w = &b->h_bwin[2 * ((size_t)p * b->plan.band_stripes + k)];
+            run += (double)(w[1] - w[0] + 1);
+        }
+        all += (double)g.nstripes * g.nchunks;
+    }
+    if (total) *total = all;
+    return run;
+}
 
 int sed_batch_set_cutoff(sed_batch *b, double max_dist) {
     if (!b) return SED_E_ARG;

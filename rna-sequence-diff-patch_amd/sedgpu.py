@@ -95,6 +95,9 @@ SIGNATURES = [
     ("sed_band_chunk_range", C.c_int, [C.c_int32] * 6 + [_i32p]),
     ("sed_band_cells", C.c_double, [_f64p, C.c_double, C.c_double, _u8p, C.c_int32, _u8p, C.c_int32, C.c_int32]),
     ("sed_batch_band_cells", C.c_double, [C.c_void_p]),
+    ("sed_batch_band_chunks_run", C.c_double, [C.c_void_p, _f64p]),
+    ("sed_band_refine_row", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                      C.c_double, _i32p, C.c_int32, C.c_int32, _i32p]),
     ("sed_batch_set_cutoff", C.c_int, [C.c_void_p, C.c_double]),
     ("sed_batch_cutoff_hits", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ("sed_batch_packed_pairs", C.c_int, [C.c_void_p]),
@@ -467,6 +470,13 @@ class Batch:
     def band_cells(self):
         """Cells the forward computes per run: below sum n*m when the batch is band-pruned (SED_OPT_BAND)."""
         return float(self._lib.sed_batch_band_cells(self.ptr))
+
+    def band_chunks_run(self):
+        """(chunks the forward ran, chunks of the same stripes unpruned) of the last run of a band-pruned batch, summed
+        from the ranges the kernel stored per stripe; None when the batch is not band-pruned or has not run."""
+        total = np.zeros(1, np.float64)
+        run = float(self._lib.sed_batch_band_chunks_run(self.ptr, total))
+        return None if run < 0 else (run, float(total[0]))
 
     @property
     def ladder_dot_keys(self):
@@ -1052,6 +1062,20 @@ def band_chunk_range(n, m, rows_per_lane, e_lo, e_hi, stripe):
     if load().sed_band_chunk_range(int(n), int(m), int(rows_per_lane), int(e_lo), int(e_hi), int(stripe), out) != 0:
         raise SedError("sed_band_chunk_range: bad arguments")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def band_refine_row(n, m, rows_per_lane, ins, dele, stripe, ub_prev, suf, drow, clo_prev, chi_prev):
+    """One stripe's refined chunk range from the row above it, as the forward kernel computes it (sed.h:
+    sed_band_refine_row): (clo, chi, the new upper bound, whether a cell survived).  suf = None where the stripe
+    boundary lies past the diagonal's end."""
+    out = np.zeros(4, np.int32)
+    row = np.ascontiguousarray(drow, np.int32)
+    if len(row) != m + 1:
+        raise SedError("band_refine_row: drow must hold m + 1 values")
+    if load().sed_band_refine_row(int(n), int(m), int(rows_per_lane), float(ins), float(dele), int(stripe), float(ub_prev),
+                                  -1.0 if suf is None else float(suf), row, int(clo_prev), int(chi_prev), out) != 0:
+        raise SedError("sed_band_refine_row: bad arguments")
+    return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
 
 
 def band_cells(sub, ins, dele, codes_a, codes_b, rows_per_lane=16):
