@@ -360,6 +360,49 @@ int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, 
 /* Device time of the last sed_fit_search's kernel, from HIP events (ms); SED_E_STATE before the first search. */
 int sed_fit_last_time(const sed_ctx *ctx, float *kernel_ms);
 
+/* Fit search over a resident index: the texts of a collection are packed and uploaded once, and every search sends
+ * only its queries.  A sed_fit_index belongs to the context it was created on (several may live on one context, beside
+ * its batches; each owns its device buffers and its pinned result buffer) and must be destroyed before the context.
+ * sed_fit_index_create: text d = codes_t[off_t[d] .. +len_t[d]), every text copied (4-byte aligned, as sed_fit_search
+ * lays them out).  It needs no cost model: the index keeps the texts' lengths and the largest code it saw, and every
+ * search runs under the context's costs of that moment, so costs and options may change between searches.  ntexts = 0
+ * is valid.  NULL on failure, with the reason in sed_last_error(ctx): SED_E_ARG conditions (NULL, a negative length or
+ * offset), more than 16 GB of text, an allocation or a copy that failed. */
+typedef struct sed_fit_index sed_fit_index;
+sed_fit_index *sed_fit_index_create(sed_ctx *ctx, const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
+                                    int32_t ntexts);
+void sed_fit_index_destroy(sed_fit_index *ix);
+int32_t sed_fit_index_texts(const sed_fit_index *ix);    /* the number of texts */
+int64_t sed_fit_index_symbols(const sed_fit_index *ix);  /* the sum of their lengths */
+/* Every query against every text, blocking, in one launch (65535 queries per launch; more run as further launches of
+ * the same call): query q = codes_p[off_p[q] .. +len_p[q]), and out_*[q * ntexts + d] = the hit (dist, start, end) of
+ * (query q, text d) as sed_fit_search defines it.  The hits equal, bit for bit, what sed_fit_search returns for the
+ * nqueries x ntexts pairs listed query-major under the same costs and the same chunk length: the plan is that batch's
+ * plan (sed_fit_index_plan), and every lane runs the same DP on the same columns.  The cost models served and the
+ * refusals are sed_fit_search's, decided per search before anything is launched: SED_E_RANGE with the failed condition
+ * in the text, SED_E_ARG (NULL, a negative length or offset, a query code >= K, or an index that holds a text code >= K
+ * under the current costs), SED_E_STATE (no costs set, or a pair in flight after sed_pair_submit).  A refused search
+ * leaves the index usable.  SED_OPT_FIT_CHUNK sets the chunk length as for sed_fit_search.  The host work of a search
+ * grows with the queries and the results, never with the texts' bytes; the per-(text, chunk) table on the device is
+ * rebuilt only when the chunk length differs from the last search's. */
+int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end);
+/* Device time of the last sed_fit_index_search's kernel(s), from HIP events (ms); SED_E_STATE before the first search
+ * that launched one. */
+int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms);
+/* What sed_fit_index_search would decide, without a device: sed_fit_plan's code and out[] for the nqueries x ntexts
+ * cross product (pair q * ntexts + d = query q, text d), computed from the queries' lengths and sums over the texts. */
+int sed_fit_index_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                       double del, int del_is_int, const int32_t *options, int noptions,
+                       const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts, double *out, int nout);
+/* The lane records sed_fit_index_search would run, without a device (for tests and tools): each from the index's
+ * (text, chunk) table and the function the kernel derives its lane with, query-major, then in the table's order (text
+ * by text, chunk by chunk).  out_lanes and out_params as sed_fit_lanes lays them out, pair = q * ntexts + d. */
+int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                        double del, int del_is_int, const int32_t *options, int noptions,
+                        const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts,
+                        int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params);
+
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,
  * 4 update) | (1 << 3 when the value is a Python int).  Always runs the fp64 kernel. */

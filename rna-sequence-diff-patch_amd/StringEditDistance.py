@@ -741,6 +741,87 @@ def fit_batch(patterns, texts, userCosts=False):
     return list(zip(dist.tolist(), start.tolist(), end.tolist()))
 
 
+class _EngineIndex:
+    """The device half of a FitIndex: the texts' codes resident on the process's engine (sedgpu.FitIndex)."""
+
+    def __init__(self, codes, off, lens):
+        self.ctx = sedgpu.context()
+        self.ix = self.ctx.fit_index(codes, off, lens)
+
+    def search(self, plan, packed):
+        self.ctx.set_costs(plan)
+        return self.ix.search(packed)
+
+    def close(self):
+        self.ix.close()
+
+
+class FitIndex:
+    """fit_batch over texts that stay on the device: fit_index(texts) encodes and uploads them once, and
+    search(patterns) sends only the patterns and runs all of them against every text in one launch.
+
+    The texts' symbols get their codes when the index is built (first-occurrence order over the texts, as batch_plan
+    resolves them; or `alphabet` first, for a collection that may grow into symbols it does not hold yet).  A search
+    whose patterns bring symbols the texts do not have appends them for that search only; more than 8 symbols in all
+    raise SedError (fit search serves at most 8).  The cost table is read at every search, so edits to it take effect,
+    and the KeyErrors are the reference's for the first offending (pattern, text) in pattern-major order."""
+
+    def __init__(self, texts, userCosts=False, alphabet=None, engine=None):
+        self.texts = list(texts)
+        self.userCosts = userCosts
+        used = sedcost.distinct_many(self.texts) if sedcost._all_str(self.texts) else \
+            list(dict.fromkeys(c for t in self.texts for c in t))
+        self._used = used  # the symbols the texts hold: the str2 side of every cost lookup
+        self.symbols = list(dict.fromkeys(list(alphabet or ()) + used))
+        if len(self.symbols) > 8:
+            raise sedgpu.SedError("fit index: the texts have %d symbols (fit search serves at most 8)" % len(self.symbols))
+        code = {c: k for k, c in enumerate(self.symbols)}
+        lens = np.fromiter(map(len, self.texts), dtype=np.int32, count=len(self.texts))
+        codes = np.fromiter((code[c] for t in self.texts for c in t), dtype=np.uint8, count=int(lens.sum()))
+        off = np.zeros(len(lens), np.int64)
+        if len(lens):
+            off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        self._dev = (engine or _EngineIndex)(codes, off, lens)
+
+    def plan(self, patterns):
+        """The reference's KeyError for the first offending (pattern, text), if any, then the search's CostPlan: the
+        index's symbols in their order, then the patterns' new ones."""
+        table = _table(self.userCosts)
+        rep = "".join(self._used) if sedcost._all_str(self.texts) and all(len(c) == 1 for c in self._used) else None
+        u1 = sedcost.distinct_many(patterns) if sedcost._all_str(patterns) else \
+            list(dict.fromkeys(c for p in patterns for c in p))
+        # one pair per pattern against a text of every symbol the index holds resolves exactly when every pair does
+        if rep is None or not sedcost._batch_resolves(table, patterns, [rep] * len(patterns), (u1, self._used)):
+            for p in patterns:
+                for t in self.texts:
+                    sedcost.check_pair(table, p, t)
+        alphabet = self.symbols + [c for c in u1 if c not in self.symbols]
+        if len(alphabet) > 8:
+            raise sedgpu.SedError("fit index: the texts and these patterns have %d symbols (fit search serves at most 8)"
+                                  % len(alphabet))
+        return sedcost.plan_over(table, alphabet, set(u1), set(self._used))
+
+    def search(self, patterns):
+        """[[(dist, start, end) for each text] for each pattern], every hit as fit_batch defines it."""
+        patterns = list(patterns)
+        plan = self.plan(patterns)
+        if not patterns:
+            return []
+        ca, la = plan.encode_many(patterns)
+        packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
+        dist, start, end = self._dev.search(plan, packed)
+        return [list(zip(d, s, e)) for d, s, e in zip(dist.tolist(), start.tolist(), end.tolist())]
+
+    def close(self):
+        self._dev.close()
+
+
+def fit_index(texts, userCosts=False, alphabet=None, engine=None):
+    """A FitIndex over texts: fit_batch for callers who search one collection query after query.  engine(codes, off,
+    lens) -> an object with search(plan, packed) and close() replaces the device (CPU tests)."""
+    return FitIndex(texts, userCosts, alphabet, engine)
+
+
 def edit_script_batch(strs1, strs2, userCosts=False):
     """[(value, generate_es(create_paths(dp)[0], s1, s2))] for each pair — one GPU launch."""
     strs1, strs2 = list(strs1), list(strs2)

@@ -1,4 +1,5 @@
-// sed_fit.hip — fit search (include/sed.h: sed_fit_search): the best approximate occurrence of a short pattern
+// sed_fit.hip — fit search (include/sed.h: sed_fit_search, and sed_fit_index_search over a resident text index, whose
+// kernel is at the end and runs the same DP, sed_fit_dp.h): the best approximate occurrence of a short pattern
 // (1 <= P <= SED_LANE_MAXM) in a long text, one lane per (pair, chunk of text columns).
 //
 // The DP is the weighted Wagner-Fischer recurrence (StringEditDistance.py:92-128) with a free start: D[0][j] = 0,
@@ -26,82 +27,44 @@
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
+#include "sed_fit_dp.h"
 
 namespace {
-
-constexpr int FIT_ROWS = SED_LANE_MAXM;
-constexpr int FIT_REBASE = 128;  // columns between rebases of the insert offset
 
 __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_kernel(const sed_fit_lane *__restrict__ lanes, int nlanes,
                                                                     const uint4 *__restrict__ pats,
                                                                     const uint32_t *__restrict__ text,
                                                                     unsigned long long *__restrict__ out,
                                                                     sed_fit_params fp) {
-    static_assert(FIT_ROWS == 32, "a pattern record is two 16-byte words");
-    __shared__ uint2 tab[9];  // kappa bytes of pattern symbol a for text symbols 0..7; row 8 (front rows): zeros
-    if (threadIdx.x < 9)
-        tab[threadIdx.x] = threadIdx.x < 8 ? make_uint2(fp.row[threadIdx.x][0], fp.row[threadIdx.x][1]) : make_uint2(0u, 0u);
-    __syncthreads();
+    __shared__ uint2 tab[9];
+    sed_fit_fill_tab(tab, fp);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nlanes) return;
     const sed_fit_lane ln = lanes[t];
-    // the pattern, right-aligned in 32 byte codes, code 8 in front of it (sed_runtime.cpp packs the records)
-    const uint4 q0 = pats[2 * (size_t)ln.pat], q1 = pats[2 * (size_t)ln.pat + 1];
-    const uint32_t pw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-    uint32_t clo[FIT_ROWS], chi[FIT_ROWS];  // register r + 1's kappa bytes
-#pragma unroll
-    for (int r = 0; r < FIT_ROWS; ++r) {
-        const uint2 e = tab[(pw[r >> 2] >> (8 * (r & 3))) & 15u];
-        clo[r] = e.x;
-        chi[r] = e.y;
-    }
-    const uint32_t pdel = (uint32_t)ln.plen * fp.del;
-    const uint32_t rebase = ((uint32_t)FIT_REBASE * fp.ins) << 16;
-    const uint32_t step = (fp.ins << 16) + 1u;  // row 0's key from one column to the next
-    uint32_t inj = ((pdel << 16) + rebase) | 0xFFFFu;
-    uint32_t V[FIT_ROWS + 1];
-#pragma unroll
-    for (int r = 0; r <= FIT_ROWS; ++r) V[r] = inj;  // the border column: D = i delete, start = this column
-    // the sink row's first strict minimum over the owned columns: bestc = (D - P delete) << 16 | owned column index
-    // (signed order), bestt = the same with end - start in the low half
-    int32_t u = -ln.lead;  // the current column's index among the owned ones
-    int32_t bestc = ln.lead == 0 ? 0 : 0x7FFFFFFF, bestt = 0;  // (an owned border column: D = P delete, start = end)
-    const uint32_t *tp = text + ln.tw;
-    uint32_t wnext = ln.nsteps > 0 ? tp[0] : 0u;
-    for (int s = 0; s < ln.nsteps; s += 4) {
-        const uint32_t w = wnext;
-        wnext = tp[(s >> 2) + 1];  // in flight during these four columns (the text buffer ends with spare words)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            // perm selector of this column: byte 2 <- kappa byte of the text symbol (0..3: clo, 4..7: chi), else 0
-            const uint32_t sel = __builtin_amdgcn_perm(w, 0x0C0C0C0Cu, 0x00000000u | ((4u + k) << 16));
-            inj -= step;
-            uint32_t dg = V[0] - __builtin_amdgcn_perm(chi[0], clo[0], sel);
-            V[0] = inj;
-#pragma unroll
-            for (int r = 1; r <= FIT_ROWS; ++r) {
-                const uint32_t old = V[r];
-                const uint32_t dnext = r < FIT_ROWS ? old - __builtin_amdgcn_perm(chi[r], clo[r], sel) : 0u;
-                V[r] = umin3(old, V[r - 1], dg);  // insert (left), delete (up), update (diagonal)
-                dg = dnext;
-            }
-            ++u;
-            const int32_t tt = (int32_t)(V[FIT_ROWS] - inj);
-            const int32_t c = (int32_t)((uint32_t)tt & 0xFFFF0000u) | (u & 0xFFFF);
-            const bool take = (uint32_t)u < (uint32_t)ln.cnt && c < (int32_t)((uint32_t)bestc & 0xFFFF0000u);
-            bestc = take ? c : bestc;
-            bestt = take ? tt : bestt;
-        }
-        if ((s & (FIT_REBASE - 1)) == FIT_REBASE - 4) {
-            inj += rebase;
-#pragma unroll
-            for (int r = 0; r <= FIT_ROWS; ++r) V[r] += rebase;
-        }
-    }
-    const uint32_t D = (uint32_t)((bestt >> 16) + (int32_t)pdel);
-    const uint32_t len = (uint32_t)bestt & 0xFFFFu;
-    const uint32_t end = (uint32_t)ln.c0 + ((uint32_t)bestc & 0xFFFFu);
-    atomicMin(out + ln.pair, ((unsigned long long)D << 48) | ((unsigned long long)end << 16) | len);
+    sed_fit_dp(ln, pats[2 * (size_t)ln.pat], pats[2 * (size_t)ln.pat + 1], tab, text, out, fp);
+}
+
+// The same DP over a resident index (sed_internal.h: sed_fit_index_args): blockIdx.y + q0 = the query, whose pattern
+// record and length are uniform across the block; blockIdx.x * 64 + threadIdx.x = the chunk record.  The lane derives
+// its record (sed_fit_derive_lane, the function the device-free sed_fit_index_lanes checks against the lane builder)
+// and reports into out[query * ntexts + text].
+__global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_kernel(const sed_fit_chunk *__restrict__ chunks,
+                                                                          int nchunks,
+                                                                          const sed_fit_text *__restrict__ texts,
+                                                                          int ntexts, const uint4 *__restrict__ pats,
+                                                                          const int32_t *__restrict__ plens, int q0,
+                                                                          const uint32_t *__restrict__ text,
+                                                                          unsigned long long *__restrict__ out,
+                                                                          int32_t chunk, int32_t W, sed_fit_params fp) {
+    __shared__ uint2 tab[9];
+    sed_fit_fill_tab(tab, fp);
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nchunks) return;
+    const int q = q0 + (int)blockIdx.y;
+    const sed_fit_chunk ck = chunks[t];
+    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
+    ln.pair = q * ntexts + ck.text;
+    sed_fit_dp(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, out, fp);
 }
 
 }  // namespace
@@ -112,4 +75,21 @@ hipError_t sed_launch_fit(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, co
     hipExtLaunchKernelGGL(sed_fit_kernel, dim3((nlanes + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK), dim3(SED_FIT_BLOCK), 0,
                           stream, ev0, ev1, 0, lanes, nlanes, (const uint4 *)pats, (const uint32_t *)text, out, fp);
     return hipGetLastError();
+}
+
+#define SED_FIT_INDEX_MAXY 65535  // queries per launch (the grid's y limit); more run as further launches
+hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                const sed_fit_params &fp) {
+    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
+    const unsigned gx = (unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK);
+    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_INDEX_MAXY) {
+        const int nq = a.nqueries - q0 < SED_FIT_INDEX_MAXY ? a.nqueries - q0 : SED_FIT_INDEX_MAXY;
+        // the events bracket the whole search: the first launch starts ev0, the last stops ev1
+        hipExtLaunchKernelGGL(sed_fit_index_kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream,
+                              q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts,
+                              a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, a.out, a.chunk, a.W, fp);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }

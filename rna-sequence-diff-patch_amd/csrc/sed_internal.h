@@ -217,6 +217,56 @@ struct sed_fit_params {
 #define SED_FIT_BLOCK 64
 hipError_t sed_launch_fit(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_lane *lanes, int nlanes,
                           const void *pats, const void *text, unsigned long long *out, const sed_fit_params &fp);
+// columns a lane that owns [c0, ...) starts before c0: min(c0, W) rounded up so that c0 - lead is a multiple of 4
+__host__ __device__ inline int32_t sed_fit_lead(int64_t W, int64_t c0) {
+    const int64_t jb = c0 <= W ? 0 : (c0 - W) & ~(int64_t)3;
+    return (int32_t)(c0 - jb);
+}
+// Fit search over a resident index (sed_fit.hip: sed_fit_index_kernel; include/sed.h: sed_fit_index_search).  The index
+// keeps one record per text (the word its copy starts at, its length) and, per chunk length, one record per (text,
+// chunk): neither depends on a query.  A lane is a (query, chunk record): it derives the sed_fit_lane sed_fit_kernel
+// would be handed for pair query * ntexts + text from the two records, the chunk length, the query's P and the
+// search's W (sed_fit_derive_lane: pair = the text, pat = 0, for the caller to set), and runs the same DP.
+struct sed_fit_chunk {
+    int32_t text, c0;  // the text and the chunk's first owned column
+};
+struct sed_fit_text {
+    uint32_t base;  // the 4-symbol word at which the text's copy starts
+    int32_t len;
+};
+__host__ __device__ inline sed_fit_lane sed_fit_derive_lane(sed_fit_chunk ck, sed_fit_text tx, int32_t chunk, int32_t plen,
+                                                            int64_t W) {
+    const int64_t ncol = (int64_t)tx.len + 1, c0 = ck.c0;
+    const int64_t c1 = chunk > 0 && c0 + chunk < ncol ? c0 + chunk : ncol;
+    const int32_t lead = sed_fit_lead(W, c0);
+    sed_fit_lane ln;
+    ln.tw = tx.base + (uint32_t)((c0 - lead) / 4);
+    ln.pair = ck.text;
+    ln.pat = 0;
+    ln.plen = plen;
+    ln.nsteps = (int32_t)(c1 - 1 - (c0 - lead));
+    ln.lead = lead;
+    ln.cnt = (int32_t)(c1 - c0);
+    ln.c0 = (int32_t)c0;
+    return ln;
+}
+// One search: queries q0 .. q0 + nq) of the grid's y run against every chunk record; pats = 32-byte pattern records,
+// plens = their lengths, by query; out[query * ntexts + text], preset to all ones.
+struct sed_fit_index_args {
+    const sed_fit_chunk *chunks;
+    int nchunks;
+    const sed_fit_text *texts;
+    int ntexts;
+    const void *pats;
+    const int32_t *plens;
+    int nqueries;
+    const void *text;
+    unsigned long long *out;
+    int32_t chunk;
+    int32_t W;
+};
+hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                const sed_fit_params &fp);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

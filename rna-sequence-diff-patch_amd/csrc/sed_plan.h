@@ -140,11 +140,24 @@ struct sed_fit_plan_t {
 };
 int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
                        sed_fit_plan_t *plan, std::string *err);
-// columns a lane that owns [c0, ...) starts before c0: min(c0, W) rounded up so that c0 - lead is a multiple of 4
-inline int32_t sed_fit_lead(int64_t W, int64_t c0) {
-    const int64_t jb = c0 <= W ? 0 : (c0 - W) & ~(int64_t)3;
-    return (int32_t)(c0 - jb);
-}
+// The same plan for an index search (include/sed.h: sed_fit_index_search): nqueries patterns against every text of an
+// index, i.e. sed_fit_plan_batch's plan of the nqueries x ntexts cross product, query-major, from the patterns' lengths
+// and the texts' sums alone (both go through one rule).  It leaves lanes and cells 0 and `first` empty: they follow from
+// the chunk table, sed_fit_build_chunks (lanes = nqueries x its records).
+struct sed_fit_index_sums {
+    int32_t ntexts = 0;
+    double cols = 0;             // sum (n + 1)
+    int64_t nmax = -1;           // the longest text
+    int32_t first_negative = -1; // the first text of negative length (the device-free exports; an index holds none)
+};
+int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err);
+// The chunk table of the texts under plan.chunk, text by text in chunk order (chunks may be null), independent of the
+// queries; returns the number of records.  *computed (if not null) += the columns the records' lanes run under plan.W,
+// warm-up included.
+int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
+                             std::vector<sed_fit_chunk> *chunks, double *computed);
+// (sed_fit_lead, the columns a lane starts before its first owned one: sed_internal.h, shared with the kernels)
 
 // The lane records of a planned batch (sed_internal.h: sed_fit_lane), lanes[plan.first[p] + k] = lane k of pair p, from
 // the plan and the lengths alone: tw counts 4-symbol words from the pair's own text start and pat is 0.  The runtime

@@ -1401,6 +1401,208 @@ int sed_fit_last_time(const sed_ctx *c, float *kernel_ms) {
     return hipEventElapsedTime(kernel_ms, c->fit_ev[0], c->fit_ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
 }
 
+// Fit search over a resident index (include/sed.h).  The index holds what no query changes: the packed texts, one
+// record per text, and for the chunk length of the last search one record per (text, chunk).  A search plans the
+// queries x texts cross product from the index's sums (sed_plan.cpp: sed_fit_plan_index), uploads the queries' pattern
+// records and lengths from pinned memory, and launches one lane per (query, chunk record); the kernel derives each lane
+// (sed_internal.h: sed_fit_derive_lane).  Per search the host touches the queries and the results only.
+struct sed_fit_index {
+    sed_ctx *ctx = nullptr;
+    sed_fit_index_sums sums;
+    int64_t symbols = 0;
+    int maxcode = -1;              // the largest text code (a search under K symbols needs maxcode < K)
+    std::vector<int32_t> len_t;    // the texts' lengths: the chunk table's input, and the bound of every reported end
+    DevBuf d_text, d_trec, d_chunks, d_query, d_out;
+    bool have_chunks = false;      // d_chunks holds the table of chunk length `chunk`, nchunks records
+    int32_t chunk = 0;
+    int64_t nchunks = 0;
+    std::vector<sed_fit_chunk> h_chunks;
+    // pinned host memory: [result keys (queries x texts) | pattern records | pattern lengths] of the search under way
+    void *pin = nullptr;
+    size_t pin_cap = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+    ~sed_fit_index() {
+        if (pin) (void)hipHostFree(pin);
+        d_text.release(); d_trec.release(); d_chunks.release(); d_query.release(); d_out.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+sed_fit_index *sed_fit_index_create(sed_ctx *c, const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
+                                    int32_t ntexts) {
+    if (!c) return nullptr;
+    if (ntexts < 0 || (ntexts > 0 && (!codes_t || !off_t || !len_t))) {
+        c->fail(SED_E_ARG, "bad fit index arguments");
+        return nullptr;
+    }
+    (void)hipSetDevice(c->device);
+    size_t words = 0;
+    for (int d = 0; d < ntexts; ++d) {
+        if (len_t[d] < 0 || off_t[d] < 0) {
+            c->fail(SED_E_ARG, "text %d: negative %s", d, len_t[d] < 0 ? "length" : "offset");
+            return nullptr;
+        }
+        words += ((size_t)len_t[d] + 3) / 4;
+        if (words > 0xFFFFFFF0u) {
+            c->fail(SED_E_RANGE, "fit search: more than 16 GB of text");
+            return nullptr;
+        }
+    }
+    sed_fit_index *ix = new sed_fit_index;
+    ix->ctx = c;
+    ix->sums.ntexts = ntexts;
+    ix->len_t.assign(len_t, len_t + ntexts);
+    // every text 4-byte aligned, zero padded, and spare words at the end: a lane reads one word past its last
+    std::vector<uint8_t> text(4 * words + 16, 0);
+    std::vector<sed_fit_text> trec((size_t)ntexts);
+    size_t at = 0;
+    uint8_t top = 0;
+    for (int d = 0; d < ntexts; ++d) {
+        const int n = len_t[d];
+        trec[d] = sed_fit_text{(uint32_t)(at / 4), n};
+        const uint8_t *src = codes_t + off_t[d];
+        for (int j = 0; j < n; ++j) top = std::max(top, text[at + j] = src[j]);
+        if (n > 0) ix->maxcode = std::max<int>(ix->maxcode, top);
+        at += ((size_t)n + 3) & ~(size_t)3;
+        ix->symbols += n;
+        ix->sums.cols += (double)n + 1;
+        ix->sums.nmax = std::max<int64_t>(ix->sums.nmax, n);
+    }
+    hipError_t e = hipSuccess;
+    if (!ix->d_text.reserve(text.size()) || !ix->d_trec.reserve(trec.size() * sizeof(sed_fit_text))) {
+        c->fail(SED_E_OOM, "device allocation failed (fit index, %zu text bytes)", text.size());
+    } else if ((e = hipMemcpyAsync(ix->d_text.p, text.data(), text.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+               (ntexts > 0 && (e = hipMemcpyAsync(ix->d_trec.p, trec.data(), trec.size() * sizeof(sed_fit_text),
+                                                  hipMemcpyHostToDevice, c->stream)) != hipSuccess) ||
+               (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+        c->hipfail(e, "upload (fit index)");
+    } else {
+        return ix;
+    }
+    delete ix;
+    return nullptr;
+}
+
+void sed_fit_index_destroy(sed_fit_index *ix) {
+    if (!ix) return;
+    (void)hipSetDevice(ix->ctx->device);
+    delete ix;
+}
+
+int32_t sed_fit_index_texts(const sed_fit_index *ix) { return ix ? ix->sums.ntexts : SED_E_ARG; }
+int64_t sed_fit_index_symbols(const sed_fit_index *ix) { return ix ? ix->symbols : SED_E_ARG; }
+
+int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+    if (!ix) return SED_E_ARG;
+    sed_ctx *c = ix->ctx;
+    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
+    const int ntexts = ix->sums.ntexts;
+    if (nqueries < 0 || (nqueries > 0 && (!codes_p || !off_p || !len_p)) ||
+        (nqueries > 0 && ntexts > 0 && (!out_dist || !out_start || !out_end)))
+        return c->fail(SED_E_ARG, "bad fit arguments");
+    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
+    (void)hipSetDevice(c->device);
+    sed_fit_plan_t plan;
+    int rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
+    const int K = c->costs.K;
+    if (ix->maxcode >= K)
+        return c->fail(SED_E_ARG, "fit index: it holds text code %d, outside the alphabet (K=%d)", ix->maxcode, K);
+    hipError_t e = hipSuccess;
+    // the chunk table: the last search's when the chunk length is the same
+    if (!ix->have_chunks || ix->chunk != plan.chunk) {
+        ix->have_chunks = false;
+        ix->nchunks = sed_fit_build_chunks(plan, ix->len_t.data(), ntexts, &ix->h_chunks, nullptr);
+        if (!ix->d_chunks.reserve(ix->h_chunks.size() * sizeof(sed_fit_chunk)))
+            return c->fail(SED_E_OOM, "device allocation failed (fit index, %lld chunk records)", (long long)ix->nchunks);
+        if ((e = hipMemcpyAsync(ix->d_chunks.p, ix->h_chunks.data(), ix->h_chunks.size() * sizeof(sed_fit_chunk),
+                                hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+            return c->hipfail(e, "upload (fit index chunk table)");
+        ix->chunk = plan.chunk;
+        ix->have_chunks = true;
+    }
+    if ((int64_t)nqueries * ix->nchunks > INT_MAX)
+        return c->fail(SED_E_RANGE, "fit search: %lld lanes", (long long)nqueries * ix->nchunks);
+    const size_t nres = (size_t)nqueries * (size_t)ntexts;
+    const size_t o_pat = 8 * nres, o_len = o_pat + (size_t)SED_LANE_MAXM * nqueries, qbytes = (SED_LANE_MAXM + 4) * (size_t)nqueries;
+    if (o_pat + qbytes > ix->pin_cap) {
+        if (ix->pin) (void)hipHostFree(ix->pin);
+        ix->pin = nullptr;
+        ix->pin_cap = 0;
+        const size_t want = std::max<size_t>(o_pat + qbytes, 1u << 16);
+        if (hipHostMalloc(&ix->pin, want, hipHostMallocDefault) != hipSuccess) {
+            ix->pin = nullptr;
+            (void)hipGetLastError();
+            return c->fail(SED_E_OOM, "pinned allocation failed (fit index, %zu bytes)", want);
+        }
+        ix->pin_cap = want;
+    }
+    // the queries: 32-byte records (right-aligned, code 8 in front), then their lengths
+    uint8_t *pats = (uint8_t *)ix->pin + o_pat;
+    int32_t *plens = (int32_t *)((uint8_t *)ix->pin + o_len);
+    memset(pats, 8, (size_t)SED_LANE_MAXM * nqueries);
+    for (int q = 0; q < nqueries; ++q) {
+        if (off_p[q] < 0) return c->fail(SED_E_ARG, "query %d: negative offset", q);
+        const int P = len_p[q];
+        uint8_t *rec = pats + (size_t)SED_LANE_MAXM * (q + 1) - P;
+        for (int i = 0; i < P; ++i) {
+            rec[i] = codes_p[off_p[q] + i];
+            if (rec[i] >= K) return c->fail(SED_E_ARG, "query %d: pattern code %d outside the alphabet (K=%d)", q, rec[i], K);
+        }
+        plens[q] = P;
+    }
+    if (!ix->d_query.reserve(qbytes) || !ix->d_out.reserve(8 * nres))
+        return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
+    for (hipEvent_t &ev : ix->ev)
+        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
+    ix->timed = false;
+    sed_fit_index_args a{};
+    a.chunks = (const sed_fit_chunk *)ix->d_chunks.p;
+    a.nchunks = (int)ix->nchunks;
+    a.texts = (const sed_fit_text *)ix->d_trec.p;
+    a.ntexts = ntexts;
+    a.pats = ix->d_query.p;
+    a.plens = (const int32_t *)((const uint8_t *)ix->d_query.p + (size_t)SED_LANE_MAXM * nqueries);
+    a.nqueries = nqueries;
+    a.text = ix->d_text.p;
+    a.out = (unsigned long long *)ix->d_out.p;
+    a.chunk = plan.chunk;
+    a.W = (int32_t)plan.W;
+    if ((e = hipMemcpyAsync(ix->d_query.p, pats, qbytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(ix->d_out.p, 0xFF, 8 * nres, c->stream)) != hipSuccess)
+        return c->hipfail(e, "upload (fit index search)");
+    if ((e = sed_launch_fit_index(c->stream, ix->ev[0], ix->ev[1], a, plan.fp)) != hipSuccess)
+        return c->hipfail(e, "fit index kernel launch");
+    const uint64_t *keys = (const uint64_t *)ix->pin;
+    if ((e = hipMemcpyAsync(ix->pin, ix->d_out.p, 8 * nres, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+        return c->hipfail(e, "download (fit index search)");
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index kernel execution");
+    ix->timed = true;
+    const double inv = std::ldexp(1.0, -plan.scale_log2);
+    size_t r = 0;
+    for (int q = 0; q < nqueries; ++q)
+        for (int d = 0; d < ntexts; ++d, ++r) {
+            const uint64_t k = keys[r];
+            const int64_t end = (int64_t)((k >> 16) & 0xFFFFFFFFu), len = (int64_t)(k & 0xFFFFu);
+            if (k == ~0ull || end > ix->len_t[d] || len > end)
+                return c->fail(SED_E_DEVICE, "query %d, text %d: no fit result from the device", q, d);
+            out_dist[r] = (double)(k >> 48) * inv;
+            out_end[r] = (int32_t)end;
+            out_start[r] = (int32_t)(end - len);
+        }
+    return SED_OK;
+}
+
+int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
+    if (!ix || !kernel_ms) return SED_E_ARG;
+    if (!ix->timed) return SED_E_STATE;
+    return hipEventElapsedTime(kernel_ms, ix->ev[0], ix->ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
+}
+
 int sed_full_matrix(sed_ctx *c, const uint8_t *codes_a, int32_t n, const uint8_t *codes_b, int32_t m, double *D,
                     uint8_t *M) {
     if (!c) return SED_E_ARG;

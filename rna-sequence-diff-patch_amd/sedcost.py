@@ -295,7 +295,12 @@ def build_plan(table, strs1, strs2, u=None):
                 seen2.setdefault(c, 0)
     syms1 = list(seen)
     alphabet = syms1 + [c for c in seen2 if c not in seen]
-    set1, set2 = set(syms1), set(seen2)
+    return plan_over(table, alphabet, set(syms1), set(seen2))
+
+
+def plan_over(table, alphabet, set1, set2):
+    """CostPlan over `alphabet` in the given order: the costs of the str1 symbols set1 against the str2 symbols set2
+    (build_plan's second half; a resident text index keeps its texts' codes and appends a query's new symbols)."""
     K = len(alphabet)
     sub = np.zeros((K, K), dtype=np.float64)
     sub_int = np.ones((K, K), dtype=np.uint8)  # unreachable combinations: int 0

@@ -129,6 +129,16 @@ SIGNATURES = [
     ("sed_fit_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                 _i32p, _i32p, C.c_int32, _i32p, C.c_int64, _u32p]),
     ("sed_fit_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("sed_fit_index_create", C.c_void_p, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32]),
+    ("sed_fit_index_destroy", None, [C.c_void_p]),
+    ("sed_fit_index_texts", C.c_int32, [C.c_void_p]),
+    ("sed_fit_index_symbols", C.c_int64, [C.c_void_p]),
+    ("sed_fit_index_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
+    ("sed_fit_index_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("sed_fit_index_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                     _i32p, C.c_int32, _i32p, C.c_int32, _f64p, C.c_int]),
+    ("sed_fit_index_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                      _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64, _u32p]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -297,6 +307,11 @@ class Context:
         self._check(self._lib.sed_fit_last_time(self.ptr, C.byref(ms)), "sed_fit_last_time")
         return ms.value
 
+    def fit_index(self, codes, off, lens):
+        """A resident text index for fit search (sed_fit_index_create): text d = codes[off[d] : off[d] + lens[d]],
+        uploaded once.  FitIndex.search then sends only the queries."""
+        return FitIndex(self, codes, off, lens)
+
     def run_pair(self, codes_a, codes_b, want_script, no_len=False):
         """One pair (codes as bytes): (dist, is_int, len, ops u32[] | None) through sed_run_pair, the per-call path of
         the drop-in module (no numpy arrays on the way in, preallocated result cells on the way out)."""
@@ -409,6 +424,68 @@ class PackedPairs:
         w = (n + m + 15) // 16
         self.ops_off = np.arange(max(P, 1) + 1, dtype=np.int64) * w
         return self
+
+
+class FitIndex:
+    """Device-resident texts for fit search (sed_fit_index_*): upload once, search many times.  search() runs under the
+    context's costs and options of that moment."""
+
+    def __init__(self, ctx, codes, off, lens):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        lens = np.ascontiguousarray(lens, np.int32)
+        off = np.ascontiguousarray(off, np.int64)
+        self.ntexts = len(lens)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        one = lambda a, t: a if len(a) else np.zeros(1, t)
+        self.ptr = self._lib.sed_fit_index_create(ctx.ptr, one(codes, np.uint8), one(off, np.int64), one(lens, np.int32),
+                                                  self.ntexts)
+        if not self.ptr:
+            msg = self._lib.sed_last_error(ctx.ptr)
+            raise SedError("sed_fit_index_create failed: %s" % (msg.decode() if msg else ""))
+
+    @classmethod
+    def from_texts(cls, ctx, texts):
+        """From a list of uint8 code arrays."""
+        lens = np.array([len(t) for t in texts], np.int32)
+        off = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]).astype(np.int64) if len(texts) else np.zeros(0, np.int64)
+        codes = np.concatenate([np.asarray(t, np.uint8) for t in texts]) if len(texts) else np.zeros(0, np.uint8)
+        return cls(ctx, codes, off, lens)
+
+    def close(self):
+        if self.ptr and self.ctx.ptr and self.ctx._pid == os.getpid():
+            self._lib.sed_fit_index_destroy(self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def symbols(self):
+        return int(self._lib.sed_fit_index_symbols(self.ptr))
+
+    def search(self, packed):
+        """packed: the queries as side a of a PackedPairs (codes_a, off_a, len_a, npairs; side b is not read).  Returns
+        (dist f64, start i32, end i32), each shaped (queries, texts): the hits Context.fit gives for every (query,
+        text), from one launch."""
+        if not self.ptr:
+            raise SedError("sed_fit_index_search: the index is closed")
+        Q, D = packed.npairs, self.ntexts
+        dist = np.zeros(max(Q * D, 1), np.float64)
+        start = np.zeros(max(Q * D, 1), np.int32)
+        end = np.zeros(max(Q * D, 1), np.int32)
+        rc = self._lib.sed_fit_index_search(self.ptr, packed.codes_a, packed.off_a, packed.len_a, Q, dist, start, end)
+        self.ctx._check(rc, "sed_fit_index_search")
+        return dist[:Q * D].reshape(Q, D), start[:Q * D].reshape(Q, D), end[:Q * D].reshape(Q, D)
+
+    def last_ms(self):
+        """Device time of the last search's kernel (ms, HIP events)."""
+        ms = C.c_float()
+        self.ctx._check(self._lib.sed_fit_index_last_time(self.ptr, C.byref(ms)), "sed_fit_index_last_time")
+        return ms.value
 
 
 def unpack_ops(ops_words, ops_off, p, length):
@@ -721,6 +798,10 @@ class EngineClient:
 
     def full_matrix(self, codes_a, codes_b):
         return self._call("full_matrix", np.asarray(codes_a, np.uint8), np.asarray(codes_b, np.uint8))
+
+    def fit_index(self, codes, off, lens):
+        raise SedError("fit_index: a forked child's engine proxy does not serve resident indexes (its texts would live "
+                       "in the serving process); use fit() here, or build the index in the process that owns the device")
 
 
 class _PlanArgs:
@@ -1040,6 +1121,43 @@ def fit_lanes(costs, options, len_p, len_t):
                               int(del_int), opts, len(options), lp, lt, len(len_p), rec.ravel(), nl, par)
     if rc != 0:
         err = SedError("sed_fit_lanes failed (%d)" % rc)
+        err.code = rc
+        raise err
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
+
+
+def _fit_index_args(costs, options, len_p, len_t):
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
+    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
+    return (int(K), np.ascontiguousarray(sub, np.float64).ravel(), np.ascontiguousarray(sub_int, np.uint8).ravel(),
+            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options), lp, len(len_p), lt, len(len_t))
+
+
+def fit_index_plan(costs, options, len_p, len_t):
+    """What FitIndex.search would decide for queries of lengths len_p against texts of lengths len_t, without a device
+    (sed_fit_index_plan): fit_plan's fields for the queries x texts cross product.  Errors as fit_plan."""
+    out = np.zeros(len(FIT_PLAN_FIELDS), np.float64)
+    rc = load().sed_fit_index_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out))
+    if rc != 0:
+        err = SedError("sed_fit_index_plan failed (%d)" % rc)
+        err.code = rc
+        raise err
+    return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
+
+
+def fit_index_lanes(costs, options, len_p, len_t):
+    """The lane records FitIndex.search would run, without a device (sed_fit_index_lanes): (lanes, params) as fit_lanes
+    returns them, query-major, pair = query * len(len_t) + text."""
+    nl = fit_index_plan(costs, options, len_p, len_t)["lanes"]
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    par = np.zeros(18, np.uint32)
+    rc = load().sed_fit_index_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl, par)
+    if rc != 0:
+        err = SedError("sed_fit_index_lanes failed (%d)" % rc)
         err.code = rc
         raise err
     lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}

@@ -122,6 +122,47 @@ def fit_search(query, seqs_or_collection, user_cost=False, max_dist=None, script
     return out
 
 
+class FitIndex:
+    """fit_search for a collection that is searched query after query: the documents are encoded and uploaded once
+    (StringEditDistance.fit_index), and each search sends only its queries.
+
+        ix = FitIndex(collection, user_cost=True)
+        ix.search(query, max_dist=3)          # == fit_search(query, collection, True, max_dist=3)
+        ix.search_many(queries)               # one such list per query, from one engine launch
+
+    index_fn(sequences, user_cost) -> an object with search(patterns) -> [[(dist, start, end)] per sequence] per
+    pattern, and close(), replaces the engine (CPU tests).  Not cached."""
+
+    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None):
+        self.seqs = _sequences(seqs_or_collection)
+        self.user_cost = user_cost
+        self._ix = (index_fn or SED.fit_index)(self.seqs, user_cost) if self.seqs else None
+
+    def search_many(self, queries, max_dist=None, scripts=False):
+        queries = list(queries)
+        if not self.seqs:
+            return [[] for _ in queries]
+        if not queries:
+            return []
+        rows = self._ix.search(queries)
+        kept = [[(s, d, a, b) for s, (d, a, b) in zip(self.seqs, hits) if max_dist is None or d <= max_dist]
+                for hits in rows]
+        out = [[(s, 1 / (1 + d), a, b) for s, d, a, b in k] for k in kept]
+        if scripts and any(kept):  # the scripts of every kept hit of every query: one edit_script_batch call
+            flat = [(q, s[a:b]) for q, k in zip(queries, kept) for s, _, a, b in k]
+            es = iter(SED.edit_script_batch([q for q, _ in flat], [w for _, w in flat], self.user_cost))
+            out = [[hit + (next(es)[1],) for hit in o] for o in out]
+        return out
+
+    def search(self, query, max_dist=None, scripts=False):
+        return self.search_many([query], max_dist, scripts)[0]
+
+    def close(self):
+        if self._ix is not None:
+            self._ix.close()
+        self._ix = None
+
+
 def search_collection(query, vector_type, collection, method, return_dict=None, callback=None):
     """IRMethods.search_collection for method == wf_score (IRMethods.py:443-477)."""
     if getattr(method, '__name__', None) != 'wf_score':
