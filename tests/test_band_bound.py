@@ -3,10 +3,12 @@ device-free entry points of libsed.so).  The checkpoint forward skips the cells 
 derived from the cost of the plain diagonal path; the results stay exact as long as every cell of every
 distance-optimal path lies inside the window.  Checked here on a few hundred small pairs against a forward plus
 backward DP in numpy, with the chunk ranges' monotonicity, clipping and coverage, and the cell count of the
-flagship shape (config 4's pairs: 0.531 of n*m)."""
+flagship shape (config 4's pairs: 0.531 of n*m); then on the tables and families of tests/band_cases.py at the sizes
+the GPU tests run them."""
 import numpy as np
 import pytest
 
+import band_cases
 from conftest import load_golden
 import sedgpu
 import synth
@@ -47,9 +49,9 @@ def _optimal_cells(sub, ins, dele, a, b):
     return F + Bk == F[-1, -1]
 
 
-@pytest.mark.parametrize("name", ["user_costs.json", "costs.json"])
+@pytest.mark.parametrize("name", ["user_costs.json", "costs.json"] + list(band_cases.NEW_TABLES))
 def test_every_optimal_path_lies_inside_the_window(name):
-    sub, ins, dele = _table(name)
+    sub, ins, dele = band_cases.costs(name)
     rng = np.random.default_rng(20260 + len(name))
     seen = set()
     for it in range(240):
@@ -70,6 +72,49 @@ def test_every_optimal_path_lies_inside_the_window(name):
         e = jj - ii
         assert e.min() >= elo and e.max() <= ehi, (n, m, elo, ehi, int(e.min()), int(e.max()))
     assert seen == {-1, 0, 1}
+
+
+# (table, family, R): the batches tests/test_gpu_band_envelope.py runs (R only sets the families' stripe height here)
+ENVELOPE = [(t, f, 4) for t in band_cases.TABLES for f in ("random", "low_complexity", "rearranged")]
+ENVELOPE += [("user_costs.json", "edges", 4), ("tight", "edges", 4), ("user_costs.json", "edges", 8),
+             ("user_costs.json", "drift", 4), ("gui_int", "drift", 4)]
+
+
+@pytest.mark.parametrize("name, family, R", ENVELOPE)
+def test_every_optimal_path_of_the_envelope_lies_inside_the_window(name, family, R):
+    """The same over band_cases' tables and families (homopolymers and short periods: co-optimal paths out to the
+    window's edges; block swaps and long indels: paths far off the diagonal), against the shared numpy DP."""
+    _, ins, dele = band_cases.costs(name)
+    for ref in band_cases.refs(name, family, R):
+        elo, ehi = sedgpu.band_bounds(ref.n, ref.m, ins, dele, ref.ub)
+        assert elo <= min(0, ref.m - ref.n) and ehi >= max(0, ref.m - ref.n)
+        assert ref.emin >= elo and ref.emax <= ehi, (ref.n, ref.m, elo, ehi, ref.emin, ref.emax)
+
+
+def test_case_tables_are_what_they_claim():
+    """band_cases.TABLES: every one eligible for the integer kernel (1 <= mismatch <= insert + delete <= 255), the
+    factorable ones accepted by sed_dot_factor at every min(n, m) the batches reach and the others refused, the classes
+    the envelope names present, and every batch within the 16-bit distance field."""
+    for name in band_cases.TABLES:
+        sub, ins, dele = band_cases.costs(name)
+        off = sub[~np.eye(4, dtype=bool)]
+        assert ins >= 1 and dele >= 1 and ins + dele <= 255 and off.min() >= 1 and off.max() <= ins + dele
+        assert np.all(sub == np.floor(sub)) and not np.diag(sub).any()
+        for maxmin in (552, 768, 769, 1537, 2100, 2600):
+            assert band_cases.factors(name, maxmin) == (name in band_cases.FACTORABLE), (name, maxmin)
+    for name in ("sum", "gui_int", "tight", "heavy"):  # a mismatch that ties with delete + insert
+        sub, ins, dele = band_cases.costs(name)
+        assert (sub == ins + dele).any()
+    assert band_cases.costs("sum")[0].max() == 3 and band_cases.costs("sum")[1:] == (1.0, 2.0)
+    assert band_cases.costs("gui_int")[1:] == (3.0, 1.0) and band_cases.costs("tight")[1:] == (2.0, 5.0)
+    assert band_cases.costs("heavy")[1:] == (20.0, 60.0)
+    for name, family, R in ENVELOPE:
+        A, B = band_cases.family_pairs(name, family, R)
+        assert band_cases.i32_fits(name, A, B, R), (name, family, R)
+    # `heavy` sits next to the limit: its widest pair is within 5 % of 65533, and m = n + 300 would pass it
+    A, B = band_cases.family_pairs("heavy", "rearranged", 4)
+    assert max(768 * 60 + (len(b) + 80) * 20 for b in B) > 0.95 * 65533
+    assert not band_cases.i32_fits("heavy", [A[0]], [np.zeros(len(A[0]) + 300, np.uint8)], 4)
 
 
 def test_bounds_formula():

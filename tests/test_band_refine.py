@@ -4,34 +4,16 @@ a smaller upper bound from the diagonal cell, then every computed cell's slack u
 range.  The results stay exact as long as every cell of every distance-optimal path lies inside its stripe's range.
 Checked against a forward plus backward DP in numpy, stripe after stripe as the kernel chains them (each stripe reads
 only the columns the one above computed), with true row values and with off-path values inflated (the kernel's values
-off the optimal paths are >= the true ones)."""
+off the optimal paths are >= the true ones).  The envelope test repeats it over the cost tables and sequence families of
+tests/band_cases.py, the inputs tests/test_gpu_band_envelope.py runs on the device."""
+import functools
+
 import numpy as np
 import pytest
 
-from conftest import load_golden
+import band_cases
+from band_cases import Ref
 import sedgpu
-
-S = "ACGU"
-
-
-def _table(name):
-    t = load_golden(name)
-    sub = np.array([[0.0 if a == b else t["update"][a][b] for b in S] for a in S])
-    return sub, float(t["insert"]), float(t["delete"])
-
-
-def _dp(sub, ins, dele, a, b):
-    """F[i, j] = the cost of the cheapest path (0, 0) -> (i, j) (integer costs: exact in float64)."""
-    n, m = len(a), len(b)
-    F = np.zeros((n + 1, m + 1))
-    F[0, :] = ins * np.arange(m + 1)
-    ramp = ins * np.arange(m + 1)
-    for i in range(1, n + 1):
-        cand = np.empty(m + 1)
-        cand[0] = dele * i
-        cand[1:] = np.minimum(F[i - 1, 1:] + dele, F[i - 1, :-1] + sub[a[i - 1], b])  # delete, update
-        F[i] = np.minimum.accumulate(cand - ramp) + ramp  # the insert chain along the row
-    return F
 
 
 def _mut(rng, x, rate=0.1):
@@ -56,17 +38,20 @@ def _pairs(rng):
     return out
 
 
-def _walk(sub, ins, dele, a, b, R, inflate_rng=None):
+@functools.lru_cache(maxsize=None)
+def _pair_refs(name):
+    """(Ref, R, kind) of _pairs under one table, for the true and the inflated walk."""
+    sub, ins, dele = band_cases.costs(name)
+    # (`heavy`, m = 900: the planner would not run the pair on 16-bit keys)
+    return [(Ref(sub, ins, dele, a, b, R), R, kind) for a, b, R, kind in _pairs(np.random.default_rng(31 + len(name)))
+            if band_cases.i32_fits(name, [a], [b], R)]
+
+
+def _walk(ref, ins, dele, R, inflate_rng=None):
     """Chains the stripes' ranges as the forward does and checks each; returns the refined and the static ranges."""
-    n, m, rows = len(a), len(b), 64 * R
-    F = _dp(sub, ins, dele, a, b)
-    Bk = _dp(sub, ins, dele, a[::-1], b[::-1])[::-1, ::-1]
-    dist = F[n, m]
-    opt = F + Bk == dist
+    n, m, rows = ref.n, ref.m, 64 * R
+    dist, diag, gap, ub = ref.dist, ref.diag, ref.gap, ref.ub
     k_ = min(n, m)
-    diag = sub[a[:k_], b[:k_]]
-    gap = ins * (m - n) if m > n else dele * (n - m)
-    ub = float(diag.sum()) + gap
     elo, ehi = sedgpu.band_bounds(n, m, ins, dele, ub)
     nstripes = (n + rows - 1) // rows
     refined, static = [], []
@@ -77,9 +62,10 @@ def _walk(sub, ins, dele, a, b, R, inflate_rng=None):
             clo, chi = s_lo, s_hi
         else:
             r0 = k * rows
-            row = F[r0].copy()
+            row, opt0 = ref.rows[r0]
+            row = row.copy()
             if inflate_rng is not None:
-                row += np.where(opt[r0], 0, inflate_rng.integers(0, 51, size=m + 1))
+                row += np.where(opt0, 0, inflate_rng.integers(0, 51, size=m + 1))
             suf = float(diag[r0:].sum()) + gap if r0 <= k_ else None
             clo, chi, ub_new, any_ = sedgpu.band_refine_row(n, m, R, ins, dele, k, ub, suf, row.astype(np.int32),
                                                             refined[-1][0], refined[-1][1])
@@ -90,24 +76,48 @@ def _walk(sub, ins, dele, a, b, R, inflate_rng=None):
             assert s_lo <= clo <= chi <= s_hi  # never wider than the static range
         refined.append((clo, chi))
         r1 = min(n, (k + 1) * rows)
-        ii, jj = np.nonzero(opt[k * rows + 1:r1 + 1, 1:])
-        t = ii // R  # the row's lane: it runs columns 64 clo + 1 .. 64 chi + 64 - t
-        jj = jj + 1
-        assert np.all(jj >= 64 * clo + 1) and np.all(jj <= 64 * chi + 64 - t), (n, m, R, k, clo, chi)
+        i = np.arange(k * rows + 1, r1 + 1)
+        i = i[ref.has[i]]  # every optimal cell of the row lies between the row's extreme ones
+        t = (i - k * rows - 1) // R  # the row's lane: it runs columns 64 clo + 1 .. 64 chi + 64 - t
+        assert np.all(ref.jmin[i] >= 64 * clo + 1) and np.all(ref.jmax[i] <= 64 * chi + 64 - t), (n, m, R, k, clo, chi)
     return refined, static
 
 
-@pytest.mark.parametrize("name", ["user_costs.json", "costs.json"])
+@pytest.mark.parametrize("name", ["user_costs.json", "costs.json"] + list(band_cases.NEW_TABLES))
 @pytest.mark.parametrize("inflated", [False, True])
 def test_every_optimal_path_lies_inside_the_refined_ranges(name, inflated):
-    sub, ins, dele = _table(name)
-    rng = np.random.default_rng(31 + len(name))
+    sub, ins, dele = band_cases.costs(name)
     narrower = 0
-    for a, b, R, kind in _pairs(rng):
-        refined, static = _walk(sub, ins, dele, a, b, R, np.random.default_rng(7) if inflated else None)
+    for ref, R, kind in _pair_refs(name):
+        refined, static = _walk(ref, ins, dele, R, np.random.default_rng(7) if inflated else None)
         assert len(refined) >= 2, kind
         narrower += sum(r[1] - r[0] < s[1] - s[0] for r, s in zip(refined, static))
     assert narrower > 0  # the refinement does narrow some stripe
+
+
+# (table, family, R): every table against the random, low-complexity and rearranged families at R = 4, the stripe and
+# chunk borders, and the ten-stripe drift (R = 4 only)
+ENVELOPE = [(t, f, 4) for t in band_cases.TABLES for f in ("random", "low_complexity", "rearranged")]
+ENVELOPE += [("user_costs.json", "edges", 4), ("tight", "edges", 4), ("user_costs.json", "edges", 8),
+             ("user_costs.json", "drift", 4), ("gui_int", "drift", 4)]
+# (the model narrows some stripe below its static range in every one of these, with true and with inflated values, so
+# narrower > 0 is asserted of all: none is left out)
+
+
+@pytest.mark.parametrize("name, family, R", ENVELOPE)
+@pytest.mark.parametrize("inflated", [False, True])
+def test_every_optimal_path_of_the_envelope_lies_inside_the_refined_ranges(name, family, R, inflated):
+    """test_every_optimal_path_lies_inside_the_refined_ranges over band_cases' tables and families: the inputs the GPU
+    tests run (tests/test_gpu_band_envelope.py) keep the model's invariants."""
+    sub, ins, dele = band_cases.costs(name)
+    narrower = 0
+    for ref in band_cases.refs(name, family, R):
+        assert band_cases.i32_fits(name, [ref.a], [ref.b], R)
+        refined, static = _walk(ref, ins, dele, R, np.random.default_rng(7) if inflated else None)
+        assert len(refined) >= 2, (ref.n, ref.m)
+        narrower += sum(r[1] - r[0] < s[1] - s[0] for r, s in zip(refined, static))
+    print("%s / %s, R = %d: %d stripes narrower than their static range" % (name, family, R, narrower))
+    assert narrower > 0
 
 
 def test_refine_row_arguments():

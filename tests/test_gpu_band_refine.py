@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from band_cases import mut as _mut, random_family as _batch
 from conftest import padding_errors
 import oracle
 import sedcost
@@ -20,27 +21,14 @@ THREADS = min(16, len(os.sched_getaffinity(0)))
 S = "ACGU"
 
 
-def _mut(rng, x, rate=0.1):
-    return np.where(rng.random(len(x)) < rate, rng.integers(0, 4, size=len(x)), x).astype(np.uint8)
-
-
-def _batch(rng, n, R):
-    """Random, identical, mutated; a last stripe below 64 rows; m - n = +-300; shifted copies (a path off the diagonal)."""
-    rows = 64 * R
-    r = lambda k: rng.integers(0, 4, size=k).astype(np.uint8)  # noqa: E731
-    a, s = r(n), r(2 * rows + 40)
-    A = [a, a, a, s, s, a, a, a[:n - 300], a, a[37:]]
-    B = [r(n), a.copy(), _mut(rng, a), _mut(rng, s), r(len(s)), np.concatenate([_mut(rng, a), r(300)]),
-         _mut(rng, a)[300:], r(n), np.concatenate([r(37), _mut(rng, a)[:n - 37]]), _mut(rng, a)]
-    return A, B
-
-
-def _run(gpu, packed, R, band, times=1):
+def _run(gpu, packed, R, band, times=1, dot=0, route=None):
+    """dot: SED_OPT_DOT for the batch (2 = distance keys); route(batch, band): further asserts on the route taken."""
     gpu.set_option(sedgpu.SED_OPT_TB, 2)
     gpu.set_option(sedgpu.SED_OPT_CHAIN, 2)
     gpu.set_option(sedgpu.SED_OPT_SPLIT, 2)
     gpu.set_option(sedgpu.SED_OPT_ROWS_PER_LANE, R)
     gpu.set_option(sedgpu.SED_OPT_BAND, band)
+    gpu.set_option(sedgpu.SED_OPT_DOT, dot)
     try:
         b = sedgpu.Batch(gpu, packed, True)
         try:
@@ -49,10 +37,13 @@ def _run(gpu, packed, R, band, times=1):
                 b.run()
                 outs.append(b.results())  # raises when any pair's err != 0
             assert b.traceback_mode == 2 and b.rows_per_lane == R
+            if route is not None:
+                route(b, band)
             return outs, b.band_chunks_run()
         finally:
             b.close()
     finally:
+        gpu.set_option(sedgpu.SED_OPT_DOT, 0)
         gpu.set_option(sedgpu.SED_OPT_BAND, 0)
         gpu.set_option(sedgpu.SED_OPT_ROWS_PER_LANE, 0)
         gpu.set_option(sedgpu.SED_OPT_SPLIT, 0)
@@ -60,12 +51,13 @@ def _run(gpu, packed, R, band, times=1):
         gpu.set_option(sedgpu.SED_OPT_TB, 0)
 
 
-def _check(gpu, table, A, B, R, times=1):
+def _check(gpu, table, A, B, R, times=1, dot=0, route=None):
+    """Returns the refined run's first results and the (run, unpruned) chunks of the refined and the static run."""
     plan = sedcost.build_plan(table, [S], [S])
     gpu.set_costs(plan)
     packed = sedgpu.PackedPairs(A, B)
-    outs, chunks = _run(gpu, packed, R, 0, times)
-    (outs3, chunks3), (outs2, chunks2) = _run(gpu, packed, R, 3), _run(gpu, packed, R, 2)
+    outs, chunks = _run(gpu, packed, R, 0, times, dot, route)
+    (outs3, chunks3), (outs2, chunks2) = _run(gpu, packed, R, 3, 1, dot, route), _run(gpu, packed, R, 2, 1, dot, route)
     assert chunks2 is None and chunks is not None and chunks3 is not None
     print("R = %d: chunks run %d refined, %d static, %d unpruned" % (R, chunks[0], chunks3[0], chunks[1]))
     assert chunks[1] == chunks3[1] and chunks[0] <= chunks3[0] <= chunks[1]
@@ -83,6 +75,7 @@ def _check(gpu, table, A, B, R, times=1):
                                                      oops[ooff[p]:ooff[p] + ol[p]])]
     assert not bad, bad[:10]
     assert not padding_errors(ops, packed.ops_off, packed.len_a, packed.len_b, ln)
+    return outs[0], chunks, chunks3
 
 
 def test_three_stripes_with_lane_pairs_r4(gpu, tables):
