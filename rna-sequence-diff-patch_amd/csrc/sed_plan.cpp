@@ -419,18 +419,148 @@ struct Planning {
     int max_n = 0, max_m = 0;
     bool want_tb = false, f64_lane = false, seg_ok = false, use_lane = false;
     double in_bytes = 0, tb_bytes = 0;
+    double sum_nm = 0, sum_len = 0;  // sum n m and sum (n + m) over the pairs
     uint64_t aw = 0, bw = 0;  // the sequences' words (integer mode) or bytes
+    std::vector<uint64_t> diag_ub;  // every pair's diagonal bound where the rows-per-lane rule took it (else empty)
 
     // the automatic rows per lane of an fp64 batch
     int auto_R_f64(int mode) const {
         return choose_R_f64(len_a, len_b, npairs, f64_lane && mode == SED_MODE_F64, seg_ok);
     }
+    // ---- the routes' conditions, each asked by the step that decides the route and by the rows-per-lane rule of
+    // banded checkpoint batches (band_rows_rule), which runs before those steps ----
+    // integer SPLIT (plan_mode): forced, or a batch too small to fill the GPU with one wave per pair
+    bool i32_split() const {
+        return o.split != 2 && (o.split == 1 || (npairs <= 256 && max_n > 256 && o.chain != 1 && o.chain < 3));
+    }
+    // offset keys at R rows per lane (plan_mode): i*delete + j*insert over every computed cell (padded rows, the
+    // columns the wave or the lane kernel runs past m) must stay below the bias, and L < 2^14
+    bool i32_fits(int R) const {
+        const int ROWS = 64 * R;
+        for (int p = 0; p < npairs; ++p) {
+            const double npad = (double)((len_a[p] + ROWS - 1) / ROWS) * ROWS;
+            const double cols = (double)std::max(len_b[p] + 64 + 64 / R, SED_LANE_MAXM);
+            if (npad * c.del + cols * c.ins > 65533.0 || npad + cols >= 16384.0) return false;
+        }
+        return true;
+    }
+    // the lane-per-pair kernels take the batch's short pairs (plan_layout)
+    bool lane_route(int mode, bool split) const {
+        return !split && o.lane != 2 && (mode == SED_MODE_I32 || (mode == SED_MODE_F64 && !want_tb && (flags & SED_NO_LEN)));
+    }
+    // pair p is one of them.  A batch of a few pairs (the per-call path) leaves the GPU empty, so one lane walking a
+    // pair alone only pays off for a small distance-only pair: a 30-nt script call took 42 us on the lane kernel and
+    // 34 us on the wave kernels, a 30-nt distance call 19 against 22 us (tools/zc_ab.py SED_OPT_LANE, profiles/r05/s38)
+    bool lane_pair(int p, bool lane_on) const {
+        const int nn = len_a[p], mm = len_b[p];
+        const bool few_pairs = npairs <= 16 && o.lane == 0;
+        return lane_on && nn >= 1 && nn <= SED_LANE_MAXN && mm >= 1 && mm <= SED_LANE_MAXM &&
+               !(few_pairs && (want_tb || (double)nn * mm > 1024.0));
+    }
+    // CK traceback (plan_traceback; R = 4/8/16 wave kernels, stripe or CHAIN, not SPLIT).  Auto: batches past the
+    // window kernel's 256 pairs whose pairs are large enough.  The forward kernel saves ~1.7 VALU per cell (n m), the
+    // tile recompute costs per path step (n + m): measured, config 4 (4096^2) step 20.4 -> 15.0 ms, config 3 (512^2)
+    // 2.90 -> 4.40 ms; break-even near 1024^2, i.e. sum(n m) / sum(n + m) = 512.
+    bool ck_route(int mode, bool split, int R) const {
+        return want_tb && mode == SED_MODE_I32 && !split && (R == 4 || R == 8 || R == 16) && o.tb != 1 &&
+               (o.tb == 2 || (npairs > 256 && sum_nm >= 512.0 * sum_len));
+    }
+    // CHAIN (plan_chain) runs at R = 4 or 8, wave pairs of one stripe with no empty side
+    bool chain_R(int R) const { return o.chain != 2 && (R == 4 || R == 8); }
+    bool chain_pair(int p, int R) const { return len_a[p] >= 1 && len_a[p] <= 64 * R && len_b[p] >= 1; }
+    // band pruning of a checkpoint batch of the stripe kernel (plan_band): not switched off, and substitution costs
+    // >= 0 over at most 4 symbols (the window's lower bound counts indels only)
+    bool band_costs_ok() const {
+        if (!(c.K <= 4 && c.ins + c.del > 0)) return false;
+        for (int e = 0; e < c.K * c.K; ++e)
+            if (!(c.sub[e] >= 0)) return false;
+        return true;
+    }
+    bool band_route() const { return o.band != 2 && o.env_band != 0 && band_costs_ok(); }
     // kappa = insert + delete - cost, the dot keys' table
     void kappa(int64_t kap[4][4]) const {
         for (int a = 0; a < 4; ++a)
             for (int bb = 0; bb < 4; ++bb) kap[a][bb] = (int64_t)b.ip.ins + b.ip.del - (int64_t)c.sub[a * 4 + bb];
     }
 };
+
+// Rows per lane of a banded checkpoint batch ("Rows per lane").  A stripe of 64 R rows sweeps its
+// window in about 64 R + 2w steps (w = the band's half-width), of which a lane does in-band work in about 2w: with
+// a narrow band most of a tall stripe's steps are its two triangular corners, and a shorter stripe computes fewer
+// cells the result does not need.  Against that a step of R rows costs R cells plus a fixed part (the lane-to-lane
+// move, the top-row read, the loop), and every stripe pays its prologue (the refinement scan of the row above, the
+// checkpoint set-up).  The model counts, for R = 16, 8 and 4, the steps of every wave pair's stripes from the static
+// windows (as plan_band counts band_cells) and takes
+//     cost(R) = steps(R) (R + BAND_STEP_C[R]) + stripes(R) BAND_STRIPE_C        (in rows of one step)
+// summed over the batch.  Fitted to the step times of 8192 x 4096^2 and 16384 x 2048^2 forced to each R, three
+// interleaved rounds (profiles/rows_rule/README.md, "Fit"): step = T0(shape) + 3.43e-9 ms x cost with one step
+// constant for every R leaves residuals of at most 0.010 ms (the runs' widest range is 0.027 ms), and 3.43e-9 ms is
+// 8.4 cycles of one of 1024 SIMDs at 2.4 GHz, the cell's two VALU ops.  Measured against modelled gains: 4096^2
+// 16 -> 8 0.571 against 0.584 ms and 8 -> 4 0.140 against 0.130; 2048^2 0.466 against 0.448 and 0.133 against 0.146.
+// A smaller R wins only by more than BAND_RESOLVE of the larger one's cost.  The project's criterion for two runs
+// to differ (ten times the wider range, here 0.27 ms) is 7 to 11 % of the modelled R = 8 forward of the two shapes,
+// and by it R = 4 and R = 8 could not be told apart on either (cost ratios 0.96 and 0.94): the larger R then
+// stands, with half the stripes and smaller checkpoints.
+const double BAND_STEP_C[3] = {0.1, 0.1, 0.1};  // R = 16, 8, 4
+const double BAND_STRIPE_C = 800.0;
+const double BAND_RESOLVE = 0.10;
+// The rule applies to batches whose wave pairs all have at least two full R = 16 stripes: a shorter pair is one
+// full stripe and a padded remainder or less, and no run has measured the rule there.
+const int BAND_RULE_MIN_ROWS = 2 * 64 * 16;
+
+double band_rows_cost(int n, int m, int R, double step_c, sed_band w) {
+    const sed_geom g = sed_stripe_geom(n, m, R, 64);
+    double steps = 0;
+    for (int k = 0; k < g.nstripes; ++k) {
+        int clo, chi;
+        sed_band_chunks(n, m, 64 * R, g.nchunks, w, k, &clo, &chi);
+        steps += (double)(std::min(g.SG, 64 * (chi + 1)) - 64 * clo);
+    }
+    return steps * (R + step_c) + (double)g.nstripes * BAND_STRIPE_C;
+}
+
+// The automatic R of an integer batch: R0 (choose_R's), or the model's choice when the batch will run the checkpoint
+// route on the stripe kernel with band pruning at every candidate.  Leaves the pairs' diagonal bounds in P.diag_ub
+// when it ran the model.
+int band_rows_rule(Planning &P, int R0) {
+    static const int cand[3] = {16, 8, 4};
+    if (R0 != 16 || P.i32_split() || !P.band_route()) return R0;
+    const bool lane_on = P.lane_route(SED_MODE_I32, false);
+    int nwave = 0;
+    for (int p = 0; p < P.npairs; ++p) {
+        if (P.len_a[p] <= 0 || P.len_b[p] <= 0 || P.lane_pair(p, lane_on)) continue;
+        if (P.len_a[p] < BAND_RULE_MIN_ROWS) return R0;  // the gate
+        ++nwave;
+    }
+    if (!nwave) return R0;
+    bool ok[3];
+    for (int k = 0; k < 3; ++k) {
+        const int R = cand[k];
+        ok[k] = P.ck_route(SED_MODE_I32, false, R) && P.i32_fits(R);
+        // CHAIN would take the wave pairs off the stripe kernel (it never does past the gate: a pair of 2048 rows is
+        // no single stripe at R = 4 or 8)
+        bool chain = P.chain_R(R);
+        for (int p = 0; p < P.npairs && chain; ++p)
+            if (!P.lane_pair(p, lane_on) && !P.chain_pair(p, R)) chain = false;
+        if (chain) ok[k] = false;
+    }
+    if (!ok[0]) return R0;
+    const sed_band_params bp = sed_band_params_from(P.c);
+    double cost[3] = {0, 0, 0};
+    P.diag_ub.assign(P.npairs, 0);
+    for (int p = 0; p < P.npairs; ++p) {
+        const int nn = P.len_a[p], mm = P.len_b[p];
+        if (nn <= 0 || mm <= 0 || P.lane_pair(p, lane_on)) continue;
+        P.diag_ub[p] = sed_band_diag_bound(bp, P.codes_a + P.off_a[p], nn, P.codes_b + P.off_b[p], mm);
+        const sed_band w = sed_band_window(nn, mm, bp.ins, bp.del, P.diag_ub[p]);
+        for (int k = 0; k < 3; ++k)
+            if (ok[k]) cost[k] += band_rows_cost(nn, mm, cand[k], BAND_STEP_C[k], w);
+    }
+    int best = 0;
+    for (int k = 1; k < 3; ++k)
+        if (ok[k] && cost[k] < cost[best] * (1.0 - BAND_RESOLVE)) best = k;
+    return cand[best];
+}
 
 int plan_validate(Planning &P) {
     if (P.npairs < 0 ||
@@ -440,6 +570,8 @@ int plan_validate(Planning &P) {
         if (P.len_a[p] < 0 || P.len_b[p] < 0) return fail(P.err, SED_E_ARG, "negative length at pair %d", p);
         P.max_n = std::max(P.max_n, P.len_a[p]);
         P.max_m = std::max(P.max_m, P.len_b[p]);
+        P.sum_nm += (double)P.len_a[p] * P.len_b[p];
+        P.sum_len += (double)P.len_a[p] + P.len_b[p];
         const uint8_t *pa = P.codes_a + P.off_a[p], *pb = P.codes_b + P.off_b[p];
         for (int i = 0; i < P.len_a[p]; ++i)
             if (pa[i] >= P.c.K) return fail(P.err, SED_E_ARG, "code %d >= K at pair %d", pa[i], p);
@@ -483,17 +615,8 @@ int plan_mode(Planning &P) {
     P.seg_ok = o.seg != 2 && nwave_f64 > 256;
     int R = (mode == SED_MODE_I32 || o.R) ? choose_R(mode, P.max_n, o.R) : P.auto_R_f64(mode);
     if (mode == SED_MODE_I32) {
-        const int ROWS = 64 * R;
-        bool fits = true;
-        for (int p = 0; p < npairs && fits; ++p) {
-            // offset keys: i*delete + j*insert over every computed cell (padded rows, the columns
-            // the wave or the lane kernel runs past m) must stay below the bias, and L < 2^14
-            const double npad = (double)((len_a[p] + ROWS - 1) / ROWS) * ROWS;
-            const double cols = (double)std::max(len_b[p] + 64 + 64 / R, SED_LANE_MAXM);
-            const double dsum = npad * c.del + cols * c.ins;
-            if (dsum > 65533.0 || npad + cols >= 16384.0) fits = false;
-        }
-        if (!fits) {
+        if (!o.R) R = band_rows_rule(P, R);
+        if (!P.i32_fits(R)) {  // (the keys' range at the R the batch runs)
             if (o.mode == 1) return fail(P.err, SED_E_RANGE, "integer key would overflow (D < 2^16, L < 2^14)");
             mode = sed_simple_typing(c) ? SED_MODE_F64 : SED_MODE_F64_TYPED;
             R = o.R ? o.R : P.auto_R_f64(mode);
@@ -507,7 +630,7 @@ int plan_mode(Planning &P) {
     // batches too small to fill the GPU with one wave per pair (config 2, GUI calls).
     bool split = false;
     if (mode == SED_MODE_I32 && o.split != 2) {
-        split = o.split == 1 || (npairs <= 256 && P.max_n > 256 && o.chain != 1 && o.chain < 3);
+        split = P.i32_split();
         if (split && !o.R) R = 4;
         if (split && R != 4 && R != 8 && R != 16 && R != 32) split = false;
     } else if (mode != SED_MODE_I32 && o.split != 2 && (!P.seg_ok || o.split == 1)) {
@@ -552,18 +675,8 @@ void plan_traceback(Planning &P) {
     sed_plan &b = P.b;
     const int R = b.R, mode = b.mode, npairs = P.npairs;
     const bool want_tb = P.want_tb;
-    // CK traceback (R = 4/8/16 wave kernels, stripe or CHAIN, not SPLIT): distance-key forward kernel +
-    // checkpoints, traceback recomputes tiles.  Auto: batches past the window kernel's 256 pairs whose pairs
-    // are large enough.  The forward kernel saves ~1.7 VALU per cell (n m), the tile recompute costs per
-    // path step (n + m): measured, config 4 (4096^2) step 20.4 -> 15.0 ms, config 3 (512^2) 2.90 -> 4.40 ms;
-    // break-even near 1024^2, i.e. sum(n m) / sum(n + m) = 512.
-    double sum_nm = 0, sum_len = 0;
-    for (int p = 0; p < npairs; ++p) {
-        sum_nm += (double)P.len_a[p] * P.len_b[p];
-        sum_len += (double)P.len_a[p] + P.len_b[p];
-    }
-    b.ck = want_tb && mode == SED_MODE_I32 && !b.split && (R == 4 || R == 8 || R == 16) && o.tb != 1 &&
-           (o.tb == 2 || (npairs > 256 && sum_nm >= 512.0 * sum_len));
+    // CK traceback: distance-key forward kernel + checkpoints, traceback recomputes tiles (Planning::ck_route)
+    b.ck = P.ck_route(mode, b.split, R);
     // SED_PIPELINE is a hint: checkpoint batches run their traceback after the DP on one stream (in parts on
     // several, run_batch_parts).  Both kernels are issue-bound, so overlapping a run's traceback with the next run's
     // forward only adds contention (config 4: 20.33 ms sequential against 20.5-20.8 ms pipelined in round 1,
@@ -595,12 +708,7 @@ void plan_layout(Planning &P) {
     b.lane.clear();
     b.seg.clear();
     // lane-per-pair kernels: integer keys (any flags), or fp64 distance-only in "simple typing" mode
-    // a batch of a few pairs (the per-call path) leaves the GPU empty, so one lane walking a pair alone only pays off
-    // for a small distance-only pair: a 30-nt script call took 42 us on the lane kernel and 34 us on the wave kernels,
-    // a 30-nt distance call 19 against 22 us (tools/zc_ab.py SED_OPT_LANE, profiles/r05/s38)
-    const bool few_pairs = npairs <= 16 && o.lane == 0;
-    P.use_lane = !split && o.lane != 2 &&
-                 (mode == SED_MODE_I32 || (mode == SED_MODE_F64 && !want_tb && (P.flags & SED_NO_LEN)));
+    P.use_lane = P.lane_route(mode, split);
     uint64_t aw = 0, bw = 0, tbw = 0, bndw = 0, opw = 0, mapw = 0;
     const bool packed = (mode == SED_MODE_I32);
     double cells = 0, in_bytes = 0, ck_bytes = 0;
@@ -622,8 +730,7 @@ void plan_layout(Planning &P) {
         d.bnd_off = bndw;
         d.ops_off = opw;
         d.map_off = (int32_t)mapw;  // stripe-parallel traceback: this pair's exit map
-        if (P.use_lane && nn >= 1 && nn <= SED_LANE_MAXN && mm >= 1 && mm <= SED_LANE_MAXM &&
-            !(few_pairs && (want_tb || (double)nn * mm > 1024.0))) {
+        if (P.lane_pair(p, P.use_lane)) {
             d.lane = 1;
             b.lane.push_back(p);
             if (want_tb) tbw += 2 * (uint64_t)nn;  // one uint2 of 2-bit ops per row
@@ -807,18 +914,18 @@ void plan_wave_x2(Planning &P, bool x2_ok) {
 void plan_chain(Planning &P) {
     const sed_opts &o = P.o;
     sed_plan &b = P.b;
-    const int32_t *len_a = P.len_a, *len_b = P.len_b;
-    const int npairs = P.npairs, R = b.R, ROWS = 64 * R;
+    const int32_t *len_b = P.len_b;
+    const int npairs = P.npairs, R = b.R;
     b.chain.clear();
     b.nchains = 0;
     b.chain_npairs = 0;
     b.chain_dyn = false;
-    if (!(b.mode == SED_MODE_I32 && !b.split && o.chain != 2 && (R == 4 || R == 8) && b.nwave > 0)) return;
+    if (!(b.mode == SED_MODE_I32 && !b.split && P.chain_R(R) && b.nwave > 0)) return;
     // SIMDs x the chain kernel's waves per SIMD, unless capped (tests: several fetched pairs per wave)
     const int resident = o.chain_waves > 0 ? o.chain_waves : 1024 * 5;
     bool ok = true;
     for (int p = 0; p < npairs && ok; ++p)
-        if (!b.pd[p].lane && (len_a[p] < 1 || len_a[p] > ROWS || len_b[p] < 1)) ok = false;
+        if (!b.pd[p].lane && !P.chain_pair(p, R)) ok = false;
     if (ok && o.chain >= 3) {  // static chains of o.chain pairs (tests, A/B)
         const int L = o.chain;
         double total = 0;
@@ -859,10 +966,8 @@ void plan_band(Planning &P) {
     const sed_costs &c = P.c;
     sed_plan &b = P.b;
     const int npairs = P.npairs, R = b.R, ROWS = 64 * R;
-    bool costs_ok = c.K <= 4 && c.ins + c.del > 0;  // (what both windows need of the table)
-    for (int e = 0; e < c.K * c.K && costs_ok; ++e)
-        if (!(c.sub[e] >= 0)) costs_ok = false;
-    b.band = b.ck && b.nchains == 0 && P.o.band != 2 && P.o.env_band != 0 && costs_ok;
+    const bool costs_ok = P.band_costs_ok();  // (what both windows need of the table)
+    b.band = b.ck && b.nchains == 0 && P.band_route();
     b.band_cells = b.cells;
     b.band_refine = false;
     b.band_stripes = 0;
@@ -885,8 +990,9 @@ void plan_band(Planning &P) {
                 bc += (double)nn * mm;
                 continue;
             }
-            const sed_band w = sed_band_window(nn, mm, bp.ins, bp.del,
-                                               sed_band_diag_bound(bp, P.codes_a + P.off_a[p], nn, P.codes_b + P.off_b[p], mm));
+            const uint64_t ub = !P.diag_ub.empty() ? P.diag_ub[p]
+                                                   : sed_band_diag_bound(bp, P.codes_a + P.off_a[p], nn, P.codes_b + P.off_b[p], mm);
+            const sed_band w = sed_band_window(nn, mm, bp.ins, bp.del, ub);
             bc += sed_band_pair_cells(nn, mm, R, w);
             const sed_geom g = sed_stripe_geom(nn, mm, R, 64);
             for (int k = 0; k < g.nstripes; ++k) {  // checkpoints of the chunks the forward runs
