@@ -403,6 +403,38 @@ int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double
                         const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts,
                         int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params);
 
+/* Every occurrence within a distance, not only the best one.  Pattern p, text t of length n and G(s, e) as for
+ * sed_fit_search.  For each end column 0 <= e <= n:
+ *   E(e) = min over 0 <= s <= e of G(s, e);
+ *   S(e) = the largest s that reaches it: the (D, -start) key of row P at column e, exactly as sed_fit_search defines it.
+ * The hits of (p, t) within T are all (e, S(e), E(e)) with E(e) <= T.  Column 0 is a column: E(0) = P * delete, S(0) = 0.
+ * A hit is decided per column and depends on nothing but that column's key, so the chunk length cannot change the set
+ * (on the columns a lane owns its keys are the full matrix's).  sed_fit_search's hit of the pair is the hit of smallest
+ * (dist, end) whenever its distance is <= T.
+ * sed_fit_index_hits: every query against every text of the index, blocking, under sed_fit_index_search's plan, lanes,
+ * cost models, refusals and state errors (and its 65535 queries per launch); max_dist = T >= 0, +inf meaning every
+ * column, NaN or negative: SED_E_ARG.  dist = D / S as the search decodes it; a distance is within T exactly when
+ * D <= floor(T * S).
+ *   *found = the total number of hits, always (when the call returns SED_OK or SED_E_RANGE for lack of room).
+ *   found <= cap: out[0 .. found) = all hits sorted by (query, text, end), which are unique keys; SED_OK.
+ *   found > cap:  nothing in out is promised; SED_E_RANGE, the text names found and cap.  The index stays usable: call
+ *                 again with room.  cap = 0 with out = NULL is a count query.
+ * The device hit list belongs to the index, grows to the largest cap seen and is apart from the search's result buffer:
+ * searches and hits searches on one index may alternate. */
+typedef struct { int32_t query, text, start, end; double dist; } sed_fit_hit;
+int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                       int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found);
+/* Device time of the last sed_fit_index_hits' kernel(s), from HIP events (ms); SED_E_STATE before the first that
+ * launched one. */
+int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms);
+/* The cutoff on the integer scale, without a device: the code sed_fit_plan returns for these arguments, else SED_E_ARG
+ * for a NaN or negative max_dist, else *out = min(floor(max_dist * S), 65535) under the plan's scale S (no scaled
+ * distance exceeds P * delete * S <= 65535, so 65535 admits every column; the kernel takes each query's own
+ * P * delete * S from it). */
+int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                          double del, int del_is_int, const int32_t *options, int noptions,
+                          const int32_t *len_p, const int32_t *len_t, int32_t npairs, double max_dist, int64_t *out);
+
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,
  * 4 update) | (1 << 3 when the value is a Python int).  Always runs the fp64 kernel. */

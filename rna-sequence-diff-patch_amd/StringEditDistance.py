@@ -752,6 +752,10 @@ class _EngineIndex:
         self.ctx.set_costs(plan)
         return self.ix.search(packed)
 
+    def hits(self, plan, packed, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.hits(packed, max_dist)
+
     def close(self):
         self.ix.close()
 
@@ -812,13 +816,28 @@ class FitIndex:
         dist, start, end = self._dev.search(plan, packed)
         return [list(zip(d, s, e)) for d, s, e in zip(dist.tolist(), start.tolist(), end.tolist())]
 
+    def hits(self, patterns, max_dist):
+        """[(pattern index, text index, start, end, dist)] sorted by (pattern, text, end): for every end column e of a
+        text (0 <= e <= its length) the smallest wagnerFisher(pattern, text[s:e]) value over s, with the largest such s
+        as start, kept when that value is <= max_dist (include/sed.h: sed_fit_index_hits; math.inf keeps every
+        column).  The same alphabet growth, KeyErrors and SedErrors as search()."""
+        patterns = list(patterns)
+        plan = self.plan(patterns)
+        if not patterns:
+            return []
+        ca, la = plan.encode_many(patterns)
+        packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
+        h = self._dev.hits(plan, packed, max_dist)
+        return list(zip(h["query"].tolist(), h["text"].tolist(), h["start"].tolist(), h["end"].tolist(), h["dist"].tolist()))
+
     def close(self):
         self._dev.close()
 
 
 def fit_index(texts, userCosts=False, alphabet=None, engine=None):
     """A FitIndex over texts: fit_batch for callers who search one collection query after query.  engine(codes, off,
-    lens) -> an object with search(plan, packed) and close() replaces the device (CPU tests)."""
+    lens) -> an object with search(plan, packed), hits(plan, packed, max_dist) and close() replaces the device (CPU
+    tests)."""
     return FitIndex(texts, userCosts, alphabet, engine)
 
 

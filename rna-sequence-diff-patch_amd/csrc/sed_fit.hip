@@ -1,6 +1,7 @@
 // sed_fit.hip — fit search (include/sed.h: sed_fit_search, and sed_fit_index_search over a resident text index, whose
 // kernel is at the end and runs the same DP, sed_fit_dp.h): the best approximate occurrence of a short pattern
-// (1 <= P <= SED_LANE_MAXM) in a long text, one lane per (pair, chunk of text columns).
+// (1 <= P <= SED_LANE_MAXM) in a long text, one lane per (pair, chunk of text columns).  The last kernel,
+// sed_fit_index_hits_kernel (sed_fit_index_hits), reports every end column within a cutoff instead of the best.
 //
 // The DP is the weighted Wagner-Fischer recurrence (StringEditDistance.py:92-128) with a free start: D[0][j] = 0,
 // D[i][0] = i delete, and every cell carries (D, -s), s = the text column its path left row 0 at, as one
@@ -67,6 +68,26 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_kernel(const s
     sed_fit_dp(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, out, fp);
 }
 
+// Every occurrence within a cutoff (include/sed.h: sed_fit_index_hits): sed_fit_index_kernel's grid, chunk table and
+// lane derivation, so sed_fit_index_lanes describes these lanes too.  Instead of the sink row's minimum a lane reports
+// every owned column e with E(e) <= the cutoff: hits[slot] = (query * ntexts + text, e, e - S(e), E(e) * S), slots from
+// *count (sed_fit_dp.h: sed_fit_append), in no particular order; the host sorts them.
+__global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_hits_kernel(
+    const sed_fit_chunk *__restrict__ chunks, int nchunks, const sed_fit_text *__restrict__ texts, int ntexts,
+    const uint4 *__restrict__ pats, const int32_t *__restrict__ plens, int q0, const uint32_t *__restrict__ text,
+    uint4 *__restrict__ hits, unsigned long long *__restrict__ count, unsigned long long cap, int32_t cut, int32_t chunk,
+    int32_t W, sed_fit_params fp) {
+    __shared__ uint2 tab[9];
+    sed_fit_fill_tab(tab, fp);
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nchunks) return;
+    const int q = q0 + (int)blockIdx.y;
+    const sed_fit_chunk ck = chunks[t];
+    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
+    ln.pair = q * ntexts + ck.text;
+    sed_fit_dp_hits(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, sed_fit_hit_list{hits, count, cap, cut}, fp);
+}
+
 }  // namespace
 
 hipError_t sed_launch_fit(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_lane *lanes, int nlanes,
@@ -88,6 +109,23 @@ hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t e
         hipExtLaunchKernelGGL(sed_fit_index_kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream,
                               q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts,
                               a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, a.out, a.chunk, a.W, fp);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t sed_launch_fit_index_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                     void *hits, unsigned long long *count, unsigned long long cap, int32_t cut,
+                                     const sed_fit_params &fp) {
+    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
+    const unsigned gx = (unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK);
+    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_INDEX_MAXY) {
+        const int nq = a.nqueries - q0 < SED_FIT_INDEX_MAXY ? a.nqueries - q0 : SED_FIT_INDEX_MAXY;
+        hipExtLaunchKernelGGL(sed_fit_index_hits_kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream,
+                              q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts,
+                              a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, (uint4 *)hits, count, cap,
+                              cut, a.chunk, a.W, fp);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

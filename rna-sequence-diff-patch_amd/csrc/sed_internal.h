@@ -267,6 +267,12 @@ struct sed_fit_index_args {
 };
 hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                 const sed_fit_params &fp);
+// The same lanes, reporting every owned column whose sink distance * S is <= cut (sed_fit.hip:
+// sed_fit_index_hits_kernel; a.out is not used): hits = 16-byte records (pair, end, end - start, D * S), room for cap;
+// *count, zeroed by the caller, counts every hit, stored or not.
+hipError_t sed_launch_fit_index_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                     void *hits, unsigned long long *count, unsigned long long cap, int32_t cut,
+                                     const sed_fit_params &fp);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

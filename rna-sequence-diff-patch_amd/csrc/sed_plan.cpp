@@ -1399,6 +1399,13 @@ int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, i
     return total;
 }
 
+int sed_fit_cutoff_rule(const sed_fit_plan_t &plan, double max_dist, int32_t *cut, std::string *err) {
+    if (!(max_dist >= 0)) return fail(err, SED_E_ARG, "fit hits: max_dist = %g is not a distance (NaN or negative)", max_dist);
+    const double scaled = std::floor(std::ldexp(max_dist, plan.scale_log2));
+    *cut = scaled >= (double)SED_FIT_CUT_ALL ? SED_FIT_CUT_ALL : (int32_t)scaled;
+    return SED_OK;
+}
+
 void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
                          std::vector<sed_fit_lane> &lanes) {
     lanes.assign((size_t)plan.lanes, sed_fit_lane{});
@@ -1553,6 +1560,19 @@ int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, i
     const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal};
     for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
     return SED_OK;
+}
+
+int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                          int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
+                          int32_t npairs, double max_dist, int64_t *out) {
+    if (!out) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
+    if (rc != SED_OK) return rc;
+    int32_t cut = 0;
+    const int rc2 = sed_fit_cutoff_rule(p, max_dist, &cut, nullptr);
+    if (rc2 == SED_OK) *out = cut;
+    return rc2;
 }
 
 int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,

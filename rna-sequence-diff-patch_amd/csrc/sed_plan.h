@@ -158,6 +158,12 @@ int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len
 int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
                              std::vector<sed_fit_chunk> *chunks, double *computed);
 // (sed_fit_lead, the columns a lane starts before its first owned one: sed_internal.h, shared with the kernels)
+// The cutoff of a hits search (include/sed.h: sed_fit_index_hits) on the plan's integer scale: *cut =
+// min(floor(max_dist S), SED_FIT_CUT_ALL).  A distance D / S is within max_dist exactly when D <= floor(max_dist S)
+// (S is a power of two, so max_dist S is exact); no D exceeds P delete S <= 65535, so SED_FIT_CUT_ALL admits every
+// column of every query, which is what +inf means.  NaN or a negative max_dist: SED_E_ARG.
+#define SED_FIT_CUT_ALL 65535
+int sed_fit_cutoff_rule(const sed_fit_plan_t &plan, double max_dist, int32_t *cut, std::string *err);
 
 // The lane records of a planned batch (sed_internal.h: sed_fit_lane), lanes[plan.first[p] + k] = lane k of pair p, from
 // the plan and the lengths alone: tw counts 4-symbol words from the pair's own text start and pat is 0.  The runtime

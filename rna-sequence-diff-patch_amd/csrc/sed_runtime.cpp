@@ -1406,6 +1406,9 @@ int sed_fit_last_time(const sed_ctx *c, float *kernel_ms) {
 // queries x texts cross product from the index's sums (sed_plan.cpp: sed_fit_plan_index), uploads the queries' pattern
 // records and lengths from pinned memory, and launches one lane per (query, chunk record); the kernel derives each lane
 // (sed_internal.h: sed_fit_derive_lane).  Per search the host touches the queries and the results only.
+struct sed_fit_hit_rec {  // one record of the device hit list (sed_fit_dp.h: sed_fit_append)
+    uint32_t pair, end, len, D;
+};
 struct sed_fit_index {
     sed_ctx *ctx = nullptr;
     sed_fit_index_sums sums;
@@ -1422,10 +1425,19 @@ struct sed_fit_index {
     size_t pin_cap = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool timed = false;
+    // hits searches (sed_fit_index_hits): the device hit list, grown to the largest cap seen, its 64-bit counter, the
+    // host copy the records are sorted in, and the events around the hits kernel; none shared with a search's
+    DevBuf d_hits, d_count;
+    std::vector<sed_fit_hit_rec> h_hits;
+    hipEvent_t hits_ev[2] = {nullptr, nullptr};
+    bool hits_timed = false;
     ~sed_fit_index() {
         if (pin) (void)hipHostFree(pin);
         d_text.release(); d_trec.release(); d_chunks.release(); d_query.release(); d_out.release();
+        d_hits.release(); d_count.release();
         for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : hits_ev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -1494,20 +1506,13 @@ void sed_fit_index_destroy(sed_fit_index *ix) {
 int32_t sed_fit_index_texts(const sed_fit_index *ix) { return ix ? ix->sums.ntexts : SED_E_ARG; }
 int64_t sed_fit_index_symbols(const sed_fit_index *ix) { return ix ? ix->symbols : SED_E_ARG; }
 
-int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
-                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
-    if (!ix) return SED_E_ARG;
+// What a search and a hits search share once their plan stands (nqueries, ntexts > 0): the chunk table of the plan's
+// chunk length, the pinned buffer [front bytes of the caller's | pattern records | pattern lengths], the queries packed
+// into it and sent to the device, and the kernel's arguments but for its output.
+static int fit_index_stage(sed_fit_index *ix, const sed_fit_plan_t &plan, const uint8_t *codes_p, const int64_t *off_p,
+                           const int32_t *len_p, int32_t nqueries, size_t front, sed_fit_index_args *args) {
     sed_ctx *c = ix->ctx;
-    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
     const int ntexts = ix->sums.ntexts;
-    if (nqueries < 0 || (nqueries > 0 && (!codes_p || !off_p || !len_p)) ||
-        (nqueries > 0 && ntexts > 0 && (!out_dist || !out_start || !out_end)))
-        return c->fail(SED_E_ARG, "bad fit arguments");
-    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
-    (void)hipSetDevice(c->device);
-    sed_fit_plan_t plan;
-    int rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
-    if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
     const int K = c->costs.K;
     if (ix->maxcode >= K)
         return c->fail(SED_E_ARG, "fit index: it holds text code %d, outside the alphabet (K=%d)", ix->maxcode, K);
@@ -1527,8 +1532,7 @@ int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_
     }
     if ((int64_t)nqueries * ix->nchunks > INT_MAX)
         return c->fail(SED_E_RANGE, "fit search: %lld lanes", (long long)nqueries * ix->nchunks);
-    const size_t nres = (size_t)nqueries * (size_t)ntexts;
-    const size_t o_pat = 8 * nres, o_len = o_pat + (size_t)SED_LANE_MAXM * nqueries, qbytes = (SED_LANE_MAXM + 4) * (size_t)nqueries;
+    const size_t o_pat = front, o_len = o_pat + (size_t)SED_LANE_MAXM * nqueries, qbytes = (SED_LANE_MAXM + 4) * (size_t)nqueries;
     if (o_pat + qbytes > ix->pin_cap) {
         if (ix->pin) (void)hipHostFree(ix->pin);
         ix->pin = nullptr;
@@ -1555,11 +1559,12 @@ int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_
         }
         plens[q] = P;
     }
-    if (!ix->d_query.reserve(qbytes) || !ix->d_out.reserve(8 * nres))
-        return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
+    if (!ix->d_query.reserve(qbytes))
+        return c->fail(SED_E_OOM, "device allocation failed (fit index, %d queries)", nqueries);
     for (hipEvent_t &ev : ix->ev)
         if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
-    ix->timed = false;
+    for (hipEvent_t &ev : ix->hits_ev)
+        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
     sed_fit_index_args a{};
     a.chunks = (const sed_fit_chunk *)ix->d_chunks.p;
     a.nchunks = (int)ix->nchunks;
@@ -1569,11 +1574,37 @@ int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_
     a.plens = (const int32_t *)((const uint8_t *)ix->d_query.p + (size_t)SED_LANE_MAXM * nqueries);
     a.nqueries = nqueries;
     a.text = ix->d_text.p;
-    a.out = (unsigned long long *)ix->d_out.p;
+    a.out = nullptr;
     a.chunk = plan.chunk;
     a.W = (int32_t)plan.W;
-    if ((e = hipMemcpyAsync(ix->d_query.p, pats, qbytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(ix->d_out.p, 0xFF, 8 * nres, c->stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(ix->d_query.p, pats, qbytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+        return c->hipfail(e, "upload (fit index queries)");
+    *args = a;
+    return SED_OK;
+}
+
+int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+    if (!ix) return SED_E_ARG;
+    sed_ctx *c = ix->ctx;
+    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
+    const int ntexts = ix->sums.ntexts;
+    if (nqueries < 0 || (nqueries > 0 && (!codes_p || !off_p || !len_p)) ||
+        (nqueries > 0 && ntexts > 0 && (!out_dist || !out_start || !out_end)))
+        return c->fail(SED_E_ARG, "bad fit arguments");
+    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
+    (void)hipSetDevice(c->device);
+    sed_fit_plan_t plan;
+    int rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
+    const size_t nres = (size_t)nqueries * (size_t)ntexts;
+    sed_fit_index_args a{};
+    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8 * nres, &a)) != SED_OK) return rc;
+    if (!ix->d_out.reserve(8 * nres)) return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
+    ix->timed = false;
+    a.out = (unsigned long long *)ix->d_out.p;
+    hipError_t e = hipSuccess;
+    if ((e = hipMemsetAsync(ix->d_out.p, 0xFF, 8 * nres, c->stream)) != hipSuccess)
         return c->hipfail(e, "upload (fit index search)");
     if ((e = sed_launch_fit_index(c->stream, ix->ev[0], ix->ev[1], a, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index kernel launch");
@@ -1601,6 +1632,74 @@ int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
     if (!ix || !kernel_ms) return SED_E_ARG;
     if (!ix->timed) return SED_E_STATE;
     return hipEventElapsedTime(kernel_ms, ix->ev[0], ix->ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
+}
+
+// Every hit within max_dist (include/sed.h).  The search's plan, chunk table and queries (fit_index_stage); the kernel
+// appends its records in whatever order the waves' atomic adds land, and counts on past `cap`.  The host reads the
+// count, then the records when they all fit, sorts them by (pair, end) - unique keys - and decodes them.
+int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                       int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
+    if (!ix) return SED_E_ARG;
+    sed_ctx *c = ix->ctx;
+    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
+    const int ntexts = ix->sums.ntexts;
+    if (nqueries < 0 || (nqueries > 0 && (!codes_p || !off_p || !len_p)) || cap < 0 || (cap > 0 && !out) || !found)
+        return c->fail(SED_E_ARG, "bad fit arguments");
+    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
+    (void)hipSetDevice(c->device);
+    sed_fit_plan_t plan;
+    int rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    int32_t cut = 0;
+    if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);
+    if (rc != SED_OK) return rc;
+    *found = 0;
+    if (nqueries == 0 || ntexts == 0) return SED_OK;
+    sed_fit_index_args a{};
+    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8, &a)) != SED_OK) return rc;
+    if ((uint64_t)cap > SIZE_MAX / sizeof(sed_fit_hit_rec) || !ix->d_count.reserve(8) ||
+        !ix->d_hits.reserve(std::max<size_t>((size_t)cap * sizeof(sed_fit_hit_rec), sizeof(sed_fit_hit_rec))))
+        return c->fail(SED_E_OOM, "device allocation failed (fit index, room for %lld hits)", (long long)cap);
+    ix->hits_timed = false;
+    hipError_t e = hipSuccess;
+    if ((e = hipMemsetAsync(ix->d_count.p, 0, 8, c->stream)) != hipSuccess) return c->hipfail(e, "upload (fit index hits)");
+    if ((e = sed_launch_fit_index_hits(c->stream, ix->hits_ev[0], ix->hits_ev[1], a, ix->d_hits.p,
+                                       (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
+        return c->hipfail(e, "fit index hits kernel launch");
+    if ((e = hipMemcpyAsync(ix->pin, ix->d_count.p, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+        return c->hipfail(e, "download (fit index hits)");
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index hits kernel execution");
+    ix->hits_timed = true;
+    const uint64_t n = *(const uint64_t *)ix->pin;
+    *found = (int64_t)n;
+    if (n > (uint64_t)cap)
+        return c->fail(SED_E_RANGE, "fit hits: found %lld hits, cap %lld: call again with room for them", (long long)n,
+                       (long long)cap);
+    if (n == 0) return SED_OK;
+    ix->h_hits.resize((size_t)n);
+    if ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(sed_fit_hit_rec), hipMemcpyDeviceToHost,
+                            c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+        return c->hipfail(e, "download (fit index hits)");
+    std::sort(ix->h_hits.begin(), ix->h_hits.end(), [](const sed_fit_hit_rec &x, const sed_fit_hit_rec &y) {
+        return x.pair != y.pair ? x.pair < y.pair : x.end < y.end;
+    });
+    const double inv = std::ldexp(1.0, -plan.scale_log2);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        const sed_fit_hit_rec &r = ix->h_hits[i];
+        const uint32_t q = r.pair / (uint32_t)ntexts, d = r.pair % (uint32_t)ntexts;
+        if (q >= (uint32_t)nqueries || r.end > (uint32_t)ix->len_t[d] || r.len > r.end || r.D > (uint32_t)cut ||
+            (i > 0 && ix->h_hits[i - 1].pair == r.pair && ix->h_hits[i - 1].end == r.end))
+            return c->fail(SED_E_DEVICE, "fit hits: record %zu from the device is no hit (query %u, text %u, end %u)", i, q, d,
+                           r.end);
+        out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, (int32_t)(r.end - r.len), (int32_t)r.end, (double)r.D * inv};
+    }
+    return SED_OK;
+}
+
+int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms) {
+    if (!ix || !kernel_ms) return SED_E_ARG;
+    if (!ix->hits_timed) return SED_E_STATE;
+    return hipEventElapsedTime(kernel_ms, ix->hits_ev[0], ix->hits_ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
 }
 
 int sed_full_matrix(sed_ctx *c, const uint8_t *codes_a, int32_t n, const uint8_t *codes_b, int32_t m, double *D,

@@ -63,6 +63,8 @@ SED_PLAN_ENV_BAND = 102
 SED_PLAN_ENV_ALT_DP = 103
 SED_PLAN_ENV_CK_HALVES = 104
 MODE_NAMES = {1: "i32", 2: "f64", 3: "f64-typed"}
+SED_E_ARG = -1
+SED_E_RANGE = -4
 
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
@@ -139,6 +141,11 @@ SIGNATURES = [
                                      _i32p, C.c_int32, _i32p, C.c_int32, _f64p, C.c_int]),
     ("sed_fit_index_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                       _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64, _u32p]),
+    ("sed_fit_index_hits", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                     C.POINTER(C.c_int64)]),
+    ("sed_fit_index_hits_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("sed_fit_cutoff_scaled", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                        _i32p, _i32p, C.c_int32, C.c_double, C.POINTER(C.c_int64)]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -426,12 +433,19 @@ class PackedPairs:
         return self
 
 
+# one sed_fit_hit (include/sed.h)
+FIT_HIT_DTYPE = np.dtype([("query", np.int32), ("text", np.int32), ("start", np.int32), ("end", np.int32),
+                          ("dist", np.float64)], align=True)
+
+
 class FitIndex:
-    """Device-resident texts for fit search (sed_fit_index_*): upload once, search many times.  search() runs under the
-    context's costs and options of that moment."""
+    """Device-resident texts for fit search (sed_fit_index_*): upload once, search many times.  search() and hits() run
+    under the context's costs and options of that moment."""
 
     def __init__(self, ctx, codes, off, lens):
         self.ctx = ctx
+        self.found = 0       # the last hits()' total count
+        self._hit_room = 0   # records the last hits(cap=None) made room for: the next one starts there
         self._lib = ctx._lib
         lens = np.ascontiguousarray(lens, np.int32)
         off = np.ascontiguousarray(off, np.int64)
@@ -485,6 +499,36 @@ class FitIndex:
         """Device time of the last search's kernel (ms, HIP events)."""
         ms = C.c_float()
         self.ctx._check(self._lib.sed_fit_index_last_time(self.ptr, C.byref(ms)), "sed_fit_index_last_time")
+        return ms.value
+
+    def hits(self, packed, max_dist, cap=None):
+        """Every hit within max_dist (sed_fit_index_hits): packed as for search().  Returns a structured array over
+        FIT_HIT_DTYPE (query, text, start, end, dist), one record per (query, text, end column) whose best distance is
+        <= max_dist, sorted by (query, text, end).  cap = the records to make room for: more hits than that raise
+        SedError (the index stays usable; FitIndex.found has the count).  cap=None asks for the count first when nothing
+        is known and retries with room, so it always returns every hit."""
+        if not self.ptr:
+            raise SedError("sed_fit_index_hits: the index is closed")
+        Q = packed.npairs
+        found = C.c_int64(0)
+        room = self._hit_room if cap is None else int(cap)
+        while True:
+            out = np.zeros(max(room, 1), FIT_HIT_DTYPE)
+            rc = self._lib.sed_fit_index_hits(self.ptr, packed.codes_a, packed.off_a, packed.len_a, Q, float(max_dist),
+                                              out.ctypes.data if room > 0 else None, room, C.byref(found))
+            self.found = int(found.value)
+            if rc == SED_E_RANGE and cap is None and self.found > room:
+                room = self.found  # (a refusal of the plan leaves found at 0 <= room)
+                continue
+            self.ctx._check(rc, "sed_fit_index_hits")
+            if cap is None:
+                self._hit_room = max(self._hit_room, room)
+            return out[:self.found]
+
+    def hits_last_ms(self):
+        """Device time of the last hits()' kernel (ms, HIP events)."""
+        ms = C.c_float()
+        self.ctx._check(self._lib.sed_fit_index_hits_last_time(self.ptr, C.byref(ms)), "sed_fit_index_hits_last_time")
         return ms.value
 
 
@@ -1100,6 +1144,26 @@ def fit_plan(costs, options, len_p, len_t):
         err.code = rc
         raise err
     return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
+
+
+def fit_cutoff_scaled(costs, options, len_p, len_t, max_dist):
+    """The cutoff FitIndex.hits hands its kernel, without a device (sed_fit_cutoff_scaled): min(floor(max_dist * S),
+    65535) under the scale S of fit_plan's plan for the same arguments.  Raises SedError carrying the code (.code):
+    fit_plan's for these arguments, else SED_E_ARG for a NaN or negative max_dist."""
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
+    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
+    out = C.c_int64(0)
+    rc = load().sed_fit_cutoff_scaled(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
+                                      np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int),
+                                      float(dele), int(del_int), opts, len(options), lp, lt, len(len_p), float(max_dist),
+                                      C.byref(out))
+    if rc != 0:
+        err = SedError("sed_fit_cutoff_scaled failed (%d)" % rc)
+        err.code = rc
+        raise err
+    return int(out.value)
 
 
 FIT_LANE_FIELDS = ("tw", "pair", "pat", "plen", "nsteps", "lead", "cnt", "c0")

@@ -129,9 +129,11 @@ class FitIndex:
         ix = FitIndex(collection, user_cost=True)
         ix.search(query, max_dist=3)          # == fit_search(query, collection, True, max_dist=3)
         ix.search_many(queries)               # one such list per query, from one engine launch
+        ix.occurrences(query, max_dist=3)     # every site within 3 of every document, not only the best one
 
     index_fn(sequences, user_cost) -> an object with search(patterns) -> [[(dist, start, end)] per sequence] per
-    pattern, and close(), replaces the engine (CPU tests).  Not cached."""
+    pattern, hits(patterns, max_dist) -> [(pattern index, sequence index, start, end, dist)] sorted, and close(),
+    replaces the engine (CPU tests).  Not cached."""
 
     def __init__(self, seqs_or_collection, user_cost=False, index_fn=None):
         self.seqs = _sequences(seqs_or_collection)
@@ -157,10 +159,62 @@ class FitIndex:
     def search(self, query, max_dist=None, scripts=False):
         return self.search_many([query], max_dist, scripts)[0]
 
+    def occurrences_many(self, queries, max_dist, all_ends=False, scripts=False):
+        """For each query, [(sequence, 1 / (1 + d), start, end)] for every occurrence within max_dist, in collection
+        order, then by end: one engine launch for all the queries (StringEditDistance.FitIndex.hits).  A hit is an end
+        column e of a document whose best distance E(e) = min over s of d(query, sequence[s:e]) is <= max_dist, with
+        the largest such s as start; the occurrences are the hits that are local minima of E (local_minima): the
+        earliest end of every valley or plateau, search()'s best hit among them.  all_ends=True returns every hit
+        unfiltered.  scripts=True appends each returned tuple's edit script of (query, sequence[start:end]), all from
+        one edit_script_batch call; patching(es, query) then gives sequence[start:end]."""
+        queries = list(queries)
+        if not self.seqs:
+            return [[] for _ in queries]
+        if not queries:
+            return []
+        hits = self._ix.hits(queries, max_dist)
+        kept = hits if all_ends else local_minima(hits)
+        out = [[] for _ in queries]
+        for q, t, a, b, d in kept:
+            out[q].append((self.seqs[t], 1 / (1 + d), a, b))
+        if scripts and kept:
+            es = iter(SED.edit_script_batch([queries[q] for q, _, _, _, _ in kept],
+                                            [self.seqs[t][a:b] for _, t, a, b, _ in kept], self.user_cost))
+            out = [[hit + (next(es)[1],) for hit in o] for o in out]
+        return out
+
+    def occurrences(self, query, max_dist, all_ends=False, scripts=False):
+        return self.occurrences_many([query], max_dist, all_ends, scripts)[0]
+
     def close(self):
         if self._ix is not None:
             self._ix.close()
         self._ix = None
+
+
+def local_minima(hits):
+    """The occurrences among hits = [(query, text, start, end, dist)] sorted by (query, text, end): a hit at end e is
+    kept iff E(e) < E(e - 1) and E(e) <= E(e + 1), where E of a column that is no hit (or lies outside the text)
+    counts as +inf - it exceeds the cutoff, and every hit is within it.  So the rule needs the hit list alone."""
+    out = []
+    for i, h in enumerate(hits):
+        q, t, _, e, d = h
+        prev = hits[i - 1] if i > 0 else None
+        nxt = hits[i + 1] if i + 1 < len(hits) else None
+        before = prev[4] if prev is not None and prev[:2] == (q, t) and prev[3] == e - 1 else math.inf
+        after = nxt[4] if nxt is not None and nxt[:2] == (q, t) and nxt[3] == e + 1 else math.inf
+        if d < before and d <= after:
+            out.append(h)
+    return out
+
+
+def fit_occurrences(query, seqs_or_collection, max_dist, user_cost=False, all_ends=False, scripts=False, index_fn=None):
+    """FitIndex.occurrences in one shot: builds an index over the documents, searches it and closes it."""
+    ix = FitIndex(seqs_or_collection, user_cost, index_fn=index_fn)
+    try:
+        return ix.occurrences(query, max_dist, all_ends, scripts)
+    finally:
+        ix.close()
 
 
 def search_collection(query, vector_type, collection, method, return_dict=None, callback=None):
