@@ -2,6 +2,7 @@
 // kernel is at the end and runs the same DP, sed_fit_dp.h): the best approximate occurrence of a short pattern
 // (1 <= P <= SED_LANE_MAXM) in a long text, one lane per (pair, chunk of text columns).  The last kernel,
 // sed_fit_index_hits_kernel (sed_fit_index_hits), reports every end column within a cutoff instead of the best.
+// The host side: sed_fit_plan.cpp decides what a search runs, sed_fit_runtime.cpp stages and launches it.
 //
 // The DP is the weighted Wagner-Fischer recurrence (StringEditDistance.py:92-128) with a free start: D[0][j] = 0,
 // D[i][0] = i delete, and every cell carries (D, -s), s = the text column its path left row 0 at, as one
@@ -20,7 +21,7 @@
 //     16-bit D field never wraps (D + (P - i) delete <= 32 * 255, 128 insert <= 128 * 255).
 //   - row 0's key of column l is inj = (P delete + B - l' insert) << 16 | (0xFFFF - l), strictly decreasing in l; a
 //     front row computes min3(own old = inj(l-1), above = inj(l), old above - 0 = inj(l-1)) = inj(l).
-// A lane owns text columns [c0, c0 + cnt) and starts `lead` columns earlier (the planner's window W, sed_plan.cpp)
+// A lane owns text columns [c0, c0 + cnt) and starts `lead` columns earlier (the planner's window W, sed_fit_plan.cpp)
 // from the border column i delete: on its own columns it computes the full matrix's keys.  After each owned column it
 // keeps the first strict minimum of the sink row: V[32] - inj = (D - P delete) << 16 | (end - start), compared as
 // (that's high half, owned column index) signed.  The lanes of a pair meet in one 64-bit atomic minimum on
@@ -45,10 +46,23 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_kernel(const sed_fit
     sed_fit_dp(ln, pats[2 * (size_t)ln.pat], pats[2 * (size_t)ln.pat + 1], tab, text, out, fp);
 }
 
-// The same DP over a resident index (sed_internal.h: sed_fit_index_args): blockIdx.y + q0 = the query, whose pattern
-// record and length are uniform across the block; blockIdx.x * 64 + threadIdx.x = the chunk record.  The lane derives
-// its record (sed_fit_derive_lane, the function the device-free sed_fit_index_lanes checks against the lane builder)
-// and reports into out[query * ntexts + text].
+// The lane of thread t of an index kernel, and its query: blockIdx.y + q0 = the query, whose pattern record and length
+// are uniform across the block; t = blockIdx.x * 64 + threadIdx.x = the chunk record.  The lane derives its record
+// (sed_fit_derive_lane, the function the device-free sed_fit_index_lanes checks against the lane builder) for pair
+// query * ntexts + text.
+__device__ __forceinline__ sed_fit_lane sed_fit_index_lane(const sed_fit_chunk *__restrict__ chunks,
+                                                           const sed_fit_text *__restrict__ texts, int ntexts,
+                                                           const int32_t *__restrict__ plens, int q0, int32_t chunk, int32_t W,
+                                                           int t, int *q) {
+    *q = q0 + (int)blockIdx.y;
+    const sed_fit_chunk ck = chunks[t];
+    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[*q], W);
+    ln.pair = *q * ntexts + ck.text;
+    return ln;
+}
+
+// The same DP over a resident index (sed_internal.h: sed_fit_index_args): one lane per (query, chunk record)
+// (sed_fit_index_lane), which reports into out[query * ntexts + text].
 __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_kernel(const sed_fit_chunk *__restrict__ chunks,
                                                                           int nchunks,
                                                                           const sed_fit_text *__restrict__ texts,
@@ -61,10 +75,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_kernel(const s
     sed_fit_fill_tab(tab, fp);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
-    const int q = q0 + (int)blockIdx.y;
-    const sed_fit_chunk ck = chunks[t];
-    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
-    ln.pair = q * ntexts + ck.text;
+    int q;
+    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q0, chunk, W, t, &q);
     sed_fit_dp(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, out, fp);
 }
 
@@ -81,10 +93,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_hits_kernel(
     sed_fit_fill_tab(tab, fp);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
-    const int q = q0 + (int)blockIdx.y;
-    const sed_fit_chunk ck = chunks[t];
-    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
-    ln.pair = q * ntexts + ck.text;
+    int q;
+    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q0, chunk, W, t, &q);
     sed_fit_dp_hits(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, sed_fit_hit_list{hits, count, cap, cut}, fp);
 }
 
@@ -99,35 +109,31 @@ hipError_t sed_launch_fit(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, co
 }
 
 #define SED_FIT_INDEX_MAXY 65535  // queries per launch (the grid's y limit); more run as further launches
-hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
-                                const sed_fit_params &fp) {
+// An index kernel over all of a's queries: the arguments the index kernels share up to the text, then `tail`.  The
+// events bracket the whole search: the first launch starts ev0, the last stops ev1.
+template <typename Kernel, typename... Tail>
+static hipError_t fit_launch_queries(Kernel kernel, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
+                                     const sed_fit_index_args &a, Tail... tail) {
     if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
     const unsigned gx = (unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK);
     for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_INDEX_MAXY) {
         const int nq = a.nqueries - q0 < SED_FIT_INDEX_MAXY ? a.nqueries - q0 : SED_FIT_INDEX_MAXY;
-        // the events bracket the whole search: the first launch starts ev0, the last stops ev1
-        hipExtLaunchKernelGGL(sed_fit_index_kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream,
-                              q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts,
-                              a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, a.out, a.chunk, a.W, fp);
+        hipExtLaunchKernelGGL(kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream, q0 == 0 ? ev0 : nullptr,
+                              q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts, a.ntexts,
+                              (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, tail...);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
+hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                const sed_fit_params &fp) {
+    return fit_launch_queries(sed_fit_index_kernel, stream, ev0, ev1, a, a.out, a.chunk, a.W, fp);
+}
+
 hipError_t sed_launch_fit_index_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                      void *hits, unsigned long long *count, unsigned long long cap, int32_t cut,
                                      const sed_fit_params &fp) {
-    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
-    const unsigned gx = (unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK);
-    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_INDEX_MAXY) {
-        const int nq = a.nqueries - q0 < SED_FIT_INDEX_MAXY ? a.nqueries - q0 : SED_FIT_INDEX_MAXY;
-        hipExtLaunchKernelGGL(sed_fit_index_hits_kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream,
-                              q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts,
-                              a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, (uint4 *)hits, count, cap,
-                              cut, a.chunk, a.W, fp);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return fit_launch_queries(sed_fit_index_hits_kernel, stream, ev0, ev1, a, (uint4 *)hits, count, cap, cut, a.chunk, a.W, fp);
 }

@@ -19,7 +19,7 @@ __device__ __forceinline__ void sed_fit_fill_tab(uint2 *tab, const sed_fit_param
 
 // The hit list of sed_fit_index_hits_kernel: rec[slot] = (pair, end, end - start, scaled D), slots handed out by one
 // atomic add per wave and column step on *count, which counts every hit; a hit whose slot is >= cap is not stored.
-// cut = the scaled cutoff (sed_plan.cpp: sed_fit_cutoff_rule), from which the lane takes its own P delete.
+// cut = the scaled cutoff (sed_fit_plan.cpp: sed_fit_cutoff_rule), from which the lane takes its own P delete.
 struct sed_fit_hit_list {
     uint4 *rec;
     unsigned long long *count;
@@ -46,7 +46,7 @@ __device__ __forceinline__ void sed_fit_append(const sed_fit_hit_list &hl, bool 
     }
 }
 
-// q0, q1 = the pattern, right-aligned in 32 byte codes, code 8 in front of it (sed_runtime.cpp packs the records).
+// q0, q1 = the pattern, right-aligned in 32 byte codes, code 8 in front of it (sed_fit_runtime.cpp: fit_pack_pattern).
 // HITS = false: the sink row's first strict minimum goes to out[ln.pair]; HITS = true: every owned column within
 // hl.cut goes to the hit list, and out is not touched.
 template <bool HITS>

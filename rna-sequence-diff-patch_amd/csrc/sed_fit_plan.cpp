@@ -1,0 +1,358 @@
+// sed_fit_plan.cpp — the fit planner (sed_fit_plan.h): scale, update addends, window, chunk length, lanes and the
+// cutoff of a fit search, from the cost model, the options and the lengths.  No HIP call.  Also the device-free fit
+// entry points of include/sed.h (sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes,
+// sed_fit_cutoff_scaled).
+#include "sed_fit_plan.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+// The device the auto chunk rule sizes for: 256 CUs x 4 SIMDs, 64 lanes a wave.  One lane per text is kept when that
+// alone gives every SIMD SED_FIT_ENOUGH_WAVES waves; else the chunk is the length that gives SED_FIT_TARGET_WAVES, but
+// never below W (a lane's warm-up is W columns, so warm-up stays at most half of its work).
+#define SED_FIT_SIMDS 1024
+#define SED_FIT_ENOUGH_WAVES 2
+#define SED_FIT_TARGET_WAVES 4
+#define SED_FIT_MAX_SPAN 65535  // columns of one lane, border column included: the 16-bit start field
+
+// What the plan takes from the pairs through sums alone (a batch of listed pairs and an index search's cross product
+// fill it their own ways): the pairs, the longest pattern, sum (n + 1) and the longest text.
+struct FitSums {
+    int64_t npairs = 0;
+    int pmax = 0;
+    double cols = 0;
+    int64_t nmax = -1;
+};
+
+// The one rule both callers share: scale, update addends and W from the costs and the longest pattern, then the chunk
+// length and the span check.  *chunk_out = the chunk every text is cut by (0: one lane per text); plan->chunk = the
+// chunk the plan reports, which cuts them the same way (it is 0 only where no text has more columns than the chunk).
+// *span_fail_cols > 0 (a span refusal) = the columns n + 1 from which a text fails, for the caller to name one.
+static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &sm, sed_fit_plan_t *plan, std::string *err,
+                         int64_t *chunk_out, int64_t *span_fail_cols) {
+    const int pmax = sm.pmax;
+    // the smallest S = 2^k, k <= 8, that makes every cost an integer in 0..255
+    int k = 0;
+    for (;; ++k) {
+        if (k > 8)
+            return sed_plan_fail(err, SED_E_RANGE,
+                                 "fit search: the costs are not all multiples of 2^-k in 0..255 * 2^-k for any k <= 8");
+        const double S = std::ldexp(1.0, k);
+        auto integral = [&](double v) { const double x = v * S; return x == std::floor(x) && x >= 0 && x < 1e9; };
+        auto byte = [&](double v) { return integral(v) && v * S <= 255; };
+        bool ok = byte(c.ins) && integral(c.del);  // (delete's range is reported below, with P)
+        for (int e = 0; e < c.K * c.K && ok; ++e) ok = byte(c.sub[e]);
+        if (ok) break;
+    }
+    const double S = std::ldexp(1.0, k);
+    const double insS = c.ins * S, delS = c.del * S;
+    if ((double)pmax * delS > 65535.0)
+        return sed_plan_fail(err, SED_E_RANGE, "fit search: P * delete * S = %d * %g exceeds 65535", pmax, delS);
+    if (delS > 255.0) return sed_plan_fail(err, SED_E_RANGE, "fit search: delete * S = %g exceeds 255", delS);
+    if (insS + delS > 255.0)
+        return sed_plan_fail(err, SED_E_RANGE, "fit search: (insert + delete) * S = %g exceeds 255 (the update addend's byte)",
+                             insS + delS);
+    const uint32_t ins = (uint32_t)insS, del = (uint32_t)delS;
+    plan->scale_log2 = k;
+    plan->fp = sed_fit_params{};
+    plan->fp.ins = ins;
+    plan->fp.del = del;
+    for (int a = 0; a < c.K; ++a)
+        for (int b = 0; b < c.K; ++b) {
+            const uint32_t v = std::min((uint32_t)(c.sub[a * c.K + b] * S), ins + del);
+            plan->fp.row[a][b >> 2] |= (ins + del - v) << (8 * (b & 3));
+        }
+    plan->W = ins ? pmax + (int64_t)pmax * del / ins : -1;
+    // the chunk length
+    int64_t chunk = 0;
+    if (ins && o.fit_chunk > 0)
+        chunk = o.fit_chunk;
+    else if (ins && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * 64) {
+        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * 64));
+        chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
+    }
+    // texts too long for one lane's start field are always split
+    if (ins && o.fit_chunk == 0 && sm.nmax + 1 > SED_FIT_MAX_SPAN && (chunk == 0 || chunk + plan->W + 3 > SED_FIT_MAX_SPAN))
+        chunk = SED_FIT_MAX_SPAN - plan->W - 3;
+    // a text of ncol columns runs in more than one lane when ncol > chunk > 0, each spanning chunk + W + 3 at most;
+    // else in one lane of ncol
+    const bool split = chunk > 0 && sm.nmax + 1 > chunk;
+    *span_fail_cols = 0;
+    if (split && chunk + plan->W + 3 > SED_FIT_MAX_SPAN)
+        *span_fail_cols = std::min<int64_t>(chunk, SED_FIT_MAX_SPAN) + 1;
+    else if (!split && sm.nmax + 1 > SED_FIT_MAX_SPAN)
+        *span_fail_cols = SED_FIT_MAX_SPAN + 1;
+    plan->chunk = split || o.fit_chunk > 0 ? (int32_t)std::min<int64_t>(chunk, INT_MAX) : 0;
+    *chunk_out = chunk;
+    return SED_OK;
+}
+static int fit_span_fail(std::string *err, const char *what, int64_t idx, bool ins) {
+    return sed_plan_fail(err, SED_E_RANGE, "fit search: %s %lld: a lane would span more than %d text columns%s", what,
+                         (long long)idx, SED_FIT_MAX_SPAN, ins ? "" : " (insert = 0: a text runs as one chunk)");
+}
+// the lanes of one text under the rule's chunk, and the columns they compute (warm-up included)
+static inline int64_t fit_text_lanes(int64_t chunk, int64_t W, int64_t n, double *computed) {
+    const int64_t ncol = n + 1;
+    const int64_t nl = chunk > 0 ? (ncol + chunk - 1) / chunk : 1;
+    if (computed)
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t c0 = l * chunk, c1 = nl > 1 ? std::min(ncol, c0 + chunk) : ncol;
+            *computed += (double)(c1 - 1 - (c0 - sed_fit_lead(W, c0)));
+        }
+    return nl;
+}
+
+int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                       sed_fit_plan_t *plan, std::string *err) {
+    if (npairs < 0 || (npairs > 0 && (!len_p || !len_t))) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
+    if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
+    FitSums sm;
+    sm.npairs = npairs;
+    for (int p = 0; p < npairs; ++p) {
+        if (len_t[p] < 0) return sed_plan_fail(err, SED_E_ARG, "pair %d: negative text length", p);
+        if (len_p[p] < 1 || len_p[p] > SED_LANE_MAXM)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: pair %d: pattern length %d outside 1..%d", p, len_p[p],
+                                 SED_LANE_MAXM);
+        sm.pmax = std::max(sm.pmax, len_p[p]);
+        sm.cols += (double)len_t[p] + 1;
+        sm.nmax = std::max<int64_t>(sm.nmax, len_t[p]);
+    }
+    int64_t chunk = 0, span_cols = 0;
+    const int rc = fit_plan_rule(c, o, sm, plan, err, &chunk, &span_cols);
+    if (rc != SED_OK) return rc;
+    plan->first.assign((size_t)npairs + 1, 0);
+    plan->cells = plan->nominal = 0;
+    for (int p = 0; p < npairs; ++p) {
+        if (span_cols && (int64_t)len_t[p] + 1 >= span_cols) return fit_span_fail(err, "pair", p, plan->fp.ins != 0);
+        double computed = 0;
+        plan->first[p + 1] = plan->first[p] + fit_text_lanes(chunk, plan->W, len_t[p], &computed);
+        plan->cells += (double)len_p[p] * computed;
+        plan->nominal += (double)len_p[p] * (double)len_t[p];
+    }
+    plan->lanes = plan->first[npairs];
+    if (plan->lanes > INT_MAX) return sed_plan_fail(err, SED_E_RANGE, "fit search: %lld lanes", (long long)plan->lanes);
+    return SED_OK;
+}
+
+int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
+    if (nqueries < 0 || (nqueries > 0 && !len_p) || tx.ntexts < 0) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
+    if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
+    FitSums sm;
+    double psum = 0;
+    // the refusals of the cross product's pairs, query-major: pair (0, 0)'s text, then its pattern, then the other
+    // texts (pairs (0, d)), then the other patterns; an empty cross product has no pair to refuse
+    for (int q = 0; q < nqueries && tx.ntexts > 0; ++q) {
+        if (tx.first_negative >= 0 && (q == 0 ? tx.first_negative == 0 : q == 1))
+            return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
+        if (len_p[q] < 1 || len_p[q] > SED_LANE_MAXM)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q],
+                                 SED_LANE_MAXM);
+        sm.pmax = std::max(sm.pmax, len_p[q]);
+        psum += (double)len_p[q];
+    }
+    if (nqueries == 1 && tx.ntexts > 0 && tx.first_negative >= 0)
+        return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
+    if (nqueries > 0 && tx.ntexts > 0) {
+        sm.npairs = (int64_t)nqueries * tx.ntexts;
+        sm.cols = (double)nqueries * tx.cols;
+        sm.nmax = tx.nmax;
+    }
+    int64_t chunk = 0, span_cols = 0;
+    const int rc = fit_plan_rule(c, o, sm, plan, err, &chunk, &span_cols);
+    if (rc != SED_OK) return rc;
+    if (span_cols) return fit_span_fail(err, "a text of length", tx.nmax, plan->fp.ins != 0);
+    plan->first.clear();
+    plan->lanes = 0;
+    plan->cells = 0;
+    plan->nominal = psum * (tx.cols - (double)tx.ntexts);
+    return SED_OK;
+}
+
+int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
+                             std::vector<sed_fit_chunk> *chunks, double *computed) {
+    int64_t total = 0;
+    if (chunks) chunks->clear();
+    for (int d = 0; d < ntexts; ++d) {
+        const int64_t nl = fit_text_lanes(plan.chunk, plan.W, len_t[d], computed);
+        total += nl;
+        if (chunks)
+            for (int64_t l = 0; l < nl; ++l) chunks->push_back(sed_fit_chunk{d, (int32_t)(l * plan.chunk)});
+    }
+    return total;
+}
+
+int sed_fit_cutoff_rule(const sed_fit_plan_t &plan, double max_dist, int32_t *cut, std::string *err) {
+    if (!(max_dist >= 0))
+        return sed_plan_fail(err, SED_E_ARG, "fit hits: max_dist = %g is not a distance (NaN or negative)", max_dist);
+    const double scaled = std::floor(std::ldexp(max_dist, plan.scale_log2));
+    *cut = scaled >= (double)SED_FIT_CUT_ALL ? SED_FIT_CUT_ALL : (int32_t)scaled;
+    return SED_OK;
+}
+
+void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                         std::vector<sed_fit_lane> &lanes) {
+    lanes.assign((size_t)plan.lanes, sed_fit_lane{});
+    for (int p = 0; p < npairs; ++p) {
+        const int64_t ncol = (int64_t)len_t[p] + 1, nl = plan.first[p + 1] - plan.first[p];
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t c0 = l * plan.chunk, c1 = nl > 1 ? std::min(ncol, c0 + plan.chunk) : ncol;
+            const int32_t lead = sed_fit_lead(plan.W, c0);
+            sed_fit_lane &ln = lanes[(size_t)(plan.first[p] + l)];
+            ln.tw = (uint32_t)((c0 - lead) / 4);
+            ln.pair = p;
+            ln.pat = 0;
+            ln.plen = len_p[p];
+            ln.nsteps = (int32_t)(c1 - 1 - (c0 - lead));
+            ln.lead = lead;
+            ln.cnt = (int32_t)(c1 - c0);
+            ln.c0 = (int32_t)c0;
+        }
+    }
+}
+
+extern "C" {
+
+// the cost model and options of the device-free fit exports, from their C arguments
+static int fit_costs_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                        int del_is_int, const int32_t *options, int noptions, sed_costs *c, sed_opts *o) {
+    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options)) return SED_E_ARG;
+    if (!std::isfinite(ins) || !std::isfinite(del)) return SED_E_ARG;
+    for (int e = 0; e < K * K; ++e)
+        if (!std::isfinite(sub[e])) return SED_E_ARG;
+    c->K = K;
+    c->sub.assign(sub, sub + K * K);
+    if (sub_int) c->sub_int.assign(sub_int, sub_int + K * K);
+    c->ins = ins;
+    c->del = del;
+    c->ins_int = ins_is_int ? 1 : 0;
+    c->del_int = del_is_int ? 1 : 0;
+    for (int i = 0; i < noptions; ++i)
+        if (!sed_opts_set(*o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    return SED_OK;
+}
+static void fit_params_out(const sed_fit_params &fp, uint32_t *out_params) {
+    for (int a = 0; a < 8; ++a) {
+        out_params[2 * a] = fp.row[a][0];
+        out_params[2 * a + 1] = fp.row[a][1];
+    }
+    out_params[16] = fp.ins;
+    out_params[17] = fp.del;
+}
+// what sed_fit_plan and sed_fit_index_plan report of a plan that stands (rc = its planning's result, handed through)
+static int fit_plan_out(int rc, const sed_fit_plan_t &p, double *out, int nout) {
+    if (rc != SED_OK) return rc;
+    const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal};
+    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}
+
+// sed_fit_plan's and sed_fit_lanes' common half: the plan of the C arguments
+static int fit_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                       int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
+                       int32_t npairs, sed_fit_plan_t *p) {
+    sed_costs c;
+    sed_opts o;
+    const int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    return rc != SED_OK ? rc : sed_fit_plan_batch(c, o, len_p, len_t, npairs, p, nullptr);
+}
+
+int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                 const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                 double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    return fit_plan_out(fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p),
+                        p, out, nout);
+}
+
+int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                          int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
+                          int32_t npairs, double max_dist, int64_t *out) {
+    if (!out) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
+    if (rc != SED_OK) return rc;
+    int32_t cut = 0;
+    const int rc2 = sed_fit_cutoff_rule(p, max_dist, &cut, nullptr);
+    if (rc2 == SED_OK) *out = cut;
+    return rc2;
+}
+
+int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                  const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                  int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    if (max_lanes < 0 || (max_lanes && !out_lanes) || !out_params) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
+    if (rc != SED_OK) return rc;
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    std::vector<sed_fit_lane> lanes;
+    sed_fit_build_lanes(p, len_p, len_t, npairs, lanes);
+    static_assert(sizeof(sed_fit_lane) == 8 * sizeof(int32_t), "a lane record is eight 32-bit words");
+    if (!lanes.empty()) std::memcpy(out_lanes, lanes.data(), lanes.size() * sizeof(sed_fit_lane));
+    fit_params_out(p.fp, out_params);
+    return SED_OK;
+}
+
+// sed_fit_index_plan's and sed_fit_index_lanes' common half: the plan of the cross product from the C arguments, the
+// chunk table and the sums the plan reports
+static int fit_index_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                             const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks) {
+    if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    const int rc0 = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc0 != SED_OK) return rc0;
+    sed_fit_index_sums tx;
+    tx.ntexts = ntexts;
+    for (int d = 0; d < ntexts; ++d) {
+        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
+        tx.cols += (double)len_t[d] + 1;
+        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
+    }
+    const int rc = sed_fit_plan_index(c, o, len_p, nqueries, tx, p, nullptr);
+    if (rc != SED_OK) return rc;
+    double computed = 0, psum = 0;
+    const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
+    for (int q = 0; q < nqueries && ntexts > 0; ++q) psum += (double)len_p[q];
+    p->lanes = nqueries * nchunks;
+    p->cells = psum * computed;
+    return p->lanes > INT_MAX ? SED_E_RANGE : SED_OK;
+}
+
+int sed_fit_index_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                       int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                       const int32_t *len_t, int32_t ntexts, double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    return fit_plan_out(fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
+                                          len_t, ntexts, &p, nullptr),
+                        p, out, nout);
+}
+
+int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                        int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                        const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    if (max_lanes < 0 || (max_lanes && !out_lanes) || !out_params) return SED_E_ARG;
+    sed_fit_plan_t p;
+    std::vector<sed_fit_chunk> chunks;
+    const int rc = fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
+                                     len_t, ntexts, &p, &chunks);
+    if (rc != SED_OK) return rc;
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    sed_fit_lane *out = (sed_fit_lane *)out_lanes;
+    for (int q = 0; q < nqueries; ++q)  // the kernel's own derivation, with each text at word 0
+        for (const sed_fit_chunk &ck : chunks) {
+            sed_fit_lane ln = sed_fit_derive_lane(ck, sed_fit_text{0u, len_t[ck.text]}, p.chunk, len_p[q], p.W);
+            ln.pair = q * ntexts + ck.text;
+            *out++ = ln;
+        }
+    fit_params_out(p.fp, out_params);
+    return SED_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,51 @@
+// sed_fit_plan.h — the device-free half of fit search (include/sed.h: sed_fit_search, sed_fit_index_search,
+// sed_fit_index_hits): what a search decides from the cost model, the options and the lengths.  sed_fit_plan.cpp calls
+// no HIP API, as the batch planner (sed_plan.h, whose sed_costs, sed_opts and sed_plan_fail it shares and nothing else);
+// its exports sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes and sed_fit_cutoff_scaled run, and
+// are tested, without a device.
+#pragma once
+#include "sed_plan.h"
+
+// Pair p's lanes are first[p] .. first[p + 1); lane k of a pair owns text columns [k chunk, min((k + 1) chunk, n + 1))
+// (chunk = 0: the pair's one lane owns them all) and starts sed_fit_lead(W, c0) columns before its first.
+struct sed_fit_plan_t {
+    int scale_log2 = 0;      // S = 2^scale_log2
+    int64_t W = 0;           // P + floor(P delete / insert) over the batch's longest pattern; -1 when insert = 0
+    int32_t chunk = 0;       // owned columns per lane; 0 = one lane per text
+    int64_t lanes = 0;
+    double cells = 0, nominal = 0;  // P x columns computed (warm-up included), and sum P n
+    std::vector<int64_t> first;
+    sed_fit_params fp{};
+};
+int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                       sed_fit_plan_t *plan, std::string *err);
+// The same plan for an index search (include/sed.h: sed_fit_index_search): nqueries patterns against every text of an
+// index, i.e. sed_fit_plan_batch's plan of the nqueries x ntexts cross product, query-major, from the patterns' lengths
+// and the texts' sums alone (both go through one rule).  It leaves lanes and cells 0 and `first` empty: they follow from
+// the chunk table, sed_fit_build_chunks (lanes = nqueries x its records).
+struct sed_fit_index_sums {
+    int32_t ntexts = 0;
+    double cols = 0;             // sum (n + 1)
+    int64_t nmax = -1;           // the longest text
+    int32_t first_negative = -1; // the first text of negative length (the device-free exports; an index holds none)
+};
+int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err);
+// The chunk table of the texts under plan.chunk, text by text in chunk order (chunks may be null), independent of the
+// queries; returns the number of records.  *computed (if not null) += the columns the records' lanes run under plan.W,
+// warm-up included.
+int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
+                             std::vector<sed_fit_chunk> *chunks, double *computed);
+// (sed_fit_lead, the columns a lane starts before its first owned one: sed_internal.h, shared with the kernels)
+// The cutoff of a hits search (include/sed.h: sed_fit_index_hits) on the plan's integer scale: *cut =
+// min(floor(max_dist S), SED_FIT_CUT_ALL).  A distance D / S is within max_dist exactly when D <= floor(max_dist S)
+// (S is a power of two, so max_dist S is exact); no D exceeds P delete S <= 65535, so SED_FIT_CUT_ALL admits every
+// column of every query, which is what +inf means.  NaN or a negative max_dist: SED_E_ARG.
+#define SED_FIT_CUT_ALL 65535
+int sed_fit_cutoff_rule(const sed_fit_plan_t &plan, double max_dist, int32_t *cut, std::string *err);
+
+// The lane records of a planned batch (sed_internal.h: sed_fit_lane), lanes[plan.first[p] + k] = lane k of pair p, from
+// the plan and the lengths alone: tw counts 4-symbol words from the pair's own text start and pat is 0.  The runtime
+// adds the base word of each text's copy and sets the pattern record (sed_fit_runtime.cpp: sed_fit_search).
+void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                         std::vector<sed_fit_lane> &lanes);

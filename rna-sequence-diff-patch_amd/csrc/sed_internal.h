@@ -1,4 +1,5 @@
-// sed_internal.h — structures shared by the kernels and the runtime (not part of the C-ABI).
+// sed_internal.h — structures shared by the kernels, the planners and the runtime (not part of the C-ABI).  Fit search's
+// are in one section ("Fit search" below), read by sed_fit.hip, sed_fit_dp.h, sed_fit_plan.h and sed_fit_runtime.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -3,9 +3,11 @@
 //   DP kernel (integer or fp64)  ->  traceback kernel
 // on one HIP stream, timed with HIP events recorded on that stream.  What a batch runs (mode, routes, layout,
 // kernel parameters) is the planner's decision (sed_plan.cpp); a fill here is: wait, plan, reserve, upload, streams.
+// Fit search's entry points are sed_fit_runtime.cpp; the context and the buffers both units use are sed_runtime.h.
 #include "../../include/sed.h"
 #include "sed_internal.h"
 #include "sed_plan.h"
+#include "sed_runtime.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -16,38 +18,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
-namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    uint64_t gen = 0;  // bumped by every (re)allocation: memory of a new generation may hold anything
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // grow-only; returns false on OOM
-    bool reserve(size_t bytes) {
-        if (bytes <= cap) return true;
-        release();
-        size_t want = std::max<size_t>(bytes, 256);
-        if (hipMalloc(&p, want) != hipSuccess) {
-            p = nullptr;
-            (void)hipGetLastError();
-            return false;
-        }
-        cap = want;
-        ++gen;
-        return true;
-    }
-};
-
-// The process's environment knobs, read once: the options of every new context start from them.
-const sed_opts &env_opts() {
+const sed_opts &sed_env_opts() {
     static const sed_opts env = [] {
         sed_opts o;
         auto knob = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
@@ -62,66 +35,19 @@ const sed_opts &env_opts() {
     return env;
 }
 
-}  // namespace
-
 // Cutoff batches: the wave pairs of a batch with x2 or CHAIN pairs move to the windowed stripe kernel when the window
 // keeps less than this share of their cells (sed_batch_set_cutoff)
 #ifndef SED_CUT_SHARE
 #define SED_CUT_SHARE (2.0 / 3.0)
 #endif
 
-struct sed_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    bool have_costs = false;
-    sed_costs costs;
-    DevBuf gtab;  // fp64 kernel table: per entry {value bits, is-int flag}
-    sed_opts opt = env_opts();
-    DevBuf selftest;
-    sed_batch *scratch = nullptr;
-    // pinned host staging (hipHostMalloc) of small batches: the upload blob, then the results' download
-    void *pin = nullptr;
-    size_t pin_cap = 0;
-    bool pin_busy = false;  // a copy from / to `pin` may still be in flight on `stream`
-    bool pair_pending = false;  // sed_pair_submit enqueued the scratch batch; sed_pair_wait has not fetched it
-    // fit search (sed_fit_search): its device arrays and the events around its kernel, kept across calls
-    DevBuf fit_text, fit_pat, fit_lanes, fit_out;
-    hipEvent_t fit_ev[2] = {nullptr, nullptr};
-    bool fit_timed = false;
-
-    int fail(int code, const char *fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
-    int hipfail(hipError_t e, const char *what) {
-        return fail(SED_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
-    }
-};
-
-struct sed_batch;
 namespace {
 // grow the context's pinned staging to `bytes` (first waiting for a copy still in flight from it)
 hipError_t pin_reserve(sed_ctx *c, size_t bytes) {
     hipError_t e = hipSuccess;
     if (c->pin_busy && (e = hipStreamSynchronize(c->stream)) != hipSuccess) return e;
     c->pin_busy = false;
-    if (bytes <= c->pin_cap) return hipSuccess;
-    if (c->pin) (void)hipHostFree(c->pin);
-    c->pin = nullptr;
-    c->pin_cap = 0;
-    const size_t want = std::max<size_t>(bytes, 1u << 20);
-    if ((e = hipHostMalloc(&c->pin, want, hipHostMallocDefault)) != hipSuccess) {
-        c->pin = nullptr;
-        return e;
-    }
-    c->pin_cap = want;
-    return hipSuccess;
+    return c->pin.reserve(bytes, 1u << 20) ? hipSuccess : hipErrorOutOfMemory;
 }
 }  // namespace
 
@@ -351,7 +277,7 @@ int upload_batch(sed_batch *b) {
     hipError_t e;
     if (p.small) {
         if ((e = pin_reserve(c, p.blob_bytes)) != hipSuccess) return c->hipfail(e, "pinned staging");
-        char *h = (char *)c->pin, *d = (char *)b->d_small.p;
+        char *h = (char *)c->pin.p, *d = (char *)b->d_small.p;
         for (int i = 0; i < SED_UP_COUNT; ++i) {
             if (p.up_copy[i]) memcpy(h + p.up_off[i], t.item[i].src, p.up_copy[i]);
             memset(h + p.up_off[i] + p.up_copy[i], 0, p.up_size[i] - p.up_copy[i]);  // (CHAIN: the counters)
@@ -737,11 +663,11 @@ int fetch_results(sed_batch *b, double *out_dist, uint8_t *out_is_int, int32_t *
         const size_t bytes = (b->plan.o_ops - b->plan.o_res) + (want_ops ? 4 * b->plan.ops_words : 0);
         const char *src = (const char *)b->h_out;
         if (!b->plan.zc) {
-            if (bytes > c->pin_cap && (e = pin_reserve(c, bytes)) != hipSuccess) return c->hipfail(e, "pinned staging");
-            if (np && (e = hipMemcpyAsync(c->pin, b->p_res[0], bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+            if (bytes > c->pin.cap && (e = pin_reserve(c, bytes)) != hipSuccess) return c->hipfail(e, "pinned staging");
+            if (np && (e = hipMemcpyAsync(c->pin.p, b->p_res[0], bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
                 return c->hipfail(e, "download results");
             c->pin_busy = true;
-            src = (const char *)c->pin;
+            src = (const char *)c->pin.p;
         }
         int rc = sync_batch(b);
         if (rc != SED_OK) return rc;
@@ -819,12 +745,10 @@ void sed_destroy(sed_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     delete c->scratch;
-    if (c->pin) (void)hipHostFree(c->pin);
+    c->pin.release();
     c->gtab.release();
     c->selftest.release();
-    c->fit_text.release(); c->fit_pat.release(); c->fit_lanes.release(); c->fit_out.release();
-    for (hipEvent_t e : c->fit_ev)
-        if (e) (void)hipEventDestroy(e);
+    sed_fit_state_destroy(c->fit);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1301,405 +1225,6 @@ int sed_pair_wait(sed_ctx *c, double *out_dist, uint8_t *out_is_int, int32_t *ou
     const bool script = (c->scratch->plan.flags & SED_WANT_SCRIPT) != 0;
     return fetch_results(c->scratch, out_dist, out_is_int, out_len ? out_len : &len, script ? out_ops : nullptr,
                          script && out_ops ? &off : nullptr);
-}
-
-// Fit search.  The planner decides scale, window and lanes from the lengths and builds the lane records
-// (sed_plan.cpp: sed_fit_plan_batch, sed_fit_build_lanes); here the
-// distinct patterns become 32-byte records (right-aligned, code 8 in front) and the distinct texts one buffer in which
-// each starts 4-byte aligned, so pairs that share a pattern or a text through their offsets share its copy.
-int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p, const uint8_t *codes_t,
-                   const int64_t *off_t, const int32_t *len_t, int32_t npairs, double *out_dist, int32_t *out_start,
-                   int32_t *out_end) {
-    if (!c) return SED_E_ARG;
-    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
-    if (npairs < 0 || (npairs > 0 && (!codes_p || !off_p || !len_p || !codes_t || !off_t || !len_t || !out_dist ||
-                                      !out_start || !out_end)))
-        return c->fail(SED_E_ARG, "bad fit arguments");
-    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
-    (void)hipSetDevice(c->device);
-    sed_fit_plan_t plan;
-    int rc = sed_fit_plan_batch(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err);
-    if (rc != SED_OK || npairs == 0) return rc;
-    const int K = c->costs.K;
-    struct Span {
-        int64_t off;
-        int32_t len;
-        bool operator==(const Span &o) const { return off == o.off && len == o.len; }
-    };
-    struct SpanHash {
-        size_t operator()(const Span &s) const { return std::hash<int64_t>()(s.off * 0x9E3779B97F4A7C15ll + s.len); }
-    };
-    std::unordered_map<Span, int64_t, SpanHash> pat_of, text_of;
-    std::vector<uint8_t> pats, text;
-    std::vector<sed_fit_lane> lanes;
-    sed_fit_build_lanes(plan, len_p, len_t, npairs, lanes);
-    for (int p = 0; p < npairs; ++p) {
-        if (off_p[p] < 0 || off_t[p] < 0) return c->fail(SED_E_ARG, "pair %d: negative offset", p);
-        const int P = len_p[p], n = len_t[p];
-        auto pi = pat_of.find(Span{off_p[p], P});
-        if (pi == pat_of.end()) {
-            pi = pat_of.emplace(Span{off_p[p], P}, (int64_t)(pats.size() / SED_LANE_MAXM)).first;
-            pats.resize(pats.size() + SED_LANE_MAXM, 8);
-            uint8_t *rec = pats.data() + pats.size() - P;
-            for (int i = 0; i < P; ++i) {
-                rec[i] = codes_p[off_p[p] + i];
-                if (rec[i] >= K) return c->fail(SED_E_ARG, "pair %d: pattern code %d outside the alphabet (K=%d)", p, rec[i], K);
-            }
-        }
-        auto ti = text_of.find(Span{off_t[p], n});
-        if (ti == text_of.end()) {
-            ti = text_of.emplace(Span{off_t[p], n}, (int64_t)(text.size() / 4)).first;
-            const size_t at = text.size();
-            text.resize(at + (((size_t)n + 3) & ~(size_t)3), 0);
-            uint8_t top = 0;
-            for (int j = 0; j < n; ++j) top |= (text[at + j] = codes_t[off_t[p] + j]) >= K ? 0x80 : 0;
-            if (top) return c->fail(SED_E_ARG, "pair %d: a text code is outside the alphabet (K=%d)", p, K);
-            if (text.size() / 4 > 0xFFFFFFF0u) return c->fail(SED_E_RANGE, "fit search: more than 16 GB of text");
-        }
-        for (int64_t l = plan.first[p]; l < plan.first[p + 1]; ++l) {  // the planner's records, at this text's copy
-            lanes[(size_t)l].tw += (uint32_t)ti->second;
-            lanes[(size_t)l].pat = (int32_t)pi->second;
-        }
-    }
-    text.resize(text.size() + 16, 0);  // (a lane reads one word past its last)
-    if (!c->fit_text.reserve(text.size()) || !c->fit_pat.reserve(pats.size()) ||
-        !c->fit_lanes.reserve(lanes.size() * sizeof(sed_fit_lane)) || !c->fit_out.reserve(8 * (size_t)npairs))
-        return c->fail(SED_E_OOM, "device allocation failed (fit search, %zu text bytes)", text.size());
-    hipError_t e = hipSuccess;
-    for (hipEvent_t &ev : c->fit_ev)
-        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
-    c->fit_timed = false;
-    std::vector<uint64_t> keys((size_t)npairs);
-    if ((e = hipMemcpyAsync(c->fit_text.p, text.data(), text.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(c->fit_pat.p, pats.data(), pats.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(c->fit_lanes.p, lanes.data(), lanes.size() * sizeof(sed_fit_lane), hipMemcpyHostToDevice,
-                            c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(c->fit_out.p, 0xFF, 8 * (size_t)npairs, c->stream)) != hipSuccess)
-        return c->hipfail(e, "upload (fit search)");
-    if ((e = sed_launch_fit(c->stream, c->fit_ev[0], c->fit_ev[1], (const sed_fit_lane *)c->fit_lanes.p, (int)lanes.size(),
-                            c->fit_pat.p, c->fit_text.p, (unsigned long long *)c->fit_out.p, plan.fp)) != hipSuccess)
-        return c->hipfail(e, "fit kernel launch");
-    if ((e = hipMemcpyAsync(keys.data(), c->fit_out.p, 8 * (size_t)npairs, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (fit search)");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit kernel execution");
-    c->fit_timed = true;
-    const double inv = std::ldexp(1.0, -plan.scale_log2);
-    for (int p = 0; p < npairs; ++p) {
-        const uint64_t k = keys[p];
-        const int64_t end = (int64_t)((k >> 16) & 0xFFFFFFFFu), len = (int64_t)(k & 0xFFFFu);
-        if (k == ~0ull || end > len_t[p] || len > end) return c->fail(SED_E_DEVICE, "pair %d: no fit result from the device", p);
-        out_dist[p] = (double)(k >> 48) * inv;
-        out_end[p] = (int32_t)end;
-        out_start[p] = (int32_t)(end - len);
-    }
-    return SED_OK;
-}
-
-int sed_fit_last_time(const sed_ctx *c, float *kernel_ms) {
-    if (!c || !kernel_ms) return SED_E_ARG;
-    if (!c->fit_timed) return SED_E_STATE;
-    return hipEventElapsedTime(kernel_ms, c->fit_ev[0], c->fit_ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
-}
-
-// Fit search over a resident index (include/sed.h).  The index holds what no query changes: the packed texts, one
-// record per text, and for the chunk length of the last search one record per (text, chunk).  A search plans the
-// queries x texts cross product from the index's sums (sed_plan.cpp: sed_fit_plan_index), uploads the queries' pattern
-// records and lengths from pinned memory, and launches one lane per (query, chunk record); the kernel derives each lane
-// (sed_internal.h: sed_fit_derive_lane).  Per search the host touches the queries and the results only.
-struct sed_fit_hit_rec {  // one record of the device hit list (sed_fit_dp.h: sed_fit_append)
-    uint32_t pair, end, len, D;
-};
-struct sed_fit_index {
-    sed_ctx *ctx = nullptr;
-    sed_fit_index_sums sums;
-    int64_t symbols = 0;
-    int maxcode = -1;              // the largest text code (a search under K symbols needs maxcode < K)
-    std::vector<int32_t> len_t;    // the texts' lengths: the chunk table's input, and the bound of every reported end
-    DevBuf d_text, d_trec, d_chunks, d_query, d_out;
-    bool have_chunks = false;      // d_chunks holds the table of chunk length `chunk`, nchunks records
-    int32_t chunk = 0;
-    int64_t nchunks = 0;
-    std::vector<sed_fit_chunk> h_chunks;
-    // pinned host memory: [result keys (queries x texts) | pattern records | pattern lengths] of the search under way
-    void *pin = nullptr;
-    size_t pin_cap = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false;
-    // hits searches (sed_fit_index_hits): the device hit list, grown to the largest cap seen, its 64-bit counter, the
-    // host copy the records are sorted in, and the events around the hits kernel; none shared with a search's
-    DevBuf d_hits, d_count;
-    std::vector<sed_fit_hit_rec> h_hits;
-    hipEvent_t hits_ev[2] = {nullptr, nullptr};
-    bool hits_timed = false;
-    ~sed_fit_index() {
-        if (pin) (void)hipHostFree(pin);
-        d_text.release(); d_trec.release(); d_chunks.release(); d_query.release(); d_out.release();
-        d_hits.release(); d_count.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : hits_ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
-sed_fit_index *sed_fit_index_create(sed_ctx *c, const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
-                                    int32_t ntexts) {
-    if (!c) return nullptr;
-    if (ntexts < 0 || (ntexts > 0 && (!codes_t || !off_t || !len_t))) {
-        c->fail(SED_E_ARG, "bad fit index arguments");
-        return nullptr;
-    }
-    (void)hipSetDevice(c->device);
-    size_t words = 0;
-    for (int d = 0; d < ntexts; ++d) {
-        if (len_t[d] < 0 || off_t[d] < 0) {
-            c->fail(SED_E_ARG, "text %d: negative %s", d, len_t[d] < 0 ? "length" : "offset");
-            return nullptr;
-        }
-        words += ((size_t)len_t[d] + 3) / 4;
-        if (words > 0xFFFFFFF0u) {
-            c->fail(SED_E_RANGE, "fit search: more than 16 GB of text");
-            return nullptr;
-        }
-    }
-    sed_fit_index *ix = new sed_fit_index;
-    ix->ctx = c;
-    ix->sums.ntexts = ntexts;
-    ix->len_t.assign(len_t, len_t + ntexts);
-    // every text 4-byte aligned, zero padded, and spare words at the end: a lane reads one word past its last
-    std::vector<uint8_t> text(4 * words + 16, 0);
-    std::vector<sed_fit_text> trec((size_t)ntexts);
-    size_t at = 0;
-    uint8_t top = 0;
-    for (int d = 0; d < ntexts; ++d) {
-        const int n = len_t[d];
-        trec[d] = sed_fit_text{(uint32_t)(at / 4), n};
-        const uint8_t *src = codes_t + off_t[d];
-        for (int j = 0; j < n; ++j) top = std::max(top, text[at + j] = src[j]);
-        if (n > 0) ix->maxcode = std::max<int>(ix->maxcode, top);
-        at += ((size_t)n + 3) & ~(size_t)3;
-        ix->symbols += n;
-        ix->sums.cols += (double)n + 1;
-        ix->sums.nmax = std::max<int64_t>(ix->sums.nmax, n);
-    }
-    hipError_t e = hipSuccess;
-    if (!ix->d_text.reserve(text.size()) || !ix->d_trec.reserve(trec.size() * sizeof(sed_fit_text))) {
-        c->fail(SED_E_OOM, "device allocation failed (fit index, %zu text bytes)", text.size());
-    } else if ((e = hipMemcpyAsync(ix->d_text.p, text.data(), text.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-               (ntexts > 0 && (e = hipMemcpyAsync(ix->d_trec.p, trec.data(), trec.size() * sizeof(sed_fit_text),
-                                                  hipMemcpyHostToDevice, c->stream)) != hipSuccess) ||
-               (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
-        c->hipfail(e, "upload (fit index)");
-    } else {
-        return ix;
-    }
-    delete ix;
-    return nullptr;
-}
-
-void sed_fit_index_destroy(sed_fit_index *ix) {
-    if (!ix) return;
-    (void)hipSetDevice(ix->ctx->device);
-    delete ix;
-}
-
-int32_t sed_fit_index_texts(const sed_fit_index *ix) { return ix ? ix->sums.ntexts : SED_E_ARG; }
-int64_t sed_fit_index_symbols(const sed_fit_index *ix) { return ix ? ix->symbols : SED_E_ARG; }
-
-// What a search and a hits search share once their plan stands (nqueries, ntexts > 0): the chunk table of the plan's
-// chunk length, the pinned buffer [front bytes of the caller's | pattern records | pattern lengths], the queries packed
-// into it and sent to the device, and the kernel's arguments but for its output.
-static int fit_index_stage(sed_fit_index *ix, const sed_fit_plan_t &plan, const uint8_t *codes_p, const int64_t *off_p,
-                           const int32_t *len_p, int32_t nqueries, size_t front, sed_fit_index_args *args) {
-    sed_ctx *c = ix->ctx;
-    const int ntexts = ix->sums.ntexts;
-    const int K = c->costs.K;
-    if (ix->maxcode >= K)
-        return c->fail(SED_E_ARG, "fit index: it holds text code %d, outside the alphabet (K=%d)", ix->maxcode, K);
-    hipError_t e = hipSuccess;
-    // the chunk table: the last search's when the chunk length is the same
-    if (!ix->have_chunks || ix->chunk != plan.chunk) {
-        ix->have_chunks = false;
-        ix->nchunks = sed_fit_build_chunks(plan, ix->len_t.data(), ntexts, &ix->h_chunks, nullptr);
-        if (!ix->d_chunks.reserve(ix->h_chunks.size() * sizeof(sed_fit_chunk)))
-            return c->fail(SED_E_OOM, "device allocation failed (fit index, %lld chunk records)", (long long)ix->nchunks);
-        if ((e = hipMemcpyAsync(ix->d_chunks.p, ix->h_chunks.data(), ix->h_chunks.size() * sizeof(sed_fit_chunk),
-                                hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-            return c->hipfail(e, "upload (fit index chunk table)");
-        ix->chunk = plan.chunk;
-        ix->have_chunks = true;
-    }
-    if ((int64_t)nqueries * ix->nchunks > INT_MAX)
-        return c->fail(SED_E_RANGE, "fit search: %lld lanes", (long long)nqueries * ix->nchunks);
-    const size_t o_pat = front, o_len = o_pat + (size_t)SED_LANE_MAXM * nqueries, qbytes = (SED_LANE_MAXM + 4) * (size_t)nqueries;
-    if (o_pat + qbytes > ix->pin_cap) {
-        if (ix->pin) (void)hipHostFree(ix->pin);
-        ix->pin = nullptr;
-        ix->pin_cap = 0;
-        const size_t want = std::max<size_t>(o_pat + qbytes, 1u << 16);
-        if (hipHostMalloc(&ix->pin, want, hipHostMallocDefault) != hipSuccess) {
-            ix->pin = nullptr;
-            (void)hipGetLastError();
-            return c->fail(SED_E_OOM, "pinned allocation failed (fit index, %zu bytes)", want);
-        }
-        ix->pin_cap = want;
-    }
-    // the queries: 32-byte records (right-aligned, code 8 in front), then their lengths
-    uint8_t *pats = (uint8_t *)ix->pin + o_pat;
-    int32_t *plens = (int32_t *)((uint8_t *)ix->pin + o_len);
-    memset(pats, 8, (size_t)SED_LANE_MAXM * nqueries);
-    for (int q = 0; q < nqueries; ++q) {
-        if (off_p[q] < 0) return c->fail(SED_E_ARG, "query %d: negative offset", q);
-        const int P = len_p[q];
-        uint8_t *rec = pats + (size_t)SED_LANE_MAXM * (q + 1) - P;
-        for (int i = 0; i < P; ++i) {
-            rec[i] = codes_p[off_p[q] + i];
-            if (rec[i] >= K) return c->fail(SED_E_ARG, "query %d: pattern code %d outside the alphabet (K=%d)", q, rec[i], K);
-        }
-        plens[q] = P;
-    }
-    if (!ix->d_query.reserve(qbytes))
-        return c->fail(SED_E_OOM, "device allocation failed (fit index, %d queries)", nqueries);
-    for (hipEvent_t &ev : ix->ev)
-        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
-    for (hipEvent_t &ev : ix->hits_ev)
-        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return c->hipfail(e, "event create");
-    sed_fit_index_args a{};
-    a.chunks = (const sed_fit_chunk *)ix->d_chunks.p;
-    a.nchunks = (int)ix->nchunks;
-    a.texts = (const sed_fit_text *)ix->d_trec.p;
-    a.ntexts = ntexts;
-    a.pats = ix->d_query.p;
-    a.plens = (const int32_t *)((const uint8_t *)ix->d_query.p + (size_t)SED_LANE_MAXM * nqueries);
-    a.nqueries = nqueries;
-    a.text = ix->d_text.p;
-    a.out = nullptr;
-    a.chunk = plan.chunk;
-    a.W = (int32_t)plan.W;
-    if ((e = hipMemcpyAsync(ix->d_query.p, pats, qbytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-        return c->hipfail(e, "upload (fit index queries)");
-    *args = a;
-    return SED_OK;
-}
-
-int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
-                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
-    if (!ix) return SED_E_ARG;
-    sed_ctx *c = ix->ctx;
-    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
-    const int ntexts = ix->sums.ntexts;
-    if (nqueries < 0 || (nqueries > 0 && (!codes_p || !off_p || !len_p)) ||
-        (nqueries > 0 && ntexts > 0 && (!out_dist || !out_start || !out_end)))
-        return c->fail(SED_E_ARG, "bad fit arguments");
-    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
-    (void)hipSetDevice(c->device);
-    sed_fit_plan_t plan;
-    int rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
-    if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
-    const size_t nres = (size_t)nqueries * (size_t)ntexts;
-    sed_fit_index_args a{};
-    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8 * nres, &a)) != SED_OK) return rc;
-    if (!ix->d_out.reserve(8 * nres)) return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
-    ix->timed = false;
-    a.out = (unsigned long long *)ix->d_out.p;
-    hipError_t e = hipSuccess;
-    if ((e = hipMemsetAsync(ix->d_out.p, 0xFF, 8 * nres, c->stream)) != hipSuccess)
-        return c->hipfail(e, "upload (fit index search)");
-    if ((e = sed_launch_fit_index(c->stream, ix->ev[0], ix->ev[1], a, plan.fp)) != hipSuccess)
-        return c->hipfail(e, "fit index kernel launch");
-    const uint64_t *keys = (const uint64_t *)ix->pin;
-    if ((e = hipMemcpyAsync(ix->pin, ix->d_out.p, 8 * nres, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (fit index search)");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index kernel execution");
-    ix->timed = true;
-    const double inv = std::ldexp(1.0, -plan.scale_log2);
-    size_t r = 0;
-    for (int q = 0; q < nqueries; ++q)
-        for (int d = 0; d < ntexts; ++d, ++r) {
-            const uint64_t k = keys[r];
-            const int64_t end = (int64_t)((k >> 16) & 0xFFFFFFFFu), len = (int64_t)(k & 0xFFFFu);
-            if (k == ~0ull || end > ix->len_t[d] || len > end)
-                return c->fail(SED_E_DEVICE, "query %d, text %d: no fit result from the device", q, d);
-            out_dist[r] = (double)(k >> 48) * inv;
-            out_end[r] = (int32_t)end;
-            out_start[r] = (int32_t)(end - len);
-        }
-    return SED_OK;
-}
-
-int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
-    if (!ix || !kernel_ms) return SED_E_ARG;
-    if (!ix->timed) return SED_E_STATE;
-    return hipEventElapsedTime(kernel_ms, ix->ev[0], ix->ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
-}
-
-// Every hit within max_dist (include/sed.h).  The search's plan, chunk table and queries (fit_index_stage); the kernel
-// appends its records in whatever order the waves' atomic adds land, and counts on past `cap`.  The host reads the
-// count, then the records when they all fit, sorts them by (pair, end) - unique keys - and decodes them.
-int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
-                       int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
-    if (!ix) return SED_E_ARG;
-    sed_ctx *c = ix->ctx;
-    if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
-    const int ntexts = ix->sums.ntexts;
-    if (nqueries < 0 || (nqueries > 0 && (!codes_p || !off_p || !len_p)) || cap < 0 || (cap > 0 && !out) || !found)
-        return c->fail(SED_E_ARG, "bad fit arguments");
-    if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
-    (void)hipSetDevice(c->device);
-    sed_fit_plan_t plan;
-    int rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
-    int32_t cut = 0;
-    if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);
-    if (rc != SED_OK) return rc;
-    *found = 0;
-    if (nqueries == 0 || ntexts == 0) return SED_OK;
-    sed_fit_index_args a{};
-    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8, &a)) != SED_OK) return rc;
-    if ((uint64_t)cap > SIZE_MAX / sizeof(sed_fit_hit_rec) || !ix->d_count.reserve(8) ||
-        !ix->d_hits.reserve(std::max<size_t>((size_t)cap * sizeof(sed_fit_hit_rec), sizeof(sed_fit_hit_rec))))
-        return c->fail(SED_E_OOM, "device allocation failed (fit index, room for %lld hits)", (long long)cap);
-    ix->hits_timed = false;
-    hipError_t e = hipSuccess;
-    if ((e = hipMemsetAsync(ix->d_count.p, 0, 8, c->stream)) != hipSuccess) return c->hipfail(e, "upload (fit index hits)");
-    if ((e = sed_launch_fit_index_hits(c->stream, ix->hits_ev[0], ix->hits_ev[1], a, ix->d_hits.p,
-                                       (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
-        return c->hipfail(e, "fit index hits kernel launch");
-    if ((e = hipMemcpyAsync(ix->pin, ix->d_count.p, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (fit index hits)");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index hits kernel execution");
-    ix->hits_timed = true;
-    const uint64_t n = *(const uint64_t *)ix->pin;
-    *found = (int64_t)n;
-    if (n > (uint64_t)cap)
-        return c->fail(SED_E_RANGE, "fit hits: found %lld hits, cap %lld: call again with room for them", (long long)n,
-                       (long long)cap);
-    if (n == 0) return SED_OK;
-    ix->h_hits.resize((size_t)n);
-    if ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(sed_fit_hit_rec), hipMemcpyDeviceToHost,
-                            c->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (fit index hits)");
-    std::sort(ix->h_hits.begin(), ix->h_hits.end(), [](const sed_fit_hit_rec &x, const sed_fit_hit_rec &y) {
-        return x.pair != y.pair ? x.pair < y.pair : x.end < y.end;
-    });
-    const double inv = std::ldexp(1.0, -plan.scale_log2);
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        const sed_fit_hit_rec &r = ix->h_hits[i];
-        const uint32_t q = r.pair / (uint32_t)ntexts, d = r.pair % (uint32_t)ntexts;
-        if (q >= (uint32_t)nqueries || r.end > (uint32_t)ix->len_t[d] || r.len > r.end || r.D > (uint32_t)cut ||
-            (i > 0 && ix->h_hits[i - 1].pair == r.pair && ix->h_hits[i - 1].end == r.end))
-            return c->fail(SED_E_DEVICE, "fit hits: record %zu from the device is no hit (query %u, text %u, end %u)", i, q, d,
-                           r.end);
-        out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, (int32_t)(r.end - r.len), (int32_t)r.end, (double)r.D * inv};
-    }
-    return SED_OK;
-}
-
-int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms) {
-    if (!ix || !kernel_ms) return SED_E_ARG;
-    if (!ix->hits_timed) return SED_E_STATE;
-    return hipEventElapsedTime(kernel_ms, ix->hits_ev[0], ix->hits_ev[1]) == hipSuccess ? SED_OK : SED_E_DEVICE;
 }
 
 int sed_full_matrix(sed_ctx *c, const uint8_t *codes_a, int32_t n, const uint8_t *codes_b, int32_t m, double *D,

@@ -227,6 +227,54 @@ def test_many_queries_ragged_chunks(gpu):
         ix.close()
 
 
+def _two_launches():
+    """65 537 queries, two more than one launch's 65 535 (the grid's y limit): all 20 patterns of length 1-2 over ACGU
+    in turn, against two texts of 6 and 9 symbols.  Returns (the 20 patterns, the queries, the texts)."""
+    base = [np.array([a], np.uint8) for a in range(4)] + [np.array([a, b], np.uint8) for a in range(4) for b in range(4)]
+    rng = np.random.default_rng(65537)
+    texts = [rng.integers(0, 4, size=n).astype(np.uint8) for n in (6, 9)]
+    return base, [base[q % 20] for q in range(65537)], texts
+
+
+def test_search_beyond_one_launch_of_queries(gpu):
+    """The search's second launch, and the events around both: every (query, text) equals oracle.fit (one run per
+    distinct pattern and text, broadcast), and the search's time is that of a run."""
+    plan = _golden_plan("user_costs.json", "ACGU")
+    base, pats, texts = _two_launches()
+    xp = _cross(base, texts)
+    want = oracle.fit(oracle.Costs.from_plan(plan), xp.codes_a, xp.off_a, xp.len_a, xp.codes_b, xp.off_b, xp.len_b,
+                      xp.npairs, 8)
+    which = np.arange(len(pats)) % 20
+    gpu.set_costs(plan)
+    ix = sedgpu.FitIndex.from_texts(gpu, texts)
+    try:
+        got = ix.search(_queries(pats))
+        for g, w in zip(got, want):
+            assert g.shape == (65537, 2) and np.array_equal(g, np.asarray(w).reshape(20, 2)[which])
+        ms = ix.last_ms()
+        assert ms > 0 and np.isfinite(ms)
+    finally:
+        ix.close()
+
+
+def test_hits_beyond_one_launch_of_queries(gpu):
+    """The same queries through hits(max_dist=0): the sorted list equals the definition's (test_gpu_fit_hits: _rows and
+    _want, one row set per distinct pattern), found is its length, and the hits kernels' time is that of a run."""
+    from test_gpu_fit_hits import _plan, _rows, _same, _want  # (that module imports this one)
+    plan = _plan("user_costs.json", "ACGU")
+    base, pats, texts = _two_launches()
+    rows = _rows(plan, base, texts)
+    want = _want([rows[q % 20] for q in range(len(pats))], 0)
+    gpu.set_costs(plan)
+    ix = sedgpu.FitIndex.from_texts(gpu, texts)
+    try:
+        got = ix.hits(_queries(pats), 0)
+        _same(got, want)
+        assert ix.found == len(want) > 65537 and ix.hits_last_ms() > 0
+    finally:
+        ix.close()
+
+
 def test_two_indexes_on_one_context(gpu):
     """Two indexes searched alternately, with a Context.fit and a sed_run_batch between: each keeps its own buffers."""
     plan = _golden_plan("user_costs.json", "ACGU")
