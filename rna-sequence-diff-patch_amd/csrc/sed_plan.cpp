@@ -620,7 +620,9 @@ int plan_mode(Planning &P) {
         if (!P.i32_fits(R)) {  // (the keys' range at the R the batch runs)
             if (o.mode == 1) return sed_plan_fail(P.err, SED_E_RANGE, "integer key would overflow (D < 2^16, L < 2^14)");
             mode = sed_simple_typing(c) ? SED_MODE_F64 : SED_MODE_F64_TYPED;
-            R = o.R ? o.R : P.auto_R_f64(mode);
+            // (a forced R the fp64 kernels do not have, 16 or 32, asked for the integer kernel this batch cannot run:
+            // the fallback picks its own, as it does unforced, instead of failing the batch)
+            R = (o.R == 2 || o.R == 4 || o.R == 8) ? o.R : P.auto_R_f64(mode);
         }
     } else if (c.K > SED_MAX_K) {
         return sed_plan_fail(P.err, SED_E_ALPHABET, "alphabet of %d symbols exceeds %d", c.K, SED_MAX_K);
@@ -850,6 +852,7 @@ void plan_lane_routes(Planning &P, bool x2_ok) {
             if ((b.umask >> cc) & 1u) b.sp.umap |= (uint32_t)__builtin_popcount(b.umask & ((1u << cc) - 1u)) << (2 * cc);
     }
     // 16-bit offset keys: n*delete + 32*insert (the lane kernel's whole block) within 0xFFFF
+    // (never false in an integer batch: i32_fits already holds n*delete + 32*insert < 65533, its cols >= m + 68 > 32)
     bool lane_fit16 = true;
     for (int32_t x : b.lane)
         if ((double)len_a[x] * c.del + SED_LANE_MAXM * c.ins > 65535.0) lane_fit16 = false;

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, padding_errors
+import key_cases
 import oracle
 import sedcost
 import sedgpu
@@ -130,6 +131,81 @@ def test_route_fuzz_vs_oracle(gpu):
         seed += 1
         runs += 1
     print("route fuzz: %d batches" % runs)
+
+
+# ---- drawn tables: the existing fuzzer's pool (1/1/1, 2/3, the GUI tables) keeps every key far from its range ----
+def _log_uniform(rng, hi):
+    return int(min(hi, max(1, 2.0 ** rng.uniform(0.0, np.log2(hi + 1)))))
+
+
+def _drawn_table(rng):
+    """An i32_eligible table over ACGU (insert and delete log-uniform in 1..254 with sum <= 255, mismatches uniform in
+    1 .. insert + delete), or one time in four a dyadic one over K = 5..8 symbols at a scale of 1, 2, 4 or 8 (fp64 mode:
+    its distance-only lane pairs run the scaled lane kernel where scaled_costs accepts it).  Returns (alphabet, table,
+    (insert, delete) of an integer table or None)."""
+    ins, dele = 255, 255
+    while ins + dele > 255:
+        ins, dele = _log_uniform(rng, 254), _log_uniform(rng, 254)
+    scaled = rng.random() < 0.25
+    K, scale = (int(rng.integers(5, 9)), float(2 ** int(rng.integers(0, 4)))) if scaled else (4, 1.0)
+    alphabet = list("ACGUYRWS"[:K])
+    sub = rng.integers(1, ins + dele + 1, size=(K, K))
+    table = {"insert": ins / scale, "delete": dele / scale,
+             "update": {a: {b: float(sub[i][j]) / scale for j, b in enumerate(alphabet) if b != a}
+                        for i, a in enumerate(alphabet)}}
+    return alphabet, table, None if scaled else (ins, dele)
+
+
+def _border_batch(rng, alphabet, indel, R):
+    """_batch's sizes with about half the pairs within 2 % of the last str2 length whose integer keys fit
+    (key_cases.border) at the batch's R; three batches in four stay at or below it, so that they run the integer
+    kernels, the others cross it and run fp64."""
+    npairs = int(rng.choice(SIZES))
+    below = rng.random() < 0.75
+    ns = [int(rng.integers(1, (40 if r < 0.4 else (600 if r < 0.93 else 1500)) + 1)) for r in rng.random(npairs)]
+    R = R or key_cases.auto_R(max(ns))
+    pairs, cells = [], 0.0
+    for n in ns:
+        near = rng.random() < 0.5
+        while near and n > 1 and key_cases.border(indel, n, R) is None:
+            n //= 2
+        edge = key_cases.border(indel, n, R) if near else None
+        if edge is not None:
+            slack = int(rng.integers(0, edge[0] // 50 + 1))
+            m = max(1, edge[0] - slack) if below or rng.random() < 0.5 else edge[1] + slack
+        else:
+            m = int(rng.integers(0, 41))
+        if cells + n * m > CELL_CAP:
+            n, m = min(n, 40), min(m, 40)
+        cells += n * m
+        a = rng.choice(alphabet, size=n)
+        b = np.where(rng.random(m) < 0.15, rng.choice(alphabet, size=m), np.resize(a, m)) if rng.random() < 0.5 else \
+            rng.choice(alphabet, size=m)
+        pairs.append(("".join(a), "".join(b)))
+    return pairs
+
+
+def test_route_fuzz_drawn_tables(gpu):
+    """The route fuzz over drawn tables and lengths next to the integer keys' range (tests/key_cases.py), with
+    _check, the flag sets and OPTIONS of the fuzzer above.  SED_FUZZ_DRAWN_SECONDS sets the budget (default 8 s, at
+    least 6 batches); seeds count up from SED_FUZZ_SEED + 500000 and a failure names its seed."""
+    budget = float(os.environ.get("SED_FUZZ_DRAWN_SECONDS", "8"))
+    seed = int(os.environ.get("SED_FUZZ_SEED", "2026")) + 500000
+    t_end = time.monotonic() + budget
+    runs = integer = 0
+    while time.monotonic() < t_end or runs < 6:
+        rng = np.random.default_rng(seed)
+        alphabet, table, indel = _drawn_table(rng)
+        mode = int(rng.integers(0, 3))
+        script, no_len = (True, False) if mode == 0 else ((False, False) if mode == 1 else (False, True))
+        opt = OPTIONS[int(rng.integers(0, len(OPTIONS)))]
+        forced = dict(opt if isinstance(opt[0], tuple) else [opt]).get(sedgpu.SED_OPT_ROWS_PER_LANE, 0)
+        pairs = _batch(rng, alphabet) if indel is None else _border_batch(rng, alphabet, indel, forced)
+        _check(gpu, table, pairs, script, no_len, opt, seed)
+        integer += indel is not None
+        seed += 1
+        runs += 1
+    print("drawn-table fuzz: %d batches, %d under integer tables" % (runs, integer))
 
 
 def test_module_fuzz_vs_pyref():
