@@ -117,6 +117,10 @@ enum {
                                    (tests and A/Bs; a value >= every text's length + 1 is one lane per text).  An
                                    option of sed_fit_search / sed_fit_plan only: sed_plan_routes, which plans batches,
                                    refuses it */
+#define SED_OPT_FIT_ROWS 19     /* the long fit calls (sed_fit_index_search_long, sed_fit_index_hits_long and their plan
+                                   calls) only: pattern rows per lane, 0 auto (each query the smallest R of 2, 4, 8, 16,
+                                   32 with 64 R >= P), else that R for every query (tests and A/Bs; a query of P > 64 R:
+                                   SED_E_RANGE).  sed_plan_routes refuses it */
 #define SED_OPT_DEBUG_CORRUPT 9 /* testing only: p + 1 overwrites one checkpoint word of pair p before its traceback,
                                    which must then fail with SED_E_DEVICE naming the pair; 0 off */
 
@@ -434,6 +438,40 @@ int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms);
 int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
                           double del, int del_is_int, const int32_t *options, int noptions,
                           const int32_t *len_p, const int32_t *len_t, int32_t npairs, double max_dist, int64_t *out);
+
+/* Long patterns: sed_fit_index_search and sed_fit_index_hits for 1 <= P <= 2048 (pre-miRNA hairpins, tRNAs, riboswitches,
+ * short transcripts).  The definition, arguments, results, errors, cap protocol and the index are those of the two calls
+ * above; the hits of a query of P <= 32 equal theirs bit for bit.  What differs is the kernel: one wave runs one (query,
+ * chunk of a text), the pattern's rows spread over its 64 lanes, R = 2, 4, 8, 16 or 32 rows a lane (the smallest with
+ * 64 R >= P; SED_OPT_FIT_ROWS forces one R for every query of a call), and the queries of a call run grouped by R, one
+ * launch per group and 65535 queries.  The cost models served (anything else: SED_E_RANGE, the text says which condition
+ * failed; there is no fallback):
+ *   at most 8 symbols; some S = 2^k, k <= 8, makes every cost an integer in 0..255 with (insert + delete) * S <= 255;
+ *   P * delete * S + 128 * insert * S <= 65535 over the call's longest pattern (distance and the 128 columns of insert a
+ *   key carries between rebases share one 16-bit field);
+ *   a wave's text columns fit 16 bits: a text runs in chunks of at most 65535 - W - 3 columns, W = P + floor(P * delete /
+ *   insert) over the call's longest pattern (so chunk + W + 3 <= 65535; the 3 is the alignment of a wave's first column
+ *   to a 4-symbol word); with insert = 0 a text runs as one chunk, n <= 65534.
+ * The automatic chunk length follows sed_fit_search's rule with waves in place of lanes.  SED_OPT_FIT_CHUNK forces it.
+ * sed_fit_search, sed_fit_index_search and sed_fit_index_hits keep refusing P > 32.
+ * sed_fit_index_last_time / sed_fit_index_hits_last_time report the last search / hits search of either kind. */
+int sed_fit_index_search_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                              int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end);
+int sed_fit_index_hits_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                            int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found);
+/* What the long calls would decide, without a device: out[] as sed_fit_index_plan lays it out (3 lanes = the waves, one
+ * per (query, chunk record); 4 cells = P x the columns a wave's chunk spans, the 63 steps of its skew not counted), and
+ * out_rows[q] (may be NULL) = the rows per lane query q runs with. */
+int sed_fit_index_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                            double del, int del_is_int, const int32_t *options, int noptions,
+                            const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts, double *out, int nout,
+                            int32_t *out_rows);
+/* The wave records of that plan, without a device: what sed_fit_index_lanes gives for the plan's chunk length (each
+ * wave derives its record as a lane of the short kernels does), in query order whatever the grouping. */
+int sed_fit_index_long_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                             double del, int del_is_int, const int32_t *options, int noptions,
+                             const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts,
+                             int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

@@ -756,6 +756,14 @@ class _EngineIndex:
         self.ctx.set_costs(plan)
         return self.ix.hits(packed, max_dist)
 
+    def search_long(self, plan, packed):
+        self.ctx.set_costs(plan)
+        return self.ix.search_long(packed)
+
+    def hits_long(self, plan, packed, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.hits_long(packed, max_dist)
+
     def close(self):
         self.ix.close()
 
@@ -805,7 +813,7 @@ class FitIndex:
                                   % len(alphabet))
         return sedcost.plan_over(table, alphabet, set(u1), set(self._used))
 
-    def search(self, patterns):
+    def search(self, patterns, _dev="search"):
         """[[(dist, start, end) for each text] for each pattern], every hit as fit_batch defines it."""
         patterns = list(patterns)
         plan = self.plan(patterns)
@@ -813,10 +821,19 @@ class FitIndex:
             return []
         ca, la = plan.encode_many(patterns)
         packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
-        dist, start, end = self._dev.search(plan, packed)
+        dist, start, end = getattr(self._dev, _dev)(plan, packed)
         return [list(zip(d, s, e)) for d, s, e in zip(dist.tolist(), start.tolist(), end.tolist())]
 
-    def hits(self, patterns, max_dist):
+    def search_long(self, patterns):
+        """search() for patterns of 1..2048 symbols (include/sed.h: sed_fit_index_search_long); the same alphabet growth
+        and errors."""
+        return self.search(patterns, "search_long")
+
+    def hits_long(self, patterns, max_dist):
+        """hits() for patterns of 1..2048 symbols (include/sed.h: sed_fit_index_hits_long)."""
+        return self.hits(patterns, max_dist, "hits_long")
+
+    def hits(self, patterns, max_dist, _dev="hits"):
         """[(pattern index, text index, start, end, dist)] sorted by (pattern, text, end): for every end column e of a
         text (0 <= e <= its length) the smallest wagnerFisher(pattern, text[s:e]) value over s, with the largest such s
         as start, kept when that value is <= max_dist (include/sed.h: sed_fit_index_hits; math.inf keeps every
@@ -827,7 +844,7 @@ class FitIndex:
             return []
         ca, la = plan.encode_many(patterns)
         packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
-        h = self._dev.hits(plan, packed, max_dist)
+        h = getattr(self._dev, _dev)(plan, packed, max_dist)
         return list(zip(h["query"].tolist(), h["text"].tolist(), h["start"].tolist(), h["end"].tolist(), h["dist"].tolist()))
 
     def close(self):
@@ -836,8 +853,8 @@ class FitIndex:
 
 def fit_index(texts, userCosts=False, alphabet=None, engine=None):
     """A FitIndex over texts: fit_batch for callers who search one collection query after query.  engine(codes, off,
-    lens) -> an object with search(plan, packed), hits(plan, packed, max_dist) and close() replaces the device (CPU
-    tests)."""
+    lens) -> an object with search(plan, packed), hits(plan, packed, max_dist), their search_long / hits_long and close()
+    replaces the device (CPU tests)."""
     return FitIndex(texts, userCosts, alphabet, engine)
 
 

@@ -1,7 +1,7 @@
 // sed_fit_plan.cpp — the fit planner (sed_fit_plan.h): scale, update addends, window, chunk length, lanes and the
 // cutoff of a fit search, from the cost model, the options and the lengths.  No HIP call.  Also the device-free fit
 // entry points of include/sed.h (sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes,
-// sed_fit_cutoff_scaled).
+// sed_fit_index_long_plan, sed_fit_index_long_lanes, sed_fit_cutoff_scaled).
 #include "sed_fit_plan.h"
 
 #include <algorithm>
@@ -26,12 +26,24 @@ struct FitSums {
     int64_t nmax = -1;
 };
 
-// The one rule both callers share: scale, update addends and W from the costs and the longest pattern, then the chunk
+// How a kernel family lays a pair out, as far as the rule cares: the short kernels run one pair's chunk in a lane, 64 to
+// a wave, and their P <= 32 keeps the D field's rebase room out of the envelope; the long kernels (sed_fit_long.hip)
+// run it in a whole wave, and P delete S shares the 16-bit D field with the FIT_REBASE insert S a key carries at most
+// between rebases.
+struct FitLayout {
+    int pmax;            // patterns of 1..pmax symbols
+    int units_per_wave;  // (pair, chunk) units a wave runs
+    int rebase_cols;     // columns of insert the D-field condition adds to P delete; 0: none
+};
+static const FitLayout FIT_SHORT = {SED_LANE_MAXM, 64, 0};
+static const FitLayout FIT_LONG = {SED_FIT_LONG_MAXP, 1, 128};  // (128 = sed_fit_dp.h: FIT_REBASE)
+
+// The one rule every caller shares: scale, update addends and W from the costs and the longest pattern, then the chunk
 // length and the span check.  *chunk_out = the chunk every text is cut by (0: one lane per text); plan->chunk = the
 // chunk the plan reports, which cuts them the same way (it is 0 only where no text has more columns than the chunk).
 // *span_fail_cols > 0 (a span refusal) = the columns n + 1 from which a text fails, for the caller to name one.
-static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &sm, sed_fit_plan_t *plan, std::string *err,
-                         int64_t *chunk_out, int64_t *span_fail_cols) {
+static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &sm, const FitLayout &lay, sed_fit_plan_t *plan,
+                         std::string *err, int64_t *chunk_out, int64_t *span_fail_cols) {
     const int pmax = sm.pmax;
     // the smallest S = 2^k, k <= 8, that makes every cost an integer in 0..255
     int k = 0;
@@ -50,6 +62,9 @@ static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &s
     const double insS = c.ins * S, delS = c.del * S;
     if ((double)pmax * delS > 65535.0)
         return sed_plan_fail(err, SED_E_RANGE, "fit search: P * delete * S = %d * %g exceeds 65535", pmax, delS);
+    if (lay.rebase_cols && (double)pmax * delS + (double)lay.rebase_cols * insS > 65535.0)
+        return sed_plan_fail(err, SED_E_RANGE, "fit search: P * delete * S + %d * insert * S = %d * %g + %d * %g exceeds 65535",
+                             lay.rebase_cols, pmax, delS, lay.rebase_cols, insS);
     if (delS > 255.0) return sed_plan_fail(err, SED_E_RANGE, "fit search: delete * S = %g exceeds 255", delS);
     if (insS + delS > 255.0)
         return sed_plan_fail(err, SED_E_RANGE, "fit search: (insert + delete) * S = %g exceeds 255 (the update addend's byte)",
@@ -69,8 +84,8 @@ static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &s
     int64_t chunk = 0;
     if (ins && o.fit_chunk > 0)
         chunk = o.fit_chunk;
-    else if (ins && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * 64) {
-        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * 64));
+    else if (ins && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * lay.units_per_wave) {
+        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * lay.units_per_wave));
         chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
     }
     // texts too long for one lane's start field are always split
@@ -120,7 +135,7 @@ int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len
         sm.nmax = std::max<int64_t>(sm.nmax, len_t[p]);
     }
     int64_t chunk = 0, span_cols = 0;
-    const int rc = fit_plan_rule(c, o, sm, plan, err, &chunk, &span_cols);
+    const int rc = fit_plan_rule(c, o, sm, FIT_SHORT, plan, err, &chunk, &span_cols);
     if (rc != SED_OK) return rc;
     plan->first.assign((size_t)npairs + 1, 0);
     plan->cells = plan->nominal = 0;
@@ -136,8 +151,9 @@ int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len
     return SED_OK;
 }
 
-int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
-                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
+// The plan of an index search under either layout; rows (the long layout's, may be null) = each query's R.
+static int fit_plan_index_of(const sed_costs &c, const sed_opts &o, const FitLayout &lay, const int32_t *len_p, int32_t nqueries,
+                             const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err) {
     if (nqueries < 0 || (nqueries > 0 && !len_p) || tx.ntexts < 0) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
     if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
     FitSums sm;
@@ -147,9 +163,12 @@ int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len
     for (int q = 0; q < nqueries && tx.ntexts > 0; ++q) {
         if (tx.first_negative >= 0 && (q == 0 ? tx.first_negative == 0 : q == 1))
             return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
-        if (len_p[q] < 1 || len_p[q] > SED_LANE_MAXM)
+        if (len_p[q] < 1 || len_p[q] > lay.pmax)
             return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q],
-                                 SED_LANE_MAXM);
+                                 lay.pmax);
+        if (lay.units_per_wave == 1 && o.fit_rows && len_p[q] > 64 * o.fit_rows)  // (the wave layout reads the option)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d exceeds the 64 * %d rows of SED_OPT_FIT_ROWS",
+                                 q, len_p[q], o.fit_rows);
         sm.pmax = std::max(sm.pmax, len_p[q]);
         psum += (double)len_p[q];
     }
@@ -161,14 +180,28 @@ int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len
         sm.nmax = tx.nmax;
     }
     int64_t chunk = 0, span_cols = 0;
-    const int rc = fit_plan_rule(c, o, sm, plan, err, &chunk, &span_cols);
+    const int rc = fit_plan_rule(c, o, sm, lay, plan, err, &chunk, &span_cols);
     if (rc != SED_OK) return rc;
     if (span_cols) return fit_span_fail(err, "a text of length", tx.nmax, plan->fp.ins != 0);
     plan->first.clear();
     plan->lanes = 0;
     plan->cells = 0;
     plan->nominal = psum * (tx.cols - (double)tx.ntexts);
+    if (rows) {
+        rows->resize((size_t)nqueries);
+        for (int q = 0; q < nqueries; ++q) (*rows)[q] = o.fit_rows ? o.fit_rows : sed_fit_long_rows(len_p[q]);
+    }
     return SED_OK;
+}
+
+int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
+    return fit_plan_index_of(c, o, FIT_SHORT, len_p, nqueries, tx, plan, nullptr, err);
+}
+
+int sed_fit_plan_index_long(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                            const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err) {
+    return fit_plan_index_of(c, o, FIT_LONG, len_p, nqueries, tx, plan, rows, err);
 }
 
 int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
@@ -301,7 +334,8 @@ int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, 
 // chunk table and the sums the plan reports
 static int fit_index_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                              int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                             const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks) {
+                             const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks,
+                             std::vector<int32_t> *long_rows = nullptr) {
     if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
     sed_costs c;
     sed_opts o;
@@ -314,7 +348,8 @@ static int fit_index_plan_of(int K, const double *sub, const uint8_t *sub_int, d
         tx.cols += (double)len_t[d] + 1;
         tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
     }
-    const int rc = sed_fit_plan_index(c, o, len_p, nqueries, tx, p, nullptr);
+    const int rc = long_rows ? sed_fit_plan_index_long(c, o, len_p, nqueries, tx, p, long_rows, nullptr)
+                             : sed_fit_plan_index(c, o, len_p, nqueries, tx, p, nullptr);
     if (rc != SED_OK) return rc;
     double computed = 0, psum = 0;
     const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
@@ -334,14 +369,16 @@ int sed_fit_index_plan(int K, const double *sub, const uint8_t *sub_int, double 
                         p, out, nout);
 }
 
-int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                        int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                        const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+// sed_fit_index_lanes' and sed_fit_index_long_lanes' common half (long_rows: the long layout's plan)
+static int fit_index_lanes_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                              int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                              const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params,
+                              std::vector<int32_t> *long_rows) {
     if (max_lanes < 0 || (max_lanes && !out_lanes) || !out_params) return SED_E_ARG;
     sed_fit_plan_t p;
     std::vector<sed_fit_chunk> chunks;
     const int rc = fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
-                                     len_t, ntexts, &p, &chunks);
+                                     len_t, ntexts, &p, &chunks, long_rows);
     if (rc != SED_OK) return rc;
     if (p.lanes > max_lanes) return SED_E_ARG;
     sed_fit_lane *out = (sed_fit_lane *)out_lanes;
@@ -353,6 +390,35 @@ int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double
         }
     fit_params_out(p.fp, out_params);
     return SED_OK;
+}
+
+int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                        int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                        const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    return fit_index_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
+                              ntexts, out_lanes, max_lanes, out_params, nullptr);
+}
+
+int sed_fit_index_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                            int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                            const int32_t *len_t, int32_t ntexts, double *out, int nout, int32_t *out_rows) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    std::vector<int32_t> rows;
+    const int rc = fit_plan_out(fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p,
+                                                  nqueries, len_t, ntexts, &p, nullptr, &rows),
+                                p, out, nout);
+    if (rc == SED_OK && out_rows && !rows.empty()) std::memcpy(out_rows, rows.data(), rows.size() * sizeof(int32_t));
+    return rc;
+}
+
+int sed_fit_index_long_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                             const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes,
+                             uint32_t *out_params) {
+    std::vector<int32_t> rows;
+    return fit_index_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
+                              ntexts, out_lanes, max_lanes, out_params, &rows);
 }
 
 }  // extern "C"

@@ -31,6 +31,13 @@ struct sed_fit_index_sums {
 };
 int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
                        const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err);
+// The plan of the long calls (include/sed.h: sed_fit_index_search_long; kernels: sed_fit_long.hip), through the same
+// rule: patterns of 1..SED_FIT_LONG_MAXP symbols, one wave per (query, chunk record), so the chunk rule counts waves
+// where the short plan counts lanes, and the D-field condition is P delete S + 128 insert S <= 65535.  rows[q] = the
+// pattern rows per lane query q runs with: o.fit_rows when set (a query it cannot hold: SED_E_RANGE), else
+// sed_fit_long_rows(P).  The chunk table, W, the parameter words and the lane records are the short plan's.
+int sed_fit_plan_index_long(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                            const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err);
 // The chunk table of the texts under plan.chunk, text by text in chunk order (chunks may be null), independent of the
 // queries; returns the number of records.  *computed (if not null) += the columns the records' lanes run under plan.W,
 // warm-up included.

@@ -52,12 +52,12 @@ static int fit_enter(sed_ctx *c, bool args_ok) {
     return SED_OK;
 }
 
-// A pattern record as the kernels read it (sed_fit_dp.h): SED_LANE_MAXM byte codes, the pattern right-aligned, code 8
-// in front.  Returns the first code outside the alphabet, or -1.
-static int fit_pack_pattern(uint8_t *rec, const uint8_t *codes, int P, int K) {
-    memset(rec, 8, (size_t)(SED_LANE_MAXM - P));
+// A pattern record as the kernels read it (sed_fit_dp.h): `rows` byte codes (SED_LANE_MAXM; the long kernels' 64 R,
+// sed_fit_long.hip), the pattern right-aligned, code 8 in front.  Returns the first code outside the alphabet, or -1.
+static int fit_pack_pattern(uint8_t *rec, const uint8_t *codes, int P, int K, int rows = SED_LANE_MAXM) {
+    memset(rec, 8, (size_t)(rows - P));
     for (int i = 0; i < P; ++i)
-        if ((rec[SED_LANE_MAXM - P + i] = codes[i]) >= K) return codes[i];
+        if ((rec[rows - P + i] = codes[i]) >= K) return codes[i];
     return -1;
 }
 
@@ -193,11 +193,24 @@ struct sed_fit_index {
     }
 };
 
+// The queries of a long call in launch order: grouped by their rows per lane R, ascending, each group in query order.
+// Group g = places first .. first + count) of qlist, its records 64 R bytes each from byte `at` of the pattern area.
+struct FitLongGroups {
+    struct Group {
+        int rows, first, count;
+        size_t at;
+    };
+    std::vector<Group> groups;
+    const int32_t *d_qlist = nullptr;  // the device copy of qlist (place -> query)
+};
+
 // What a search and a hits search share once their plan stands (nqueries, ntexts > 0): the chunk table of the plan's
 // chunk length, the pinned buffer [front bytes of the caller's | pattern records | pattern lengths], the queries packed
-// into it and sent to the device, and the kernel's arguments but for its output.
+// into it and sent to the device, and the kernel's arguments but for its output.  A long call (rows = each query's R,
+// lg = its groups, out) lays the pattern records out group by group, 64 R bytes a query, and appends qlist.
 static int fit_index_stage(sed_fit_index *ix, const sed_fit_plan_t &plan, const uint8_t *codes_p, const int64_t *off_p,
-                           const int32_t *len_p, int32_t nqueries, size_t front, sed_fit_index_args *args) {
+                           const int32_t *len_p, int32_t nqueries, size_t front, sed_fit_index_args *args,
+                           const std::vector<int32_t> *rows = nullptr, FitLongGroups *lg = nullptr) {
     sed_ctx *c = ix->ctx;
     const int ntexts = ix->sums.ntexts;
     const int K = c->costs.K;
@@ -219,18 +232,39 @@ static int fit_index_stage(sed_fit_index *ix, const sed_fit_plan_t &plan, const 
     }
     if ((int64_t)nqueries * ix->nchunks > INT_MAX)
         return c->fail(SED_E_RANGE, "fit search: %lld lanes", (long long)nqueries * ix->nchunks);
-    const size_t o_pat = front, o_len = o_pat + (size_t)SED_LANE_MAXM * nqueries, qbytes = (SED_LANE_MAXM + 4) * (size_t)nqueries;
+    // where each query's record goes: by query, or (long) by group
+    std::vector<size_t> rec_at((size_t)nqueries);
+    std::vector<int32_t> place_q;
+    size_t patbytes = 0;
+    if (rows) {
+        lg->groups.clear();
+        for (int R = 2; R <= 32; R *= 2) {
+            FitLongGroups::Group g{R, (int)place_q.size(), 0, patbytes};
+            for (int q = 0; q < nqueries; ++q)
+                if ((*rows)[q] == R) {
+                    rec_at[q] = patbytes;
+                    patbytes += (size_t)64 * R;
+                    place_q.push_back(q);
+                }
+            if ((g.count = (int)place_q.size() - g.first) > 0) lg->groups.push_back(g);
+        }
+    } else {
+        for (int q = 0; q < nqueries; ++q) rec_at[q] = (size_t)SED_LANE_MAXM * q;
+        patbytes = (size_t)SED_LANE_MAXM * nqueries;
+    }
+    const size_t o_pat = front, o_len = o_pat + patbytes, qbytes = patbytes + (rows ? 8 : 4) * (size_t)nqueries;
     if (!ix->pin.reserve(o_pat + qbytes, 1u << 16))
         return c->fail(SED_E_OOM, "pinned allocation failed (fit index, %zu bytes)", std::max<size_t>(o_pat + qbytes, 1u << 16));
-    // the queries: their pattern records, then their lengths
+    // the queries: their pattern records, then their lengths (then, long, the groups' query list)
     uint8_t *pats = (uint8_t *)ix->pin.p + o_pat;
     int32_t *plens = (int32_t *)((uint8_t *)ix->pin.p + o_len);
     for (int q = 0; q < nqueries; ++q) {
         if (off_p[q] < 0) return c->fail(SED_E_ARG, "query %d: negative offset", q);
-        const int bad = fit_pack_pattern(pats + (size_t)SED_LANE_MAXM * q, codes_p + off_p[q], len_p[q], K);
+        const int bad = fit_pack_pattern(pats + rec_at[q], codes_p + off_p[q], len_p[q], K, rows ? 64 * (*rows)[q] : SED_LANE_MAXM);
         if (bad >= 0) return c->fail(SED_E_ARG, "query %d: pattern code %d outside the alphabet (K=%d)", q, bad, K);
         plens[q] = len_p[q];
     }
+    if (rows) memcpy(plens + nqueries, place_q.data(), sizeof(int32_t) * (size_t)nqueries);
     if (!ix->d_query.reserve(qbytes))
         return c->fail(SED_E_OOM, "device allocation failed (fit index, %d queries)", nqueries);
     sed_fit_index_args a{};
@@ -239,7 +273,8 @@ static int fit_index_stage(sed_fit_index *ix, const sed_fit_plan_t &plan, const 
     a.texts = (const sed_fit_text *)ix->d_trec.p;
     a.ntexts = ntexts;
     a.pats = ix->d_query.p;
-    a.plens = (const int32_t *)((const uint8_t *)ix->d_query.p + (size_t)SED_LANE_MAXM * nqueries);
+    a.plens = (const int32_t *)((const uint8_t *)ix->d_query.p + patbytes);
+    if (rows) lg->d_qlist = a.plens + nqueries;
     a.nqueries = nqueries;
     a.text = ix->d_text.p;
     a.out = nullptr;
@@ -317,8 +352,17 @@ void sed_fit_index_destroy(sed_fit_index *ix) {
 int32_t sed_fit_index_texts(const sed_fit_index *ix) { return ix ? ix->sums.ntexts : SED_E_ARG; }
 int64_t sed_fit_index_symbols(const sed_fit_index *ix) { return ix ? ix->symbols : SED_E_ARG; }
 
-int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
-                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+// One R group's share of a long call's arguments
+static sed_fit_index_args fit_long_group_args(const sed_fit_index_args &a, const FitLongGroups::Group &g) {
+    sed_fit_index_args ga = a;
+    ga.pats = (const uint8_t *)a.pats + g.at;
+    ga.nqueries = g.count;
+    return ga;
+}
+
+// sed_fit_index_search and sed_fit_index_search_long: the plan and the launches differ, nothing else
+static int fit_index_search_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                               int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
     const int ntexts = ix->sums.ntexts;
@@ -326,19 +370,29 @@ int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_
                                             (ntexts == 0 || (out_dist && out_start && out_end))));
     if (rc != SED_OK) return rc;
     sed_fit_plan_t plan;
-    rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    std::vector<int32_t> rows;
+    FitLongGroups lg;
+    rc = lng ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &rows, &c->err)
+             : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
     if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
     const size_t nres = (size_t)nqueries * (size_t)ntexts;
     sed_fit_index_args a{};
-    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8 * nres, &a)) != SED_OK) return rc;
+    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8 * nres, &a, lng ? &rows : nullptr, &lg)) != SED_OK)
+        return rc;
     if (!ix->d_out.reserve(8 * nres)) return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     a.out = (unsigned long long *)ix->d_out.p;
     if ((e = hipMemsetAsync(ix->d_out.p, 0xFF, 8 * nres, c->stream)) != hipSuccess)
         return c->hipfail(e, "upload (fit index search)");
-    if ((e = sed_launch_fit_index(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, plan.fp)) != hipSuccess)
+    if (!lng && (e = sed_launch_fit_index(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index kernel launch");
+    for (size_t g = 0; lng && g < lg.groups.size(); ++g)  // the events bracket the groups' launches
+        if ((e = sed_launch_fit_index_long(c->stream, g == 0 ? ix->timer.ev[0] : nullptr,
+                                           g + 1 == lg.groups.size() ? ix->timer.ev[1] : nullptr,
+                                           fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
+                                           lg.groups[g].rows, plan.fp)) != hipSuccess)
+            return c->hipfail(e, "fit index long kernel launch");
     const uint64_t *keys = (const uint64_t *)ix->pin.p;
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_out.p, 8 * nres, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (fit index search)");
@@ -353,6 +407,15 @@ int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_
     return SED_OK;
 }
 
+int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                         int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+    return fit_index_search_of(ix, false, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
+}
+int sed_fit_index_search_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                              int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+    return fit_index_search_of(ix, true, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
+}
+
 int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
     return ix && kernel_ms ? ix->timer.elapsed(kernel_ms) : SED_E_ARG;
 }
@@ -360,31 +423,41 @@ int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
 // Every hit within max_dist (include/sed.h).  The search's plan, chunk table and queries (fit_index_stage); the kernel
 // appends its records in whatever order the waves' atomic adds land, and counts on past `cap`.  The host reads the
 // count, then the records when they all fit, sorts them by (pair, end) - unique keys - and decodes them.
-int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
-                       int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
+static int fit_index_hits_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                             int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
     const int ntexts = ix->sums.ntexts;
     int rc = fit_enter(c, (nqueries == 0 || (nqueries > 0 && codes_p && off_p && len_p)) && cap >= 0 && (cap == 0 || out) && found);
     if (rc != SED_OK) return rc;
     sed_fit_plan_t plan;
-    rc = sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    std::vector<int32_t> rows;
+    FitLongGroups lg;
+    rc = lng ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &rows, &c->err)
+             : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
     int32_t cut = 0;
     if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);
     if (rc != SED_OK) return rc;
     *found = 0;
     if (nqueries == 0 || ntexts == 0) return SED_OK;
     sed_fit_index_args a{};
-    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8, &a)) != SED_OK) return rc;
+    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8, &a, lng ? &rows : nullptr, &lg)) != SED_OK) return rc;
     if ((uint64_t)cap > SIZE_MAX / sizeof(sed_fit_hit_rec) || !ix->d_count.reserve(8) ||
         !ix->d_hits.reserve(std::max<size_t>((size_t)cap * sizeof(sed_fit_hit_rec), sizeof(sed_fit_hit_rec))))
         return c->fail(SED_E_OOM, "device allocation failed (fit index, room for %lld hits)", (long long)cap);
     hipError_t e = hipSuccess;
     if ((e = ix->hits_timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     if ((e = hipMemsetAsync(ix->d_count.p, 0, 8, c->stream)) != hipSuccess) return c->hipfail(e, "upload (fit index hits)");
-    if ((e = sed_launch_fit_index_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a, ix->d_hits.p,
-                                       (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
+    if (!lng && (e = sed_launch_fit_index_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a, ix->d_hits.p,
+                                               (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index hits kernel launch");
+    for (size_t g = 0; lng && g < lg.groups.size(); ++g)
+        if ((e = sed_launch_fit_index_long_hits(c->stream, g == 0 ? ix->hits_timer.ev[0] : nullptr,
+                                                g + 1 == lg.groups.size() ? ix->hits_timer.ev[1] : nullptr,
+                                                fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
+                                                lg.groups[g].rows, ix->d_hits.p, (unsigned long long *)ix->d_count.p,
+                                                (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
+            return c->hipfail(e, "fit index long hits kernel launch");
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (fit index hits)");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index hits kernel execution");
@@ -414,6 +487,15 @@ int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t 
         out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, (int32_t)(r.end - r.len), (int32_t)r.end, (double)r.D * inv};
     }
     return SED_OK;
+}
+
+int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                       int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
+    return fit_index_hits_of(ix, false, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
+}
+int sed_fit_index_hits_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                            int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
+    return fit_index_hits_of(ix, true, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
 }
 
 int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms) {

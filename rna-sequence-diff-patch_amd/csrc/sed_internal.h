@@ -274,6 +274,23 @@ hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t e
 hipError_t sed_launch_fit_index_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                      void *hits, unsigned long long *count, unsigned long long cap, int32_t cut,
                                      const sed_fit_params &fp);
+// Long patterns (sed_fit_long.hip; include/sed.h: sed_fit_index_search_long): one wave per (query, chunk record), the
+// pattern's rows over the wave's 64 lanes, `rows` = R in {2, 4, 8, 16, 32} consecutive rows a lane, P <= 64 R.  One
+// launch serves the a.nqueries queries of one R: a.pats = their records of 64 R bytes (the pattern right-aligned, code
+// 8 in front), qlist[k] = the query whose record is the k-th, a.plens by query.  The wave derives the chunk's
+// sed_fit_lane as the short kernels do and reports in their words, into out[query * ntexts + text] or the hit list.
+// ev0 / ev1 may be null (a search of several R starts the first group's and stops the last's).
+#define SED_FIT_LONG_MAXP 2048
+__host__ __device__ inline int sed_fit_long_rows(int P) {  // the smallest R with 64 R >= P
+    int R = 2;
+    while (64 * R < P) R *= 2;
+    return R;
+}
+hipError_t sed_launch_fit_index_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                     const int32_t *qlist, int rows, const sed_fit_params &fp);
+hipError_t sed_launch_fit_index_long_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                          const int32_t *qlist, int rows, void *hits, unsigned long long *count,
+                                          unsigned long long cap, int32_t cut, const sed_fit_params &fp);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

@@ -1193,6 +1193,7 @@ const OptSpec opt_table[] = {
     {SED_OPT_CUT, &sed_opts::cut, 0, 2},
     {SED_OPT_BAND, &sed_opts::band, V(0, 2, 3), 0},
     {SED_OPT_FIT_CHUNK, &sed_opts::fit_chunk, 0, INT_MAX},
+    {SED_OPT_FIT_ROWS, &sed_opts::fit_rows, V(0, 2, 4) | V(8, 16, 32), 0},
     {SED_OPT_DEBUG_CORRUPT, &sed_opts::debug_corrupt, 0, INT_MAX},
     {SED_OPT_CHAIN, &sed_opts::chain, 0, 1024},
     {SED_OPT_ROWS_PER_LANE, &sed_opts::R, V(0, 1, 2) | V(4, 8, 16) | V(32), 0},
@@ -1304,8 +1305,10 @@ int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins
     c.ins_int = ins_is_int ? 1 : 0;
     c.del_int = del_is_int ? 1 : 0;
     sed_opts o;
-    for (int i = 0; i < noptions; ++i)  // (SED_OPT_FIT_CHUNK is no option of a batch: sed_fit_plan takes it)
-        if (options[2 * i] == SED_OPT_FIT_CHUNK || !sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    for (int i = 0; i < noptions; ++i)  // (the fit options are no options of a batch: the fit plan calls take them)
+        if (options[2 * i] == SED_OPT_FIT_CHUNK || options[2 * i] == SED_OPT_FIT_ROWS ||
+            !sed_opts_set(o, options[2 * i], options[2 * i + 1], true))
+            return SED_E_ARG;
     sed_plan p;
     const int rc = sed_plan_batch(c, o, codes_a, off_a, len_a, codes_b, off_b, len_b, npairs, flags, &p, nullptr);
     if (rc != SED_OK) return rc;

@@ -38,6 +38,7 @@ struct sed_opts {
                             // should pay), 1 whenever eligible, 2 never (filter only)
     int fit_chunk = 0;      // SED_OPT_FIT_CHUNK: fit search (sed_fit_plan.h), owned text columns per lane: 0 auto, else
                             // the chunk length
+    int fit_rows = 0;       // SED_OPT_FIT_ROWS: the long fit calls (sed_fit_plan.h), pattern rows per lane: 0 auto, else R
     int env_tbpar = -1;     // SED_TBPAR: 0/1 overrides the stripe-parallel traceback's rule (A/B), -1 unset
     int env_band = 1;       // SED_BAND: 0 turns band pruning off, 3 ("static") keeps the static windows (A/B through bench.py)
     int env_alt_dp = 1;     // SED_ALT_DP: 0 keeps every DP on the context's stream (A/B)

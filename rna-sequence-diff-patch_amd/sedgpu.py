@@ -57,6 +57,7 @@ SED_OPT_ZEROCOPY = 15
 SED_OPT_BAND = 16
 SED_OPT_CUT = 17
 SED_OPT_FIT_CHUNK = 18
+SED_OPT_FIT_ROWS = 19
 # sed_plan_routes only: the environment knobs the runtime reads once per process, as options of a plan
 SED_PLAN_ENV_TBPAR = 101
 SED_PLAN_ENV_BAND = 102
@@ -146,6 +147,13 @@ SIGNATURES = [
     ("sed_fit_index_hits_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("sed_fit_cutoff_scaled", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                         _i32p, _i32p, C.c_int32, C.c_double, C.POINTER(C.c_int64)]),
+    ("sed_fit_index_search_long", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
+    ("sed_fit_index_hits_long", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                          C.POINTER(C.c_int64)]),
+    ("sed_fit_index_long_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                          _i32p, C.c_int32, _i32p, C.c_int32, _f64p, C.c_int, _i32p]),
+    ("sed_fit_index_long_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                           _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64, _u32p]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -481,19 +489,38 @@ class FitIndex:
     def symbols(self):
         return int(self._lib.sed_fit_index_symbols(self.ptr))
 
-    def search(self, packed):
+    def search(self, packed, _call="sed_fit_index_search"):
         """packed: the queries as side a of a PackedPairs (codes_a, off_a, len_a, npairs; side b is not read).  Returns
         (dist f64, start i32, end i32), each shaped (queries, texts): the hits Context.fit gives for every (query,
         text), from one launch."""
         if not self.ptr:
-            raise SedError("sed_fit_index_search: the index is closed")
+            raise SedError("%s: the index is closed" % _call)
         Q, D = packed.npairs, self.ntexts
         dist = np.zeros(max(Q * D, 1), np.float64)
         start = np.zeros(max(Q * D, 1), np.int32)
         end = np.zeros(max(Q * D, 1), np.int32)
-        rc = self._lib.sed_fit_index_search(self.ptr, packed.codes_a, packed.off_a, packed.len_a, Q, dist, start, end)
-        self.ctx._check(rc, "sed_fit_index_search")
+        rc = getattr(self._lib, _call)(self.ptr, packed.codes_a, packed.off_a, packed.len_a, Q, dist, start, end)
+        self.ctx._check(rc, _call)
         return dist[:Q * D].reshape(Q, D), start[:Q * D].reshape(Q, D), end[:Q * D].reshape(Q, D)
+
+    def search_long(self, packed):
+        """search() for queries of 1..2048 symbols (sed_fit_index_search_long): one wave per (query, chunk of a text).
+        The same results, bit for bit, where search() serves the queries."""
+        return self.search(packed, "sed_fit_index_search_long")
+
+    def hits_long(self, packed, max_dist, cap=None):
+        """hits() for queries of 1..2048 symbols (sed_fit_index_hits_long)."""
+        return self.hits(packed, max_dist, cap, "sed_fit_index_hits_long")
+
+    @staticmethod
+    def long_plan(costs, options, len_p, len_t):
+        """What search_long / hits_long would decide, without a device: fit_index_long_plan."""
+        return fit_index_long_plan(costs, options, len_p, len_t)
+
+    @staticmethod
+    def long_lanes(costs, options, len_p, len_t):
+        """The wave records search_long / hits_long would run, without a device: fit_index_long_lanes."""
+        return fit_index_long_lanes(costs, options, len_p, len_t)
 
     def last_ms(self):
         """Device time of the last search's kernel (ms, HIP events)."""
@@ -501,26 +528,26 @@ class FitIndex:
         self.ctx._check(self._lib.sed_fit_index_last_time(self.ptr, C.byref(ms)), "sed_fit_index_last_time")
         return ms.value
 
-    def hits(self, packed, max_dist, cap=None):
+    def hits(self, packed, max_dist, cap=None, _call="sed_fit_index_hits"):
         """Every hit within max_dist (sed_fit_index_hits): packed as for search().  Returns a structured array over
         FIT_HIT_DTYPE (query, text, start, end, dist), one record per (query, text, end column) whose best distance is
         <= max_dist, sorted by (query, text, end).  cap = the records to make room for: more hits than that raise
         SedError (the index stays usable; FitIndex.found has the count).  cap=None asks for the count first when nothing
         is known and retries with room, so it always returns every hit."""
         if not self.ptr:
-            raise SedError("sed_fit_index_hits: the index is closed")
+            raise SedError("%s: the index is closed" % _call)
         Q = packed.npairs
         found = C.c_int64(0)
         room = self._hit_room if cap is None else int(cap)
         while True:
             out = np.zeros(max(room, 1), FIT_HIT_DTYPE)
-            rc = self._lib.sed_fit_index_hits(self.ptr, packed.codes_a, packed.off_a, packed.len_a, Q, float(max_dist),
-                                              out.ctypes.data if room > 0 else None, room, C.byref(found))
+            rc = getattr(self._lib, _call)(self.ptr, packed.codes_a, packed.off_a, packed.len_a, Q, float(max_dist),
+                                           out.ctypes.data if room > 0 else None, room, C.byref(found))
             self.found = int(found.value)
             if rc == SED_E_RANGE and cap is None and self.found > room:
                 room = self.found  # (a refusal of the plan leaves found at 0 <= room)
                 continue
-            self.ctx._check(rc, "sed_fit_index_hits")
+            self.ctx._check(rc, _call)
             if cap is None:
                 self._hit_room = max(self._hit_room, room)
             return out[:self.found]
@@ -1222,6 +1249,38 @@ def fit_index_lanes(costs, options, len_p, len_t):
     rc = load().sed_fit_index_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl, par)
     if rc != 0:
         err = SedError("sed_fit_index_lanes failed (%d)" % rc)
+        err.code = rc
+        raise err
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
+
+
+def fit_index_long_plan(costs, options, len_p, len_t):
+    """What FitIndex.search_long would decide, without a device (sed_fit_index_long_plan): fit_index_plan's fields
+    (lanes = the waves) and "rows": int32[queries], the pattern rows per lane each query runs with.  Errors as
+    fit_plan."""
+    out = np.zeros(len(FIT_PLAN_FIELDS), np.float64)
+    rows = np.zeros(max(len(len_p), 1), np.int32)
+    rc = load().sed_fit_index_long_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out), rows)
+    if rc != 0:
+        err = SedError("sed_fit_index_long_plan failed (%d)" % rc)
+        err.code = rc
+        raise err
+    plan = {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
+    plan["rows"] = rows[:len(len_p)]
+    return plan
+
+
+def fit_index_long_lanes(costs, options, len_p, len_t):
+    """The wave records FitIndex.search_long would run, without a device (sed_fit_index_long_lanes): (lanes, params) as
+    fit_index_lanes returns them, one record per (query, chunk record), query-major."""
+    nl = fit_index_long_plan(costs, options, len_p, len_t)["lanes"]
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    par = np.zeros(18, np.uint32)
+    rc = load().sed_fit_index_long_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl, par)
+    if rc != 0:
+        err = SedError("sed_fit_index_long_lanes failed (%d)" % rc)
         err.code = rc
         raise err
     lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}

@@ -133,20 +133,38 @@ class FitIndex:
 
     index_fn(sequences, user_cost) -> an object with search(patterns) -> [[(dist, start, end)] per sequence] per
     pattern, hits(patterns, max_dist) -> [(pattern index, sequence index, start, end, dist)] sorted, and close(),
-    replaces the engine (CPU tests).  Not cached."""
+    replaces the engine (CPU tests).  Not cached.
+
+    long_patterns=True (search, search_many, occurrences, occurrences_many) serves queries of up to 2048 symbols: those
+    of at most 32 go through the calls above, the longer ones through the index's search_long / hits_long, and the
+    results merge in query order.  The default refuses a query over 32 as before."""
+
+    SHORT = 32  # the longest query search() / hits() serve
 
     def __init__(self, seqs_or_collection, user_cost=False, index_fn=None):
         self.seqs = _sequences(seqs_or_collection)
         self.user_cost = user_cost
         self._ix = (index_fn or SED.fit_index)(self.seqs, user_cost) if self.seqs else None
 
-    def search_many(self, queries, max_dist=None, scripts=False):
+    def _split(self, queries, long_patterns):
+        """(indices the short calls serve, indices the long calls serve)"""
+        if not long_patterns:
+            return list(range(len(queries))), []
+        return ([i for i, q in enumerate(queries) if len(q) <= self.SHORT],
+                [i for i, q in enumerate(queries) if len(q) > self.SHORT])
+
+    def search_many(self, queries, max_dist=None, scripts=False, long_patterns=False):
         queries = list(queries)
         if not self.seqs:
             return [[] for _ in queries]
         if not queries:
             return []
-        rows = self._ix.search(queries)
+        short, lng = self._split(queries, long_patterns)
+        rows = [None] * len(queries)
+        for idx, call in ((short, self._ix.search), (lng, getattr(self._ix, "search_long", None))):
+            if idx:
+                for i, r in zip(idx, call([queries[i] for i in idx])):
+                    rows[i] = r
         kept = [[(s, d, a, b) for s, (d, a, b) in zip(self.seqs, hits) if max_dist is None or d <= max_dist]
                 for hits in rows]
         out = [[(s, 1 / (1 + d), a, b) for s, d, a, b in k] for k in kept]
@@ -156,10 +174,10 @@ class FitIndex:
             out = [[hit + (next(es)[1],) for hit in o] for o in out]
         return out
 
-    def search(self, query, max_dist=None, scripts=False):
-        return self.search_many([query], max_dist, scripts)[0]
+    def search(self, query, max_dist=None, scripts=False, long_patterns=False):
+        return self.search_many([query], max_dist, scripts, long_patterns)[0]
 
-    def occurrences_many(self, queries, max_dist, all_ends=False, scripts=False):
+    def occurrences_many(self, queries, max_dist, all_ends=False, scripts=False, long_patterns=False):
         """For each query, [(sequence, 1 / (1 + d), start, end)] for every occurrence within max_dist, in collection
         order, then by end: one engine launch for all the queries (StringEditDistance.FitIndex.hits).  A hit is an end
         column e of a document whose best distance E(e) = min over s of d(query, sequence[s:e]) is <= max_dist, with
@@ -172,7 +190,12 @@ class FitIndex:
             return [[] for _ in queries]
         if not queries:
             return []
-        hits = self._ix.hits(queries, max_dist)
+        short, lng = self._split(queries, long_patterns)
+        hits = []
+        for idx, call in ((short, self._ix.hits), (lng, getattr(self._ix, "hits_long", None))):
+            if idx:
+                hits += [(idx[q], t, a, b, d) for q, t, a, b, d in call([queries[i] for i in idx], max_dist)]
+        hits.sort(key=lambda h: (h[0], h[1], h[3]))  # (each call's list is sorted; the merge is by query)
         kept = hits if all_ends else local_minima(hits)
         out = [[] for _ in queries]
         for q, t, a, b, d in kept:
@@ -183,8 +206,8 @@ class FitIndex:
             out = [[hit + (next(es)[1],) for hit in o] for o in out]
         return out
 
-    def occurrences(self, query, max_dist, all_ends=False, scripts=False):
-        return self.occurrences_many([query], max_dist, all_ends, scripts)[0]
+    def occurrences(self, query, max_dist, all_ends=False, scripts=False, long_patterns=False):
+        return self.occurrences_many([query], max_dist, all_ends, scripts, long_patterns)[0]
 
     def close(self):
         if self._ix is not None:
@@ -208,11 +231,12 @@ def local_minima(hits):
     return out
 
 
-def fit_occurrences(query, seqs_or_collection, max_dist, user_cost=False, all_ends=False, scripts=False, index_fn=None):
+def fit_occurrences(query, seqs_or_collection, max_dist, user_cost=False, all_ends=False, scripts=False, index_fn=None,
+                    long_patterns=False):
     """FitIndex.occurrences in one shot: builds an index over the documents, searches it and closes it."""
     ix = FitIndex(seqs_or_collection, user_cost, index_fn=index_fn)
     try:
-        return ix.occurrences(query, max_dist, all_ends, scripts)
+        return ix.occurrences(query, max_dist, all_ends, scripts, long_patterns)
     finally:
         ix.close()
 
