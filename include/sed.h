@@ -221,6 +221,22 @@ int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins
                     const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
                     const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b,
                     int32_t npairs, uint32_t flags, double *out, int nout);
+/* The launches of one run of that batch, without a device: the planner's schedule, which sed_batch_run executes step by
+ * step.  cut_on / cut_win = the cutoff state sed_batch_set_cutoff left the batch in (a cutoff is set; its wave pairs run
+ * the windowed stripe kernel); a state no batch of this plan can be in is SED_E_ARG.  out receives up to max_steps rows
+ * of 6: launcher (0 windowed cutoff forward, 1 packed forward, 2 CHAIN, 3 integer stripe forward, 4 checkpoint codes,
+ * 5 fp64, 6 fp64 segments, 7 lane, 8 cutoff filter, 9 checkpoint traceback, 10 per-cell-code traceback,
+ * 11 stripe-parallel traceback, 12 segment traceback), phase (0 DP, 1 traceback), stream (0 the run's DP stream, 1 the
+ * traceback stream, 2 the part's stream), part, and whether the launch carries its part's start / end event of the
+ * phase.  info (or null) receives: whether untimed runs record events too, the event of a buffer slot's previous run
+ * the next one waits for (0 none, 1 DP end, 3 traceback end), the parts, and the most steps a schedule holds.
+ * Returns the number of steps or the SED_E_* code sed_plan_routes would return. */
+int sed_plan_schedule(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                      int del_is_int, const int32_t *options, int noptions,
+                      const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
+                      const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b,
+                      int32_t npairs, uint32_t flags, int cut_on, int cut_win, int32_t *out, int max_steps,
+                      int32_t *info);
 int sed_batch_dot_keys(const sed_batch *b);           /* bit 0: the checkpoint forward kernel runs dot keys, bit 1: the
                                                          CHAIN kernel runs ladder dot keys (SED_OPT_DOT), bit 2: over
                                                          the wide ladder (L unit 16) */

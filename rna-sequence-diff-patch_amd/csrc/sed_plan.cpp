@@ -681,7 +681,7 @@ void plan_traceback(Planning &P) {
     // CK traceback: distance-key forward kernel + checkpoints, traceback recomputes tiles (Planning::ck_route)
     b.ck = P.ck_route(mode, b.split, R);
     // SED_PIPELINE is a hint: checkpoint batches run their traceback after the DP on one stream (in parts on
-    // several, run_batch_parts).  Both kernels are issue-bound, so overlapping a run's traceback with the next run's
+    // several, sed_plan_run).  Both kernels are issue-bound, so overlapping a run's traceback with the next run's
     // forward only adds contention (config 4: 20.33 ms sequential against 20.5-20.8 ms pipelined in round 1,
     // profiles/r01_ck/ab_pipeline.jsonl; 11.13 against 9.78 ms for 2 pipelined parts in round 5,
     // profiles/r05/s14/ab.jsonl) and saves two checkpoint buffers.
@@ -1288,14 +1288,84 @@ void sed_pack_sequences(const sed_plan &plan, const uint8_t *codes_a, const int6
     }
 }
 
-extern "C" {
+bool sed_plan_cut_window_ok(const sed_plan &p) {
+    int nwork = 0;  // wave pairs with cells
+    for (const sed_pair_desc &d : p.pd) nwork += d.lane != 1 && d.n > 0 && d.m > 0;
+    return p.mode == SED_MODE_I32 && !p.split && (p.flags & SED_NO_LEN) && p.nseg == 0 &&
+           (p.R == 4 || p.R == 8 || p.R == 16) && p.cut_costs_ok && nwork > 0;
+}
 
-int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                    int del_is_int, const int32_t *options, int noptions, const uint8_t *codes_a, const int64_t *off_a,
-                    const int32_t *len_a, const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b,
-                    int32_t npairs, uint32_t flags, double *out, int nout) {
-    if (K < 1 || K > 255 || !sub || !sub_int || noptions < 0 || (noptions && !options) || nout < 0 || (nout && !out))
-        return SED_E_ARG;
+sed_run_plan sed_plan_run(const sed_plan &p, bool cut_on, bool cut_win) {
+    sed_run_plan s;
+    const bool want_tb = (p.flags & SED_WANT_SCRIPT) != 0;
+    s.tb = want_tb;
+    // rotating buffers are ordered through the events of their runs; two-slot lane batches order by stream instead
+    s.need_ev = p.nbuf > 1 && !(p.alt_dp && p.nbuf == 2 && !want_tb);
+    // a slot was last read by its previous run's traceback (distance only: written by its DP)
+    if (p.nbuf > 1 && (want_tb || (p.alt_dp && p.nbuf != 2))) s.reuse = want_tb ? SED_REUSE_TB_END : SED_REUSE_DP_END;
+    if (p.npairs == 0) return s;
+    auto add = [&s](uint8_t kind, uint8_t phase, uint8_t on, int part) {
+        if (s.n < SED_MAX_STEPS) s.step[s.n++] = sed_step{kind, phase, on, (uint8_t)part, false, false};
+    };
+    if (p.nparts > 1 && want_tb) {
+        // A checkpoint batch in parts: part i runs its forward and then its traceback on its own stream.  The whole
+        // batch's lane kernel follows part 0's forward inside part 0's DP window.
+        s.nparts = std::min(p.nparts, SED_MAX_PARTS);
+        for (int i = 0; i < s.nparts; ++i) add(SED_STEP_I32, SED_PHASE_DP, SED_ON_PART, i);
+        if (p.nlane > 0) add(SED_STEP_LANE, SED_PHASE_DP, SED_ON_PART, 0);
+        for (int i = 0; i < s.nparts; ++i) add(SED_STEP_TB_CK, SED_PHASE_TB, SED_ON_PART, i);
+    } else {
+        const int nw64 = p.nwave - p.nseg;  // wave pairs of the one-wave-per-pair kernels
+        const bool i32 = p.mode == SED_MODE_I32;
+        const bool tb_apart = p.nbuf > 1;  // the traceback has a stream of its own
+        // a cutoff: the filter as the DP phase's last kernel, and under cut_win the wave pairs on the windowed stripe
+        // kernel instead of their own routes
+        s.cut = cut_on && !want_tb;
+        if (s.cut && cut_win) {
+            add(SED_STEP_WIN, SED_PHASE_DP, SED_ON_DP, 0);
+        } else {
+            if (p.nwave_x2 > 0) add(SED_STEP_X2, SED_PHASE_DP, SED_ON_DP, 0);
+            if (nw64 > 0) add(i32 && p.nchains ? SED_STEP_CHAIN : i32 ? SED_STEP_I32 : SED_STEP_F64, SED_PHASE_DP, SED_ON_DP, 0);
+            // split_ck: the tile codes close the DP phase when the traceback shares its stream; pipelined runs open the
+            // traceback phase with them, so the next run's forward follows this one directly (config 2 ran
+            // 0.297-0.301 ms per step with it on the DP stream)
+            if (nw64 > 0 && i32 && !p.nchains && p.split_ck && !tb_apart) add(SED_STEP_CODES, SED_PHASE_DP, SED_ON_DP, 0);
+            if (p.nseg > 0) add(SED_STEP_F64_SEG, SED_PHASE_DP, SED_ON_DP, 0);
+        }
+        if (p.nlane > 0) add(SED_STEP_LANE, SED_PHASE_DP, SED_ON_DP, 0);
+        if (s.cut) add(SED_STEP_FILTER, SED_PHASE_DP, SED_ON_DP, 0);
+        if (want_tb && p.nwave > 0) {
+            if (p.split_ck && tb_apart) add(SED_STEP_CODES, SED_PHASE_TB, SED_ON_TB, 0);
+            if (p.tbpar) {  // (the map kernel zeroes the scripts the segments OR into)
+                add(SED_STEP_TB_STRIPES, SED_PHASE_TB, SED_ON_TB, 0);
+            } else {
+                if (nw64 > 0) add(p.ck ? SED_STEP_TB_CK : SED_STEP_TB_CODES, SED_PHASE_TB, SED_ON_TB, 0);
+                if (p.nseg > 0) add(SED_STEP_TB_SEG, SED_PHASE_TB, SED_ON_TB, 0);
+            }
+        }
+    }
+    // the events: the first and the last step of every (phase, part)
+    int first[2][SED_MAX_PARTS], last[2][SED_MAX_PARTS];
+    std::fill(&first[0][0], &first[0][0] + 2 * SED_MAX_PARTS, -1);
+    std::fill(&last[0][0], &last[0][0] + 2 * SED_MAX_PARTS, -1);
+    for (int i = 0; i < s.n; ++i) {
+        const sed_step &st = s.step[i];
+        if (first[st.phase][st.part] < 0) first[st.phase][st.part] = i;
+        last[st.phase][st.part] = i;
+    }
+    for (int ph = 0; ph < 2; ++ph)
+        for (int part = 0; part < SED_MAX_PARTS; ++part)
+            if (first[ph][part] >= 0) s.step[first[ph][part]].first = s.step[last[ph][part]].last = true;
+    return s;
+}
+
+namespace {
+// the costs, options and pairs of a device-free probe (sed_plan_routes, sed_plan_schedule) as a plan
+int probe_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+               const int32_t *options, int noptions, const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
+               const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b, int32_t npairs, uint32_t flags,
+               sed_opts *o, sed_plan *p) {
+    if (K < 1 || K > 255 || !sub || !sub_int || noptions < 0 || (noptions && !options)) return SED_E_ARG;
     sed_costs c;
     c.K = K;
     c.sub.assign(sub, sub + K * K);
@@ -1304,20 +1374,59 @@ int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins
     c.del = del;
     c.ins_int = ins_is_int ? 1 : 0;
     c.del_int = del_is_int ? 1 : 0;
-    sed_opts o;
     for (int i = 0; i < noptions; ++i)  // (the fit options are no options of a batch: the fit plan calls take them)
         if (options[2 * i] == SED_OPT_FIT_CHUNK || options[2 * i] == SED_OPT_FIT_ROWS ||
-            !sed_opts_set(o, options[2 * i], options[2 * i + 1], true))
+            !sed_opts_set(*o, options[2 * i], options[2 * i + 1], true))
             return SED_E_ARG;
+    return sed_plan_batch(c, *o, codes_a, off_a, len_a, codes_b, off_b, len_b, npairs, flags, p, nullptr);
+}
+}  // namespace
+
+extern "C" {
+
+int sed_plan_routes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                    int del_is_int, const int32_t *options, int noptions, const uint8_t *codes_a, const int64_t *off_a,
+                    const int32_t *len_a, const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b,
+                    int32_t npairs, uint32_t flags, double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_opts o;
     sed_plan p;
-    const int rc = sed_plan_batch(c, o, codes_a, off_a, len_a, codes_b, off_b, len_b, npairs, flags, &p, nullptr);
+    const int rc = probe_plan(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, codes_a, off_a, len_a,
+                              codes_b, off_b, len_b, npairs, flags, &o, &p);
     if (rc != SED_OK) return rc;
-    const double v[] = {(double)p.mode, (double)p.R, (double)p.nlane, (double)sed_plan_chains(p, false),
+    const double v[] ={(double)p.mode, (double)p.R, (double)p.nlane, (double)sed_plan_chains(p, false),
                         (double)sed_plan_traceback_mode(p), (double)sed_plan_dot_keys(p), (double)sed_plan_bitpar_pairs(p),
                         (double)p.nseg, (double)sed_plan_split_tasks(p), (double)sed_plan_scaled_pairs(p),
                         (double)sed_plan_packed_pairs(p, false), (double)p.nparts, p.band_cells, p.cells, p.algo_bytes};
     for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
     return SED_OK;
+}
+
+int sed_plan_schedule(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                      int del_is_int, const int32_t *options, int noptions, const uint8_t *codes_a, const int64_t *off_a,
+                      const int32_t *len_a, const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b,
+                      int32_t npairs, uint32_t flags, int cut_on, int cut_win, int32_t *out, int max_steps,
+                      int32_t *info) {
+    if (max_steps < 0 || (max_steps && !out)) return SED_E_ARG;
+    sed_opts o;
+    sed_plan p;
+    const int rc = probe_plan(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, codes_a, off_a, len_a,
+                              codes_b, off_b, len_b, npairs, flags, &o, &p);
+    if (rc != SED_OK) return rc;
+    // the cutoff states sed_batch_set_cutoff can leave a batch in
+    if ((cut_on && (flags & SED_WANT_SCRIPT)) || (cut_win && !(cut_on && o.cut != 2 && sed_plan_cut_window_ok(p))))
+        return SED_E_ARG;
+    const sed_run_plan s = sed_plan_run(p, cut_on != 0, cut_win != 0);
+    for (int i = 0; i < s.n && i < max_steps; ++i) {
+        const sed_step &st = s.step[i];
+        const int32_t row[6] = {st.kind, st.phase, st.on, st.part, st.first, st.last};
+        std::copy(row, row + 6, out + 6 * i);
+    }
+    if (info) {
+        const int32_t v[4] = {s.need_ev, s.reuse, s.nparts, SED_MAX_STEPS};
+        std::copy(v, v + 4, info);
+    }
+    return s.n;
 }
 
 int sed_dot_factor(const double *sub, double ins, double del, int maxmin, int ladder_maxsum, uint32_t *out) {

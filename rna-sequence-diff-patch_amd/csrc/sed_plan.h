@@ -1,7 +1,8 @@
 // sed_plan.h — the device-free half of a batch fill: everything the runtime decides about a batch (mode, rows per lane,
 // every route, the layout of every buffer, the kernels' parameters) as a function of the cost model, the options and
 // the pairs.  sed_plan.cpp calls no HIP API, so the planner runs, and is tested, without a device
-// (include/sed.h: sed_plan_routes; tests/test_plan_routes.py).  Fit search plans in a unit of its own, sed_fit_plan.h,
+// (include/sed.h: sed_plan_routes; tests/test_plan_routes.py), and so does the launch sequence of a run under a plan
+// (sed_plan_run below; sed_plan_schedule; tests/test_plan_schedule.py).  Fit search plans in a unit of its own, sed_fit_plan.h,
 // which takes sed_costs, sed_opts and sed_plan_fail from here.
 #pragma once
 #include "../../include/sed.h"
@@ -132,6 +133,60 @@ int sed_plan_batch(const sed_costs &c, const sed_opts &o, const uint8_t *codes_a
 void sed_pack_sequences(const sed_plan &plan, const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
                         const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b, std::vector<uint32_t> &ha,
                         std::vector<uint32_t> &hb);
+
+// ---- what a run launches ----
+// One step = one launcher call of the runtime's loop (sed_runtime.cpp: run_batch).  A launcher keeps its helper kernels
+// inside: the stripe forward its band kernel, the windowed forward its window kernel, the stripe-parallel walk its three.
+enum sed_step_kind : uint8_t {
+    SED_STEP_WIN,         // windowed cutoff forward (sed_launch_i32_cut)
+    SED_STEP_X2,          // packed forward, two pairs per wave
+    SED_STEP_CHAIN,
+    SED_STEP_I32,         // integer stripe forward (with checkpoints in a ck or split_ck batch)
+    SED_STEP_CODES,       // split_ck: every tile's codes from the forward's checkpoints
+    SED_STEP_F64,
+    SED_STEP_F64_SEG,
+    SED_STEP_LANE,        // the lane kernel the plan's lane route names (the runtime picks among the five launchers)
+    SED_STEP_FILTER,      // cutoff filter
+    SED_STEP_TB_CK,       // traceback from checkpoints
+    SED_STEP_TB_CODES,    // traceback over per-cell codes
+    SED_STEP_TB_STRIPES,  // stripe-parallel traceback
+    SED_STEP_TB_SEG,      // traceback of the fp64 segment pairs
+};
+enum : uint8_t { SED_PHASE_DP, SED_PHASE_TB };
+// the stream a step runs on: this run's DP stream (the context's, or the second DP stream on odd runs of an alt_dp
+// batch), the traceback stream (the DP stream's when buffers do not rotate), or the stream of the step's part
+enum : uint8_t { SED_ON_DP, SED_ON_TB, SED_ON_PART };
+// a rotating buffer's next user waits for this event of the slot's previous run (the value = its place in an event-log
+// entry {DP start, DP end, traceback start, traceback end})
+enum : uint8_t { SED_REUSE_NONE = 0, SED_REUSE_DP_END = 1, SED_REUSE_TB_END = 3 };
+#define SED_MAX_PARTS 4
+// (the longest schedules: four forwards, the lane kernel and four tracebacks of a batch in parts; packed, forward,
+// segments, lane, filter and three traceback steps of one in a single part)
+#define SED_MAX_STEPS 12
+
+struct sed_step {
+    uint8_t kind, phase, on;
+    // part's pairs are [npairs * part / nparts, npairs * (part + 1) / nparts); the lane step addresses the whole batch's
+    // lane pairs by index and belongs to part 0 for its stream and events only
+    uint8_t part;
+    // the timing events ride on the kernels' own dispatch packets: the first step of a (phase, part) carries that
+    // part's start event of the phase and the last one its end event
+    bool first, last;
+};
+// Fixed capacity, no heap: the per-call path refills a batch, and so rebuilds this, on every call.
+struct sed_run_plan {
+    int n = 0, nparts = 1;
+    bool tb = false;       // the run has a traceback phase (a phase without steps records its two events directly)
+    bool cut = false;      // the DP phase ends with the cutoff filter
+    bool need_ev = false;  // the run's events order the reuse of rotating buffers: recorded on untimed runs too
+    uint8_t reuse = SED_REUSE_NONE;
+    sed_step step[SED_MAX_STEPS] = {};
+};
+// The launches of one run of the planned batch, in order; cut_on / cut_win: the batch's cutoff state
+// (sed_batch_set_cutoff).  A batch without pairs launches nothing.
+sed_run_plan sed_plan_run(const sed_plan &p, bool cut_on, bool cut_win);
+// whether a cutoff may move the batch's wave pairs to the windowed stripe kernel (cut_win)
+bool sed_plan_cut_window_ok(const sed_plan &p);
 
 bool sed_simple_typing(const sed_costs &c);  // a cell's value is an int exactly when it equals 0
 sed_band_params sed_band_params_from(const sed_costs &c);

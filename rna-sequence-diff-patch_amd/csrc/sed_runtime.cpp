@@ -2,7 +2,9 @@
 // cost model, device-resident batches and the launch sequence
 //   DP kernel (integer or fp64)  ->  traceback kernel
 // on one HIP stream, timed with HIP events recorded on that stream.  What a batch runs (mode, routes, layout,
-// kernel parameters) is the planner's decision (sed_plan.cpp); a fill here is: wait, plan, reserve, upload, streams.
+// kernel parameters) and what a run launches (sed_plan_run: the launcher calls in order, their streams and who carries
+// which event) is the planner's decision (sed_plan.cpp); a fill here is: wait, plan, reserve, upload, streams, and a
+// run is one loop over the planned steps (run_batch).
 // Fit search's entry points are sed_fit_runtime.cpp; the context and the buffers both units use are sed_runtime.h.
 #include "../../include/sed.h"
 #include "sed_internal.h"
@@ -54,6 +56,7 @@ hipError_t pin_reserve(sed_ctx *c, size_t bytes) {
 struct sed_batch {
     sed_ctx *ctx = nullptr;
     sed_plan plan;                // what the last fill decided (sed_plan.h)
+    sed_run_plan sched;           // what a run launches under the plan and the cutoff state (set_cut_state)
     std::vector<uint32_t> ha, hb;  // the packed sequences on their way up (kept across refills)
     DevBuf d_pd, d_seqa, d_seqb, d_bnd, d_ops, d_tasks, d_lane, d_chain, d_x2, d_tbmap, d_seg;
     // small batches (plan.small) keep every input array and the results in one blob, d_small; the kernels' pointers
@@ -331,6 +334,14 @@ int make_streams(sed_batch *b) {
     return SED_OK;
 }
 
+// The cutoff state, and the launches of a run under it.  The schedule is rebuilt where its inputs change (a fill, a
+// cutoff) and nowhere else: a run only reads it.
+void set_cut_state(sed_batch *b, bool on, bool win) {
+    b->cut_on = on;
+    b->cut_win = win;
+    b->sched = sed_plan_run(b->plan, on, win);
+}
+
 int fill_batch(sed_batch *b, const uint8_t *codes_a, const int64_t *off_a, const int32_t *len_a,
                const uint8_t *codes_b, const int64_t *off_b, const int32_t *len_b, int32_t npairs,
                uint32_t flags) {
@@ -342,7 +353,8 @@ int fill_batch(sed_batch *b, const uint8_t *codes_a, const int64_t *off_a, const
     if (rc != SED_OK) return rc;
     b->ran = false;
     b->runs = 0;
-    b->cut_on = b->cut_win = b->cut_ready = b->cut_last = false;  // (a refill starts without a cutoff)
+    b->cut_ready = b->cut_last = false;
+    set_cut_state(b, false, false);  // (a refill starts without a cutoff)
     b->band_cells = b->plan.band_cells;
     b->chain_launches[0] = b->chain_launches[1] = b->chain_launches[2] = 0;
     if ((rc = reserve_batch(b)) != SED_OK) return rc;
@@ -370,265 +382,206 @@ bool debug_corrupt_on(const sed_batch *b) {
     return b->ctx->opt.debug_corrupt > 0 && b->ctx->opt.debug_corrupt <= b->plan.npairs;
 }
 
-// A checkpoint batch in parts on as many streams (b->plan.nparts).  Stream i runs forward(part i) then
-// traceback(part i).  The other streams start each run after stream 0's previous work, and nothing joins the
-// streams at a run's end, so the parts settle into a stagger: one part's traceback runs beside another part's
-// forward (config 4: 11.42-11.47 ms in one part, 10.85-11.0 in two, 10.77-10.83 in three, 11.6-11.8 in four;
-// with the select-free hold 9.86-9.93 in two against 10.30-10.54 in three, profiles/r03/parts2/;
-// joined at every run's end two halves ran in lockstep and gained nothing; profiles/r03/halves/, parts/).  The
-// parts share no buffer region (every pair has its own
-// checkpoints, bottom rows, script words and result), and sync_batch waits for every stream.  The run's event
-// log keeps every part's kernels, one launch each: sed_batch_times reports the mean launch (sed_batch_dp_launches() =
-// nparts).
-int run_batch_parts(sed_batch *b, const std::array<hipEvent_t, 4> &lg, sed_launch L, const sed_i32_params &ip,
-                    bool len) {
-    sed_ctx *c = b->ctx;
-    hipError_t e;
-    const int P = b->plan.nparts;
-    auto stream = [&](int i) { return i == 0 ? c->stream : b->part_stream[i - 1]; };
-    auto first = [&](int i) { return (int)((int64_t)b->plan.npairs * i / P); };
-    // the other streams start after everything queued before this run (uploads, the previous run's part 0)
-    if ((e = hipEventRecord(b->ev_start, c->stream)) != hipSuccess) return c->hipfail(e, "stream fork");
-    for (int i = 1; i < P; ++i)
-        if ((e = hipStreamWaitEvent(stream(i), b->ev_start, 0)) != hipSuccess) return c->hipfail(e, "stream fork");
-    // every part's kernels carry their own events (sed_batch_times averages the parts' launches); grow_log created
-    // the parts' entries with the run's own
-    std::array<hipEvent_t, 12> pl{};  // (an untimed run: none)
-    if (lg[0]) {
-        const size_t li = b->nlog - 1;
-        if (b->plog.size() <= li) return c->fail(SED_E_STATE, "parts event log not grown");
-        pl = b->plog[li];
-    }
-    auto part = [&](int i, int ph) {  // ph 0: forward, 1: traceback
-        sed_launch Li = L;
-        Li.pd = L.pd + first(i);
-        Li.res = L.res + first(i);
-        Li.band = L.band ? L.band + first(i) : nullptr;
-        Li.bwin = L.bwin ? L.bwin + (size_t)first(i) * L.bstripes : nullptr;
-        Li.bsuf = L.bsuf ? L.bsuf + (size_t)first(i) * L.bstripes : nullptr;
-        Li.npairs = first(i + 1) - first(i);
-        Li.stream = stream(i);
-        Li.ev0 = i == 0 ? lg[2 * ph] : pl[4 * (i - 1) + 2 * ph];
-        Li.ev1 = i == 0 ? lg[2 * ph + 1] : pl[4 * (i - 1) + 2 * ph + 1];
-        return Li;
-    };
-    for (int i = 0; i < P; ++i) {
-        sed_launch Lp = part(i, 0);
-        if (i == 0 && b->plan.nlane > 0) Lp.ev1 = nullptr;  // part 0's DP window ends with the lane kernel below
-        if ((e = sed_launch_i32(Lp, ip, len)) != hipSuccess) return c->hipfail(e, "DP kernel launch");
-    }
-    if (b->plan.nlane > 0) {  // lane pairs (the whole batch's, by index) after part 0's forward, inside its DP window
-        sed_launch Ll = L;
-        Ll.ev0 = nullptr;
-        Ll.ev1 = lg[1];
-        if ((e = sed_launch_lane_i32(Ll, (const int32_t *)b->p_lane, b->plan.nlane, ip, len)) != hipSuccess)
-            return c->hipfail(e, "lane kernel launch");
-    }
-    if (debug_corrupt_on(b)) {  // on the stream of the part that holds the pair
-        int ip_ = 0;
-        while (ip_ + 1 < P && c->opt.debug_corrupt - 1 >= first(ip_ + 1)) ++ip_;
-        if ((e = debug_corrupt(b, L.tb, stream(ip_))) != hipSuccess) return c->hipfail(e, "debug corrupt");
-    }
-    for (int i = 0; i < P; ++i)
-        if ((e = sed_launch_traceback_ck(part(i, 1), (uint32_t *)b->p_ops, ip)) != hipSuccess)
-            return c->hipfail(e, "traceback kernel launch");
-    b->evk[0] = lg;
-    ++b->runs;
-    b->ran = true;
-    return SED_OK;
-}
-
+// One run: the planner's schedule (b->sched; sed_plan.h: sed_plan_run), step by step.  Which launcher runs when, on
+// which stream role, and which launch carries which event is decided there; here a step gets its pairs, its stream,
+// its events and its launcher's arguments.
+//
+// The event log's timestamps ride on the kernels' own dispatch packets (SED_LAUNCH): the first launch of a phase records
+// the phase's start event at its start and the last one its end event at its end.  An event record is a marker packet
+// on the queue: with records around the kernels, consecutive config-2 DP kernels were ~18 us apart, and for the
+// ~25 us lane kernel (config 5) every avoided packet is measurable.  A phase that launches nothing records its events
+// directly.
+//
+// A checkpoint batch in parts (sched.nparts): stream i runs forward(part i) then traceback(part i).  The other streams
+// start each run after stream 0's previous work, and nothing joins the streams at a run's end, so the parts settle
+// into a stagger: one part's traceback runs beside another part's forward (config 4: 11.42-11.47 ms in one part,
+// 10.85-11.0 in two, 10.77-10.83 in three, 11.6-11.8 in four; with the select-free hold 9.86-9.93 in two against
+// 10.30-10.54 in three, profiles/r03/parts2/; joined at every run's end two halves ran in lockstep and gained nothing;
+// profiles/r03/halves/, parts/).  The parts share no buffer region (every pair has its own checkpoints, bottom rows,
+// script words and result), and sync_batch waits for every stream.  Part 0's events are the run's own log entry,
+// parts 1..3's are plog's: sed_batch_times reports the mean launch (sed_batch_dp_launches() = nparts).
 int run_batch(sed_batch *b) {
     sed_ctx *c = b->ctx;
-    if (b->plan.npairs == 0) {
+    const sed_plan &p = b->plan;
+    const sed_run_plan &S = b->sched;
+    if (p.npairs == 0) {
         b->ran = true;
         ++b->runs;
         return SED_OK;
     }
-    const int k = (int)(b->runs % b->plan.nbuf);
-    const bool want_tb = (b->plan.flags & SED_WANT_SCRIPT) != 0;
+    const int k = (int)(b->runs % p.nbuf);
+    const bool want_tb = (p.flags & SED_WANT_SCRIPT) != 0;
     hipError_t e;
-    if (b->plan.zc) b->zc_busy = true;
-    // The run's events time it (sed_batch_times) and, when buffers rotate, order their reuse (evk below; two-slot lane
-    // batches order by stream instead).  Untimed runs (sed_batch_set_timing) launch without them.
-    const bool need_ev = b->plan.nbuf > 1 && !(b->plan.alt_dp && b->plan.nbuf == 2 && !want_tb);
-    const bool timed = need_ev || b->time_every == 1 || (b->time_every > 1 && b->runs % b->time_every == 0);
-    std::array<hipEvent_t, 4> lg{};
+    if (p.zc) b->zc_busy = true;
+    // The run's events time it (sed_batch_times) and, when buffers rotate, order their reuse (evk below; S.need_ev).
+    // Untimed runs (sed_batch_set_timing) launch without them.
+    const bool timed = S.need_ev || b->time_every == 1 || (b->time_every > 1 && b->runs % b->time_every == 0);
+    std::array<hipEvent_t, 4> lg{};   // part 0's {DP start, DP end, traceback start, traceback end}
+    std::array<hipEvent_t, 12> pl{};  // parts 1..3's (grow_log created them with the run's own)
     if (timed) {
         if (b->nlog == b->log.size() && (e = grow_log(b, 64)) != hipSuccess) return c->hipfail(e, "event create");
         b->last_log = (long)b->nlog;
         lg = b->log[b->nlog++];
+        if (S.nparts > 1) {
+            if (b->plog.size() <= (size_t)b->last_log) return c->fail(SED_E_STATE, "parts event log not grown");
+            pl = b->plog[b->last_log];
+        }
     }
-    hipStream_t ts = b->plan.nbuf > 1 ? b->tb_stream : c->stream;
-    const hipStream_t ds = b->plan.alt_dp && (b->runs & 1) ? b->dp2_stream : c->stream;  // this run's DP stream
+    const hipStream_t ds = p.alt_dp && (b->runs & 1) ? b->dp2_stream : c->stream;  // this run's DP stream
+    const hipStream_t ts = p.nbuf > 1 ? b->tb_stream : c->stream;
+    auto part_stream = [&](int i) { return i == 0 ? c->stream : b->part_stream[i - 1]; };
+    auto part_first = [&](int i) { return (int)((int64_t)p.npairs * i / S.nparts); };
     sed_launch L{};
     L.pd = (const sed_pair_desc *)b->p_pd;
-    L.npairs = b->plan.npairs;
+    L.npairs = p.npairs;
     L.seqa = b->p_seqa;
     L.seqb = b->p_seqb;
     L.tb = want_tb ? (uint32_t *)b->d_tb[k].p : nullptr;
     L.ops = (uint32_t *)b->p_ops;
     L.bnd = (uint32_t *)b->d_bnd.p;
     L.res = (sed_result *)b->p_res[k];
-    L.R = b->plan.R;
-    L.stream = ds;
-    L.tb_ladder = b->plan.mode == SED_MODE_I32 && !b->plan.split_ck;  // (split_ck codes are the plain ops)
-    L.tb_wide = b->plan.lad && b->plan.ip.lad == 2;  // (a ladder-dot batch is a CHAIN batch: every wave pair's codes come from the LDOT kernel)
-    L.ck = b->plan.ck;
-    L.band = b->plan.band ? (sed_band *)b->d_band.p : nullptr;
-    L.bandp = &b->plan.bandp;
-    if (L.band && b->plan.band_stripes > 0) {
-        const size_t per = (size_t)b->plan.npairs * b->plan.band_stripes;
-        L.bstripes = b->plan.band_stripes;
-        L.bsuf = b->plan.band_refine ? (uint32_t *)b->d_bwin.p : nullptr;
+    L.R = p.R;
+    L.tb_ladder = p.mode == SED_MODE_I32 && !p.split_ck;  // (split_ck codes are the plain ops)
+    L.tb_wide = p.lad && p.ip.lad == 2;  // (a ladder-dot batch is a CHAIN batch: every wave pair's codes come from the LDOT kernel)
+    L.ck = p.ck;
+    L.band = p.band ? (sed_band *)b->d_band.p : nullptr;
+    L.bandp = &p.bandp;
+    if (L.band && p.band_stripes > 0) {
+        const size_t per = (size_t)p.npairs * p.band_stripes;
+        L.bstripes = p.band_stripes;
+        L.bsuf = p.band_refine ? (uint32_t *)b->d_bwin.p : nullptr;
         L.bwin = (int2 *)((uint32_t *)b->d_bwin.p + per);
     }
-    L.tasks = b->plan.split ? (const int2 *)b->p_tasks : nullptr;
-    L.ntasks = b->plan.split ? b->plan.ntasks : 0;
+    L.tasks = p.split ? (const int2 *)b->p_tasks : nullptr;
+    L.ntasks = p.split ? p.ntasks : 0;
     // buffer k was last read by the traceback of run runs-3 (written by its DP, distance only): wait for it unless it
     // has finished already (a cross-queue wait is a barrier packet between this run's kernel and the previous one)
-    const int kev = want_tb ? 3 : 1;
-    if (b->plan.nbuf > 1 && (want_tb || (b->plan.alt_dp && b->plan.nbuf != 2)) && b->runs >= b->plan.nbuf &&
-        hipEventQuery(b->evk[k][kev]) != hipSuccess &&
-        (e = hipStreamWaitEvent(ds, b->evk[k][kev], 0)) != hipSuccess)
+    if (S.reuse != SED_REUSE_NONE && b->runs >= p.nbuf && hipEventQuery(b->evk[k][S.reuse]) != hipSuccess &&
+        (e = hipStreamWaitEvent(ds, b->evk[k][S.reuse], 0)) != hipSuccess)
         return c->hipfail(e, "stream wait");
-    // The event log's timestamps ride on the kernels' own dispatch packets (SED_LAUNCH: the DP phase's first
-    // kernel records lg[0] at its start and its last kernel lg[1] at its end; the same for the traceback phase
-    // with lg[2] / lg[3]).  An event record is a marker packet on the queue: with records around the kernels,
-    // consecutive config-2 DP kernels were ~18 us apart, and for the ~25 us lane kernel (config 5) every
-    // avoided packet is measurable.  A phase that launches nothing records its events directly.
-    const int nw64 = b->plan.nwave - b->plan.nseg;  // wave pairs of the one-wave-per-pair kernels
-    // a cutoff: the wave pairs on the windowed stripe kernel instead of their own routes (cut_win), and the filter as
-    // the DP phase's last kernel
-    const bool cut = b->cut_on && !want_tb, win = cut && b->cut_win;
-    const int ndp = (win ? 1 : (b->plan.nwave_x2 > 0) + (nw64 > 0) + (b->plan.nseg > 0)) + (b->plan.nlane > 0) + (cut ? 1 : 0);
-    uint32_t *const hits = cut ? (uint32_t *)b->d_cut.p + b->cut_list.size() + (size_t)b->plan.npairs + k : nullptr;
-    if (cut && (e = hipMemsetAsync(hits, 0, 4, ds)) != hipSuccess) return c->hipfail(e, "reset cutoff hits");
-    b->cut_last = cut;
-    int idp = 0;
-    auto dp_events = [&]() {
-        L.ev0 = idp == 0 ? lg[0] : nullptr;
-        L.ev1 = idp == ndp - 1 ? lg[1] : nullptr;
-        ++idp;
-    };
-    if (ndp == 0 && lg[0] && (e = hipEventRecord(lg[0], ds)) != hipSuccess) return c->hipfail(e, "event record");
+    uint32_t *const hits = S.cut ? (uint32_t *)b->d_cut.p + b->cut_list.size() + (size_t)p.npairs + k : nullptr;
+    if (S.cut && (e = hipMemsetAsync(hits, 0, 4, ds)) != hipSuccess) return c->hipfail(e, "reset cutoff hits");
+    b->cut_last = S.cut;
     // SPLIT hand-off words carry the run's epoch (1..32767, next_split_epoch); every kernel writes all result
     // fields, err included
-    sed_i32_params ip = b->plan.ip;
+    sed_i32_params ip = p.ip;
     if ((e = next_split_epoch(b, ds, &ip.epoch)) != hipSuccess) return c->hipfail(e, "memset hand-off words");
-    const bool len = want_tb || !(b->plan.flags & SED_NO_LEN);
-    if (b->plan.nparts > 1 && want_tb) return run_batch_parts(b, lg, L, ip, len);
-    if (win) {
-        dp_events();
-        sed_launch Lw = L;
-        Lw.band = (sed_band *)b->d_band.p;
-        Lw.bandp = &b->plan.cut_bp;
-        if ((e = sed_launch_i32_cut(Lw, (const int32_t *)b->d_cut.p, (int)b->cut_list.size(), ip, b->cut_key)) != hipSuccess)
-            return c->hipfail(e, "windowed DP kernel launch");
+    const bool len = want_tb || !(p.flags & SED_NO_LEN);
+    if (S.nparts > 1) {  // the other parts' streams start after everything queued before this run (uploads, the previous run's part 0)
+        if ((e = hipEventRecord(b->ev_start, c->stream)) != hipSuccess) return c->hipfail(e, "stream fork");
+        for (int i = 1; i < S.nparts; ++i)
+            if ((e = hipStreamWaitEvent(part_stream(i), b->ev_start, 0)) != hipSuccess) return c->hipfail(e, "stream fork");
     }
-    if (!win && b->plan.nwave_x2 > 0) {
-        dp_events();
-        if ((e = sed_launch_i32x2(L, (const int32_t *)b->p_x2, b->plan.nwave_x2, ip)) != hipSuccess)
-            return c->hipfail(e, "packed DP kernel launch");
-    }
-    if (!win && nw64 > 0) {
-        dp_events();
-        if (b->plan.mode == SED_MODE_I32 && b->plan.nchains) {
-            L.chain_pairs = (const int32_t *)b->p_chain;
-            L.chain_off = (const int32_t *)b->p_chain + b->plan.chain_npairs;
-            L.nchains = b->plan.nchains;
-            L.chain_list = (int)b->plan.chain_npairs;
-            L.chain_counter = nullptr;
-            if (b->plan.chain_dyn) {  // zeroed on a batch's first launch only: a launch takes list + waves values
+    auto launch = [&](const sed_step &st) {
+        sed_launch Li = L;
+        Li.stream = st.on == SED_ON_PART ? part_stream(st.part) : st.on == SED_ON_TB ? ts : ds;
+        const int ev = 2 * st.phase;
+        Li.ev0 = !st.first ? nullptr : st.part == 0 ? lg[ev] : pl[4 * (st.part - 1) + ev];
+        Li.ev1 = !st.last ? nullptr : st.part == 0 ? lg[ev + 1] : pl[4 * (st.part - 1) + ev + 1];
+        if (S.nparts > 1 && st.kind != SED_STEP_LANE) {  // the part's pairs (the lane list indexes the whole batch's)
+            const int p0 = part_first(st.part);
+            Li.pd += p0;
+            Li.res += p0;
+            if (Li.band) Li.band += p0;
+            if (Li.bwin) Li.bwin += (size_t)p0 * L.bstripes;
+            if (Li.bsuf) Li.bsuf += (size_t)p0 * L.bstripes;
+            Li.npairs = part_first(st.part + 1) - p0;
+        }
+        uint32_t *const ops = (uint32_t *)b->p_ops;
+        const double *const gtab = (const double *)c->gtab.p;
+        const int32_t *const lane = (const int32_t *)b->p_lane;
+        const bool typed = p.mode == SED_MODE_F64_TYPED;
+        const char *what = st.phase == SED_PHASE_DP ? "DP kernel launch" : "traceback kernel launch";
+        hipError_t le = hipSuccess;
+        switch (st.kind) {
+        case SED_STEP_WIN:
+            what = "windowed DP kernel launch";
+            Li.band = (sed_band *)b->d_band.p;
+            Li.bandp = &p.cut_bp;
+            le = sed_launch_i32_cut(Li, (const int32_t *)b->d_cut.p, (int)b->cut_list.size(), ip, b->cut_key);
+            break;
+        case SED_STEP_X2:
+            what = "packed DP kernel launch";
+            le = sed_launch_i32x2(Li, (const int32_t *)b->p_x2, p.nwave_x2, ip);
+            break;
+        case SED_STEP_CHAIN:
+            Li.chain_pairs = (const int32_t *)b->p_chain;
+            Li.chain_off = (const int32_t *)b->p_chain + p.chain_npairs;
+            Li.nchains = p.nchains;
+            Li.chain_list = (int)p.chain_npairs;
+            if (p.chain_dyn) {  // zeroed on a batch's first launch only: a launch takes list + waves values
                 // (counted per launch, not per run: a run that fails after its CHAIN launch has still advanced it)
-                L.chain_counter = (uint32_t *)b->p_chain + b->plan.chain_npairs + 1 + k;
-                L.chain_base = (uint32_t)((uint64_t)b->chain_launches[k] * (uint64_t)(b->plan.chain_npairs + b->plan.nchains));
-                if (b->chain_launches[k] == 0 && (e = hipMemsetAsync(L.chain_counter, 0, 4, ds)) != hipSuccess)
-                    return c->hipfail(e, "reset chain counter");
+                Li.chain_counter = (uint32_t *)b->p_chain + p.chain_npairs + 1 + k;
+                Li.chain_base = (uint32_t)((uint64_t)b->chain_launches[k] * (uint64_t)(p.chain_npairs + p.nchains));
+                what = "reset chain counter";
+                if (b->chain_launches[k] == 0 && (le = hipMemsetAsync(Li.chain_counter, 0, 4, Li.stream)) != hipSuccess) break;
+                what = "DP kernel launch";
             }
-            e = sed_launch_i32_chain(L, ip, len);
-            if (e == hipSuccess && b->plan.chain_dyn) ++b->chain_launches[k];
-        } else if (b->plan.mode == SED_MODE_I32 && b->plan.split_ck) {  // forward with checkpoints, then every tile's codes
-            // (pipelined runs: the codes kernel opens the traceback phase on its stream below, so the next run's
-            // forward follows this one directly: config 2 ran 0.297-0.301 ms per step with it on the DP stream)
-            sed_launch Lf = L;
-            Lf.ck = true;
-            if (ts == ds) Lf.ev1 = nullptr;
-            e = sed_launch_i32(Lf, ip, len);
-            if (e == hipSuccess && ts == ds) {
-                sed_launch Lc = L;
-                Lc.ev0 = nullptr;
-                e = sed_launch_ck_codes(Lc, b->plan.ck_tiles, ip);
-            }
-        } else if (b->plan.mode == SED_MODE_I32)
-            e = sed_launch_i32(L, ip, len);
-        else {
-            sed_f64_params fp = b->plan.fp;
+            le = sed_launch_i32_chain(Li, ip, len);
+            if (le == hipSuccess && p.chain_dyn) ++b->chain_launches[k];
+            break;
+        case SED_STEP_I32:
+            Li.ck = p.ck || p.split_ck;  // (a split_ck batch's forward stores checkpoints for the codes kernel)
+            le = sed_launch_i32(Li, ip, len);
+            break;
+        case SED_STEP_CODES:  // the tile codes of this run's checkpoints
+            if (st.phase == SED_PHASE_TB) what = "codes kernel launch";
+            le = sed_launch_ck_codes(Li, p.ck_tiles, ip);
+            break;
+        case SED_STEP_F64: {
+            sed_f64_params fp = p.fp;
             fp.epoch = ip.epoch;
-            e = sed_launch_f64(L, (const double *)c->gtab.p, fp, b->plan.mode == SED_MODE_F64_TYPED);
+            le = sed_launch_f64(Li, gtab, fp, typed);
+            break;
         }
-        if (e != hipSuccess) return c->hipfail(e, "DP kernel launch");
-    }
-    if (!win && b->plan.nseg > 0) {  // fp64 pairs in 16-lane segments, four per wave
-        dp_events();
-        if ((e = sed_launch_f64_seg(L, (const double *)c->gtab.p, b->plan.fp, b->plan.mode == SED_MODE_F64_TYPED,
-                                    (const int32_t *)b->p_seg, b->plan.nseg)) != hipSuccess)
-            return c->hipfail(e, "segment DP kernel launch");
-    }
-    if (b->plan.nlane > 0) {
-        dp_events();
-        if (b->plan.lane_bitpar)
-            e = sed_launch_lane_bitpar(L, (const int32_t *)b->p_lane, b->plan.nlane);
-        else if (b->plan.nlane_x2 > 0)
-            e = sed_launch_lane_i32x2(L, (const int32_t *)b->p_lane, b->plan.nlane_x2, ip);
-        else if (b->plan.mode == SED_MODE_I32)
-            e = sed_launch_lane_i32(L, (const int32_t *)b->p_lane, b->plan.nlane, ip, len);
-        else if (b->plan.scaled)
-            e = sed_launch_lane_scaled(L, (const int32_t *)b->p_lane, b->plan.nlane, b->plan.sp);
-        else
-            e = sed_launch_lane_f64(L, (const int32_t *)b->p_lane, b->plan.nlane, (const double *)c->gtab.p, c->costs.ins,
-                                    c->costs.del, c->costs.K, b->plan.umask);
-        if (e != hipSuccess) return c->hipfail(e, "lane kernel launch");
-    }
-    if (cut) {
-        dp_events();
-        if ((e = sed_launch_cut_filter(L, b->cut_cmp, hits)) != hipSuccess) return c->hipfail(e, "cutoff filter launch");
-    }
-    if (ndp == 0 && lg[1] && (e = hipEventRecord(lg[1], ds)) != hipSuccess) return c->hipfail(e, "event record");
-    L.ev0 = L.ev1 = nullptr;
-    if (want_tb && b->plan.ck && debug_corrupt_on(b) && (e = debug_corrupt(b, L.tb, ds)) != hipSuccess)
-        return c->hipfail(e, "debug corrupt");
-    if (want_tb) {
+        case SED_STEP_F64_SEG:  // fp64 pairs in 16-lane segments, four per wave
+            what = "segment DP kernel launch";
+            le = sed_launch_f64_seg(Li, gtab, p.fp, typed, (const int32_t *)b->p_seg, p.nseg);
+            break;
+        case SED_STEP_LANE:
+            what = "lane kernel launch";
+            if (p.lane_bitpar)
+                le = sed_launch_lane_bitpar(Li, lane, p.nlane);
+            else if (p.nlane_x2 > 0)
+                le = sed_launch_lane_i32x2(Li, lane, p.nlane_x2, ip);
+            else if (p.mode == SED_MODE_I32)
+                le = sed_launch_lane_i32(Li, lane, p.nlane, ip, len);
+            else if (p.scaled)
+                le = sed_launch_lane_scaled(Li, lane, p.nlane, p.sp);
+            else
+                le = sed_launch_lane_f64(Li, lane, p.nlane, gtab, c->costs.ins, c->costs.del, c->costs.K, p.umask);
+            break;
+        case SED_STEP_FILTER:
+            what = "cutoff filter launch";
+            le = sed_launch_cut_filter(Li, b->cut_cmp, hits);
+            break;
+        case SED_STEP_TB_CK: le = sed_launch_traceback_ck(Li, ops, ip); break;
+        case SED_STEP_TB_CODES: le = sed_launch_traceback(Li, ops); break;
+        case SED_STEP_TB_STRIPES:
+            le = sed_launch_traceback_stripes(Li, ops, (uint32_t *)b->d_tbmap.p, p.tbpar_items, p.tbpar_kmax);
+            break;
+        case SED_STEP_TB_SEG: le = sed_launch_traceback_seg(Li, ops, (const int32_t *)b->p_seg, p.nseg); break;
+        default: return c->fail(SED_E_STATE, "unknown step %d in the run's schedule", (int)st.kind);
+        }
+        return le == hipSuccess ? SED_OK : c->hipfail(le, what);
+    };
+    int i = 0, rc;
+    for (; i < S.n && S.step[i].phase == SED_PHASE_DP; ++i)
+        if ((rc = launch(S.step[i])) != SED_OK) return rc;
+    if (i == 0 && lg[0] && ((e = hipEventRecord(lg[0], ds)) != hipSuccess || (e = hipEventRecord(lg[1], ds)) != hipSuccess))
+        return c->hipfail(e, "event record");
+    if (S.tb) {
+        if (p.ck && debug_corrupt_on(b)) {  // on the stream of the part that holds the pair
+            int part = 0;
+            while (part + 1 < S.nparts && c->opt.debug_corrupt - 1 >= part_first(part + 1)) ++part;
+            if ((e = debug_corrupt(b, L.tb, S.nparts > 1 ? part_stream(part) : ds)) != hipSuccess)
+                return c->hipfail(e, "debug corrupt");
+        }
         if (ts != ds && (e = hipStreamWaitEvent(ts, lg[1], 0)) != hipSuccess) return c->hipfail(e, "stream wait");
-        if (b->plan.nwave == 0 && lg[2] && (e = hipEventRecord(lg[2], ts)) != hipSuccess) return c->hipfail(e, "event record");
-        if (b->plan.nwave > 0) {
-            L.stream = ts;
-            L.ev0 = lg[2];
-            L.ev1 = lg[3];
-            if (b->plan.split_ck && ts != ds) {  // the tile codes of this run's checkpoints (see the DP phase)
-                sed_launch Lc = L;
-                Lc.ev1 = nullptr;
-                if ((e = sed_launch_ck_codes(Lc, b->plan.ck_tiles, ip)) != hipSuccess) return c->hipfail(e, "codes kernel launch");
-                L.ev0 = nullptr;
-            }
-            if (b->plan.tbpar) {  // (the map kernel zeroes the scripts the segments OR into)
-                e = sed_launch_traceback_stripes(L, (uint32_t *)b->p_ops, (uint32_t *)b->d_tbmap.p, b->plan.tbpar_items,
-                                                 b->plan.tbpar_kmax);
-            } else {
-                const hipEvent_t tb_end = L.ev1;
-                if (b->plan.nseg > 0) L.ev1 = nullptr;  // the segment pairs' traceback below ends the phase
-                e = nw64 <= 0 ? hipSuccess
-                    : b->plan.ck   ? sed_launch_traceback_ck(L, (uint32_t *)b->p_ops, ip)
-                              : sed_launch_traceback(L, (uint32_t *)b->p_ops);
-                if (e == hipSuccess && b->plan.nseg > 0) {
-                    L.ev0 = nw64 <= 0 ? L.ev0 : nullptr;
-                    L.ev1 = tb_end;
-                    e = sed_launch_traceback_seg(L, (uint32_t *)b->p_ops, (const int32_t *)b->p_seg, b->plan.nseg);
-                }
-            }
-            if (e != hipSuccess) return c->hipfail(e, "traceback kernel launch");
-        }
-        if (b->plan.nwave == 0 && lg[3] && (e = hipEventRecord(lg[3], ts)) != hipSuccess) return c->hipfail(e, "event record");
+        if (i == S.n && lg[2] && ((e = hipEventRecord(lg[2], ts)) != hipSuccess || (e = hipEventRecord(lg[3], ts)) != hipSuccess))
+            return c->hipfail(e, "event record");
+        for (; i < S.n; ++i)
+            if ((rc = launch(S.step[i])) != SED_OK) return rc;
     }
     b->evk[k] = lg;
     ++b->runs;
@@ -853,7 +806,7 @@ int sed_batch_set_cutoff(sed_batch *b, double max_dist) {
     int rc = sync_batch(b);  // a run in flight reads the windows and the cutoff's pair list
     if (rc != SED_OK) return rc;
     if (std::isinf(max_dist)) {
-        b->cut_on = b->cut_win = false;
+        set_cut_state(b, false, false);
         b->band_cells = b->plan.cells;
         return SED_OK;
     }
@@ -863,10 +816,7 @@ int sed_batch_set_cutoff(sed_batch *b, double max_dist) {
         b->cut_list.clear();
         for (int p = 0; p < np; ++p)
             if (b->plan.pd[p].lane != 1) b->cut_list.push_back(p);
-        int nwork = 0;  // wave pairs with cells
-        for (int32_t p : b->cut_list) nwork += b->plan.pd[p].n > 0 && b->plan.pd[p].m > 0;
-        b->cut_prune_ok = b->plan.mode == SED_MODE_I32 && !b->plan.split && (b->plan.flags & SED_NO_LEN) && b->plan.nseg == 0 &&
-                          (b->plan.R == 4 || b->plan.R == 8 || b->plan.R == 16) && b->plan.cut_costs_ok && nwork > 0;
+        b->cut_prune_ok = sed_plan_cut_window_ok(b->plan);
         const size_t nl = b->cut_list.size();
         if (!b->d_cut.reserve(4 * (nl + (size_t)np + 4)) || (b->cut_prune_ok && !b->d_band.reserve(sizeof(sed_band) * (size_t)np)))
             return c->fail(SED_E_OOM, "device allocation failed (cutoff)");
@@ -899,7 +849,7 @@ int sed_batch_set_cutoff(sed_batch *b, double max_dist) {
         b->cut_cmp = max_dist;
         b->cut_key = 0;
     }
-    b->cut_win = false;
+    bool win = false;
     b->band_cells = b->plan.cells;
     if (b->cut_prune_ok && c->opt.cut != 2) {
         double nominal = 0, bc = 0;
@@ -915,10 +865,10 @@ int sed_batch_set_cutoff(sed_batch *b, double max_dist) {
         // x2 runs 4 VALU per 2 cells and CHAIN saves its pairs' ramps; the windowed kernel's cell costs 3 VALU
         // (SED_CUT_SHARE: DESIGN.md 3.6d); pairs already on the plain stripe kernel gain whatever the window skips
         const double share = (b->plan.nwave_x2 > 0 || b->plan.nchains > 0) ? SED_CUT_SHARE : 1.0;
-        b->cut_win = c->opt.cut == 1 || bc < share * nominal;
-        if (b->cut_win) b->band_cells = b->plan.cells - nominal + bc;
+        win = c->opt.cut == 1 || bc < share * nominal;
+        if (win) b->band_cells = b->plan.cells - nominal + bc;
     }
-    b->cut_on = true;
+    set_cut_state(b, true, win);
     return SED_OK;
 }
 

@@ -23,6 +23,7 @@ SED_ENGINE=worker keeps HIP out of the calling process always; SED_ENGINE=inproc
 forbids both (a forked child then raises SedError).  An inherited Context is
 never touched by the child (not even by __del__).
 """
+import collections
 import ctypes as C
 import os
 import pickle
@@ -93,6 +94,9 @@ SIGNATURES = [
     ("sed_batch_dot_keys", C.c_int, [C.c_void_p]),
     ("sed_plan_routes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                   _u8p, _i64p, _i32p, _u8p, _i64p, _i32p, C.c_int32, C.c_uint32, _f64p, C.c_int]),
+    ("sed_plan_schedule", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                    _u8p, _i64p, _i32p, _u8p, _i64p, _i32p, C.c_int32, C.c_uint32, C.c_int, C.c_int,
+                                    _i32p, C.c_int, _i32p]),
     ("sed_dot_factor", C.c_int, [_f64p, C.c_double, C.c_double, C.c_int, C.c_int, _u32p]),
     ("sed_band_bounds", C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _i32p]),
     ("sed_band_chunk_range", C.c_int, [C.c_int32] * 6 + [_i32p]),
@@ -1149,6 +1153,42 @@ def plan_routes(costs, options, packed, flags):
         raise err
     return {k: (float(v) if k in ("band_cells", "cells", "algo_bytes") else int(v))
             for k, v in zip(PLAN_ROUTE_FIELDS, out)}
+
+
+STEP_LAUNCHERS = ("win", "x2", "chain", "i32", "codes", "f64", "f64_seg", "lane", "filter", "tb_ck", "tb_codes",
+                  "tb_stripes", "tb_seg")
+STEP_PHASES = ("dp", "tb")
+STEP_STREAMS = ("dp", "tb", "part")
+Step = collections.namedtuple("Step", "launcher phase stream part start end")
+
+
+class Schedule(list):
+    """The Steps of one run, with need_ev (untimed runs record events too), reuse_wait (None, "dp_end" or "tb_end": what
+    a rotating buffer's next user waits for), parts and capacity (the most steps a schedule holds)."""
+
+
+def plan_schedule(costs, options, packed, flags, cut_on=False, cut_win=False):
+    """The launches of one run, without a device (sed_plan_schedule): the Schedule a Batch of `packed` created under
+    these costs and options (as plan_routes takes them) executes per run in the cutoff state (cut_on, cut_win).  Raises
+    SedError carrying the SED_E_* code (.code): batch creation's, or SED_E_ARG for a cutoff state the batch cannot be
+    in."""
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    rows, info = np.zeros((64, 6), np.int32), np.zeros(4, np.int32)
+    n = load().sed_plan_schedule(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
+                                 np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
+                                 int(del_int), opts, len(options), packed.codes_a, packed.off_a, packed.len_a,
+                                 packed.codes_b, packed.off_b, packed.len_b, packed.npairs, flags, int(bool(cut_on)),
+                                 int(bool(cut_win)), rows, len(rows), info)
+    if n < 0:
+        err = SedError("sed_plan_schedule failed (%d)" % n)
+        err.code = n
+        raise err
+    s = Schedule(Step(STEP_LAUNCHERS[k], STEP_PHASES[ph], STEP_STREAMS[on], int(part), bool(a), bool(z))
+                 for k, ph, on, part, a, z in rows[:n].tolist())
+    s.need_ev, s.reuse_wait = bool(info[0]), {0: None, 1: "dp_end", 3: "tb_end"}[int(info[1])]
+    s.parts, s.capacity = int(info[2]), int(info[3])
+    return s
 
 
 FIT_PLAN_FIELDS = ("scale", "W", "chunk", "lanes", "cells", "nominal_cells")
