@@ -342,7 +342,8 @@ int sed_batch_work(const sed_batch *b, double *cells, double *algo_bytes);
  *   start = the largest s with G(s, end) = dist   (the tightest window ending earliest).
  * It is the sink scan of the DP with borders D[0][j] = 0, D[i][0] = i * delete and the reference's recurrence, every
  * cell carrying (D, -s) as one lexicographic key: the first strict minimum of row P over j.
- * Cost models served (anything else: SED_E_RANGE, the text says which condition failed; there is no fallback):
+ * Cost models served (anything else: SED_E_RANGE, the text says which condition failed; this call has no fallback of
+ * its own: sed_fit_search_f64 below serves what it refuses, and sed_fit_route says which of the two serves a search):
  *   at most 8 symbols (K <= 8); some S = 2^k, k <= 8, makes insert, delete and every substitution cost an integer in
  *   0..255 with (insert + delete) * S <= 255 and P * delete * S <= 65535; a lane's text columns fit 16 bits (a text runs
  *   in chunks of at most 65535 - W columns, W = P + floor(P * delete / insert); with insert = 0 a text runs as one
@@ -461,7 +462,7 @@ int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, doub
  * chunk of a text), the pattern's rows spread over its 64 lanes, R = 2, 4, 8, 16 or 32 rows a lane (the smallest with
  * 64 R >= P; SED_OPT_FIT_ROWS forces one R for every query of a call), and the queries of a call run grouped by R, one
  * launch per group and 65535 queries.  The cost models served (anything else: SED_E_RANGE, the text says which condition
- * failed; there is no fallback):
+ * failed; the long calls have no fp64 fallback, the _f64 calls below serve P <= 32 only):
  *   at most 8 symbols; some S = 2^k, k <= 8, makes every cost an integer in 0..255 with (insert + delete) * S <= 255;
  *   P * delete * S + 128 * insert * S <= 65535 over the call's longest pattern (distance and the 128 columns of insert a
  *   key carries between rebases share one 16-bit field);
@@ -488,6 +489,61 @@ int sed_fit_index_long_lanes(int K, const double *sub, const uint8_t *sub_int, d
                              double del, int del_is_int, const int32_t *options, int noptions,
                              const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts,
                              int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params);
+
+/* The fp64 route: sed_fit_search, sed_fit_index_search and sed_fit_index_hits for the cost tables and alphabets their
+ * integer keys refuse.  Arguments, results, state errors, the cap protocol and the index are those of the three calls
+ * above; the index is used as it stands, so integer and fp64 searches may alternate on one index.  What differs:
+ *   cost models served: at most 16 symbols (K <= 16; more: SED_E_RANGE, the text names the bound); insert, delete and
+ *   every substitution cost finite and >= 0 (a negative cost: SED_E_RANGE, the text names it; -0.0 counts as +0.0);
+ *   1 <= P <= 32.  No scale, no byte ranges, and no limit on a text's columns (starts are 32 bits): any int32 length.
+ *   The definition met is sed_fit_search's, evaluated as oracle/sed_oracle.c: sed_oracle_fit_pair states it: every
+ *   candidate of a cell is ONE fp64 add (left + insert, up + delete, diagonal + cost), borders D[0][j] = 0 and
+ *   D[i][0] = (double)i * delete, every cell the lexicographic minimum of (D, -start), the hit the first strict
+ *   minimum of row P.  out_dist / sed_fit_hit.dist is that fp64 value itself, bit for bit, whatever the chunk length:
+ *   for tables whose sums are not exact in fp64 this is the value of that one fixed order of additions.
+ *   A hit of sed_fit_index_hits_f64 is a column with E(e) <= max_dist as fp64 numbers; there is no scaled cutoff.
+ *   On tables the integer calls serve, the results of the two routes are equal bit for bit (every sum is exact).
+ *   A text runs in chunks as in sed_fit_search, the lanes warming up over W = P + floor(P * delete / insert) + 2
+ *   columns (DESIGN.md 3.6i proves the owned columns exact under rounding); with insert = 0, costs outside
+ *   2^-900 .. 2^900 or P * delete / insert above 2^20 every text runs as one lane.  SED_OPT_FIT_CHUNK as before.
+ * sed_fit_last_time, sed_fit_index_last_time and sed_fit_index_hits_last_time report the last search of either kind
+ * (the fp64 times include the small kernel that reduces the lanes' records per pair).  A refused call leaves the
+ * context and the index usable. */
+int sed_fit_search_f64(sed_ctx *ctx,
+                       const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                       const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
+                       int32_t npairs, double *out_dist, int32_t *out_start, int32_t *out_end);
+int sed_fit_index_search_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                             int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end);
+int sed_fit_index_hits_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                           int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found);
+/* What the fp64 calls would decide, without a device: out[] as sed_fit_plan / sed_fit_index_plan lay it out, with
+ * 0 = 0 (no scale: fp64), 1 W (-1: one lane per text), and 6 = why every text runs as one lane: 0 it does not have to,
+ * 1 insert = 0, 2 the window argument's conditions on the costs fail.  The lanes are the eight-word records of
+ * sed_fit_lanes / sed_fit_index_lanes (there are no parameter words). */
+int sed_fit_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                     double del, int del_is_int, const int32_t *options, int noptions,
+                     const int32_t *len_p, const int32_t *len_t, int32_t npairs, double *out, int nout);
+int sed_fit_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                      double del, int del_is_int, const int32_t *options, int noptions,
+                      const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                      int32_t *out_lanes, int64_t max_lanes);
+int sed_fit_index_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                           double del, int del_is_int, const int32_t *options, int noptions,
+                           const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts, double *out, int nout);
+int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                            double del, int del_is_int, const int32_t *options, int noptions,
+                            const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts,
+                            int32_t *out_lanes, int64_t max_lanes);
+/* Which route serves the search sed_fit_plan's arguments describe, without a device: SED_FIT_ROUTE_INT (sed_fit_search
+ * serves it; it is preferred whenever it does), SED_FIT_ROUTE_F64 (only sed_fit_search_f64 does; why = the integer
+ * route's refusal text), or the negative code both fail with (why = both texts, "; " between them).  why (room for
+ * why_len bytes, may be NULL with 0) is always terminated. */
+#define SED_FIT_ROUTE_INT 0
+#define SED_FIT_ROUTE_F64 1
+int sed_fit_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                  double del, int del_is_int, const int32_t *options, int noptions,
+                  const int32_t *len_p, const int32_t *len_t, int32_t npairs, char *why, int why_len);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

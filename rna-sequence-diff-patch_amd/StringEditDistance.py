@@ -724,11 +724,16 @@ def distance_deepen(strs1, strs2, k, first, last, userCosts=False, plan=None):
     return [int(d) if t else float(d) for d, t in zip(dist.tolist(), is_int.tolist())], cuts
 
 
-def fit_batch(patterns, texts, userCosts=False):
+FIT_F64_SYMBOLS = 16  # the fp64 route's table bound (include/sed.h: sed_fit_search_f64)
+
+
+def fit_batch(patterns, texts, userCosts=False, f64=False):
     """[(dist, start, end)] for each (pattern, text): the smallest wagnerFisher(pattern, text[start:end]) value over
     all substrings of the text (the empty one included), for the occurrence that ends earliest and, among those, starts
-    latest — one GPU launch (sedgpu.Context.fit).  Patterns have 1..32 symbols; the engine serves dyadic cost tables
-    over at most 8 symbols and raises SedError otherwise (include/sed.h: sed_fit_search).  dist is a float (no int
+    latest — one GPU launch (sedgpu.Context.fit).  Patterns have 1..32 symbols; the integer kernels serve dyadic cost
+    tables over at most 8 symbols and raise SedError otherwise (include/sed.h: sed_fit_search).  f64=True runs the fp64
+    kernels instead (sedgpu.Context.fit_f64): any table of costs >= 0 over at most 16 symbols, the full IUPAC alphabet
+    of costs.json among them; sedgpu.fit_route says which a batch needs.  dist is a float (no int
     typing: run the window through wagnerFisher for the reference's typed value).  Same KeyErrors as the reference
     would raise for (pattern, text)."""
     patterns, texts = list(patterns), list(texts)
@@ -737,7 +742,7 @@ def fit_batch(patterns, texts, userCosts=False):
         return []
     ctx = sedgpu.context()
     ctx.set_costs(plan)
-    dist, start, end = ctx.fit(_packed(plan, patterns, texts))
+    dist, start, end = (ctx.fit_f64 if f64 else ctx.fit)(_packed(plan, patterns, texts))
     return list(zip(dist.tolist(), start.tolist(), end.tolist()))
 
 
@@ -764,6 +769,14 @@ class _EngineIndex:
         self.ctx.set_costs(plan)
         return self.ix.hits_long(packed, max_dist)
 
+    def search_f64(self, plan, packed):
+        self.ctx.set_costs(plan)
+        return self.ix.search_f64(packed)
+
+    def hits_f64(self, plan, packed, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.hits_f64(packed, max_dist)
+
     def close(self):
         self.ix.close()
 
@@ -775,18 +788,23 @@ class FitIndex:
     The texts' symbols get their codes when the index is built (first-occurrence order over the texts, as batch_plan
     resolves them; or `alphabet` first, for a collection that may grow into symbols it does not hold yet).  A search
     whose patterns bring symbols the texts do not have appends them for that search only; more than 8 symbols in all
-    raise SedError (fit search serves at most 8).  The cost table is read at every search, so edits to it take effect,
+    raise SedError (the integer kernels serve at most 8).  f64=True builds the index for the fp64 route instead: the
+    bound is 16 symbols, and search_f64 / hits_f64 serve any table of costs >= 0 (search / hits still run the integer
+    kernels and refuse what those refuse).  The cost table is read at every search, so edits to it take effect,
     and the KeyErrors are the reference's for the first offending (pattern, text) in pattern-major order."""
 
-    def __init__(self, texts, userCosts=False, alphabet=None, engine=None):
+    def __init__(self, texts, userCosts=False, alphabet=None, engine=None, f64=False):
         self.texts = list(texts)
         self.userCosts = userCosts
+        self.f64 = bool(f64)
+        self.max_symbols = FIT_F64_SYMBOLS if self.f64 else 8
         used = sedcost.distinct_many(self.texts) if sedcost._all_str(self.texts) else \
             list(dict.fromkeys(c for t in self.texts for c in t))
         self._used = used  # the symbols the texts hold: the str2 side of every cost lookup
         self.symbols = list(dict.fromkeys(list(alphabet or ()) + used))
-        if len(self.symbols) > 8:
-            raise sedgpu.SedError("fit index: the texts have %d symbols (fit search serves at most 8)" % len(self.symbols))
+        if len(self.symbols) > self.max_symbols:
+            raise sedgpu.SedError("fit index: the texts have %d symbols (fit search serves at most %d%s)"
+                                  % (len(self.symbols), self.max_symbols, "" if self.f64 else "; f64=True serves 16"))
         code = {c: k for k, c in enumerate(self.symbols)}
         lens = np.fromiter(map(len, self.texts), dtype=np.int32, count=len(self.texts))
         codes = np.fromiter((code[c] for t in self.texts for c in t), dtype=np.uint8, count=int(lens.sum()))
@@ -808,9 +826,9 @@ class FitIndex:
                 for t in self.texts:
                     sedcost.check_pair(table, p, t)
         alphabet = self.symbols + [c for c in u1 if c not in self.symbols]
-        if len(alphabet) > 8:
-            raise sedgpu.SedError("fit index: the texts and these patterns have %d symbols (fit search serves at most 8)"
-                                  % len(alphabet))
+        if len(alphabet) > self.max_symbols:
+            raise sedgpu.SedError("fit index: the texts and these patterns have %d symbols (fit search serves at most %d%s)"
+                                  % (len(alphabet), self.max_symbols, "" if self.f64 else "; f64=True serves 16"))
         return sedcost.plan_over(table, alphabet, set(u1), set(self._used))
 
     def search(self, patterns, _dev="search"):
@@ -833,6 +851,15 @@ class FitIndex:
         """hits() for patterns of 1..2048 symbols (include/sed.h: sed_fit_index_hits_long)."""
         return self.hits(patterns, max_dist, "hits_long")
 
+    def search_f64(self, patterns):
+        """search() through the fp64 kernels (include/sed.h: sed_fit_index_search_f64): any table of costs >= 0; with
+        an index built f64=True, up to 16 symbols."""
+        return self.search(patterns, "search_f64")
+
+    def hits_f64(self, patterns, max_dist):
+        """hits() through the fp64 kernels (include/sed.h: sed_fit_index_hits_f64)."""
+        return self.hits(patterns, max_dist, "hits_f64")
+
     def hits(self, patterns, max_dist, _dev="hits"):
         """[(pattern index, text index, start, end, dist)] sorted by (pattern, text, end): for every end column e of a
         text (0 <= e <= its length) the smallest wagnerFisher(pattern, text[s:e]) value over s, with the largest such s
@@ -851,11 +878,11 @@ class FitIndex:
         self._dev.close()
 
 
-def fit_index(texts, userCosts=False, alphabet=None, engine=None):
+def fit_index(texts, userCosts=False, alphabet=None, engine=None, f64=False):
     """A FitIndex over texts: fit_batch for callers who search one collection query after query.  engine(codes, off,
-    lens) -> an object with search(plan, packed), hits(plan, packed, max_dist), their search_long / hits_long and close()
-    replaces the device (CPU tests)."""
-    return FitIndex(texts, userCosts, alphabet, engine)
+    lens) -> an object with search(plan, packed), hits(plan, packed, max_dist), their search_long / hits_long,
+    search_f64 / hits_f64 and close() replaces the device (CPU tests)."""
+    return FitIndex(texts, userCosts, alphabet, engine, f64)
 
 
 def edit_script_batch(strs1, strs2, userCosts=False):

@@ -1,12 +1,14 @@
 // sed_fit_plan.cpp — the fit planner (sed_fit_plan.h): scale, update addends, window, chunk length, lanes and the
 // cutoff of a fit search, from the cost model, the options and the lengths.  No HIP call.  Also the device-free fit
 // entry points of include/sed.h (sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes,
-// sed_fit_index_long_plan, sed_fit_index_long_lanes, sed_fit_cutoff_scaled).
+// sed_fit_index_long_plan, sed_fit_index_long_lanes, sed_fit_cutoff_scaled, sed_fit_f64_plan, sed_fit_f64_lanes,
+// sed_fit_index_f64_plan, sed_fit_index_f64_lanes, sed_fit_route).
 #include "sed_fit_plan.h"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 // The device the auto chunk rule sizes for: 256 CUs x 4 SIMDs, 64 lanes a wave.  One lane per text is kept when that
@@ -202,6 +204,120 @@ int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len
 int sed_fit_plan_index_long(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
                             const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err) {
     return fit_plan_index_of(c, o, FIT_LONG, len_p, nqueries, tx, plan, rows, err);
+}
+
+// ---- the fp64 route ----
+// The rule of the fp64 plans: the envelope, the table the kernels read, W and the chunk.  The chunk rule is
+// fit_plan_rule's (the short layout: 64 lanes a wave; its two wave constants carried over, not measured for this
+// kernel), without the span limit.
+static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSums &sm, sed_fit_plan_t *plan, std::string *err,
+                             int64_t *chunk_out) {
+    if (c.K > SED_FIT_F64_MAXK)
+        return sed_plan_fail(err, SED_E_RANGE, "fit search (fp64): the batch has %d symbols (at most %d)", c.K, SED_FIT_F64_MAXK);
+    auto cost_ok = [](double v) { return std::isfinite(v) && v >= 0; };  // (-0.0 >= 0)
+    if (!cost_ok(c.ins)) return sed_plan_fail(err, SED_E_RANGE, "fit search (fp64): insert = %g is not a finite cost >= 0", c.ins);
+    if (!cost_ok(c.del)) return sed_plan_fail(err, SED_E_RANGE, "fit search (fp64): delete = %g is not a finite cost >= 0", c.del);
+    for (int e = 0; e < c.K * c.K; ++e)
+        if (!cost_ok(c.sub[e]))
+            return sed_plan_fail(err, SED_E_RANGE, "fit search (fp64): cost(%d -> %d) = %g is not a finite cost >= 0", e / c.K,
+                                 e % c.K, c.sub[e]);
+    plan->scale_log2 = 0;
+    plan->fp = sed_fit_params{};
+    plan->f64_ins = c.ins + 0.0;  // (-0.0 + 0.0 = +0.0)
+    plan->f64_del = c.del + 0.0;
+    plan->f64_sub.assign((size_t)SED_FIT_F64_MAXK * SED_FIT_F64_MAXK, 0.0);
+    for (int a = 0; a < c.K; ++a)
+        for (int b = 0; b < c.K; ++b) plan->f64_sub[(size_t)a * SED_FIT_F64_MAXK + b] = c.sub[a * c.K + b] + 0.0;
+    // W = P + Y, Y = floor(P delete / insert) + 2, under the hypotheses of DESIGN.md 3.6i: insert, and delete unless 0,
+    // within 2^-900 .. 2^900 (no product here under- or overflows), P delete / insert <= 2^20, and, checked as
+    // computed, (Y - 1) insert >= P delete (1 + 2^-30).  Anything else: one lane per text.
+    const int pmax = sm.pmax;
+    const double ins = plan->f64_ins, del = plan->f64_del, lo = std::ldexp(1.0, -900), hi = std::ldexp(1.0, 900);
+    plan->W = -1;
+    plan->one_lane = ins == 0 ? SED_FIT_F64_INSERT_ZERO : SED_FIT_F64_NO_WINDOW;
+    if (ins >= lo && ins <= hi && (del == 0 || (del >= lo && del <= hi))) {
+        const double pd = (double)pmax * del, x = pd / ins;
+        if (x <= 1048576.0) {
+            const double Y = std::floor(x) + 2;
+            if ((Y - 1) * ins >= pd * (1 + std::ldexp(1.0, -30))) {
+                plan->W = pmax + (int64_t)Y;
+                plan->one_lane = SED_FIT_F64_CHUNKED;
+            }
+        }
+    }
+    int64_t chunk = 0;
+    if (plan->W >= 0 && o.fit_chunk > 0)
+        chunk = o.fit_chunk;
+    else if (plan->W >= 0 && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * FIT_SHORT.units_per_wave) {
+        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * FIT_SHORT.units_per_wave));
+        chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
+    }
+    const bool split = chunk > 0 && sm.nmax + 1 > chunk;
+    plan->chunk = split || (plan->W >= 0 && o.fit_chunk > 0) ? (int32_t)std::min<int64_t>(chunk, INT_MAX) : 0;
+    *chunk_out = chunk;
+    return SED_OK;
+}
+
+int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                           sed_fit_plan_t *plan, std::string *err) {
+    if (npairs < 0 || (npairs > 0 && (!len_p || !len_t))) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
+    FitSums sm;
+    sm.npairs = npairs;
+    for (int p = 0; p < npairs; ++p) {
+        if (len_t[p] < 0) return sed_plan_fail(err, SED_E_ARG, "pair %d: negative text length", p);
+        if (len_p[p] < 1 || len_p[p] > SED_LANE_MAXM)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: pair %d: pattern length %d outside 1..%d", p, len_p[p],
+                                 SED_LANE_MAXM);
+        sm.pmax = std::max(sm.pmax, len_p[p]);
+        sm.cols += (double)len_t[p] + 1;
+        sm.nmax = std::max<int64_t>(sm.nmax, len_t[p]);
+    }
+    int64_t chunk = 0;
+    const int rc = fit_plan_rule_f64(c, o, sm, plan, err, &chunk);
+    if (rc != SED_OK) return rc;
+    plan->first.assign((size_t)npairs + 1, 0);
+    plan->cells = plan->nominal = 0;
+    for (int p = 0; p < npairs; ++p) {
+        double computed = 0;
+        plan->first[p + 1] = plan->first[p] + fit_text_lanes(chunk, plan->W, len_t[p], &computed);
+        plan->cells += (double)len_p[p] * computed;
+        plan->nominal += (double)len_p[p] * (double)len_t[p];
+    }
+    plan->lanes = plan->first[npairs];
+    if (plan->lanes > INT_MAX) return sed_plan_fail(err, SED_E_RANGE, "fit search: %lld lanes", (long long)plan->lanes);
+    return SED_OK;
+}
+
+int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                           const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
+    if (nqueries < 0 || (nqueries > 0 && !len_p) || tx.ntexts < 0) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
+    FitSums sm;
+    double psum = 0;
+    // the cross product's refusals in sed_fit_plan_batch_f64's order (fit_plan_index_of)
+    for (int q = 0; q < nqueries && tx.ntexts > 0; ++q) {
+        if (tx.first_negative >= 0 && (q == 0 ? tx.first_negative == 0 : q == 1))
+            return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
+        if (len_p[q] < 1 || len_p[q] > SED_LANE_MAXM)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q],
+                                 SED_LANE_MAXM);
+        sm.pmax = std::max(sm.pmax, len_p[q]);
+        psum += (double)len_p[q];
+    }
+    if (nqueries == 1 && tx.ntexts > 0 && tx.first_negative >= 0)
+        return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
+    if (nqueries > 0 && tx.ntexts > 0) {
+        sm.npairs = (int64_t)nqueries * tx.ntexts;
+        sm.cols = (double)nqueries * tx.cols;
+        sm.nmax = tx.nmax;
+    }
+    int64_t chunk = 0;
+    const int rc = fit_plan_rule_f64(c, o, sm, plan, err, &chunk);
+    if (rc != SED_OK) return rc;
+    plan->first.clear();
+    plan->lanes = 0;
+    plan->cells = 0;
+    plan->nominal = psum * (tx.cols - (double)tx.ntexts);
+    return SED_OK;
 }
 
 int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
@@ -419,6 +535,121 @@ int sed_fit_index_long_lanes(int K, const double *sub, const uint8_t *sub_int, d
     std::vector<int32_t> rows;
     return fit_index_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
                               ntexts, out_lanes, max_lanes, out_params, &rows);
+}
+
+// ---- the fp64 route's device-free exports ----
+static int fit_f64_plan_out(int rc, const sed_fit_plan_t &p, double *out, int nout) {
+    if (rc != SED_OK) return rc;
+    const double v[] = {0.0, (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal, (double)p.one_lane};
+    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}
+static int fit_f64_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                           int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
+                           int32_t npairs, sed_fit_plan_t *p, std::string *err = nullptr) {
+    sed_costs c;
+    sed_opts o;
+    const int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    return rc != SED_OK ? rc : sed_fit_plan_batch_f64(c, o, len_p, len_t, npairs, p, err);
+}
+// sed_fit_index_f64_plan's and sed_fit_index_f64_lanes' common half (fit_index_plan_of for the fp64 plan)
+static int fit_index_f64_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                 int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                                 const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks) {
+    if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    const int rc0 = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc0 != SED_OK) return rc0;
+    sed_fit_index_sums tx;
+    tx.ntexts = ntexts;
+    for (int d = 0; d < ntexts; ++d) {
+        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
+        tx.cols += (double)len_t[d] + 1;
+        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
+    }
+    const int rc = sed_fit_plan_index_f64(c, o, len_p, nqueries, tx, p, nullptr);
+    if (rc != SED_OK) return rc;
+    double computed = 0, psum = 0;
+    const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
+    for (int q = 0; q < nqueries && ntexts > 0; ++q) psum += (double)len_p[q];
+    p->lanes = nqueries * nchunks;
+    p->cells = psum * computed;
+    return p->lanes > INT_MAX ? SED_E_RANGE : SED_OK;
+}
+
+int sed_fit_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                     const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                     double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    return fit_f64_plan_out(fit_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t,
+                                            npairs, &p),
+                            p, out, nout);
+}
+
+int sed_fit_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                      const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                      int32_t *out_lanes, int64_t max_lanes) {
+    if (max_lanes < 0 || (max_lanes && !out_lanes)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = fit_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
+    if (rc != SED_OK) return rc;
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    std::vector<sed_fit_lane> lanes;
+    sed_fit_build_lanes(p, len_p, len_t, npairs, lanes);
+    if (!lanes.empty()) std::memcpy(out_lanes, lanes.data(), lanes.size() * sizeof(sed_fit_lane));
+    return SED_OK;
+}
+
+int sed_fit_index_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                           int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                           const int32_t *len_t, int32_t ntexts, double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    return fit_f64_plan_out(fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p,
+                                                  nqueries, len_t, ntexts, &p, nullptr),
+                            p, out, nout);
+}
+
+int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                            int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                            const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
+    if (max_lanes < 0 || (max_lanes && !out_lanes)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    std::vector<sed_fit_chunk> chunks;
+    const int rc = fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
+                                         len_t, ntexts, &p, &chunks);
+    if (rc != SED_OK) return rc;
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    sed_fit_lane *out = (sed_fit_lane *)out_lanes;
+    for (int q = 0; q < nqueries; ++q)  // the kernel's own derivation, with each text at word 0
+        for (const sed_fit_chunk &ck : chunks) {
+            sed_fit_lane ln = sed_fit_derive_lane(ck, sed_fit_text{0u, len_t[ck.text]}, p.chunk, len_p[q], p.W);
+            ln.pair = q * ntexts + ck.text;
+            *out++ = ln;
+        }
+    return SED_OK;
+}
+
+int sed_fit_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                  const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs, char *why,
+                  int why_len) {
+    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
+    if (why_len) why[0] = 0;
+    sed_costs c;
+    sed_opts o;
+    int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return rc;
+    sed_fit_plan_t p;
+    std::string e_int, e_f64;
+    if ((rc = sed_fit_plan_batch(c, o, len_p, len_t, npairs, &p, &e_int)) == SED_OK) return SED_FIT_ROUTE_INT;
+    if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
+    sed_fit_plan_t pf;
+    rc = sed_fit_plan_batch_f64(c, o, len_p, len_t, npairs, &pf, &e_f64);
+    const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
+    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
+    return rc == SED_OK ? SED_FIT_ROUTE_F64 : rc;
 }
 
 }  // extern "C"

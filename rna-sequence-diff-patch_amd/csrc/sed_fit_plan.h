@@ -1,8 +1,8 @@
 // sed_fit_plan.h — the device-free half of fit search (include/sed.h: sed_fit_search, sed_fit_index_search,
 // sed_fit_index_hits): what a search decides from the cost model, the options and the lengths.  sed_fit_plan.cpp calls
 // no HIP API, as the batch planner (sed_plan.h, whose sed_costs, sed_opts and sed_plan_fail it shares and nothing else);
-// its exports sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes and sed_fit_cutoff_scaled run, and
-// are tested, without a device.
+// its exports sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes, sed_fit_cutoff_scaled, their
+// _long and _f64 siblings and sed_fit_route run, and are tested, without a device.
 #pragma once
 #include "sed_plan.h"
 
@@ -16,6 +16,10 @@ struct sed_fit_plan_t {
     double cells = 0, nominal = 0;  // P x columns computed (warm-up included), and sum P n
     std::vector<int64_t> first;
     sed_fit_params fp{};
+    // the fp64 route (sed_fit_plan_batch_f64, sed_fit_plan_index_f64) alone; scale_log2 and fp are not used there
+    int one_lane = 0;             // SED_FIT_F64_* below: why every text runs as one lane whatever the chunk option says
+    double f64_ins = 0, f64_del = 0;
+    std::vector<double> f64_sub;  // SED_FIT_F64_MAXK x SED_FIT_F64_MAXK, zeros past K, -0.0 normalised to +0.0
 };
 int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
                        sed_fit_plan_t *plan, std::string *err);
@@ -56,3 +60,17 @@ int sed_fit_cutoff_rule(const sed_fit_plan_t &plan, double max_dist, int32_t *cu
 // adds the base word of each text's copy and sets the pattern record (sed_fit_runtime.cpp: sed_fit_search).
 void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
                          std::vector<sed_fit_lane> &lanes);
+
+// The fp64 route (include/sed.h: sed_fit_search_f64; kernels: sed_fit_f64.hip): the short layout's lanes and chunk rule
+// for any table of finite costs >= 0 over at most SED_FIT_F64_MAXK symbols, 1 <= P <= 32.  There is no scale and no
+// span limit (starts are 32 bits).  W = P + floor(P delete / insert) + 2, the integer route's window plus the slack the
+// rounding argument needs; where that argument cannot be made every text runs as one lane, W = -1,
+// and plan->one_lane says why.  first / lanes / cells / nominal as the integer plans fill them.
+#define SED_FIT_F64_CHUNKED 0
+#define SED_FIT_F64_INSERT_ZERO 1   // insert = 0: no window is finite (the integer route's rule)
+#define SED_FIT_F64_NO_WINDOW 2     // the window argument's hypotheses fail: a cost outside 2^-900 .. 2^900, P delete /
+                                    // insert above 2^20, or its checked inequality
+int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                           sed_fit_plan_t *plan, std::string *err);
+int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                           const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err);

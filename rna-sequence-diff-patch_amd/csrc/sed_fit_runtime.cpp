@@ -1,7 +1,8 @@
 // sed_fit_runtime.cpp — fit search's entry points of the C-ABI (include/sed.h): sed_fit_search over listed pairs, and
-// sed_fit_index_* over a resident text index (best hit per (query, text), or every hit within a distance).  What a
-// search runs is the fit planner's decision (sed_fit_plan.cpp), the kernels are sed_fit.hip; here: pack, reserve,
-// upload, launch, download, decode, on the context's stream (sed_runtime.h).
+// sed_fit_index_* over a resident text index (best hit per (query, text), or every hit within a distance), each also as
+// its _f64 sibling.  What a search runs is the fit planner's decision (sed_fit_plan.cpp), the kernels are sed_fit.hip,
+// sed_fit_long.hip and sed_fit_f64.hip; here: pack, reserve, upload, launch, download, decode, on the context's stream
+// (sed_runtime.h).  The routes of a call differ in the plan, the launch and the decoding, and share the staging.
 #include "sed_fit_plan.h"
 #include "sed_runtime.h"
 
@@ -36,8 +37,9 @@ struct FitTimer {
 // sed_fit_search's device arrays and the timer of its kernel, kept across calls
 struct sed_fit_state {
     DevBuf text, pat, lanes, out;
+    DevBuf rec, tab;  // the fp64 route's per-lane records and its cost table
     FitTimer timer;
-    ~sed_fit_state() { text.release(); pat.release(); lanes.release(); out.release(); }
+    ~sed_fit_state() { text.release(); pat.release(); lanes.release(); out.release(); rec.release(); tab.release(); }
 };
 void sed_fit_state_destroy(sed_fit_state *s) { delete s; }
 
@@ -72,19 +74,35 @@ static bool fit_decode_key(uint64_t k, int32_t text_len, double inv, double *dis
     return true;
 }
 
-extern "C" {
+// A result record of the fp64 kernels (sed_fit_f64.hip) for a text of text_len symbols; false = no result (the preset
+// bytes, or one no lane of that text can have written).
+static bool fit_decode_f64(const sed_fit_f64_best &b, int32_t text_len, double *dist, int32_t *start, int32_t *end) {
+    if (!(b.D >= 0) || b.end < 0 || b.end > text_len || b.start < 0 || b.start > b.end) return false;
+    *dist = b.D;
+    *start = b.start;
+    *end = b.end;
+    return true;
+}
+// The fp64 plan's cost table on the device, and the kernels' cost arguments
+static hipError_t fit_f64_costs_upload(sed_ctx *c, const sed_fit_plan_t &plan, DevBuf &tab, sed_fit_f64_costs *fc) {
+    if (!tab.reserve(plan.f64_sub.size() * sizeof(double))) return hipErrorOutOfMemory;
+    *fc = sed_fit_f64_costs{(const double *)tab.p, plan.f64_ins, plan.f64_del};
+    return hipMemcpyAsync(tab.p, plan.f64_sub.data(), plan.f64_sub.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
+}
 
 // The planner decides scale, window and lanes from the lengths and builds the lane records (sed_fit_plan.cpp:
 // sed_fit_plan_batch, sed_fit_build_lanes); here the distinct patterns become records and the distinct texts one buffer
 // in which each starts 4-byte aligned, so pairs that share a pattern or a text through their offsets share its copy.
-int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p, const uint8_t *codes_t,
-                   const int64_t *off_t, const int32_t *len_t, int32_t npairs, double *out_dist, int32_t *out_start,
-                   int32_t *out_end) {
+// sed_fit_search and sed_fit_search_f64: the plan, the launch and the decoding differ, nothing else.
+static int fit_search_of(sed_ctx *c, bool f64, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                         const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t, int32_t npairs, double *out_dist,
+                         int32_t *out_start, int32_t *out_end) {
     int rc = fit_enter(c, npairs == 0 || (npairs > 0 && codes_p && off_p && len_p && codes_t && off_t && len_t && out_dist &&
                                           out_start && out_end));
     if (rc != SED_OK) return rc;
     sed_fit_plan_t plan;
-    rc = sed_fit_plan_batch(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err);
+    rc = f64 ? sed_fit_plan_batch_f64(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err)
+             : sed_fit_plan_batch(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err);
     if (rc != SED_OK || npairs == 0) return rc;
     const int K = c->costs.K;
     struct Span {
@@ -127,30 +145,52 @@ int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, con
     text.resize(text.size() + 16, 0);  // (a lane reads one word past its last)
     if (!c->fit) c->fit = new sed_fit_state;
     sed_fit_state &f = *c->fit;
+    const size_t outbytes = (f64 ? sizeof(sed_fit_f64_best) : 8) * (size_t)npairs;
     if (!f.text.reserve(text.size()) || !f.pat.reserve(pats.size()) || !f.lanes.reserve(lanes.size() * sizeof(sed_fit_lane)) ||
-        !f.out.reserve(8 * (size_t)npairs))
+        !f.out.reserve(outbytes) || (f64 && !f.rec.reserve(lanes.size() * sizeof(sed_fit_f64_best))))
         return c->fail(SED_E_OOM, "device allocation failed (fit search, %zu text bytes)", text.size());
     hipError_t e = hipSuccess;
     if ((e = f.timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
-    std::vector<uint64_t> keys((size_t)npairs);
+    std::vector<uint64_t> keys(outbytes / 8);
+    sed_fit_f64_costs fc{};
+    if (f64 && (e = fit_f64_costs_upload(c, plan, f.tab, &fc)) != hipSuccess) return c->hipfail(e, "upload (fit search costs)");
     if ((e = hipMemcpyAsync(f.text.p, text.data(), text.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(f.pat.p, pats.data(), pats.size(), hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
         (e = hipMemcpyAsync(f.lanes.p, lanes.data(), lanes.size() * sizeof(sed_fit_lane), hipMemcpyHostToDevice,
                             c->stream)) != hipSuccess ||
-        (e = hipMemsetAsync(f.out.p, 0xFF, 8 * (size_t)npairs, c->stream)) != hipSuccess)
+        (e = hipMemsetAsync(f.out.p, 0xFF, outbytes, c->stream)) != hipSuccess)
         return c->hipfail(e, "upload (fit search)");
-    if ((e = sed_launch_fit(c->stream, f.timer.ev[0], f.timer.ev[1], (const sed_fit_lane *)f.lanes.p, (int)lanes.size(),
+    if (f64) {
+        if ((e = sed_launch_fit_f64(c->stream, f.timer.ev[0], f.timer.ev[1], (const sed_fit_lane *)f.lanes.p, (int)lanes.size(),
+                                    f.pat.p, f.text.p, (sed_fit_f64_best *)f.rec.p, (sed_fit_f64_best *)f.out.p, fc)) != hipSuccess)
+            return c->hipfail(e, "fit fp64 kernel launch");
+    } else if ((e = sed_launch_fit(c->stream, f.timer.ev[0], f.timer.ev[1], (const sed_fit_lane *)f.lanes.p, (int)lanes.size(),
                             f.pat.p, f.text.p, (unsigned long long *)f.out.p, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit kernel launch");
-    if ((e = hipMemcpyAsync(keys.data(), f.out.p, 8 * (size_t)npairs, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(keys.data(), f.out.p, outbytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (fit search)");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit kernel execution");
     f.timer.timed = true;
     const double inv = std::ldexp(1.0, -plan.scale_log2);
+    const sed_fit_f64_best *best = (const sed_fit_f64_best *)keys.data();
     for (int p = 0; p < npairs; ++p)
-        if (!fit_decode_key(keys[p], len_t[p], inv, &out_dist[p], &out_start[p], &out_end[p]))
+        if (f64 ? !fit_decode_f64(best[p], len_t[p], &out_dist[p], &out_start[p], &out_end[p])
+                : !fit_decode_key(keys[p], len_t[p], inv, &out_dist[p], &out_start[p], &out_end[p]))
             return c->fail(SED_E_DEVICE, "pair %d: no fit result from the device", p);
     return SED_OK;
+}
+
+extern "C" {
+
+int sed_fit_search(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p, const uint8_t *codes_t,
+                   const int64_t *off_t, const int32_t *len_t, int32_t npairs, double *out_dist, int32_t *out_start,
+                   int32_t *out_end) {
+    return fit_search_of(c, false, codes_p, off_p, len_p, codes_t, off_t, len_t, npairs, out_dist, out_start, out_end);
+}
+int sed_fit_search_f64(sed_ctx *c, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p, const uint8_t *codes_t,
+                       const int64_t *off_t, const int32_t *len_t, int32_t npairs, double *out_dist, int32_t *out_start,
+                       int32_t *out_end) {
+    return fit_search_of(c, true, codes_p, off_p, len_p, codes_t, off_t, len_t, npairs, out_dist, out_start, out_end);
 }
 
 int sed_fit_last_time(const sed_ctx *c, float *kernel_ms) {
@@ -185,11 +225,16 @@ struct sed_fit_index {
     // host copy the records are sorted in, and the timer of the hits kernel; none shared with a search's
     DevBuf d_hits, d_count;
     std::vector<sed_fit_hit_rec> h_hits;
+    // the fp64 route (sed_fit_f64.hip): the lanes' records of a search, the cost table, and a hits search's host copy
+    // (its device list is d_hits, sized in its own records)
+    DevBuf d_rec, d_tab;
+    std::vector<sed_fit_f64_hit> h_hits64;
     FitTimer hits_timer;
     ~sed_fit_index() {
         pin.release();
         d_text.release(); d_trec.release(); d_chunks.release(); d_query.release(); d_out.release();
         d_hits.release(); d_count.release();
+        d_rec.release(); d_tab.release();
     }
 };
 
@@ -360,8 +405,16 @@ static sed_fit_index_args fit_long_group_args(const sed_fit_index_args &a, const
     return ga;
 }
 
-// sed_fit_index_search and sed_fit_index_search_long: the plan and the launches differ, nothing else
-static int fit_index_search_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+// sed_fit_index_search, sed_fit_index_search_long and sed_fit_index_search_f64: the plan, the launches and the result
+// records differ, nothing else
+enum FitKind { FIT_SHORT_KEYS, FIT_LONG_KEYS, FIT_F64 };
+static int fit_index_plan_kind(sed_ctx *c, FitKind kind, const int32_t *len_p, int32_t nqueries, const sed_fit_index_sums &sums,
+                               sed_fit_plan_t *plan, std::vector<int32_t> *rows) {
+    return kind == FIT_LONG_KEYS ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, sums, plan, rows, &c->err)
+           : kind == FIT_F64     ? sed_fit_plan_index_f64(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err)
+                                 : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err);
+}
+static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                                int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
@@ -372,20 +425,27 @@ static int fit_index_search_of(sed_fit_index *ix, bool lng, const uint8_t *codes
     sed_fit_plan_t plan;
     std::vector<int32_t> rows;
     FitLongGroups lg;
-    rc = lng ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &rows, &c->err)
-             : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    const bool lng = kind == FIT_LONG_KEYS, f64 = kind == FIT_F64;
+    rc = fit_index_plan_kind(c, kind, len_p, nqueries, ix->sums, &plan, &rows);
     if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
-    const size_t nres = (size_t)nqueries * (size_t)ntexts;
+    const size_t nres = (size_t)nqueries * (size_t)ntexts, resbytes = (f64 ? sizeof(sed_fit_f64_best) : 8) * nres;
     sed_fit_index_args a{};
-    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8 * nres, &a, lng ? &rows : nullptr, &lg)) != SED_OK)
+    if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, resbytes, &a, lng ? &rows : nullptr, &lg)) != SED_OK)
         return rc;
-    if (!ix->d_out.reserve(8 * nres)) return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
+    if (!ix->d_out.reserve(resbytes) ||
+        (f64 && !ix->d_rec.reserve((size_t)nqueries * (size_t)ix->nchunks * sizeof(sed_fit_f64_best))))
+        return c->fail(SED_E_OOM, "device allocation failed (fit index, %zu results)", nres);
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     a.out = (unsigned long long *)ix->d_out.p;
-    if ((e = hipMemsetAsync(ix->d_out.p, 0xFF, 8 * nres, c->stream)) != hipSuccess)
+    if ((e = hipMemsetAsync(ix->d_out.p, 0xFF, resbytes, c->stream)) != hipSuccess)
         return c->hipfail(e, "upload (fit index search)");
-    if (!lng && (e = sed_launch_fit_index(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, plan.fp)) != hipSuccess)
+    sed_fit_f64_costs fc{};
+    if (f64 && ((e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess ||
+                (e = sed_launch_fit_index_f64(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, (sed_fit_f64_best *)ix->d_rec.p,
+                                              (sed_fit_f64_best *)ix->d_out.p, fc)) != hipSuccess))
+        return c->hipfail(e, "fit index fp64 kernel launch");
+    if (kind == FIT_SHORT_KEYS && (e = sed_launch_fit_index(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index kernel launch");
     for (size_t g = 0; lng && g < lg.groups.size(); ++g)  // the events bracket the groups' launches
         if ((e = sed_launch_fit_index_long(c->stream, g == 0 ? ix->timer.ev[0] : nullptr,
@@ -394,7 +454,7 @@ static int fit_index_search_of(sed_fit_index *ix, bool lng, const uint8_t *codes
                                            lg.groups[g].rows, plan.fp)) != hipSuccess)
             return c->hipfail(e, "fit index long kernel launch");
     const uint64_t *keys = (const uint64_t *)ix->pin.p;
-    if ((e = hipMemcpyAsync(ix->pin.p, ix->d_out.p, 8 * nres, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(ix->pin.p, ix->d_out.p, resbytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (fit index search)");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index kernel execution");
     ix->timer.timed = true;
@@ -402,18 +462,23 @@ static int fit_index_search_of(sed_fit_index *ix, bool lng, const uint8_t *codes
     size_t r = 0;
     for (int q = 0; q < nqueries; ++q)
         for (int d = 0; d < ntexts; ++d, ++r)
-            if (!fit_decode_key(keys[r], ix->len_t[d], inv, &out_dist[r], &out_start[r], &out_end[r]))
+            if (f64 ? !fit_decode_f64(((const sed_fit_f64_best *)ix->pin.p)[r], ix->len_t[d], &out_dist[r], &out_start[r], &out_end[r])
+                    : !fit_decode_key(keys[r], ix->len_t[d], inv, &out_dist[r], &out_start[r], &out_end[r]))
                 return c->fail(SED_E_DEVICE, "query %d, text %d: no fit result from the device", q, d);
     return SED_OK;
 }
 
 int sed_fit_index_search(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                          int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
-    return fit_index_search_of(ix, false, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
+    return fit_index_search_of(ix, FIT_SHORT_KEYS, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
+}
+int sed_fit_index_search_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                             int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+    return fit_index_search_of(ix, FIT_F64, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
 }
 int sed_fit_index_search_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                               int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
-    return fit_index_search_of(ix, true, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
+    return fit_index_search_of(ix, FIT_LONG_KEYS, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
 }
 
 int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
@@ -423,7 +488,7 @@ int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
 // Every hit within max_dist (include/sed.h).  The search's plan, chunk table and queries (fit_index_stage); the kernel
 // appends its records in whatever order the waves' atomic adds land, and counts on past `cap`.  The host reads the
 // count, then the records when they all fit, sorts them by (pair, end) - unique keys - and decodes them.
-static int fit_index_hits_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                              int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
@@ -433,22 +498,29 @@ static int fit_index_hits_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p
     sed_fit_plan_t plan;
     std::vector<int32_t> rows;
     FitLongGroups lg;
-    rc = lng ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &rows, &c->err)
-             : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &c->err);
+    const bool lng = kind == FIT_LONG_KEYS, f64 = kind == FIT_F64;
+    rc = fit_index_plan_kind(c, kind, len_p, nqueries, ix->sums, &plan, &rows);
     int32_t cut = 0;
-    if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);
+    if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);  // (fp64: its check of max_dist alone)
     if (rc != SED_OK) return rc;
     *found = 0;
     if (nqueries == 0 || ntexts == 0) return SED_OK;
     sed_fit_index_args a{};
     if ((rc = fit_index_stage(ix, plan, codes_p, off_p, len_p, nqueries, 8, &a, lng ? &rows : nullptr, &lg)) != SED_OK) return rc;
-    if ((uint64_t)cap > SIZE_MAX / sizeof(sed_fit_hit_rec) || !ix->d_count.reserve(8) ||
-        !ix->d_hits.reserve(std::max<size_t>((size_t)cap * sizeof(sed_fit_hit_rec), sizeof(sed_fit_hit_rec))))
+    const size_t recbytes = f64 ? sizeof(sed_fit_f64_hit) : sizeof(sed_fit_hit_rec);
+    if ((uint64_t)cap > SIZE_MAX / recbytes || !ix->d_count.reserve(8) ||
+        !ix->d_hits.reserve(std::max<size_t>((size_t)cap * recbytes, recbytes)))
         return c->fail(SED_E_OOM, "device allocation failed (fit index, room for %lld hits)", (long long)cap);
     hipError_t e = hipSuccess;
     if ((e = ix->hits_timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     if ((e = hipMemsetAsync(ix->d_count.p, 0, 8, c->stream)) != hipSuccess) return c->hipfail(e, "upload (fit index hits)");
-    if (!lng && (e = sed_launch_fit_index_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a, ix->d_hits.p,
+    sed_fit_f64_costs fc{};
+    if (f64 && ((e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess ||
+                (e = sed_launch_fit_index_f64_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a,
+                                                   (sed_fit_f64_hit *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
+                                                   (unsigned long long)cap, max_dist, fc)) != hipSuccess))
+        return c->hipfail(e, "fit index fp64 hits kernel launch");
+    if (kind == FIT_SHORT_KEYS && (e = sed_launch_fit_index_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a, ix->d_hits.p,
                                                (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index hits kernel launch");
     for (size_t g = 0; lng && g < lg.groups.size(); ++g)
@@ -468,6 +540,27 @@ static int fit_index_hits_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p
         return c->fail(SED_E_RANGE, "fit hits: found %lld hits, cap %lld: call again with room for them", (long long)n,
                        (long long)cap);
     if (n == 0) return SED_OK;
+    if (f64) {  // the same steps over the wider records: download, sort by (pair, end), check, decode
+        ix->h_hits64.resize((size_t)n);
+        if ((e = hipMemcpyAsync(ix->h_hits64.data(), ix->d_hits.p, (size_t)n * sizeof(sed_fit_f64_hit), hipMemcpyDeviceToHost,
+                                c->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+            return c->hipfail(e, "download (fit index hits)");
+        std::sort(ix->h_hits64.begin(), ix->h_hits64.end(), [](const sed_fit_f64_hit &x, const sed_fit_f64_hit &y) {
+            return x.pair != y.pair ? x.pair < y.pair : x.end < y.end;
+        });
+        for (size_t i = 0; i < (size_t)n; ++i) {
+            const sed_fit_f64_hit &r = ix->h_hits64[i];
+            const uint32_t q = r.pair / (uint32_t)ntexts, d = r.pair % (uint32_t)ntexts;
+            if (q >= (uint32_t)nqueries || r.end > (uint32_t)ix->len_t[d] || r.start < 0 || (uint32_t)r.start > r.end ||
+                !(r.D >= 0 && r.D <= max_dist) ||
+                (i > 0 && ix->h_hits64[i - 1].pair == r.pair && ix->h_hits64[i - 1].end == r.end))
+                return c->fail(SED_E_DEVICE, "fit hits: record %zu from the device is no hit (query %u, text %u, end %u)", i, q,
+                               d, r.end);
+            out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, r.start, (int32_t)r.end, r.D};
+        }
+        return SED_OK;
+    }
     ix->h_hits.resize((size_t)n);
     if ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(sed_fit_hit_rec), hipMemcpyDeviceToHost,
                             c->stream)) != hipSuccess ||
@@ -491,11 +584,15 @@ static int fit_index_hits_of(sed_fit_index *ix, bool lng, const uint8_t *codes_p
 
 int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                        int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
-    return fit_index_hits_of(ix, false, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
+    return fit_index_hits_of(ix, FIT_SHORT_KEYS, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
+}
+int sed_fit_index_hits_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                           int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
+    return fit_index_hits_of(ix, FIT_F64, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
 }
 int sed_fit_index_hits_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                             int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
-    return fit_index_hits_of(ix, true, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
+    return fit_index_hits_of(ix, FIT_LONG_KEYS, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
 }
 
 int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms) {

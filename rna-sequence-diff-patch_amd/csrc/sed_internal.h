@@ -291,6 +291,36 @@ hipError_t sed_launch_fit_index_long(hipStream_t stream, hipEvent_t ev0, hipEven
 hipError_t sed_launch_fit_index_long_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                           const int32_t *qlist, int rows, void *hits, unsigned long long *count,
                                           unsigned long long cap, int32_t cut, const sed_fit_params &fp);
+// The fp64 route (sed_fit_f64.hip; include/sed.h: sed_fit_search_f64): the short kernels' lanes, chunk table and
+// pattern records, the DP in fp64 as the oracle states it, for the tables and alphabets the integer keys refuse.
+// sub = SED_FIT_F64_MAXK x SED_FIT_F64_MAXK doubles on the device, row a = pattern symbol a, zeros past K.  A lane
+// writes rec[its lane index] = its first strict minimum over the columns it owns; sed_launch_fit_f64_reduce then takes,
+// per pair, the first strict minimum over the pair's lanes in chunk order into out[pair] (D = all ones: no result).
+#define SED_FIT_F64_MAXK 16
+struct sed_fit_f64_best {
+    double D;
+    int32_t start, end;
+};
+struct sed_fit_f64_hit {  // one record of the fp64 hit list
+    uint32_t pair, end;
+    int32_t start;
+    uint32_t zero;
+    double D;
+};
+struct sed_fit_f64_costs {
+    const double *sub;
+    double ins, del;
+};
+hipError_t sed_launch_fit_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_lane *lanes, int nlanes,
+                              const void *pats, const void *text, sed_fit_f64_best *rec, sed_fit_f64_best *out,
+                              const sed_fit_f64_costs &fc);
+// a.out is not used: rec = a.nqueries x a.nchunks records (query-major), out = a.nqueries x a.ntexts
+hipError_t sed_launch_fit_index_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                    sed_fit_f64_best *rec, sed_fit_f64_best *out, const sed_fit_f64_costs &fc);
+// every owned column whose sink value is <= max_dist (a plain fp64 compare), appended as sed_fit_index_hits' kernel does
+hipError_t sed_launch_fit_index_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                         sed_fit_f64_hit *hits, unsigned long long *count, unsigned long long cap,
+                                         double max_dist, const sed_fit_f64_costs &fc);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

@@ -158,6 +158,20 @@ SIGNATURES = [
                                           _i32p, C.c_int32, _i32p, C.c_int32, _f64p, C.c_int, _i32p]),
     ("sed_fit_index_long_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                            _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64, _u32p]),
+    ("sed_fit_search_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
+    ("sed_fit_index_search_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
+    ("sed_fit_index_hits_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64)]),
+    ("sed_fit_f64_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                   _i32p, _i32p, C.c_int32, _f64p, C.c_int]),
+    ("sed_fit_f64_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                    _i32p, _i32p, C.c_int32, _i32p, C.c_int64]),
+    ("sed_fit_index_f64_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                         _i32p, C.c_int32, _i32p, C.c_int32, _f64p, C.c_int]),
+    ("sed_fit_index_f64_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                          _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64]),
+    ("sed_fit_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                _i32p, _i32p, C.c_int32, C.c_char_p, C.c_int]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -307,18 +321,24 @@ class Context:
         finally:
             batch.close()
 
-    def fit(self, packed):
+    def fit(self, packed, _call="sed_fit_search"):
         """Fit search (sed_fit_search): packed = PackedPairs with the patterns (1..32 symbols) as side a and the texts
         as side b.  Returns (dist f64[], start i32[], end i32[]): for each pair the smallest distance of the pattern to
-        any substring text[start:end], the occurrence ending earliest and, among those, the shortest."""
+        any substring text[start:end], the occurrence ending earliest and, among those, the shortest.  Serves dyadic
+        tables over at most 8 symbols; fit_f64 serves the rest, and fit_route says which a search needs."""
         np_ = packed.npairs
         dist = np.zeros(max(np_, 1), np.float64)
         start = np.zeros(max(np_, 1), np.int32)
         end = np.zeros(max(np_, 1), np.int32)
-        rc = self._lib.sed_fit_search(self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.codes_b,
-                                      packed.off_b, packed.len_b, np_, dist, start, end)
-        self._check(rc, "sed_fit_search")
+        rc = getattr(self._lib, _call)(self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.codes_b,
+                                       packed.off_b, packed.len_b, np_, dist, start, end)
+        self._check(rc, _call)
         return dist[:np_], start[:np_], end[:np_]
+
+    def fit_f64(self, packed):
+        """fit() through the fp64 kernels (sed_fit_search_f64): any table of finite costs >= 0 over at most 16 symbols;
+        dist is the fp64 value of the definition's own order of additions."""
+        return self.fit(packed, "sed_fit_search_f64")
 
     def fit_last_ms(self):
         """Device time of the last fit()'s kernel (ms, HIP events)."""
@@ -515,6 +535,15 @@ class FitIndex:
     def hits_long(self, packed, max_dist, cap=None):
         """hits() for queries of 1..2048 symbols (sed_fit_index_hits_long)."""
         return self.hits(packed, max_dist, cap, "sed_fit_index_hits_long")
+
+    def search_f64(self, packed):
+        """search() through the fp64 kernels (sed_fit_index_search_f64): the tables and alphabets (up to 16 symbols)
+        search() refuses, on the same resident texts."""
+        return self.search(packed, "sed_fit_index_search_f64")
+
+    def hits_f64(self, packed, max_dist, cap=None):
+        """hits() through the fp64 kernels (sed_fit_index_hits_f64): a hit is a column whose fp64 value is <= max_dist."""
+        return self.hits(packed, max_dist, cap, "sed_fit_index_hits_f64")
 
     @staticmethod
     def long_plan(costs, options, len_p, len_t):
@@ -871,6 +900,9 @@ class EngineClient:
     def fit(self, packed):
         return self._call("fit", packed)
 
+    def fit_f64(self, packed):
+        return self._call("fit_f64", packed)
+
     def full_matrix(self, codes_a, codes_b):
         return self._call("full_matrix", np.asarray(codes_a, np.uint8), np.asarray(codes_b, np.uint8))
 
@@ -940,6 +972,8 @@ def _serve(rx, tx, device, pooled=False):
                 val = ctx.deepen(*args)
             elif op == "fit":
                 val = ctx.fit(*args)
+            elif op == "fit_f64":
+                val = ctx.fit_f64(*args)
             elif op == "full_matrix":
                 val = ctx.full_matrix(*args)
             else:
@@ -1257,6 +1291,90 @@ def fit_lanes(costs, options, len_p, len_t):
     lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
     lanes["tw"] &= 0xFFFFFFFF
     return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
+
+
+FIT_F64_PLAN_FIELDS = FIT_PLAN_FIELDS + ("one_lane",)
+FIT_ROUTES = {0: "int", 1: "f64"}
+
+
+def _fit_pair_args(costs, options, len_p, len_t):
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
+    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
+    return (int(K), np.ascontiguousarray(sub, np.float64).ravel(), np.ascontiguousarray(sub_int, np.uint8).ravel(),
+            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options), lp, lt, len(len_p))
+
+
+def _fit_fail(name, rc):
+    err = SedError("%s failed (%d)" % (name, rc))
+    err.code = rc
+    return err
+
+
+def _fit_f64_plan_dict(out):
+    return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_F64_PLAN_FIELDS, out)}
+
+
+def fit_f64_plan(costs, options, len_p, len_t):
+    """What Context.fit_f64 would decide, without a device (sed_fit_f64_plan): fit_plan's fields with scale = 0 (fp64)
+    and "one_lane": 0, or why every text runs as one lane (1 insert = 0, 2 the window argument's conditions fail).
+    Arguments and errors as fit_plan."""
+    out = np.zeros(len(FIT_F64_PLAN_FIELDS), np.float64)
+    rc = load().sed_fit_f64_plan(*_fit_pair_args(costs, options, len_p, len_t), out, len(out))
+    if rc != 0:
+        raise _fit_fail("sed_fit_f64_plan", rc)
+    return _fit_f64_plan_dict(out)
+
+
+def fit_f64_lanes(costs, options, len_p, len_t):
+    """The lane records Context.fit_f64 would run, without a device (sed_fit_f64_lanes): {field: int64[nlanes]} over
+    FIT_LANE_FIELDS, as fit_lanes' first result."""
+    nl = fit_f64_plan(costs, options, len_p, len_t)["lanes"]
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    rc = load().sed_fit_f64_lanes(*_fit_pair_args(costs, options, len_p, len_t), rec.ravel(), nl)
+    if rc != 0:
+        raise _fit_fail("sed_fit_f64_lanes", rc)
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    return lanes
+
+
+def fit_index_f64_plan(costs, options, len_p, len_t):
+    """What FitIndex.search_f64 would decide, without a device (sed_fit_index_f64_plan): fit_f64_plan's fields for the
+    queries x texts cross product."""
+    out = np.zeros(len(FIT_F64_PLAN_FIELDS), np.float64)
+    rc = load().sed_fit_index_f64_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out))
+    if rc != 0:
+        raise _fit_fail("sed_fit_index_f64_plan", rc)
+    return _fit_f64_plan_dict(out)
+
+
+def fit_index_f64_lanes(costs, options, len_p, len_t):
+    """The lane records FitIndex.search_f64 / hits_f64 would run, without a device (sed_fit_index_f64_lanes), query-major,
+    pair = query * len(len_t) + text."""
+    nl = fit_index_f64_plan(costs, options, len_p, len_t)["lanes"]
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    rc = load().sed_fit_index_f64_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl)
+    if rc != 0:
+        raise _fit_fail("sed_fit_index_f64_lanes", rc)
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    return lanes
+
+
+def fit_route(costs, options, len_p, len_t):
+    """Which route serves the search fit_plan's arguments describe, without a device (sed_fit_route): (route, why).
+    route = "int" (Context.fit serves it), "f64" (only Context.fit_f64 does; why = the integer route's refusal) or
+    None (neither; why = both refusals).  Bad arguments raise SedError as fit_plan does."""
+    why = C.create_string_buffer(1024)
+    rc = load().sed_fit_route(*_fit_pair_args(costs, options, len_p, len_t), why, len(why))
+    text = why.value.decode()
+    if rc in FIT_ROUTES:
+        return FIT_ROUTES[rc], text
+    if rc == SED_E_RANGE:
+        return None, text
+    raise _fit_fail("sed_fit_route", rc)
 
 
 def _fit_index_args(costs, options, len_p, len_t):

@@ -18,6 +18,7 @@ import math
 from collections import OrderedDict
 
 import StringEditDistance as SED
+import sedgpu
 
 _CACHE = OrderedDict()
 _CACHE_SIZE = 8
@@ -103,17 +104,55 @@ def nearest(query, seqs, k, user_cost=False, distance_fn=None):
     return [(seqs[i], 1 / (1 + v)) for v, i in order]
 
 
-def fit_search(query, seqs_or_collection, user_cost=False, max_dist=None, scripts=False, fit_fn=None):
+ROUTES = ("int", "f64", "auto")
+
+
+def fit_route(queries, seqs, user_cost=False):
+    """"int" or "f64": the fit kernels that serve these queries against these documents (route="auto").  The integer
+    kernels whenever sedgpu.fit_route says they serve the cost table over the symbols of queries and documents, the
+    longest query and the longest document; the fp64 kernels when only they do.  A search neither serves, or one whose
+    symbols the cost table does not resolve, goes to the integer call, which raises what it always raised."""
+    queries, seqs = list(queries), list(seqs)
+    if not queries or not seqs:
+        return "int"
+    n = max(len(queries), len(seqs))  # every query and every document once: the plan's alphabet is the search's
+    try:
+        plan = SED.batch_plan([queries[i % len(queries)] for i in range(n)], [seqs[i % len(seqs)] for i in range(n)],
+                              user_cost)
+    except KeyError:
+        return "int"
+    costs = (plan.K, plan.sub, plan.sub_int, plan.ins, plan.ins_int, plan.dele, plan.del_int)
+    longest = max(map(len, seqs))
+    route, _ = sedgpu.fit_route(costs, {}, [len(q) for q in queries], [longest] * len(queries))
+    return "f64" if route == "f64" else "int"
+
+
+def _resolve_route(route, queries, seqs, user_cost):
+    if route not in ROUTES:
+        raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
+    return fit_route(queries, seqs, user_cost) if route == "auto" else route
+
+
+def fit_search(query, seqs_or_collection, user_cost=False, max_dist=None, scripts=False, fit_fn=None, route="int"):
     """Where in each document does query occur, approximately: [(sequence, 1 / (1 + dist), start, end)] in collection
     order, dist = the smallest distance from query to any substring sequence[start:end] (the one ending earliest, then
     the shortest; StringEditDistance.fit_batch), one engine launch for the collection.  max_dist keeps only the hits
     with dist <= max_dist.  scripts=True appends the edit script of (query, sequence[start:end]) to each kept hit, from
     one edit_script_batch call; patching(es, query) then gives the matched substring.
-    fit_fn(patterns, texts, user_cost) -> [(dist, start, end)] replaces the engine (CPU tests).  Not cached."""
+    route: "int" (the default) runs the integer kernels, which serve dyadic cost tables over at most 8 symbols and raise
+    SedError otherwise; "f64" runs the fp64 kernels, which serve any table of costs >= 0 over at most 16 symbols (IUPAC
+    documents under costs.json); "auto" takes the integer kernels whenever they serve the search (fit_route).  The
+    scripts need no route: the batch engine has its own fp64 path.
+    fit_fn(patterns, texts, user_cost) -> [(dist, start, end)] replaces the engine (CPU tests); the fp64 route calls it
+    with f64=True as a fourth, keyword argument.  Not cached."""
     seqs = _sequences(seqs_or_collection)
     if not seqs:
         return []
-    hits = (fit_fn or SED.fit_batch)([query] * len(seqs), seqs, user_cost)
+    engine = fit_fn or SED.fit_batch
+    if _resolve_route(route, [query], seqs, user_cost) == "f64":
+        hits = engine([query] * len(seqs), seqs, user_cost, f64=True)
+    else:
+        hits = engine([query] * len(seqs), seqs, user_cost)
     kept = [(s, d, a, b) for s, (d, a, b) in zip(seqs, hits) if max_dist is None or d <= max_dist]
     out = [(s, 1 / (1 + d), a, b) for s, d, a, b in kept]
     if scripts and kept:
@@ -137,14 +176,31 @@ class FitIndex:
 
     long_patterns=True (search, search_many, occurrences, occurrences_many) serves queries of up to 2048 symbols: those
     of at most 32 go through the calls above, the longer ones through the index's search_long / hits_long, and the
-    results merge in query order.  The default refuses a query over 32 as before."""
+    results merge in query order.  The default refuses a query over 32 as before.
+
+    route (the constructor's, and per call on search, search_many, occurrences, occurrences_many; None = the
+    constructor's): "int", "f64" or "auto" as fit_search takes it, for the queries of at most 32 symbols (the long calls
+    have integer kernels only).  An index whose constructor route is "f64" or "auto" is built with f64=True (up to 16
+    symbols; index_fn is called with that keyword), and serves integer searches too; one built under the default keeps
+    the 8-symbol bound, whatever route a later call names.  The fp64 route calls the index's search_f64 / hits_f64."""
 
     SHORT = 32  # the longest query search() / hits() serve
 
-    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None):
+    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None, route="int"):
+        if route not in ROUTES:
+            raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
         self.seqs = _sequences(seqs_or_collection)
         self.user_cost = user_cost
-        self._ix = (index_fn or SED.fit_index)(self.seqs, user_cost) if self.seqs else None
+        self.route = route
+        make = index_fn or SED.fit_index
+        self._ix = (make(self.seqs, user_cost) if route == "int" else make(self.seqs, user_cost, f64=True)) \
+            if self.seqs else None
+
+    def _calls(self, route, queries, short):
+        """(the search call, the hits call) that serve the short queries under route"""
+        r = _resolve_route(self.route if route is None else route, [queries[i] for i in short], self.seqs,
+                           self.user_cost) if short else "int"
+        return (self._ix.search_f64, self._ix.hits_f64) if r == "f64" else (self._ix.search, self._ix.hits)
 
     def _split(self, queries, long_patterns):
         """(indices the short calls serve, indices the long calls serve)"""
@@ -153,7 +209,7 @@ class FitIndex:
         return ([i for i, q in enumerate(queries) if len(q) <= self.SHORT],
                 [i for i, q in enumerate(queries) if len(q) > self.SHORT])
 
-    def search_many(self, queries, max_dist=None, scripts=False, long_patterns=False):
+    def search_many(self, queries, max_dist=None, scripts=False, long_patterns=False, route=None):
         queries = list(queries)
         if not self.seqs:
             return [[] for _ in queries]
@@ -161,7 +217,7 @@ class FitIndex:
             return []
         short, lng = self._split(queries, long_patterns)
         rows = [None] * len(queries)
-        for idx, call in ((short, self._ix.search), (lng, getattr(self._ix, "search_long", None))):
+        for idx, call in ((short, self._calls(route, queries, short)[0]), (lng, getattr(self._ix, "search_long", None))):
             if idx:
                 for i, r in zip(idx, call([queries[i] for i in idx])):
                     rows[i] = r
@@ -174,10 +230,10 @@ class FitIndex:
             out = [[hit + (next(es)[1],) for hit in o] for o in out]
         return out
 
-    def search(self, query, max_dist=None, scripts=False, long_patterns=False):
-        return self.search_many([query], max_dist, scripts, long_patterns)[0]
+    def search(self, query, max_dist=None, scripts=False, long_patterns=False, route=None):
+        return self.search_many([query], max_dist, scripts, long_patterns, route)[0]
 
-    def occurrences_many(self, queries, max_dist, all_ends=False, scripts=False, long_patterns=False):
+    def occurrences_many(self, queries, max_dist, all_ends=False, scripts=False, long_patterns=False, route=None):
         """For each query, [(sequence, 1 / (1 + d), start, end)] for every occurrence within max_dist, in collection
         order, then by end: one engine launch for all the queries (StringEditDistance.FitIndex.hits).  A hit is an end
         column e of a document whose best distance E(e) = min over s of d(query, sequence[s:e]) is <= max_dist, with
@@ -192,7 +248,7 @@ class FitIndex:
             return []
         short, lng = self._split(queries, long_patterns)
         hits = []
-        for idx, call in ((short, self._ix.hits), (lng, getattr(self._ix, "hits_long", None))):
+        for idx, call in ((short, self._calls(route, queries, short)[1]), (lng, getattr(self._ix, "hits_long", None))):
             if idx:
                 hits += [(idx[q], t, a, b, d) for q, t, a, b, d in call([queries[i] for i in idx], max_dist)]
         hits.sort(key=lambda h: (h[0], h[1], h[3]))  # (each call's list is sorted; the merge is by query)
@@ -206,8 +262,8 @@ class FitIndex:
             out = [[hit + (next(es)[1],) for hit in o] for o in out]
         return out
 
-    def occurrences(self, query, max_dist, all_ends=False, scripts=False, long_patterns=False):
-        return self.occurrences_many([query], max_dist, all_ends, scripts, long_patterns)[0]
+    def occurrences(self, query, max_dist, all_ends=False, scripts=False, long_patterns=False, route=None):
+        return self.occurrences_many([query], max_dist, all_ends, scripts, long_patterns, route)[0]
 
     def close(self):
         if self._ix is not None:
@@ -232,9 +288,9 @@ def local_minima(hits):
 
 
 def fit_occurrences(query, seqs_or_collection, max_dist, user_cost=False, all_ends=False, scripts=False, index_fn=None,
-                    long_patterns=False):
+                    long_patterns=False, route="int"):
     """FitIndex.occurrences in one shot: builds an index over the documents, searches it and closes it."""
-    ix = FitIndex(seqs_or_collection, user_cost, index_fn=index_fn)
+    ix = FitIndex(seqs_or_collection, user_cost, index_fn=index_fn, route=route)
     try:
         return ix.occurrences(query, max_dist, all_ends, scripts, long_patterns)
     finally:
