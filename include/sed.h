@@ -462,7 +462,7 @@ int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, doub
  * chunk of a text), the pattern's rows spread over its 64 lanes, R = 2, 4, 8, 16 or 32 rows a lane (the smallest with
  * 64 R >= P; SED_OPT_FIT_ROWS forces one R for every query of a call), and the queries of a call run grouped by R, one
  * launch per group and 65535 queries.  The cost models served (anything else: SED_E_RANGE, the text says which condition
- * failed; the long calls have no fp64 fallback, the _f64 calls below serve P <= 32 only):
+ * failed; the _long_f64 calls below serve what these refuse, and sed_fit_long_route says which of the two serves a search):
  *   at most 8 symbols; some S = 2^k, k <= 8, makes every cost an integer in 0..255 with (insert + delete) * S <= 255;
  *   P * delete * S + 128 * insert * S <= 65535 over the call's longest pattern (distance and the 128 columns of insert a
  *   key carries between rebases share one 16-bit field);
@@ -495,7 +495,7 @@ int sed_fit_index_long_lanes(int K, const double *sub, const uint8_t *sub_int, d
  * above; the index is used as it stands, so integer and fp64 searches may alternate on one index.  What differs:
  *   cost models served: at most 16 symbols (K <= 16; more: SED_E_RANGE, the text names the bound); insert, delete and
  *   every substitution cost finite and >= 0 (a negative cost: SED_E_RANGE, the text names it; -0.0 counts as +0.0);
- *   1 <= P <= 32.  No scale, no byte ranges, and no limit on a text's columns (starts are 32 bits): any int32 length.
+ *   1 <= P <= 32 (the _long_f64 calls below: 1 <= P <= 2048).  No scale, no byte ranges, and no limit on a text's columns (starts are 32 bits): any int32 length.
  *   The definition met is sed_fit_search's, evaluated as oracle/sed_oracle.c: sed_oracle_fit_pair states it: every
  *   candidate of a cell is ONE fp64 add (left + insert, up + delete, diagonal + cost), borders D[0][j] = 0 and
  *   D[i][0] = (double)i * delete, every cell the lexicographic minimum of (D, -start), the hit the first strict
@@ -544,6 +544,42 @@ int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, do
 int sed_fit_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
                   double del, int del_is_int, const int32_t *options, int noptions,
                   const int32_t *len_p, const int32_t *len_t, int32_t npairs, char *why, int why_len);
+
+/* The fp64 route for long patterns: sed_fit_index_search_long and sed_fit_index_hits_long for the cost tables and
+ * alphabets their integer keys refuse, i.e. the _f64 calls above for 1 <= P <= 2048.  Arguments, results, state errors,
+ * the cap protocol and the index are those of the _long calls; integer, fp64, long and long-fp64 searches may alternate
+ * on one index.  The kernel is the long calls' wave (one per (query, chunk of a text), R = 2 .. 32 rows a lane, the
+ * smallest with 64 R >= P, SED_OPT_FIT_ROWS forcing one; one launch per R group and 65535 queries) running the fp64
+ * calls' cell: every candidate ONE fp64 add, the (D, -start) minimum, no scale, 32-bit starts.  So the results are the
+ * oracle's values bit for bit; a query of P <= 32 gives what sed_fit_index_search_f64 / sed_fit_index_hits_f64 give, and
+ * on a table the _long calls serve the results equal theirs, bit for bit.  Envelope: K <= 16, every cost finite and >= 0,
+ * 1 <= P <= 2048 over the call; anything else is SED_E_RANGE and the text names the bound or the cost.  Chunks: the
+ * _long calls' rule (waves for lanes), never below W = P + floor(P * delete / insert) + 2 over the call's longest
+ * pattern; with insert = 0, costs outside 2^-900 .. 2^900 or P * delete / insert above 2^20 every text runs as one wave
+ * (DESIGN.md 3.6j).  SED_OPT_FIT_CHUNK forces the chunk.  sed_fit_index_last_time / sed_fit_index_hits_last_time report
+ * these calls too (the search's time includes the reduce kernels).  A refused call leaves the context and the index
+ * usable. */
+int sed_fit_index_search_long_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                                  int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end);
+int sed_fit_index_hits_long_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                                int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found);
+/* What the long fp64 calls would decide, without a device: out[] as sed_fit_index_f64_plan lays it out (3 lanes = the
+ * waves; 6 = why every text runs as one wave), out_rows[q] (may be NULL) as sed_fit_index_long_plan; and the wave
+ * records, as sed_fit_index_f64_lanes lays them out (for P <= 32 and the same chunk length they are its records). */
+int sed_fit_index_long_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                                double del, int del_is_int, const int32_t *options, int noptions,
+                                const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts, double *out,
+                                int nout, int32_t *out_rows);
+int sed_fit_index_long_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                                 double del, int del_is_int, const int32_t *options, int noptions,
+                                 const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts,
+                                 int32_t *out_lanes, int64_t max_lanes);
+/* sed_fit_route for the long calls, over sed_fit_index_long_plan's arguments: SED_FIT_ROUTE_INT whenever
+ * sed_fit_index_search_long serves the search, SED_FIT_ROUTE_F64 when only sed_fit_index_search_long_f64 does (why = the
+ * integer route's refusal), else the negative code both fail with (why = both texts, "; " between them). */
+int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                       double del, int del_is_int, const int32_t *options, int noptions,
+                       const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts, char *why, int why_len);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

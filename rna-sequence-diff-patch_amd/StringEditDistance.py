@@ -777,6 +777,14 @@ class _EngineIndex:
         self.ctx.set_costs(plan)
         return self.ix.hits_f64(packed, max_dist)
 
+    def search_long_f64(self, plan, packed):
+        self.ctx.set_costs(plan)
+        return self.ix.search_long_f64(packed)
+
+    def hits_long_f64(self, plan, packed, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.hits_long_f64(packed, max_dist)
+
     def close(self):
         self.ix.close()
 
@@ -789,7 +797,8 @@ class FitIndex:
     resolves them; or `alphabet` first, for a collection that may grow into symbols it does not hold yet).  A search
     whose patterns bring symbols the texts do not have appends them for that search only; more than 8 symbols in all
     raise SedError (the integer kernels serve at most 8).  f64=True builds the index for the fp64 route instead: the
-    bound is 16 symbols, and search_f64 / hits_f64 serve any table of costs >= 0 (search / hits still run the integer
+    bound is 16 symbols, and search_f64 / hits_f64 (and search_long_f64 / hits_long_f64 for patterns of up to 2048
+    symbols) serve any table of costs >= 0 (search / hits still run the integer
     kernels and refuse what those refuse).  The cost table is read at every search, so edits to it take effect,
     and the KeyErrors are the reference's for the first offending (pattern, text) in pattern-major order."""
 
@@ -860,6 +869,15 @@ class FitIndex:
         """hits() through the fp64 kernels (include/sed.h: sed_fit_index_hits_f64)."""
         return self.hits(patterns, max_dist, "hits_f64")
 
+    def search_long_f64(self, patterns):
+        """search_f64() for patterns of 1..2048 symbols (include/sed.h: sed_fit_index_search_long_f64): what search_long
+        refuses, e.g. a 76-nt query over IUPAC documents under costs.json, on an index built f64=True."""
+        return self.search(patterns, "search_long_f64")
+
+    def hits_long_f64(self, patterns, max_dist):
+        """hits_f64() for patterns of 1..2048 symbols (include/sed.h: sed_fit_index_hits_long_f64)."""
+        return self.hits(patterns, max_dist, "hits_long_f64")
+
     def hits(self, patterns, max_dist, _dev="hits"):
         """[(pattern index, text index, start, end, dist)] sorted by (pattern, text, end): for every end column e of a
         text (0 <= e <= its length) the smallest wagnerFisher(pattern, text[s:e]) value over s, with the largest such s
@@ -881,7 +899,7 @@ class FitIndex:
 def fit_index(texts, userCosts=False, alphabet=None, engine=None, f64=False):
     """A FitIndex over texts: fit_batch for callers who search one collection query after query.  engine(codes, off,
     lens) -> an object with search(plan, packed), hits(plan, packed, max_dist), their search_long / hits_long,
-    search_f64 / hits_f64 and close() replaces the device (CPU tests)."""
+    search_f64 / hits_f64, search_long_f64 / hits_long_f64 and close() replaces the device (CPU tests)."""
     return FitIndex(texts, userCosts, alphabet, engine, f64)
 
 

@@ -2,7 +2,8 @@
 // cutoff of a fit search, from the cost model, the options and the lengths.  No HIP call.  Also the device-free fit
 // entry points of include/sed.h (sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes,
 // sed_fit_index_long_plan, sed_fit_index_long_lanes, sed_fit_cutoff_scaled, sed_fit_f64_plan, sed_fit_f64_lanes,
-// sed_fit_index_f64_plan, sed_fit_index_f64_lanes, sed_fit_route).
+// sed_fit_index_f64_plan, sed_fit_index_f64_lanes, sed_fit_route, sed_fit_index_long_f64_plan,
+// sed_fit_index_long_f64_lanes, sed_fit_long_route).
 #include "sed_fit_plan.h"
 
 #include <algorithm>
@@ -39,6 +40,7 @@ struct FitLayout {
 };
 static const FitLayout FIT_SHORT = {SED_LANE_MAXM, 64, 0};
 static const FitLayout FIT_LONG = {SED_FIT_LONG_MAXP, 1, 128};  // (128 = sed_fit_dp.h: FIT_REBASE)
+static const FitLayout FIT_LONG_F64 = {SED_FIT_LONG_MAXP, 1, 0};  // sed_fit_long_f64.hip: the waves, no key field to share
 
 // The one rule every caller shares: scale, update addends and W from the costs and the longest pattern, then the chunk
 // length and the span check.  *chunk_out = the chunk every text is cut by (0: one lane per text); plan->chunk = the
@@ -208,10 +210,10 @@ int sed_fit_plan_index_long(const sed_costs &c, const sed_opts &o, const int32_t
 
 // ---- the fp64 route ----
 // The rule of the fp64 plans: the envelope, the table the kernels read, W and the chunk.  The chunk rule is
-// fit_plan_rule's (the short layout: 64 lanes a wave; its two wave constants carried over, not measured for this
-// kernel), without the span limit.
-static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSums &sm, sed_fit_plan_t *plan, std::string *err,
-                             int64_t *chunk_out) {
+// fit_plan_rule's under the layout (FIT_SHORT: 64 lanes a wave; FIT_LONG_F64: one unit a wave; its two wave constants
+// carried over, measured for neither fp64 kernel), without the span limit.
+static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSums &sm, const FitLayout &lay, sed_fit_plan_t *plan,
+                             std::string *err, int64_t *chunk_out) {
     if (c.K > SED_FIT_F64_MAXK)
         return sed_plan_fail(err, SED_E_RANGE, "fit search (fp64): the batch has %d symbols (at most %d)", c.K, SED_FIT_F64_MAXK);
     auto cost_ok = [](double v) { return std::isfinite(v) && v >= 0; };  // (-0.0 >= 0)
@@ -230,7 +232,8 @@ static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSum
         for (int b = 0; b < c.K; ++b) plan->f64_sub[(size_t)a * SED_FIT_F64_MAXK + b] = c.sub[a * c.K + b] + 0.0;
     // W = P + Y, Y = floor(P delete / insert) + 2, under the hypotheses of DESIGN.md 3.6i: insert, and delete unless 0,
     // within 2^-900 .. 2^900 (no product here under- or overflows), P delete / insert <= 2^20, and, checked as
-    // computed, (Y - 1) insert >= P delete (1 + 2^-30).  Anything else: one lane per text.
+    // computed, (Y - 1) insert >= P delete (1 + 2^-30).  Anything else: one lane per text.  The argument holds for the
+    // long layout's P <= 2048 as it stands (the straight-down path's (1 + u)^2047 is below 1 + 2^-42).
     const int pmax = sm.pmax;
     const double ins = plan->f64_ins, del = plan->f64_del, lo = std::ldexp(1.0, -900), hi = std::ldexp(1.0, 900);
     plan->W = -1;
@@ -248,8 +251,8 @@ static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSum
     int64_t chunk = 0;
     if (plan->W >= 0 && o.fit_chunk > 0)
         chunk = o.fit_chunk;
-    else if (plan->W >= 0 && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * FIT_SHORT.units_per_wave) {
-        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * FIT_SHORT.units_per_wave));
+    else if (plan->W >= 0 && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * lay.units_per_wave) {
+        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * lay.units_per_wave));
         chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
     }
     const bool split = chunk > 0 && sm.nmax + 1 > chunk;
@@ -273,7 +276,7 @@ int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t 
         sm.nmax = std::max<int64_t>(sm.nmax, len_t[p]);
     }
     int64_t chunk = 0;
-    const int rc = fit_plan_rule_f64(c, o, sm, plan, err, &chunk);
+    const int rc = fit_plan_rule_f64(c, o, sm, FIT_SHORT, plan, err, &chunk);
     if (rc != SED_OK) return rc;
     plan->first.assign((size_t)npairs + 1, 0);
     plan->cells = plan->nominal = 0;
@@ -288,8 +291,10 @@ int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t 
     return SED_OK;
 }
 
-int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
-                           const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
+// The fp64 plan of an index search under either layout; rows (the wave layout's, may be null) = each query's R.
+static int fit_plan_index_f64_of(const sed_costs &c, const sed_opts &o, const FitLayout &lay, const int32_t *len_p,
+                                 int32_t nqueries, const sed_fit_index_sums &tx, sed_fit_plan_t *plan,
+                                 std::vector<int32_t> *rows, std::string *err) {
     if (nqueries < 0 || (nqueries > 0 && !len_p) || tx.ntexts < 0) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
     FitSums sm;
     double psum = 0;
@@ -297,9 +302,12 @@ int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t 
     for (int q = 0; q < nqueries && tx.ntexts > 0; ++q) {
         if (tx.first_negative >= 0 && (q == 0 ? tx.first_negative == 0 : q == 1))
             return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
-        if (len_p[q] < 1 || len_p[q] > SED_LANE_MAXM)
+        if (len_p[q] < 1 || len_p[q] > lay.pmax)
             return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q],
-                                 SED_LANE_MAXM);
+                                 lay.pmax);
+        if (lay.units_per_wave == 1 && o.fit_rows && len_p[q] > 64 * o.fit_rows)  // (the wave layout reads the option)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d exceeds the 64 * %d rows of SED_OPT_FIT_ROWS",
+                                 q, len_p[q], o.fit_rows);
         sm.pmax = std::max(sm.pmax, len_p[q]);
         psum += (double)len_p[q];
     }
@@ -311,13 +319,28 @@ int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t 
         sm.nmax = tx.nmax;
     }
     int64_t chunk = 0;
-    const int rc = fit_plan_rule_f64(c, o, sm, plan, err, &chunk);
+    const int rc = fit_plan_rule_f64(c, o, sm, lay, plan, err, &chunk);
     if (rc != SED_OK) return rc;
     plan->first.clear();
     plan->lanes = 0;
     plan->cells = 0;
     plan->nominal = psum * (tx.cols - (double)tx.ntexts);
+    if (rows) {
+        rows->resize((size_t)nqueries);
+        for (int q = 0; q < nqueries; ++q) (*rows)[q] = o.fit_rows ? o.fit_rows : sed_fit_long_rows(len_p[q]);
+    }
     return SED_OK;
+}
+
+int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                           const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
+    return fit_plan_index_f64_of(c, o, FIT_SHORT, len_p, nqueries, tx, plan, nullptr, err);
+}
+
+int sed_fit_plan_index_long_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                                const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows,
+                                std::string *err) {
+    return fit_plan_index_f64_of(c, o, FIT_LONG_F64, len_p, nqueries, tx, plan, rows, err);
 }
 
 int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
@@ -555,7 +578,8 @@ static int fit_f64_plan_of(int K, const double *sub, const uint8_t *sub_int, dou
 // sed_fit_index_f64_plan's and sed_fit_index_f64_lanes' common half (fit_index_plan_of for the fp64 plan)
 static int fit_index_f64_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                                 const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks) {
+                                 const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks,
+                                 std::vector<int32_t> *long_rows = nullptr) {
     if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
     sed_costs c;
     sed_opts o;
@@ -568,7 +592,8 @@ static int fit_index_f64_plan_of(int K, const double *sub, const uint8_t *sub_in
         tx.cols += (double)len_t[d] + 1;
         tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
     }
-    const int rc = sed_fit_plan_index_f64(c, o, len_p, nqueries, tx, p, nullptr);
+    const int rc = long_rows ? sed_fit_plan_index_long_f64(c, o, len_p, nqueries, tx, p, long_rows, nullptr)
+                             : sed_fit_plan_index_f64(c, o, len_p, nqueries, tx, p, nullptr);
     if (rc != SED_OK) return rc;
     double computed = 0, psum = 0;
     const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
@@ -612,14 +637,16 @@ int sed_fit_index_f64_plan(int K, const double *sub, const uint8_t *sub_int, dou
                             p, out, nout);
 }
 
-int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                            int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                            const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
+// sed_fit_index_f64_lanes' and sed_fit_index_long_f64_lanes' common half (long_rows: the wave layout's plan)
+static int fit_index_f64_lanes_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                                  const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes,
+                                  std::vector<int32_t> *long_rows) {
     if (max_lanes < 0 || (max_lanes && !out_lanes)) return SED_E_ARG;
     sed_fit_plan_t p;
     std::vector<sed_fit_chunk> chunks;
     const int rc = fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
-                                         len_t, ntexts, &p, &chunks);
+                                         len_t, ntexts, &p, &chunks, long_rows);
     if (rc != SED_OK) return rc;
     if (p.lanes > max_lanes) return SED_E_ARG;
     sed_fit_lane *out = (sed_fit_lane *)out_lanes;
@@ -630,6 +657,34 @@ int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, do
             *out++ = ln;
         }
     return SED_OK;
+}
+
+int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                            int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                            const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
+    return fit_index_f64_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
+                                  ntexts, out_lanes, max_lanes, nullptr);
+}
+
+int sed_fit_index_long_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                                const int32_t *len_t, int32_t ntexts, double *out, int nout, int32_t *out_rows) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    std::vector<int32_t> rows;
+    const int rc = fit_f64_plan_out(fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions,
+                                                          len_p, nqueries, len_t, ntexts, &p, nullptr, &rows),
+                                    p, out, nout);
+    if (rc == SED_OK && out_rows && !rows.empty()) std::memcpy(out_rows, rows.data(), rows.size() * sizeof(int32_t));
+    return rc;
+}
+
+int sed_fit_index_long_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                 int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                                 const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
+    std::vector<int32_t> rows;
+    return fit_index_f64_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
+                                  ntexts, out_lanes, max_lanes, &rows);
 }
 
 int sed_fit_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
@@ -647,6 +702,35 @@ int sed_fit_route(int K, const double *sub, const uint8_t *sub_int, double ins, 
     if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
     sed_fit_plan_t pf;
     rc = sed_fit_plan_batch_f64(c, o, len_p, len_t, npairs, &pf, &e_f64);
+    const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
+    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
+    return rc == SED_OK ? SED_FIT_ROUTE_F64 : rc;
+}
+
+int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                       int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                       const int32_t *len_t, int32_t ntexts, char *why, int why_len) {
+    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
+    if (why_len) why[0] = 0;
+    if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return rc;
+    sed_fit_index_sums tx;
+    tx.ntexts = ntexts;
+    for (int d = 0; d < ntexts; ++d) {
+        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
+        tx.cols += (double)len_t[d] + 1;
+        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
+    }
+    sed_fit_plan_t p;
+    std::vector<int32_t> rows;
+    std::string e_int, e_f64;
+    if ((rc = sed_fit_plan_index_long(c, o, len_p, nqueries, tx, &p, &rows, &e_int)) == SED_OK) return SED_FIT_ROUTE_INT;
+    if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
+    sed_fit_plan_t pf;
+    rc = sed_fit_plan_index_long_f64(c, o, len_p, nqueries, tx, &pf, &rows, &e_f64);
     const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
     if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
     return rc == SED_OK ? SED_FIT_ROUTE_F64 : rc;

@@ -74,3 +74,10 @@ int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t 
                            sed_fit_plan_t *plan, std::string *err);
 int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
                            const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err);
+// The fp64 plan of the long calls (include/sed.h: sed_fit_index_search_long_f64; kernels: sed_fit_long_f64.hip), through
+// the same fp64 rule under the wave layout: patterns of 1..SED_FIT_LONG_MAXP symbols, the chunk rule counting waves, the
+// same W and one_lane (the window argument does not depend on P <= 32: DESIGN.md 3.6j), and rows[q] as
+// sed_fit_plan_index_long fills them.  For P <= 32 and the same chunk the records are sed_fit_plan_index_f64's.
+int sed_fit_plan_index_long_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                                const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows,
+                                std::string *err);

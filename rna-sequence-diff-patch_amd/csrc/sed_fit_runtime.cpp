@@ -1,7 +1,7 @@
 // sed_fit_runtime.cpp — fit search's entry points of the C-ABI (include/sed.h): sed_fit_search over listed pairs, and
 // sed_fit_index_* over a resident text index (best hit per (query, text), or every hit within a distance), each also as
-// its _f64 sibling.  What a search runs is the fit planner's decision (sed_fit_plan.cpp), the kernels are sed_fit.hip,
-// sed_fit_long.hip and sed_fit_f64.hip; here: pack, reserve, upload, launch, download, decode, on the context's stream
+// its _f64 sibling, the index calls also as _long and _long_f64.  What a search runs is the fit planner's decision
+// (sed_fit_plan.cpp), the kernels are sed_fit.hip, sed_fit_long.hip, sed_fit_f64.hip and sed_fit_long_f64.hip; here: pack, reserve, upload, launch, download, decode, on the context's stream
 // (sed_runtime.h).  The routes of a call differ in the plan, the launch and the decoding, and share the staging.
 #include "sed_fit_plan.h"
 #include "sed_runtime.h"
@@ -405,14 +405,17 @@ static sed_fit_index_args fit_long_group_args(const sed_fit_index_args &a, const
     return ga;
 }
 
-// sed_fit_index_search, sed_fit_index_search_long and sed_fit_index_search_f64: the plan, the launches and the result
-// records differ, nothing else
-enum FitKind { FIT_SHORT_KEYS, FIT_LONG_KEYS, FIT_F64 };
+// sed_fit_index_search, sed_fit_index_search_long, sed_fit_index_search_f64 and sed_fit_index_search_long_f64: the plan,
+// the launches and the result records differ, nothing else
+enum FitKind { FIT_SHORT_KEYS, FIT_LONG_KEYS, FIT_F64, FIT_LONG_F64 };
+static inline bool fit_kind_long(FitKind k) { return k == FIT_LONG_KEYS || k == FIT_LONG_F64; }
+static inline bool fit_kind_f64(FitKind k) { return k == FIT_F64 || k == FIT_LONG_F64; }
 static int fit_index_plan_kind(sed_ctx *c, FitKind kind, const int32_t *len_p, int32_t nqueries, const sed_fit_index_sums &sums,
                                sed_fit_plan_t *plan, std::vector<int32_t> *rows) {
-    return kind == FIT_LONG_KEYS ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, sums, plan, rows, &c->err)
-           : kind == FIT_F64     ? sed_fit_plan_index_f64(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err)
-                                 : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err);
+    return kind == FIT_LONG_KEYS  ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, sums, plan, rows, &c->err)
+           : kind == FIT_LONG_F64 ? sed_fit_plan_index_long_f64(c->costs, c->opt, len_p, nqueries, sums, plan, rows, &c->err)
+           : kind == FIT_F64      ? sed_fit_plan_index_f64(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err)
+                                  : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err);
 }
 static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                                int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
@@ -425,7 +428,7 @@ static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *c
     sed_fit_plan_t plan;
     std::vector<int32_t> rows;
     FitLongGroups lg;
-    const bool lng = kind == FIT_LONG_KEYS, f64 = kind == FIT_F64;
+    const bool lng = fit_kind_long(kind), f64 = fit_kind_f64(kind);
     rc = fit_index_plan_kind(c, kind, len_p, nqueries, ix->sums, &plan, &rows);
     if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
     const size_t nres = (size_t)nqueries * (size_t)ntexts, resbytes = (f64 ? sizeof(sed_fit_f64_best) : 8) * nres;
@@ -441,13 +444,20 @@ static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *c
     if ((e = hipMemsetAsync(ix->d_out.p, 0xFF, resbytes, c->stream)) != hipSuccess)
         return c->hipfail(e, "upload (fit index search)");
     sed_fit_f64_costs fc{};
-    if (f64 && ((e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess ||
-                (e = sed_launch_fit_index_f64(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, (sed_fit_f64_best *)ix->d_rec.p,
-                                              (sed_fit_f64_best *)ix->d_out.p, fc)) != hipSuccess))
+    if (f64 && (e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess) return c->hipfail(e, "upload (fit index costs)");
+    if (kind == FIT_F64 && (e = sed_launch_fit_index_f64(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, (sed_fit_f64_best *)ix->d_rec.p,
+                                                         (sed_fit_f64_best *)ix->d_out.p, fc)) != hipSuccess)
         return c->hipfail(e, "fit index fp64 kernel launch");
     if (kind == FIT_SHORT_KEYS && (e = sed_launch_fit_index(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index kernel launch");
-    for (size_t g = 0; lng && g < lg.groups.size(); ++g)  // the events bracket the groups' launches
+    for (size_t g = 0; kind == FIT_LONG_F64 && g < lg.groups.size(); ++g)  // each group: its waves, then its reduce
+        if ((e = sed_launch_fit_index_long_f64(c->stream, g == 0 ? ix->timer.ev[0] : nullptr,
+                                               g + 1 == lg.groups.size() ? ix->timer.ev[1] : nullptr,
+                                               fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
+                                               lg.groups[g].rows, (sed_fit_f64_best *)ix->d_rec.p,
+                                               (sed_fit_f64_best *)ix->d_out.p, fc)) != hipSuccess)
+            return c->hipfail(e, "fit index long fp64 kernel launch");
+    for (size_t g = 0; kind == FIT_LONG_KEYS && g < lg.groups.size(); ++g)  // the events bracket the groups' launches
         if ((e = sed_launch_fit_index_long(c->stream, g == 0 ? ix->timer.ev[0] : nullptr,
                                            g + 1 == lg.groups.size() ? ix->timer.ev[1] : nullptr,
                                            fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
@@ -481,6 +491,11 @@ int sed_fit_index_search_long(sed_fit_index *ix, const uint8_t *codes_p, const i
     return fit_index_search_of(ix, FIT_LONG_KEYS, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
 }
 
+int sed_fit_index_search_long_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                                  int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
+    return fit_index_search_of(ix, FIT_LONG_F64, codes_p, off_p, len_p, nqueries, out_dist, out_start, out_end);
+}
+
 int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
     return ix && kernel_ms ? ix->timer.elapsed(kernel_ms) : SED_E_ARG;
 }
@@ -498,7 +513,7 @@ static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *cod
     sed_fit_plan_t plan;
     std::vector<int32_t> rows;
     FitLongGroups lg;
-    const bool lng = kind == FIT_LONG_KEYS, f64 = kind == FIT_F64;
+    const bool lng = fit_kind_long(kind), f64 = fit_kind_f64(kind);
     rc = fit_index_plan_kind(c, kind, len_p, nqueries, ix->sums, &plan, &rows);
     int32_t cut = 0;
     if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);  // (fp64: its check of max_dist alone)
@@ -515,15 +530,23 @@ static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *cod
     if ((e = ix->hits_timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     if ((e = hipMemsetAsync(ix->d_count.p, 0, 8, c->stream)) != hipSuccess) return c->hipfail(e, "upload (fit index hits)");
     sed_fit_f64_costs fc{};
-    if (f64 && ((e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess ||
-                (e = sed_launch_fit_index_f64_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a,
-                                                   (sed_fit_f64_hit *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
-                                                   (unsigned long long)cap, max_dist, fc)) != hipSuccess))
+    if (f64 && (e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess) return c->hipfail(e, "upload (fit index costs)");
+    if (kind == FIT_F64 && (e = sed_launch_fit_index_f64_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a,
+                                                              (sed_fit_f64_hit *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
+                                                              (unsigned long long)cap, max_dist, fc)) != hipSuccess)
         return c->hipfail(e, "fit index fp64 hits kernel launch");
+    for (size_t g = 0; kind == FIT_LONG_F64 && g < lg.groups.size(); ++g)
+        if ((e = sed_launch_fit_index_long_f64_hits(c->stream, g == 0 ? ix->hits_timer.ev[0] : nullptr,
+                                                    g + 1 == lg.groups.size() ? ix->hits_timer.ev[1] : nullptr,
+                                                    fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
+                                                    lg.groups[g].rows, (sed_fit_f64_hit *)ix->d_hits.p,
+                                                    (unsigned long long *)ix->d_count.p, (unsigned long long)cap, max_dist,
+                                                    fc)) != hipSuccess)
+            return c->hipfail(e, "fit index long fp64 hits kernel launch");
     if (kind == FIT_SHORT_KEYS && (e = sed_launch_fit_index_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a, ix->d_hits.p,
                                                (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
         return c->hipfail(e, "fit index hits kernel launch");
-    for (size_t g = 0; lng && g < lg.groups.size(); ++g)
+    for (size_t g = 0; kind == FIT_LONG_KEYS && g < lg.groups.size(); ++g)
         if ((e = sed_launch_fit_index_long_hits(c->stream, g == 0 ? ix->hits_timer.ev[0] : nullptr,
                                                 g + 1 == lg.groups.size() ? ix->hits_timer.ev[1] : nullptr,
                                                 fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
@@ -593,6 +616,11 @@ int sed_fit_index_hits_f64(sed_fit_index *ix, const uint8_t *codes_p, const int6
 int sed_fit_index_hits_long(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                             int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
     return fit_index_hits_of(ix, FIT_LONG_KEYS, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
+}
+
+int sed_fit_index_hits_long_f64(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
+                                int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
+    return fit_index_hits_of(ix, FIT_LONG_F64, codes_p, off_p, len_p, nqueries, max_dist, out, cap, found);
 }
 
 int sed_fit_index_hits_last_time(const sed_fit_index *ix, float *kernel_ms) {

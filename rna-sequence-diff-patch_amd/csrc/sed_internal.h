@@ -321,6 +321,16 @@ hipError_t sed_launch_fit_index_f64(hipStream_t stream, hipEvent_t ev0, hipEvent
 hipError_t sed_launch_fit_index_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                          sed_fit_f64_hit *hits, unsigned long long *count, unsigned long long cap,
                                          double max_dist, const sed_fit_f64_costs &fc);
+// The fp64 route for long patterns (sed_fit_long_f64.hip; include/sed.h: sed_fit_index_search_long_f64): the long
+// kernels' waves, R groups, pattern records and qlist, the fp64 kernels' cell, cost table, records and hit list.  One
+// call serves one R group: its waves write rec[query * a.nchunks + chunk record], then its reduce kernel writes
+// out[query * a.ntexts + text]; a.out is not used.
+hipError_t sed_launch_fit_index_long_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                         const int32_t *qlist, int rows, sed_fit_f64_best *rec, sed_fit_f64_best *out,
+                                         const sed_fit_f64_costs &fc);
+hipError_t sed_launch_fit_index_long_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
+                                              const int32_t *qlist, int rows, sed_fit_f64_hit *hits, unsigned long long *count,
+                                              unsigned long long cap, double max_dist, const sed_fit_f64_costs &fc);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

@@ -172,6 +172,15 @@ SIGNATURES = [
                                           _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64]),
     ("sed_fit_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                 _i32p, _i32p, C.c_int32, C.c_char_p, C.c_int]),
+    ("sed_fit_index_search_long_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, _f64p, _i32p, _i32p]),
+    ("sed_fit_index_hits_long_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                              C.POINTER(C.c_int64)]),
+    ("sed_fit_index_long_f64_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                              _i32p, C.c_int32, _i32p, C.c_int32, _f64p, C.c_int, _i32p]),
+    ("sed_fit_index_long_f64_lanes", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                               _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64]),
+    ("sed_fit_long_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                     _i32p, C.c_int32, _i32p, C.c_int32, C.c_char_p, C.c_int]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -535,6 +544,15 @@ class FitIndex:
     def hits_long(self, packed, max_dist, cap=None):
         """hits() for queries of 1..2048 symbols (sed_fit_index_hits_long)."""
         return self.hits(packed, max_dist, cap, "sed_fit_index_hits_long")
+
+    def search_long_f64(self, packed):
+        """search_long() through the fp64 kernels (sed_fit_index_search_long_f64): queries of 1..2048 symbols under the
+        tables and alphabets (up to 16 symbols) search_long refuses; the values are the oracle's, bit for bit."""
+        return self.search(packed, "sed_fit_index_search_long_f64")
+
+    def hits_long_f64(self, packed, max_dist, cap=None):
+        """hits_long() through the fp64 kernels (sed_fit_index_hits_long_f64)."""
+        return self.hits(packed, max_dist, cap, "sed_fit_index_hits_long_f64")
 
     def search_f64(self, packed):
         """search() through the fp64 kernels (sed_fit_index_search_f64): the tables and alphabets (up to 16 symbols)
@@ -1444,6 +1462,46 @@ def fit_index_long_lanes(costs, options, len_p, len_t):
     lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
     lanes["tw"] &= 0xFFFFFFFF
     return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
+
+
+def fit_index_long_f64_plan(costs, options, len_p, len_t):
+    """What FitIndex.search_long_f64 would decide, without a device (sed_fit_index_long_f64_plan): fit_index_f64_plan's
+    fields (lanes = the waves) and "rows": int32[queries], as fit_index_long_plan."""
+    out = np.zeros(len(FIT_F64_PLAN_FIELDS), np.float64)
+    rows = np.zeros(max(len(len_p), 1), np.int32)
+    rc = load().sed_fit_index_long_f64_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out), rows)
+    if rc != 0:
+        raise _fit_fail("sed_fit_index_long_f64_plan", rc)
+    plan = _fit_f64_plan_dict(out)
+    plan["rows"] = rows[:len(len_p)]
+    return plan
+
+
+def fit_index_long_f64_lanes(costs, options, len_p, len_t):
+    """The wave records FitIndex.search_long_f64 / hits_long_f64 would run, without a device
+    (sed_fit_index_long_f64_lanes): as fit_index_f64_lanes, one record per (query, chunk record), query-major."""
+    nl = fit_index_long_f64_plan(costs, options, len_p, len_t)["lanes"]
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    rc = load().sed_fit_index_long_f64_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl)
+    if rc != 0:
+        raise _fit_fail("sed_fit_index_long_f64_lanes", rc)
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    return lanes
+
+
+def fit_long_route(costs, options, len_p, len_t):
+    """fit_route for the long calls, over fit_index_long_plan's arguments (sed_fit_long_route): (route, why).  route =
+    "int" whenever FitIndex.search_long serves the search, "f64" when only search_long_f64 does (why = the integer
+    route's refusal), None when neither does (why = both refusals)."""
+    why = C.create_string_buffer(1024)
+    rc = load().sed_fit_long_route(*_fit_index_args(costs, options, len_p, len_t), why, len(why))
+    text = why.value.decode()
+    if rc in FIT_ROUTES:
+        return FIT_ROUTES[rc], text
+    if rc == SED_E_RANGE:
+        return None, text
+    raise _fit_fail("sed_fit_long_route", rc)
 
 
 def band_bounds(n, m, ins, dele, ub):

@@ -127,6 +127,24 @@ def fit_route(queries, seqs, user_cost=False):
     return "f64" if route == "f64" else "int"
 
 
+def fit_long_route(queries, seqs, user_cost=False):
+    """fit_route for the long calls of an index (queries of up to 2048 symbols): "int" whenever
+    sedgpu.fit_long_route says the integer long calls serve these queries against these documents, "f64" when only
+    the fp64 long calls do; a search neither serves goes to the integer call, as in fit_route."""
+    queries, seqs = list(queries), list(seqs)
+    if not queries or not seqs:
+        return "int"
+    n = max(len(queries), len(seqs))
+    try:
+        plan = SED.batch_plan([queries[i % len(queries)] for i in range(n)], [seqs[i % len(seqs)] for i in range(n)],
+                              user_cost)
+    except KeyError:
+        return "int"
+    costs = (plan.K, plan.sub, plan.sub_int, plan.ins, plan.ins_int, plan.dele, plan.del_int)
+    route, _ = sedgpu.fit_long_route(costs, {}, [len(q) for q in queries], [len(s) for s in seqs])
+    return "f64" if route == "f64" else "int"
+
+
 def _resolve_route(route, queries, seqs, user_cost):
     if route not in ROUTES:
         raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
@@ -179,8 +197,10 @@ class FitIndex:
     results merge in query order.  The default refuses a query over 32 as before.
 
     route (the constructor's, and per call on search, search_many, occurrences, occurrences_many; None = the
-    constructor's): "int", "f64" or "auto" as fit_search takes it, for the queries of at most 32 symbols (the long calls
-    have integer kernels only).  An index whose constructor route is "f64" or "auto" is built with f64=True (up to 16
+    constructor's): "int", "f64" or "auto" as fit_search takes it.  It holds for the short and, apart, for the long
+    queries of a call: under "f64" the long ones run the index's search_long_f64 / hits_long_f64, under "auto" they
+    take the integer long calls whenever fit_long_route says those serve them and the fp64 long calls otherwise, so
+    only a refusal turns into a result.  An index whose constructor route is "f64" or "auto" is built with f64=True (up to 16
     symbols; index_fn is called with that keyword), and serves integer searches too; one built under the default keeps
     the 8-symbol bound, whatever route a later call names.  The fp64 route calls the index's search_f64 / hits_f64."""
 
@@ -202,6 +222,16 @@ class FitIndex:
                            self.user_cost) if short else "int"
         return (self._ix.search_f64, self._ix.hits_f64) if r == "f64" else (self._ix.search, self._ix.hits)
 
+    def _long_calls(self, route, queries, lng):
+        """(the search call, the hits call) that serve the long queries under route"""
+        route = self.route if route is None else route
+        if route not in ROUTES:
+            raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
+        r = "int" if not lng or route == "int" else \
+            fit_long_route([queries[i] for i in lng], self.seqs, self.user_cost) if route == "auto" else route
+        return (self._ix.search_long_f64, self._ix.hits_long_f64) if r == "f64" else \
+            (getattr(self._ix, "search_long", None), getattr(self._ix, "hits_long", None))
+
     def _split(self, queries, long_patterns):
         """(indices the short calls serve, indices the long calls serve)"""
         if not long_patterns:
@@ -217,7 +247,7 @@ class FitIndex:
             return []
         short, lng = self._split(queries, long_patterns)
         rows = [None] * len(queries)
-        for idx, call in ((short, self._calls(route, queries, short)[0]), (lng, getattr(self._ix, "search_long", None))):
+        for idx, call in ((short, self._calls(route, queries, short)[0]), (lng, self._long_calls(route, queries, lng)[0])):
             if idx:
                 for i, r in zip(idx, call([queries[i] for i in idx])):
                     rows[i] = r
@@ -248,7 +278,7 @@ class FitIndex:
             return []
         short, lng = self._split(queries, long_patterns)
         hits = []
-        for idx, call in ((short, self._calls(route, queries, short)[1]), (lng, getattr(self._ix, "hits_long", None))):
+        for idx, call in ((short, self._calls(route, queries, short)[1]), (lng, self._long_calls(route, queries, lng)[1])):
             if idx:
                 hits += [(idx[q], t, a, b, d) for q, t, a, b, d in call([queries[i] for i in idx], max_dist)]
         hits.sort(key=lambda h: (h[0], h[1], h[3]))  # (each call's list is sorted; the merge is by query)
