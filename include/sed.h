@@ -121,6 +121,12 @@ enum {
                                    calls) only: pattern rows per lane, 0 auto (each query the smallest R of 2, 4, 8, 16,
                                    32 with 64 R >= P), else that R for every query (tests and A/Bs; a query of P > 64 R:
                                    SED_E_RANGE).  sed_plan_routes refuses it */
+#define SED_OPT_JOIN_DP 20      /* the similarity join (sed_join_self, sed_join_search, sed_join_plan) only: 0 auto (the
+                                   bit-parallel kernel when the codes present have unit costs), 2 the scaled DP kernel always
+                                   (tests and A/Bs).  sed_plan_routes refuses it */
+#define SED_OPT_JOIN_ROWS 21    /* the similarity join only, for tests: the rows one launch takes, 0 auto (the grid's limit,
+                                   65535 row groups); a call with more rows runs further launches.  sed_plan_routes
+                                   refuses it */
 #define SED_OPT_DEBUG_CORRUPT 9 /* testing only: p + 1 overwrites one checkpoint word of pair p before its traceback,
                                    which must then fail with SED_E_DEVICE naming the pair; 0 off */
 
@@ -580,6 +586,67 @@ int sed_fit_index_long_f64_lanes(int K, const double *sub, const uint8_t *sub_in
 int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
                        double del, int del_is_int, const int32_t *options, int noptions,
                        const int32_t *len_p, int32_t nqueries, const int32_t *len_t, int32_t ntexts, char *why, int why_len);
+
+/* Similarity join (an extension; it batches what the reference does pair by pair: wf_score(query, doc) over a whole
+ * collection, IRMethods.py:435-440 inside search_collection's loop, IRMethods.py:443-477, each a full
+ * wagnerFisher(str1, str2), StringEditDistance.py:133-224): every (row, column) pair of short sequences with
+ * wagnerFisher(row, column).value <= max_dist, as a compact sorted hit list; the pairs are enumerated on the device.
+ * Rows are str1 and columns str2 (the direction of wf_score(query, doc)); cost tables may be asymmetric, so (i, j) and
+ * (j, i) are different pairs.
+ * A sed_join_index holds nseqs sequences of 0..32 symbols each, resident on the device: sequence i = codes[off[i] ..
+ * +len[i]).  It needs no cost model (it keeps the sequences, their lengths and a 32-bit mask of the codes it holds; its
+ * columns are stored sorted by length, and hits carry the original indices); every call runs under the context's costs
+ * and options of that moment.  It belongs to its context and is destroyed before it.  nseqs = 0 is valid.  NULL on
+ * failure, the reason in sed_last_error(ctx): SED_E_ARG conditions (NULL, a length above 32, a negative length or
+ * offset), an allocation or a copy that failed.
+ *   sed_join_self:   rows = the index's own sequences row_lo <= i < row_hi, columns = every sequence j != i.  (i, i) is
+ *                    never reported; duplicates (i != j, equal sequences) are, in both directions.
+ *   sed_join_search: rows = nqueries host sequences of 0..32 symbols, columns = every sequence of the index; nothing is
+ *                    excluded.
+ * Hits: dist = D / S, the scaled-integer lane kernel's number (no is_int, as for fit search); a pair is within max_dist
+ * exactly when D <= floor(max_dist * S); +inf admits every pair (the dense matrix as a hit list); NaN or a negative
+ * max_dist: SED_E_ARG.  Empty sequences are ordinary: their distances are n * delete and m * insert.
+ * The cap protocol is sed_fit_index_hits': *found = the total, always; found <= cap: out[0 .. found) sorted by (row, col),
+ * SED_OK; found > cap: SED_E_RANGE, the text names both numbers, the index stays usable; cap = 0 with out = NULL is a count
+ * query.  The device hit list belongs to the index and grows to the largest cap seen.
+ * Cost models served (anything else: SED_E_RANGE before any launch, the text names the failed condition, the index stays
+ * usable): at most 8 symbols; some S = 2^k, k <= 8, makes insert, delete and every substitution cost an integer;
+ * insert * S and delete * S >= 1; every cost <= insert + delete; (insert + delete) * S <= 255.  For such tables every fp64
+ * sum of the reference is exact, so D / S is the reference's value bit for bit.  A row or column code >= K: SED_E_ARG.
+ * State errors: sed_fit_index_search's.
+ * One kernel variant per launch (sed_join_plan's out[1]): bit-parallel when insert = delete = 1 and the codes present
+ * (the index's, OR'd with the queries' for a search) are at most four symbols with unit costs among themselves, else the
+ * scaled DP; SED_OPT_JOIN_DP forces the DP.  A pair whose length bound insert * (m - n)+ + delete * (n - m)+ exceeds
+ * max_dist is never computed, and a wave whose 64 columns all fail it skips the row.  More rows than one launch takes
+ * (65535 groups of sed_join_rows_per_group rows; SED_OPT_JOIN_ROWS) run as further launches of the same call.
+ * Not served: tables the conditions refuse (IUPAC: an fp64 route), sequences over 32 symbols, edit scripts of the hits,
+ * k-nearest lists, the i < j half alone for symmetric tables, a per-tile mix of the two variants. */
+typedef struct sed_join_index sed_join_index;
+typedef struct { int32_t row, col; double dist; } sed_join_hit;
+sed_join_index *sed_join_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
+                                      int32_t nseqs);
+void sed_join_index_destroy(sed_join_index *ix);
+int32_t sed_join_index_seqs(const sed_join_index *ix);
+int sed_join_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
+                  int64_t *found);
+int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                    int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+/* Device time of the last join's kernel(s), from HIP events (ms); SED_E_STATE before the first that launched one. */
+int sed_join_last_time(const sed_join_index *ix, float *kernel_ms);
+/* The pairs the last join's waves ran (those in scope whose length bound passed), counted on the device: equal to
+ * sed_join_plan's out[4] for the same call.  SED_E_STATE before the first join that got past its plan. */
+int sed_join_pairs_run(const sed_join_index *ix, int64_t *pairs);
+/* The rows a block's waves run against their columns (the row side of the launch geometry). */
+int32_t sed_join_rows_per_group(void);
+/* What a join would decide, without a device: the code it would return for these costs (as sed_set_costs takes them),
+ * options (as sed_plan_routes takes them), lengths, codes seen (bit c set when code c occurs; bit 31: any code >= 31) and
+ * cutoff; self != 0: the rows are nrows of the ncols columns and each row's own column is out of scope.
+ * out[0 .. nout) = 0 the scale S, 1 the kernel (1 DP, 2 bit-parallel), 2 waves launched, 3 pairs in scope, 4 pairs the
+ * waves run (after the length skip), 5 the cells n * m of those pairs. */
+int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                  double del, int del_is_int, const int32_t *options, int noptions,
+                  const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                  uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

@@ -903,6 +903,110 @@ def fit_index(texts, userCosts=False, alphabet=None, engine=None, f64=False):
     return FitIndex(texts, userCosts, alphabet, engine, f64)
 
 
+JOIN_MAX_LEN = 32  # the join's longest sequence (include/sed.h: sed_join_index_create)
+
+
+class _EngineJoin:
+    """The device half of a JoinIndex: the sequences' codes resident on the process's engine (sedgpu.JoinIndex)."""
+
+    def __init__(self, codes, off, lens):
+        self.ctx = sedgpu.context()
+        self.ix = self.ctx.join_index(codes, off, lens)
+
+    def self_join(self, plan, max_dist, rows):
+        self.ctx.set_costs(plan)
+        return self.ix.self_join(max_dist, rows)
+
+    def search(self, plan, packed, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.search(packed, max_dist)
+
+    def close(self):
+        self.ix.close()
+
+
+class JoinIndex:
+    """Every pair of short sequences within a distance, over sequences that stay on the device: join_index(seqs) encodes
+    and uploads them once (0..32 symbols each); self_join(max_dist) returns [(i, j, dist)] for every i != j with
+    wagnerFisher(seqs[i], seqs[j]).value <= max_dist, search(queries, max_dist) returns [(q, j, dist)] for every query
+    against every sequence, both sorted by (row, column); rows are str1, columns str2 (include/sed.h: sed_join_self,
+    sed_join_search).  dist is a float (no int typing).  Symbols get their codes as in FitIndex; the engine serves dyadic
+    cost tables over at most 8 symbols and raises SedError otherwise.  The cost table is read at every call, and the
+    KeyErrors are the reference's for the first offending (row, column) in row-major order."""
+
+    def __init__(self, seqs, userCosts=False, alphabet=None, engine=None):
+        self.seqs = list(seqs)
+        self.userCosts = userCosts
+        for i, s in enumerate(self.seqs):
+            if len(s) > JOIN_MAX_LEN:
+                raise sedgpu.SedError("join index: sequence %d has %d symbols (the join serves at most %d)"
+                                      % (i, len(s), JOIN_MAX_LEN))
+        used = sedcost.distinct_many(self.seqs) if sedcost._all_str(self.seqs) else \
+            list(dict.fromkeys(c for t in self.seqs for c in t))
+        self._used = used
+        self.symbols = list(dict.fromkeys(list(alphabet or ()) + used))
+        if len(self.symbols) > 8:
+            raise sedgpu.SedError("join index: the sequences have %d symbols (the join serves at most 8)" % len(self.symbols))
+        code = {c: k for k, c in enumerate(self.symbols)}
+        lens = np.fromiter(map(len, self.seqs), dtype=np.int32, count=len(self.seqs))
+        codes = np.fromiter((code[c] for t in self.seqs for c in t), dtype=np.uint8, count=int(lens.sum()))
+        off = np.zeros(len(lens), np.int64)
+        if len(lens):
+            off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        self._dev = (engine or _EngineJoin)(codes, off, lens)
+
+    def plan(self, rows):
+        """The reference's KeyError for the first offending (row, sequence), if any, then the call's CostPlan: the
+        index's symbols in their order, then the rows' new ones."""
+        table = _table(self.userCosts)
+        rep = "".join(self._used) if sedcost._all_str(self.seqs) and all(len(c) == 1 for c in self._used) else None
+        u1 = sedcost.distinct_many(rows) if sedcost._all_str(rows) else list(dict.fromkeys(c for p in rows for c in p))
+        # one pair per row against a sequence of every symbol the index holds resolves exactly when every pair does
+        if rep is None or not sedcost._batch_resolves(table, rows, [rep] * len(rows), (u1, self._used)):
+            for p in rows:
+                for t in self.seqs:
+                    sedcost.check_pair(table, p, t)
+        alphabet = self.symbols + [c for c in u1 if c not in self.symbols]
+        if len(alphabet) > 8:
+            raise sedgpu.SedError("join index: the sequences and these rows have %d symbols (the join serves at most 8)"
+                                  % len(alphabet))
+        return sedcost.plan_over(table, alphabet, set(u1), set(self._used))
+
+    def self_join(self, max_dist, rows=None):
+        lo, hi = (0, len(self.seqs)) if rows is None else rows
+        if not 0 <= lo <= hi <= len(self.seqs):
+            raise ValueError("rows=(%r, %r) is no range of the index's %d sequences" % (lo, hi, len(self.seqs)))
+        plan = self.plan(self.seqs[lo:hi])
+        if lo == hi:
+            return []
+        h = self._dev.self_join(plan, max_dist, (lo, hi))
+        return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
+
+    def search(self, queries, max_dist):
+        queries = list(queries)
+        for q, s in enumerate(queries):
+            if len(s) > JOIN_MAX_LEN:
+                raise sedgpu.SedError("join: query %d has %d symbols (the join serves at most %d)" % (q, len(s), JOIN_MAX_LEN))
+        plan = self.plan(queries)
+        if not queries or not self.seqs:
+            return []
+        ca, la = plan.encode_many(queries)
+        packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
+        h = self._dev.search(plan, packed, max_dist)
+        return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
+
+    def close(self):
+        self._dev.close()
+
+
+def join_index(seqs, userCosts=False, alphabet=None, engine=None):
+    """A JoinIndex over seqs (0..32 symbols each): every pair within a distance, for clustering, de-duplication,
+    neighbour graphs, or many queries against one collection.  engine(codes, off, lens) -> an object with
+    self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), both returning sedgpu.JOIN_HIT_DTYPE records,
+    and close() replaces the device (CPU tests)."""
+    return JoinIndex(seqs, userCosts, alphabet, engine)
+
+
 def edit_script_batch(strs1, strs2, userCosts=False):
     """[(value, generate_es(create_paths(dp)[0], s1, s2))] for each pair — one GPU launch."""
     strs1, strs2 = list(strs1), list(strs2)

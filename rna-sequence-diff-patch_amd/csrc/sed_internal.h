@@ -331,6 +331,41 @@ hipError_t sed_launch_fit_index_long_f64(hipStream_t stream, hipEvent_t ev0, hip
 hipError_t sed_launch_fit_index_long_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                               const int32_t *qlist, int rows, sed_fit_f64_hit *hits, unsigned long long *count,
                                               unsigned long long cap, double max_dist, const sed_fit_f64_costs &fc);
+// Similarity join (sed_join.hip; include/sed.h: sed_join_self, sed_join_search).  Every sequence is a record of
+// SED_JOIN_MAXLEN byte codes, zero padded.  A lane owns one column record (the index's sequences sorted by length,
+// col_orig[t] = the original index of sorted column t) and the block's waves walk the rows row0 + SED_JOIN_G blockIdx.y
+// .. of the row records (the index's sequences in their own order, or a search's queries): grid = (column blocks of
+// SED_JOIN_BLOCK lanes) x (row groups of SED_JOIN_G rows).  The row loads are wave-uniform and read up to two words past
+// a record, so both record buffers end with 16 spare bytes.
+//   tab[a] = the 8 bytes (cost(a -> b) * S - ins - del - 1) & 0xFF (sed_scaled_params::row) on the device;
+//   umap   = the 2-bit code of every symbol < 8 at bits 2c, for the bit-parallel variant;
+//   cut    = floor(max_dist * S); a pair is a hit when D * S <= cut, and is not computed when its length bound
+//            insert (m - n)+ + delete (n - m)+ on the integer scale exceeds cut (a wave whose lanes all fail it skips
+//            the row);
+//   hits   = 16-byte records (row, original column, D * S, 0), room for cap; count[0] counts every hit, stored or not,
+//            count[1] the pairs in scope whose bound passed (the pairs the waves ran); both zeroed by the caller.
+// self: the pair (r, column of original index r) is out of scope.
+#define SED_JOIN_G 4
+#define SED_JOIN_BLOCK 256
+#define SED_JOIN_MAXLEN 32
+#define SED_JOIN_MAX_GROUPS 65535  // a grid's y extent
+struct sed_join_args {
+    const void *rows;
+    const int32_t *row_len;
+    int32_t row0, nrows;
+    const void *cols;
+    const int32_t *col_len, *col_orig;
+    int32_t ncols;
+    int32_t self;
+    const uint2 *tab;
+    uint32_t ins, del, umap;
+    int32_t shift;  // log2 S: the bit-parallel variant's D << shift is the scaled distance
+    int32_t cut;
+    uint4 *hits;
+    unsigned long long *count;
+    unsigned long long cap;
+};
+hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

@@ -1,0 +1,130 @@
+// sed_join.hip — similarity join over short sequences (include/sed.h: sed_join_self, sed_join_search): every (row,
+// column) pair of 0..32 symbols whose distance is within a cutoff, appended to a hit list on the device.
+//
+// The lane kernels (sed_lane.hip) give every lane its own pair; here a lane owns a COLUMN sequence (str2) and the wave
+// walks the rows (str1).  The lane builds what depends on its column once - the 32 perm selectors of the scaled DP, or
+// the two bit planes E0 / E1 of the bit-parallel variant - and runs SED_JOIN_G rows against it.  A row is uniform across
+// the wave: its length, its symbols and its 8-byte cost row come from scalar loads, and the row loop has one trip count
+// for all 64 lanes.  The cells are sed_lane_dp.h's, shared with the lane kernels, so the scaled distance D * S is the
+// lane kernels' number.
+//
+// Length skip: insert (m - n)+ + delete (n - m)+ bounds the distance from below.  The columns are sorted by length, so
+// the 64 columns of a wave have nearly one length, and a wave none of whose lanes can be within the cutoff for the
+// current row leaves that row out.  count[1] counts the pairs whose bound passed: the pairs of the waves that ran.
+#include <hip/hip_ext.h>
+#include "sed_internal.h"
+#include "sed_dev.h"
+#include "sed_lane_dp.h"
+
+namespace {
+
+// One hit per lane, decided for the whole wave (sed_fit_dp.h: sed_fit_append): the first hitting lane takes popcount
+// slots with one atomic add, every hitting lane stores at the first slot + its rank among them; slots >= cap only count.
+__device__ __forceinline__ void join_append(const sed_join_args &a, bool hit, int32_t row, int32_t col, uint32_t D) {
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
+    if (b == 0) return;
+    if (hit) {
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        unsigned long long base = 0;
+        if (rank == 0) base = atomicAdd(a.count, (unsigned long long)__popcll(b));
+        // (the first active lane here is the hitting lane of rank 0)
+        const unsigned long long slot =
+            (((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+             __builtin_amdgcn_readfirstlane((uint32_t)base)) + rank;
+        if (slot < a.cap) a.hits[slot] = make_uint4((uint32_t)row, (uint32_t)col, D, 0u);
+    }
+}
+
+template <bool BITPAR>
+__global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t *__restrict__ rows,
+                                                                  const int32_t *__restrict__ row_len,
+                                                                  const uint2 *__restrict__ tab, const sed_join_args a) {
+    // (rows, row_len, tab = a's, as restrict parameters: the hit list's stores cannot alias them, so their uniform
+    // loads are scalar loads)
+    constexpr int MM = SED_JOIN_MAXLEN;
+    static_assert(MM == 32, "a record is two 16-byte words; the bit-parallel state is one 32-bit word");
+    const int t = blockIdx.x * SED_JOIN_BLOCK + threadIdx.x;
+    const bool valid = t < a.ncols;
+    const int tc = valid ? t : a.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
+    const uint4 *pc = reinterpret_cast<const uint4 *>(a.cols) + 2 * (size_t)tc;
+    const uint4 q0 = pc[0], q1 = pc[1];
+    const int m = a.col_len[tc];
+    const int orig = a.col_orig[tc];
+    const uint32_t bw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    // what the lane keeps of its column
+    uint32_t sel[BITPAR ? 1 : MM];
+    uint32_t E0 = 0, E1 = 0;
+    if constexpr (BITPAR) {
+#pragma unroll
+        for (int j = 0; j < MM; ++j) {
+            const uint32_t u = __builtin_amdgcn_ubfe(a.umap, 2 * ((bw[j >> 2] >> (8 * (j & 3))) & 7u), 2);
+            E0 |= (u & 1u) << j;
+            E1 |= (u >> 1) << j;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < MM; ++j) sel[j] = sed_scaled_sel(bw[j >> 2] >> (8 * (j & 3)));
+    }
+    const int rbeg = a.row0 + (int)blockIdx.y * SED_JOIN_G;
+    const int rend = min(rbeg + SED_JOIN_G, a.row0 + a.nrows);
+    uint32_t ran = 0;
+    for (int r = rbeg; r < rend; ++r) {
+        const int n = row_len[r];  // (uniform: a scalar load)
+        const uint32_t lb = m > n ? (uint32_t)(m - n) * a.ins : (uint32_t)(n - m) * a.del;
+        const bool go = valid && !(a.self && orig == r) && lb <= (uint32_t)a.cut;
+        const unsigned long long gb = __builtin_amdgcn_ballot_w64(go);
+        if (gb == 0) continue;  // no column of this wave can be within the cutoff of row r
+        ran += (uint32_t)__popcll(gb);
+        const uint32_t *pr = rows + 8 * (size_t)r;
+        uint32_t w0 = pr[0], w1 = pr[1];  // rows 0..3 and 4..7 (the buffer ends with spare words)
+        uint32_t D;
+        if constexpr (BITPAR) {
+            uint32_t Pv = ~0u, Mv = 0u;
+            for (int i = 0; i < n; ++i) {
+                const uint32_t c = (w0 >> (8 * (i & 3))) & 7u;
+                if ((i & 3) == 3) {
+                    w0 = w1;
+                    w1 = pr[(i >> 2) + 2];
+                }
+                sed_bitpar_step(Pv, Mv, sed_bitpar_tq(E0, E1, __builtin_amdgcn_ubfe(a.umap, 2 * c, 2)));
+            }
+            D = sed_bitpar_sink(n, m, Pv, Mv) << a.shift;
+        } else {
+            uint32_t V[MM + 1];
+#pragma unroll
+            for (int j = 0; j <= MM; ++j) V[j] = SED_KB;  // row 0 and column 0: the offset key B
+            uint2 rt = tab[w0 & 7u];
+            for (int i = 0; i < n; ++i) {
+                const uint2 cur = rt;  // row i's costs; row i + 1's are read during this row
+                const int i1 = i + 1;
+                if ((i1 & 3) == 0) {
+                    w0 = w1;
+                    w1 = pr[(i1 >> 2) + 1];
+                }
+                rt = tab[(w0 >> (8 * (i1 & 3))) & 7u];
+                sed_scaled_row<MM>(V, sel, cur);
+            }
+            uint32_t cap = V[0];  // m = 0: the border column
+#pragma unroll
+            for (int j = 1; j <= MM; ++j) cap = (j == m) ? V[j] : cap;
+            D = sed_scaled_decode(cap, n, m, a.ins, a.del);
+        }
+        join_append(a, go && D <= (uint32_t)a.cut, r, orig, D);
+    }
+    if (ran != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.count + 1, (unsigned long long)ran);
+}
+
+}  // namespace
+
+hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar) {
+    if (a.nrows <= 0 || a.ncols <= 0) return hipSuccess;
+    const dim3 grid((a.ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK, (a.nrows + SED_JOIN_G - 1) / SED_JOIN_G);
+    if (grid.y > SED_JOIN_MAX_GROUPS) return hipErrorInvalidValue;
+    if (bitpar)
+        hipExtLaunchKernelGGL(sed_join_kernel<true>, grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0,
+                              (const uint32_t *)a.rows, a.row_len, a.tab, a);
+    else
+        hipExtLaunchKernelGGL(sed_join_kernel<false>, grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0,
+                              (const uint32_t *)a.rows, a.row_len, a.tab, a);
+    return hipGetLastError();
+}

@@ -1,0 +1,143 @@
+// sed_join_plan.cpp — the join planner (sed_join_plan.h): scale and cost rows, the kernel variant, the cutoff on the
+// integer scale, the launches and the pair counts of a similarity join.  No HIP call.  Also the device-free entry point
+// sed_join_plan of include/sed.h.
+#include "sed_join_plan.h"
+
+#include <algorithm>
+#include <cmath>
+
+int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *err) {
+    if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "join: %d symbols (the scaled cost rows hold at most 8)", c.K);
+    auto finite = [](double v) { return std::isfinite(v) && v >= 0; };
+    bool ok = finite(c.ins) && finite(c.del);
+    for (int e = 0; e < c.K * c.K && ok; ++e) ok = finite(c.sub[e]);
+    if (!ok) return sed_plan_fail(err, SED_E_RANGE, "join: a cost is negative or not finite");
+    int k = 0;
+    for (;; ++k) {
+        if (k > 8)
+            return sed_plan_fail(err, SED_E_RANGE, "join: the costs are not all multiples of 2^-k for any k <= 8 (no scale makes them integers)");
+        const double S = std::ldexp(1.0, k);
+        auto integral = [&](double v) { const double x = v * S; return x == std::floor(x); };
+        ok = integral(c.ins) && integral(c.del);
+        for (int e = 0; e < c.K * c.K && ok; ++e) ok = integral(c.sub[e]);
+        if (ok) break;
+    }
+    const double S = std::ldexp(1.0, k);
+    if (c.ins * S < 1 || c.del * S < 1)
+        return sed_plan_fail(err, SED_E_RANGE, "join: insert * S = %g, delete * S = %g: both must be at least 1", c.ins * S, c.del * S);
+    for (int e = 0; e < c.K * c.K; ++e)
+        if (c.sub[e] > c.ins + c.del)
+            return sed_plan_fail(err, SED_E_RANGE, "join: cost(%d -> %d) = %g exceeds insert + delete = %g", e / c.K, e % c.K,
+                                 c.sub[e], c.ins + c.del);
+    if ((c.ins + c.del) * S > 255)
+        return sed_plan_fail(err, SED_E_RANGE, "join: (insert + delete) * S = %g exceeds 255 (the update addend's byte)",
+                             (c.ins + c.del) * S);
+    plan->scale_log2 = k;
+    sed_scaled_params &sp = plan->sp;
+    sp = sed_scaled_params{};
+    sp.ins = (uint32_t)(c.ins * S);
+    sp.del = (uint32_t)(c.del * S);
+    sp.inv_scale = std::ldexp(1.0, -k);
+    for (int a = 0; a < 8; ++a)
+        for (int b = 0; b < 8; ++b) {
+            const uint32_t v = (a < c.K && b < c.K) ? (uint32_t)(c.sub[a * c.K + b] * S) : 0u;
+            sp.row[a][b >> 2] |= ((v - sp.ins - sp.del - 1u) & 0xFFu) << (8 * (b & 3));
+        }
+    return SED_OK;
+}
+
+// unit_costs' conditions (sed_plan.cpp) on the numbers, restricted to the cells a join can meet: insert = delete = 1, at
+// most four codes in all, and cost(a -> b) = 1 (0 when a = b) for every row code a and column code b.  *umap = the
+// codes' 2-bit codes, in code order.
+static bool join_unit_costs(const sed_costs &c, uint32_t row_codes, uint32_t col_codes, uint32_t *umap) {
+    const uint32_t seen = row_codes | col_codes;
+    if (c.ins != 1.0 || c.del != 1.0 || __builtin_popcount(seen) > 4) return false;
+    uint32_t map = 0, next = 0;
+    for (int a = 0; a < c.K; ++a) {
+        if (!((seen >> a) & 1u)) continue;
+        for (int b = 0; b < c.K && ((row_codes >> a) & 1u); ++b)
+            if (((col_codes >> b) & 1u) && c.sub[a * c.K + b] != (a == b ? 0.0 : 1.0)) return false;
+        map |= next++ << (2 * a);
+    }
+    *umap = map;
+    return true;
+}
+
+int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
+                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
+                     sed_join_plan_t *plan, std::string *err) {
+    if (nrows < 0 || ncols < 0 || (nrows && !len_rows) || (ncols && !len_cols) || (self && nrows > ncols))
+        return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    if (std::isnan(max_dist) || max_dist < 0) return sed_plan_fail(err, SED_E_ARG, "join: max_dist is NaN or negative");
+    int rc = sed_join_costs_rule(c, plan, err);
+    if (rc != SED_OK) return rc;
+    const uint32_t seen = row_codes | col_codes;
+    if (c.K < 32 && (seen >> c.K) != 0) {
+        const bool in_cols = (col_codes >> c.K) != 0;
+        return sed_plan_fail(err, SED_E_ARG, "join: a %s code is outside the alphabet (K=%d)", in_cols ? "column" : "row", c.K);
+    }
+    double hr[SED_JOIN_MAXLEN + 1] = {}, hc[SED_JOIN_MAXLEN + 1] = {};
+    double own_cells = 0;  // sum n n over the rows: the (i, i) pairs a self join leaves out
+    for (int i = 0; i < nrows; ++i) {
+        if (len_rows[i] < 0 || len_rows[i] > SED_JOIN_MAXLEN)
+            return sed_plan_fail(err, SED_E_ARG, "join: row %d has %d symbols (0..%d)", i, len_rows[i], SED_JOIN_MAXLEN);
+        hr[len_rows[i]] += 1;
+        own_cells += (double)len_rows[i] * len_rows[i];
+    }
+    for (int j = 0; j < ncols; ++j) {
+        if (len_cols[j] < 0 || len_cols[j] > SED_JOIN_MAXLEN)
+            return sed_plan_fail(err, SED_E_ARG, "join: column %d has %d symbols (0..%d)", j, len_cols[j], SED_JOIN_MAXLEN);
+        hc[len_cols[j]] += 1;
+    }
+    uint32_t umap = 0;
+    plan->kernel = o.join_dp != 2 && join_unit_costs(c, row_codes, col_codes, &umap) ? SED_JOIN_KERNEL_BITPAR : SED_JOIN_KERNEL_DP;
+    plan->sp.umap = umap;
+    // floor(max_dist S): S is a power of two, so the product is exact (or overflows to +inf, which the clamp takes)
+    const double cs = std::floor(std::ldexp(max_dist, plan->scale_log2));
+    plan->cut = cs >= SED_JOIN_CUT_ALL ? SED_JOIN_CUT_ALL : (int32_t)cs;
+    plan->launch_rows = o.join_rows > 0 ? o.join_rows : (int64_t)SED_JOIN_MAX_GROUPS * SED_JOIN_G;
+    const double blocks = (ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK;
+    double groups = 0;
+    for (int64_t r = 0; r < nrows; r += plan->launch_rows)
+        groups += (double)((std::min<int64_t>(plan->launch_rows, nrows - r) + SED_JOIN_G - 1) / SED_JOIN_G);
+    plan->waves = ncols > 0 ? blocks * groups * (SED_JOIN_BLOCK / 64) : 0;
+    plan->scope = (double)nrows * ncols - (self ? nrows : 0);
+    plan->run = plan->cells = 0;
+    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n)
+        for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
+            const uint32_t lb = m > n ? (uint32_t)(m - n) * plan->sp.ins : (uint32_t)(n - m) * plan->sp.del;
+            if (lb > (uint32_t)plan->cut) continue;
+            plan->run += hr[n] * hc[m];
+            plan->cells += hr[n] * hc[m] * n * m;
+        }
+    if (self) {  // every (i, i) has bound 0 and was counted
+        plan->run -= nrows;
+        plan->cells -= own_cells;
+    }
+    return SED_OK;
+}
+
+extern "C" int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows,
+                             const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
+                             uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options) || nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    c.K = K;
+    c.sub.assign(sub, sub + K * K);
+    if (sub_int) c.sub_int.assign(sub_int, sub_int + K * K);
+    c.ins = ins;
+    c.del = del;
+    c.ins_int = ins_is_int ? 1 : 0;
+    c.del_int = del_is_int ? 1 : 0;
+    for (int i = 0; i < noptions; ++i)
+        if (!sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    sed_join_plan_t p;
+    const int rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen,
+                                    max_dist, &p, nullptr);
+    if (rc != SED_OK) return rc;
+    const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.kernel, p.waves, p.scope, p.run, p.cells};
+    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}

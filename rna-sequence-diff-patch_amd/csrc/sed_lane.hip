@@ -17,6 +17,7 @@
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
+#include "sed_lane_dp.h"
 
 namespace {
 
@@ -257,17 +258,10 @@ __global__ __launch_bounds__(256) void sed_lane_bitpar_kernel(const sed_pair_des
             if (u >= cnt) break;
             const uint32_t c0 = (uint32_t)__builtin_amdgcn_sbfe((int)w, 2 * u, 1);  // 0 or ~0
             const uint32_t c1 = (uint32_t)__builtin_amdgcn_sbfe((int)w, 2 * u + 1, 1);
-            const uint32_t tq = (E0 ^ c0) | (E1 ^ c1);  // ~Eq
-            const uint32_t Xv = Mv | ~tq;
-            const uint32_t Xh = (((Pv & ~tq) + Pv) ^ Pv) | ~tq;
-            const uint32_t Ph = (Mv | ~(Xh | Pv)) << 1 | 1u;  // (the top border's +1)
-            const uint32_t Mh = (Pv & Xh) << 1;
-            Pv = Mh | ~(Xv | Ph);
-            Mv = Ph & Xv;
+            sed_bitpar_step(Pv, Mv, (E0 ^ c0) | (E1 ^ c1));  // ~Eq
         }
     }
-    const uint32_t keep = m >= 32 ? ~0u : (1u << m) - 1u;
-    const uint32_t D = (uint32_t)n + (uint32_t)__builtin_popcount(Pv & keep) - (uint32_t)__builtin_popcount(Mv & keep);
+    const uint32_t D = sed_bitpar_sink(n, m, Pv, Mv);
     sed_result r;
     r.dist = (double)D;
     r.len = -1;
@@ -302,16 +296,9 @@ __device__ __forceinline__ uint32_t bitpar_bytes(const uint8_t *pa, const uint8_
     uint32_t Pv = ~0u, Mv = 0u;
     for (int i = 0; i < n; ++i) {
         const uint32_t a = unit_code(pa[i], umask);
-        const uint32_t tq = (E0 ^ (0u - (a & 1u))) | (E1 ^ (0u - (a >> 1)));  // ~Eq
-        const uint32_t Xv = Mv | ~tq;
-        const uint32_t Xh = (((Pv & ~tq) + Pv) ^ Pv) | ~tq;
-        const uint32_t Ph = (Mv | ~(Xh | Pv)) << 1 | 1u;
-        const uint32_t Mh = (Pv & Xh) << 1;
-        Pv = Mh | ~(Xv | Ph);
-        Mv = Ph & Xv;
+        sed_bitpar_step(Pv, Mv, sed_bitpar_tq(E0, E1, a));
     }
-    const uint32_t keep = m >= 32 ? ~0u : (1u << m) - 1u;
-    return (uint32_t)n + (uint32_t)__builtin_popcount(Pv & keep) - (uint32_t)__builtin_popcount(Mv & keep);
+    return sed_bitpar_sink(n, m, Pv, Mv);
 }
 
 template <int MM>
@@ -429,16 +416,9 @@ __global__ __launch_bounds__(256) void sed_lane_scaled_kernel(const sed_pair_des
                 w1 = pa4[(i >> 2) + 2];
             }
             const uint32_t u = __builtin_amdgcn_ubfe(sp.umap, 2 * a, 2);
-            const uint32_t tq = (E0 ^ (0u - (u & 1u))) | (E1 ^ (0u - (u >> 1)));  // ~Eq
-            const uint32_t Xv = Mv | ~tq;
-            const uint32_t Xh = (((Pv & ~tq) + Pv) ^ Pv) | ~tq;
-            const uint32_t Ph = (Mv | ~(Xh | Pv)) << 1 | 1u;
-            const uint32_t Mh = (Pv & Xh) << 1;
-            Pv = Mh | ~(Xv | Ph);
-            Mv = Ph & Xv;
+            sed_bitpar_step(Pv, Mv, sed_bitpar_tq(E0, E1, u));
         }
-        const uint32_t keep = m >= 32 ? ~0u : (1u << m) - 1u;
-        const uint32_t Dv = (uint32_t)n + (uint32_t)__builtin_popcount(Pv & keep) - (uint32_t)__builtin_popcount(Mv & keep);
+        const uint32_t Dv = sed_bitpar_sink(n, m, Pv, Mv);
         r.dist = (double)Dv;
         r.is_int = (Dv == 0);
         res[pair] = r;
@@ -446,8 +426,7 @@ __global__ __launch_bounds__(256) void sed_lane_scaled_kernel(const sed_pair_des
     }
     uint32_t sel[MM], V[MM + 1];
 #pragma unroll
-    for (int j = 0; j < MM; ++j)  // perm: byte 3 <- 0xFF, byte 2 <- table byte b_j, bytes 1:0 <- 0xFF
-        sel[j] = 0x0D000D0Du | (((bw[j >> 2] >> (8 * (j & 3))) & 7u) << 16);
+    for (int j = 0; j < MM; ++j) sel[j] = sed_scaled_sel(bw[j >> 2] >> (8 * (j & 3)));
 #pragma unroll
     for (int j = 0; j <= MM; ++j) V[j] = SED_KB;  // row 0 and column 0: the offset key B
     uint2 rt = tab[w0 & 7u];
@@ -459,23 +438,12 @@ __global__ __launch_bounds__(256) void sed_lane_scaled_kernel(const sed_pair_des
             w1 = pa4[(i1 >> 2) + 1];
         }
         rt = tab[(w0 >> (8 * (i1 & 3))) & 7u];
-        // the addend ((cost - ins - del) << 16) - 1 of the update candidate; candidates left (insert), up (delete)
-        uint32_t dg = V[0] + __builtin_amdgcn_perm(cur.y, cur.x, sel[0]);
-        uint32_t left = V[0];  // stays B
-#pragma unroll
-        for (int j = 1; j <= MM; ++j) {
-            const uint32_t up = V[j];
-            const uint32_t dnext = j < MM ? up + __builtin_amdgcn_perm(cur.y, cur.x, sel[j]) : 0u;
-            const uint32_t v = umin3(left, up, dg);
-            dg = dnext;
-            V[j] = v;
-            left = v;
-        }
+        sed_scaled_row<MM>(V, sel, cur);
     }
     uint32_t cap = V[1];
 #pragma unroll
     for (int j = 2; j <= MM; ++j) cap = (j == m) ? V[j] : cap;
-    const uint32_t D = (cap - SED_KB + (((uint32_t)n * sp.del + (uint32_t)m * sp.ins) << 16) + 0xFFFFu) >> 16;
+    const uint32_t D = sed_scaled_decode(cap, n, m, sp.ins, sp.del);
     r.dist = (double)D * sp.inv_scale;  // exact: a power of two
     r.is_int = (D == 0);
     res[pair] = r;

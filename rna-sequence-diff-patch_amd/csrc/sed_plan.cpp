@@ -1194,6 +1194,8 @@ const OptSpec opt_table[] = {
     {SED_OPT_BAND, &sed_opts::band, V(0, 2, 3), 0},
     {SED_OPT_FIT_CHUNK, &sed_opts::fit_chunk, 0, INT_MAX},
     {SED_OPT_FIT_ROWS, &sed_opts::fit_rows, V(0, 2, 4) | V(8, 16, 32), 0},
+    {SED_OPT_JOIN_DP, &sed_opts::join_dp, V(0, 2), 0},
+    {SED_OPT_JOIN_ROWS, &sed_opts::join_rows, 0, INT_MAX},
     {SED_OPT_DEBUG_CORRUPT, &sed_opts::debug_corrupt, 0, INT_MAX},
     {SED_OPT_CHAIN, &sed_opts::chain, 0, 1024},
     {SED_OPT_ROWS_PER_LANE, &sed_opts::R, V(0, 1, 2) | V(4, 8, 16) | V(32), 0},
@@ -1374,8 +1376,9 @@ int probe_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int
     c.del = del;
     c.ins_int = ins_is_int ? 1 : 0;
     c.del_int = del_is_int ? 1 : 0;
-    for (int i = 0; i < noptions; ++i)  // (the fit options are no options of a batch: the fit plan calls take them)
+    for (int i = 0; i < noptions; ++i)  // (the fit and join options are no options of a batch: their plan calls take them)
         if (options[2 * i] == SED_OPT_FIT_CHUNK || options[2 * i] == SED_OPT_FIT_ROWS ||
+            options[2 * i] == SED_OPT_JOIN_DP || options[2 * i] == SED_OPT_JOIN_ROWS ||
             !sed_opts_set(*o, options[2 * i], options[2 * i + 1], true))
             return SED_E_ARG;
     return sed_plan_batch(c, *o, codes_a, off_a, len_a, codes_b, off_b, len_b, npairs, flags, p, nullptr);

@@ -40,6 +40,9 @@ struct sed_opts {
     int fit_chunk = 0;      // SED_OPT_FIT_CHUNK: fit search (sed_fit_plan.h), owned text columns per lane: 0 auto, else
                             // the chunk length
     int fit_rows = 0;       // SED_OPT_FIT_ROWS: the long fit calls (sed_fit_plan.h), pattern rows per lane: 0 auto, else R
+    int join_dp = 0;        // SED_OPT_JOIN_DP: the similarity join (sed_join_plan.h): 0 auto (bit-parallel under unit costs),
+                            // 2 the scaled DP kernel always
+    int join_rows = 0;      // SED_OPT_JOIN_ROWS: the join's rows per launch: 0 auto (the grid's limit), else that many (tests)
     int env_tbpar = -1;     // SED_TBPAR: 0/1 overrides the stripe-parallel traceback's rule (A/B), -1 unset
     int env_band = 1;       // SED_BAND: 0 turns band pruning off, 3 ("static") keeps the static windows (A/B through bench.py)
     int env_alt_dp = 1;     // SED_ALT_DP: 0 keeps every DP on the context's stream (A/B)

@@ -59,6 +59,8 @@ SED_OPT_BAND = 16
 SED_OPT_CUT = 17
 SED_OPT_FIT_CHUNK = 18
 SED_OPT_FIT_ROWS = 19
+SED_OPT_JOIN_DP = 20
+SED_OPT_JOIN_ROWS = 21
 # sed_plan_routes only: the environment knobs the runtime reads once per process, as options of a plan
 SED_PLAN_ENV_TBPAR = 101
 SED_PLAN_ENV_BAND = 102
@@ -181,6 +183,19 @@ SIGNATURES = [
                                                _i32p, C.c_int32, _i32p, C.c_int32, _i32p, C.c_int64]),
     ("sed_fit_long_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                      _i32p, C.c_int32, _i32p, C.c_int32, C.c_char_p, C.c_int]),
+    ("sed_join_index_create", C.c_void_p, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32]),
+    ("sed_join_index_destroy", None, [C.c_void_p]),
+    ("sed_join_index_seqs", C.c_int32, [C.c_void_p]),
+    ("sed_join_self", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                C.POINTER(C.c_int64)]),
+    ("sed_join_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                  C.POINTER(C.c_int64)]),
+    ("sed_join_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("sed_join_pairs_run", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("sed_join_rows_per_group", C.c_int32, []),
+    ("sed_join_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
+                                _f64p, C.c_int]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -359,6 +374,11 @@ class Context:
         """A resident text index for fit search (sed_fit_index_create): text d = codes[off[d] : off[d] + lens[d]],
         uploaded once.  FitIndex.search then sends only the queries."""
         return FitIndex(self, codes, off, lens)
+
+    def join_index(self, codes, off, lens):
+        """A resident index of short sequences for the similarity join (sed_join_index_create): sequence i =
+        codes[off[i] : off[i] + lens[i]], 0..32 symbols, uploaded once."""
+        return JoinIndex(self, codes, off, lens)
 
     def run_pair(self, codes_a, codes_b, want_script, no_len=False):
         """One pair (codes as bytes): (dist, is_int, len, ops u32[] | None) through sed_run_pair, the per-call path of
@@ -608,6 +628,131 @@ class FitIndex:
         ms = C.c_float()
         self.ctx._check(self._lib.sed_fit_index_hits_last_time(self.ptr, C.byref(ms)), "sed_fit_index_hits_last_time")
         return ms.value
+
+
+# one sed_join_hit (include/sed.h)
+JOIN_HIT_DTYPE = np.dtype([("row", np.int32), ("col", np.int32), ("dist", np.float64)], align=True)
+
+
+def join_rows_per_group():
+    """The rows a block of the join kernel runs against its columns (sed_join_rows_per_group)."""
+    return int(load().sed_join_rows_per_group())
+
+
+class JoinIndex:
+    """Device-resident short sequences (0..32 symbols each) for the similarity join (sed_join_*): upload once, then
+    self_join() / search() return every (row, col) pair within a distance as a JOIN_HIT_DTYPE array sorted by (row, col),
+    under the context's costs and options of that moment.  Rows are str1, columns str2."""
+
+    def __init__(self, ctx, codes, off, lens):
+        self.ctx = ctx
+        self.found = 0       # the last call's total count
+        self._hit_room = 0   # records the last cap=None call made room for: the next one starts there
+        self._lib = ctx._lib
+        lens = np.ascontiguousarray(lens, np.int32)
+        off = np.ascontiguousarray(off, np.int64)
+        self.nseqs = len(lens)
+        codes = np.ascontiguousarray(codes, np.uint8)
+        one = lambda a, t: a if len(a) else np.zeros(1, t)
+        self.ptr = self._lib.sed_join_index_create(ctx.ptr, one(codes, np.uint8), one(off, np.int64), one(lens, np.int32),
+                                                   self.nseqs)
+        if not self.ptr:
+            msg = self._lib.sed_last_error(ctx.ptr)
+            raise SedError("sed_join_index_create failed: %s" % (msg.decode() if msg else ""))
+
+    @classmethod
+    def from_seqs(cls, ctx, seqs):
+        """From a list of uint8 code arrays."""
+        lens = np.array([len(t) for t in seqs], np.int32)
+        off = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]).astype(np.int64) if len(seqs) else np.zeros(0, np.int64)
+        codes = np.concatenate([np.asarray(t, np.uint8) for t in seqs]) if len(seqs) else np.zeros(0, np.uint8)
+        return cls(ctx, codes, off, lens)
+
+    def close(self):
+        if self.ptr and self.ctx.ptr and self.ctx._pid == os.getpid():
+            self._lib.sed_join_index_destroy(self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _hits(self, what, call, cap):
+        if not self.ptr:
+            raise SedError("%s: the index is closed" % what)
+        found = C.c_int64(0)
+        room = self._hit_room if cap is None else int(cap)
+        while True:
+            out = np.zeros(max(room, 1), JOIN_HIT_DTYPE)
+            rc = call(out.ctypes.data if room > 0 else None, room, C.byref(found))
+            self.found = int(found.value)
+            if rc == SED_E_RANGE and cap is None and self.found > room:
+                room = self.found  # (a refusal of the plan leaves found at 0 <= room)
+                continue
+            self.ctx._check(rc, what)
+            if cap is None:
+                self._hit_room = max(self._hit_room, room)
+            return out[:self.found]
+
+    def self_join(self, max_dist, rows=None, cap=None):
+        """Every (i, j), i != j, i in rows = (lo, hi) (default: every sequence), with distance(seq i -> seq j) <=
+        max_dist (sed_join_self).  cap = the records to make room for: more hits raise SedError (the index stays
+        usable; found has the count; cap=0 is a count query).  cap=None retries once with room, so it returns every hit."""
+        lo, hi = (0, self.nseqs) if rows is None else rows
+        return self._hits("sed_join_self", lambda out, room, found: self._lib.sed_join_self(
+            self.ptr, int(lo), int(hi), float(max_dist), out, room, found), cap)
+
+    def search(self, packed, max_dist, cap=None):
+        """Every (q, j) with distance(query q -> seq j) <= max_dist (sed_join_search); packed: the queries as side a of
+        a PackedPairs, 0..32 symbols each.  cap as for self_join."""
+        return self._hits("sed_join_search", lambda out, room, found: self._lib.sed_join_search(
+            self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.npairs, float(max_dist), out, room, found), cap)
+
+    def last_ms(self):
+        """Device time of the last join's kernel(s) (ms, HIP events)."""
+        ms = C.c_float()
+        self.ctx._check(self._lib.sed_join_last_time(self.ptr, C.byref(ms)), "sed_join_last_time")
+        return ms.value
+
+    def pairs_run(self):
+        """The pairs the last join's waves ran, counted on the device (sed_join_pairs_run): join_plan's "run"."""
+        n = C.c_int64()
+        self.ctx._check(self._lib.sed_join_pairs_run(self.ptr, C.byref(n)), "sed_join_pairs_run")
+        return int(n.value)
+
+
+JOIN_PLAN_FIELDS = ("scale", "kernel", "waves", "scope", "run", "cells")
+JOIN_KERNELS = {1: "dp", 2: "bitpar"}
+
+
+def codes_seen(codes):
+    """The mask sed_join_plan takes: bit c set when code c occurs (bit 31: any code >= 31)."""
+    mask = 0
+    for c in np.unique(np.asarray(codes, np.uint8)).tolist():
+        mask |= 1 << min(c, 31)
+    return mask
+
+
+def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
+    """What JoinIndex.self_join / search would decide, without a device (sed_join_plan): {field: number} over
+    JOIN_PLAN_FIELDS.  costs and options as plan_routes takes them; row_codes / col_codes from codes_seen.  Raises
+    SedError carrying the SED_E_* code (.code) the join would fail with."""
+    K, sub, sub_int, ins, ins_int, dele, del_int = costs
+    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
+    lr = np.ascontiguousarray(len_rows if len(len_rows) else [0], np.int32)
+    lc = np.ascontiguousarray(len_cols if len(len_cols) else [0], np.int32)
+    out = np.zeros(len(JOIN_PLAN_FIELDS), np.float64)
+    rc = load().sed_join_plan(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
+                              np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
+                              int(del_int), opts, len(options), lr, len(len_rows), lc, len(len_cols), int(bool(self_join)),
+                              int(row_codes), int(col_codes), float(max_dist), out, len(out))
+    if rc != 0:
+        err = SedError("sed_join_plan failed (%d)" % rc)
+        err.code = rc
+        raise err
+    return {k: (float(v) if k in ("scale", "cells") else int(v)) for k, v in zip(JOIN_PLAN_FIELDS, out)}
 
 
 def unpack_ops(ops_words, ops_off, p, length):
@@ -927,6 +1072,10 @@ class EngineClient:
     def fit_index(self, codes, off, lens):
         raise SedError("fit_index: a forked child's engine proxy does not serve resident indexes (its texts would live "
                        "in the serving process); use fit() here, or build the index in the process that owns the device")
+
+    def join_index(self, codes, off, lens):
+        raise SedError("join_index: a forked child's engine proxy does not serve resident indexes (its sequences would "
+                       "live in the serving process); build the index in the process that owns the device")
 
 
 class _PlanArgs:

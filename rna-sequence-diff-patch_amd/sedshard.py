@@ -60,3 +60,38 @@ def all_vs_all(seqs, userCosts=False, world=1, rank=0, device=None, distance_fn=
     if rank != 0:
         return None
     return got[0].cpu().numpy().reshape(len(seqs), len(seqs))
+
+
+def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, join_fn=None):
+    """Every ordered pair (i, j), i != j, of the short sequences seqs (0..32 symbols) whose distance from seqs[i] to
+    seqs[j] is <= max_dist, as a numpy record array (row, col, dist) sorted by (row, col), on rank 0 (None on other
+    ranks).  Rank r joins its block of rows, shard_range(len(seqs), world, r), against every sequence on its own GPU
+    (StringEditDistance.join_index; every rank holds the whole collection, which is small: 32 bytes a sequence), and
+    only its hits travel, once, to rank 0; the blocks are contiguous, so their concatenation is sorted.
+    join_fn(seqs, lo, hi, max_dist, userCosts) -> [(i, j, dist)] sorted replaces the engine (the CPU tests inject the
+    oracle to check the sharding and reassembly)."""
+    import torch
+    if join_fn is None:
+        import StringEditDistance as SED
+
+        def join_fn(seqs, lo, hi, max_dist, userCosts):
+            ix = SED.join_index(seqs, userCosts)
+            try:
+                return ix.self_join(max_dist, (lo, hi))
+            finally:
+                ix.close()
+    lo, hi = shard_range(len(seqs), world, rank)
+    hits = list(join_fn(seqs, lo, hi, max_dist, userCosts)) if hi > lo else []
+    dtype = np.dtype([("row", np.int32), ("col", np.int32), ("dist", np.float64)])
+    rows = np.array([h[0] for h in hits], np.int32)
+    cols = np.array([h[1] for h in hits], np.int32)
+    dist = np.array([h[2] for h in hits], np.float64)
+    if world > 1:
+        dev = device if device is not None else "cpu"
+        got = gather_to_rank0([torch.from_numpy(x).to(dev) for x in (rows, cols, dist)], world, rank)
+        if rank != 0:
+            return None
+        rows, cols, dist = (g.cpu().numpy() for g in got)
+    out = np.zeros(len(rows), dtype)
+    out["row"], out["col"], out["dist"] = rows, cols, dist
+    return out

@@ -327,6 +327,60 @@ def fit_occurrences(query, seqs_or_collection, max_dist, user_cost=False, all_en
         ix.close()
 
 
+class JoinIndex:
+    """Every pair of short sequences (0..32 symbols) within a distance, for a collection that stays on the device
+    (StringEditDistance.join_index): clustering, de-duplication, neighbour graphs, many queries against one collection.
+
+        ix = JoinIndex(collection, user_cost=True)
+        ix.neighbors(2)                      # [(i, j, 1 / (1 + d))] for every i != j with d(seq i -> seq j) <= 2
+        ix.search_many(queries, 2)           # per query, == search_within(query, collection, 2, True)
+        ix.search(query, 2)
+
+    Rows (i, the queries) are str1 and columns (j, the documents) str2, the direction of wf_score(query, doc).
+    index_fn(sequences, user_cost) -> an object with self_join(max_dist, rows) -> [(i, j, d)] and
+    search(queries, max_dist) -> [(q, j, d)], both sorted, and close(), replaces the engine (CPU tests).  Not cached."""
+
+    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None):
+        self.seqs = _sequences(seqs_or_collection)
+        self.user_cost = user_cost
+        self._ix = (index_fn or SED.join_index)(self.seqs, user_cost) if self.seqs else None
+
+    def neighbors(self, max_dist, rows=None):
+        """[(i, j, 1 / (1 + d))] sorted by (i, j): every ordered pair i != j, i in rows = (lo, hi) (default: all), whose
+        distance d from sequence i to sequence j is <= max_dist."""
+        if self._ix is None:
+            return []
+        return [(i, j, 1 / (1 + d)) for i, j, d in self._ix.self_join(max_dist, rows)]
+
+    def search_many(self, queries, max_dist):
+        """Per query, [(sequence, 1 / (1 + d))] for the documents within max_dist, in collection order: what
+        search_within(query, seqs, max_dist, user_cost) returns, for all the queries from one engine call."""
+        queries = list(queries)
+        out = [[] for _ in queries]
+        if self._ix is None or not queries:
+            return out
+        for q, j, d in self._ix.search(queries, max_dist):
+            out[q].append((self.seqs[j], 1 / (1 + d)))
+        return out
+
+    def search(self, query, max_dist):
+        return self.search_many([query], max_dist)[0]
+
+    def close(self):
+        if self._ix is not None:
+            self._ix.close()
+        self._ix = None
+
+
+def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None):
+    """JoinIndex.neighbors in one shot: builds an index over the sequences, joins it with itself and closes it."""
+    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn)
+    try:
+        return ix.neighbors(max_dist)
+    finally:
+        ix.close()
+
+
 def search_collection(query, vector_type, collection, method, return_dict=None, callback=None):
     """IRMethods.search_collection for method == wf_score (IRMethods.py:443-477)."""
     if getattr(method, '__name__', None) != 'wf_score':
