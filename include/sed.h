@@ -619,8 +619,8 @@ int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double 
  * scaled DP; SED_OPT_JOIN_DP forces the DP.  A pair whose length bound insert * (m - n)+ + delete * (n - m)+ exceeds
  * max_dist is never computed, and a wave whose 64 columns all fail it skips the row.  More rows than one launch takes
  * (65535 groups of sed_join_rows_per_group rows; SED_OPT_JOIN_ROWS) run as further launches of the same call.
- * Not served: tables the conditions refuse (IUPAC: an fp64 route), sequences over 32 symbols, edit scripts of the hits,
- * k-nearest lists, the i < j half alone for symmetric tables, a per-tile mix of the two variants. */
+ * Not served: tables the conditions refuse (IUPAC: the _f64 calls below serve them), sequences over 32 symbols, edit
+ * scripts of the hits, k-nearest lists, the i < j half alone for symmetric tables, a per-tile mix of the two variants. */
 typedef struct sed_join_index sed_join_index;
 typedef struct { int32_t row, col; double dist; } sed_join_hit;
 sed_join_index *sed_join_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
@@ -647,6 +647,47 @@ int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, 
                   double del, int del_is_int, const int32_t *options, int noptions,
                   const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
                   uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
+
+/* The fp64 route of the similarity join: sed_join_self / sed_join_search for the cost tables and alphabets their scaled
+ * integer cells refuse (the 15-symbol IUPAC table of costs.json among them).  Arguments, hit records, sort order, cap
+ * protocol, state errors and error order are those of the integer calls; the index is the same (it stores one code per
+ * byte), and calls of either kind may alternate on it.
+ * A pair (row, column) is a hit exactly when wagnerFisher(row, column).value (StringEditDistance.py:133-224; the
+ * recurrence of lines 143-224 in fp64: row 0 = j * insert, column 0 = i * delete, a cell = min(left + insert, up +
+ * delete, diagonal + cost), each one fp64 add) is <= max_dist as a plain fp64 compare, and dist is that double bit for
+ * bit: there is no scale, no floor and no offset key.  +inf admits every pair; NaN or a negative max_dist: SED_E_ARG.
+ * Cost models served: at most 16 symbols, every cost finite and >= 0 (-0.0 counts as 0; subnormal
+ * costs are served and come out as the reference's); anything else is SED_E_RANGE before any launch, and the text names
+ * the bound or the cost.  A row or column code >= K: SED_E_ARG.
+ * Length skip: the reference's value is a sequentially rounded sum and can lie below the product |m - n| * cost, so a
+ * pair of lengths (n, m) is left out only when fl(|m - n| * cost) * (1 - 2^-40) > max_dist (with n, m >= 1, max_dist
+ * finite, the product finite and >= 2^-900), or, with n = 0 or m = 0, when the border product itself exceeds max_dist
+ * (DESIGN.md 3.6l).  It never drops a pair the reference keeps; it may run pairs the integer route's bound would skip.
+ * SED_OPT_JOIN_ROWS splits the rows into launches as for the integer calls; SED_OPT_JOIN_DP does not concern this
+ * route.  sed_join_last_time and sed_join_pairs_run report the last call of either kind. */
+int sed_join_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
+                      int64_t *found);
+int sed_join_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                        int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+/* What the fp64 calls would decide, without a device: sed_join_plan's arguments and out[] slots, with 0 = 0 (no scale)
+ * and 1 = 3 (the fp64 kernel). */
+int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                      double del, int del_is_int, const int32_t *options, int noptions,
+                      const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                      uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
+/* The fp64 length skip alone: keep[n], n = 0..32, bit m set when a row of n and a column of m symbols are computed under
+ * these costs (finite, >= 0) and cutoff (>= 0 or +inf); anything else: SED_E_ARG. */
+int sed_join_f64_keep(double ins, double del, double max_dist, uint64_t *keep);
+/* Which route serves the join sed_join_plan's arguments describe, without a device, with sed_fit_route's conventions:
+ * SED_JOIN_ROUTE_INT (sed_join_self / sed_join_search serve it; preferred whenever they do), SED_JOIN_ROUTE_F64 (only
+ * the _f64 calls do; why = the integer route's refusal text), or the negative code both fail with (why = both texts,
+ * "; " between them).  why (room for why_len bytes, may be NULL with 0) is always terminated. */
+#define SED_JOIN_ROUTE_INT 0
+#define SED_JOIN_ROUTE_F64 1
+int sed_join_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                   double del, int del_is_int, const int32_t *options, int noptions,
+                   const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                   uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, char *why, int why_len);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

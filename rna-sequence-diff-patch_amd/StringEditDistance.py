@@ -904,6 +904,7 @@ def fit_index(texts, userCosts=False, alphabet=None, engine=None, f64=False):
 
 
 JOIN_MAX_LEN = 32  # the join's longest sequence (include/sed.h: sed_join_index_create)
+JOIN_F64_SYMBOLS = 16  # the fp64 route's table bound (include/sed.h: sed_join_self_f64)
 
 
 class _EngineJoin:
@@ -921,6 +922,14 @@ class _EngineJoin:
         self.ctx.set_costs(plan)
         return self.ix.search(packed, max_dist)
 
+    def self_join_f64(self, plan, max_dist, rows):
+        self.ctx.set_costs(plan)
+        return self.ix.self_join_f64(max_dist, rows)
+
+    def search_f64(self, plan, packed, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.search_f64(packed, max_dist)
+
     def close(self):
         self.ix.close()
 
@@ -931,12 +940,17 @@ class JoinIndex:
     wagnerFisher(seqs[i], seqs[j]).value <= max_dist, search(queries, max_dist) returns [(q, j, dist)] for every query
     against every sequence, both sorted by (row, column); rows are str1, columns str2 (include/sed.h: sed_join_self,
     sed_join_search).  dist is a float (no int typing).  Symbols get their codes as in FitIndex; the engine serves dyadic
-    cost tables over at most 8 symbols and raises SedError otherwise.  The cost table is read at every call, and the
+    cost tables over at most 8 symbols and raises SedError otherwise.  f64=True builds the index for the fp64 route
+    instead: the bound is 16 symbols (the refusal names the bound in force; the default's text is unchanged), and
+    self_join_f64 / search_f64 serve any table of costs >= 0 (self_join / search still run the integer kernels and
+    refuse what those refuse).  The cost table is read at every call, and the
     KeyErrors are the reference's for the first offending (row, column) in row-major order."""
 
-    def __init__(self, seqs, userCosts=False, alphabet=None, engine=None):
+    def __init__(self, seqs, userCosts=False, alphabet=None, engine=None, f64=False):
         self.seqs = list(seqs)
         self.userCosts = userCosts
+        self.f64 = bool(f64)
+        self.max_symbols = JOIN_F64_SYMBOLS if self.f64 else 8
         for i, s in enumerate(self.seqs):
             if len(s) > JOIN_MAX_LEN:
                 raise sedgpu.SedError("join index: sequence %d has %d symbols (the join serves at most %d)"
@@ -945,8 +959,9 @@ class JoinIndex:
             list(dict.fromkeys(c for t in self.seqs for c in t))
         self._used = used
         self.symbols = list(dict.fromkeys(list(alphabet or ()) + used))
-        if len(self.symbols) > 8:
-            raise sedgpu.SedError("join index: the sequences have %d symbols (the join serves at most 8)" % len(self.symbols))
+        if len(self.symbols) > self.max_symbols:
+            raise sedgpu.SedError("join index: the sequences have %d symbols (the join serves at most %d)"
+                                  % (len(self.symbols), self.max_symbols))
         code = {c: k for k, c in enumerate(self.symbols)}
         lens = np.fromiter(map(len, self.seqs), dtype=np.int32, count=len(self.seqs))
         codes = np.fromiter((code[c] for t in self.seqs for c in t), dtype=np.uint8, count=int(lens.sum()))
@@ -967,22 +982,31 @@ class JoinIndex:
                 for t in self.seqs:
                     sedcost.check_pair(table, p, t)
         alphabet = self.symbols + [c for c in u1 if c not in self.symbols]
-        if len(alphabet) > 8:
-            raise sedgpu.SedError("join index: the sequences and these rows have %d symbols (the join serves at most 8)"
-                                  % len(alphabet))
+        if len(alphabet) > self.max_symbols:
+            raise sedgpu.SedError("join index: the sequences and these rows have %d symbols (the join serves at most %d)"
+                                  % (len(alphabet), self.max_symbols))
         return sedcost.plan_over(table, alphabet, set(u1), set(self._used))
 
-    def self_join(self, max_dist, rows=None):
+    def self_join(self, max_dist, rows=None, _dev="self_join"):
         lo, hi = (0, len(self.seqs)) if rows is None else rows
         if not 0 <= lo <= hi <= len(self.seqs):
             raise ValueError("rows=(%r, %r) is no range of the index's %d sequences" % (lo, hi, len(self.seqs)))
         plan = self.plan(self.seqs[lo:hi])
         if lo == hi:
             return []
-        h = self._dev.self_join(plan, max_dist, (lo, hi))
+        h = getattr(self._dev, _dev)(plan, max_dist, (lo, hi))
         return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
 
-    def search(self, queries, max_dist):
+    def self_join_f64(self, max_dist, rows=None):
+        """self_join() through the fp64 kernel (include/sed.h: sed_join_self_f64): any table of costs >= 0; with an
+        index built f64=True, up to 16 symbols."""
+        return self.self_join(max_dist, rows, "self_join_f64")
+
+    def search_f64(self, queries, max_dist):
+        """search() through the fp64 kernel (include/sed.h: sed_join_search_f64)."""
+        return self.search(queries, max_dist, "search_f64")
+
+    def search(self, queries, max_dist, _dev="search"):
         queries = list(queries)
         for q, s in enumerate(queries):
             if len(s) > JOIN_MAX_LEN:
@@ -992,19 +1016,39 @@ class JoinIndex:
             return []
         ca, la = plan.encode_many(queries)
         packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
-        h = self._dev.search(plan, packed, max_dist)
+        h = getattr(self._dev, _dev)(plan, packed, max_dist)
         return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
 
     def close(self):
         self._dev.close()
 
 
-def join_index(seqs, userCosts=False, alphabet=None, engine=None):
+def join_index(seqs, userCosts=False, alphabet=None, engine=None, f64=False):
     """A JoinIndex over seqs (0..32 symbols each): every pair within a distance, for clustering, de-duplication,
     neighbour graphs, or many queries against one collection.  engine(codes, off, lens) -> an object with
-    self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), both returning sedgpu.JOIN_HIT_DTYPE records,
-    and close() replaces the device (CPU tests)."""
-    return JoinIndex(seqs, userCosts, alphabet, engine)
+    self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), their self_join_f64 / search_f64, all returning
+    sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU tests)."""
+    return JoinIndex(seqs, userCosts, alphabet, engine, f64)
+
+
+def join_route(rows, seqs, max_dist, userCosts=False):
+    """"int" or "f64": the join kernels that serve rows (str1) against seqs (str2) within max_dist.  The integer kernels
+    whenever sedgpu.join_route says they serve the cost table over the symbols of both sides; the fp64 kernel when only
+    it does.  A join neither serves, one with bad arguments, or one whose symbols the cost table does not resolve goes to
+    the integer call, which raises what it always raised."""
+    rows, seqs = list(rows), list(seqs)
+    if not rows or not seqs:
+        return "int"
+    n = max(len(rows), len(seqs))  # every row and every sequence once: the plan's alphabet is the join's
+    try:
+        plan = batch_plan([rows[i % len(rows)] for i in range(n)], [seqs[i % len(seqs)] for i in range(n)], userCosts)
+        costs = (plan.K, plan.sub, plan.sub_int, plan.ins, plan.ins_int, plan.dele, plan.del_int)
+        route, _ = sedgpu.join_route(costs, {}, [len(r) for r in rows], [len(t) for t in seqs], False,
+                                     sedgpu.codes_seen(plan.encode_many(rows)[0]),
+                                     sedgpu.codes_seen(plan.encode_many(seqs)[0]), max_dist)
+    except (KeyError, sedgpu.SedError):
+        return "int"
+    return "f64" if route == "f64" else "int"
 
 
 def edit_script_batch(strs1, strs2, userCosts=False):

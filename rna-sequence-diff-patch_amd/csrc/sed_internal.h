@@ -366,6 +366,30 @@ struct sed_join_args {
     unsigned long long cap;
 };
 hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar);
+// The fp64 route of the join (sed_join_f64.hip; include/sed.h: sed_join_self_f64, sed_join_search_f64): the same records,
+// grid, counters and self rule.
+//   sub      = SED_JOIN_F64_MAXK x SED_JOIN_F64_MAXK doubles on the device, row a = row symbol a, zeros past K;
+//   keep[n]  = 33 words on the device, bit m set when a row of n and a column of m symbols are computed (the planner's
+//              length skip, sed_join_plan.h: sed_join_f64_keep_rule); the kernel tests the bit and nothing else;
+//   max_dist = the cutoff: a pair is a hit when its fp64 distance D <= max_dist;
+//   hits     = 16-byte records (row, original column, D's low word, D's high word).
+#define SED_JOIN_F64_MAXK 16
+struct sed_join_f64_args {
+    const void *rows;
+    const int32_t *row_len;
+    int32_t row0, nrows;
+    const void *cols;
+    const int32_t *col_len, *col_orig;
+    int32_t ncols;
+    int32_t self;
+    const double *sub;
+    const unsigned long long *keep;
+    double ins, del, max_dist;
+    uint4 *hits;
+    unsigned long long *count;
+    unsigned long long cap;
+};
+hipError_t sed_launch_join_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_f64_args &a);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 
 int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *err) {
     if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "join: %d symbols (the scaled cost rows hold at most 8)", c.K);
@@ -115,6 +116,157 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
         plan->cells -= own_cells;
     }
     return SED_OK;
+}
+
+// ---- the fp64 route ----
+int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::string *err) {
+    if (c.K > SED_JOIN_F64_MAXK)
+        return sed_plan_fail(err, SED_E_RANGE, "join (fp64): %d symbols (at most %d)", c.K, SED_JOIN_F64_MAXK);
+    auto cost_ok = [](double v) { return std::isfinite(v) && v >= 0; };  // (-0.0 >= 0)
+    if (!cost_ok(c.ins)) return sed_plan_fail(err, SED_E_RANGE, "join (fp64): insert = %g is not a finite cost >= 0", c.ins);
+    if (!cost_ok(c.del)) return sed_plan_fail(err, SED_E_RANGE, "join (fp64): delete = %g is not a finite cost >= 0", c.del);
+    for (int e = 0; e < c.K * c.K; ++e)
+        if (!cost_ok(c.sub[e]))
+            return sed_plan_fail(err, SED_E_RANGE, "join (fp64): cost(%d -> %d) = %g is not a finite cost >= 0", e / c.K, e % c.K,
+                                 c.sub[e]);
+    plan->ins = c.ins + 0.0;  // (-0.0 + 0.0 = +0.0)
+    plan->del = c.del + 0.0;
+    std::fill(plan->sub, plan->sub + SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK, 0.0);
+    for (int a = 0; a < c.K; ++a)
+        for (int b = 0; b < c.K; ++b) plan->sub[a * SED_JOIN_F64_MAXK + b] = c.sub[a * c.K + b] + 0.0;
+    return SED_OK;
+}
+
+void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t keep[SED_JOIN_MAXLEN + 1]) {
+    const double tiny = std::ldexp(1.0, -900), shrink = std::ldexp(1.0, -40);
+    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n) {
+        keep[n] = 0;
+        for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
+            bool run = true;
+            if (n == 0 || m == 0) {  // D is this product itself (0.0 when n = m = 0)
+                run = (n == 0 ? (double)m * ins : (double)n * del) <= max_dist;
+            } else if (n != m && std::isfinite(max_dist)) {
+                const double p = m > n ? (double)(m - n) * ins : (double)(n - m) * del;
+                // D > p (1 - 2^-46) >= fl(p - p 2^-40) for a finite p >= 2^-900 (p 2^-40 is exact there)
+                if (std::isfinite(p) && p >= tiny) run = !(p - p * shrink > max_dist);
+            }
+            if (run) keep[n] |= (uint64_t)1 << m;
+        }
+    }
+}
+
+int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows,
+                         const int32_t *len_cols, int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes,
+                         double max_dist, sed_join_f64_plan_t *plan, std::string *err) {
+    if (nrows < 0 || ncols < 0 || (nrows && !len_rows) || (ncols && !len_cols) || (self && nrows > ncols))
+        return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    if (std::isnan(max_dist) || max_dist < 0) return sed_plan_fail(err, SED_E_ARG, "join: max_dist is NaN or negative");
+    int rc = sed_join_f64_costs_rule(c, plan, err);
+    if (rc != SED_OK) return rc;
+    const uint32_t seen = row_codes | col_codes;
+    if ((seen >> c.K) != 0) {  // (K <= 16)
+        const bool in_cols = (col_codes >> c.K) != 0;
+        return sed_plan_fail(err, SED_E_ARG, "join: a %s code is outside the alphabet (K=%d)", in_cols ? "column" : "row", c.K);
+    }
+    double hr[SED_JOIN_MAXLEN + 1] = {}, hc[SED_JOIN_MAXLEN + 1] = {};
+    double own_cells = 0;  // sum n n over the rows: the (i, i) pairs a self join leaves out
+    for (int i = 0; i < nrows; ++i) {
+        if (len_rows[i] < 0 || len_rows[i] > SED_JOIN_MAXLEN)
+            return sed_plan_fail(err, SED_E_ARG, "join: row %d has %d symbols (0..%d)", i, len_rows[i], SED_JOIN_MAXLEN);
+        hr[len_rows[i]] += 1;
+        own_cells += (double)len_rows[i] * len_rows[i];
+    }
+    for (int j = 0; j < ncols; ++j) {
+        if (len_cols[j] < 0 || len_cols[j] > SED_JOIN_MAXLEN)
+            return sed_plan_fail(err, SED_E_ARG, "join: column %d has %d symbols (0..%d)", j, len_cols[j], SED_JOIN_MAXLEN);
+        hc[len_cols[j]] += 1;
+    }
+    plan->max_dist = max_dist;
+    sed_join_f64_keep_rule(plan->ins, plan->del, max_dist, plan->keep);
+    plan->launch_rows = o.join_rows > 0 ? o.join_rows : (int64_t)SED_JOIN_MAX_GROUPS * SED_JOIN_G;
+    const double blocks = (ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK;
+    double groups = 0;
+    for (int64_t r = 0; r < nrows; r += plan->launch_rows)
+        groups += (double)((std::min<int64_t>(plan->launch_rows, nrows - r) + SED_JOIN_G - 1) / SED_JOIN_G);
+    plan->waves = ncols > 0 ? blocks * groups * (SED_JOIN_BLOCK / 64) : 0;
+    plan->scope = (double)nrows * ncols - (self ? nrows : 0);
+    plan->run = plan->cells = 0;
+    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n)
+        for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
+            if (!((plan->keep[n] >> m) & 1u)) continue;
+            plan->run += hr[n] * hc[m];
+            plan->cells += hr[n] * hc[m] * n * m;
+        }
+    if (self) {  // every (i, i) has n = m, which the rule always computes, and was counted
+        plan->run -= nrows;
+        plan->cells -= own_cells;
+    }
+    return SED_OK;
+}
+
+// sed_join_plan's, sed_join_f64_plan's and sed_join_route's arguments as the planner's costs and options
+static int join_costs_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                         int del_is_int, const int32_t *options, int noptions, sed_costs *c, sed_opts *o) {
+    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options)) return SED_E_ARG;
+    c->K = K;
+    c->sub.assign(sub, sub + K * K);
+    if (sub_int) c->sub_int.assign(sub_int, sub_int + K * K);
+    c->ins = ins;
+    c->del = del;
+    c->ins_int = ins_is_int ? 1 : 0;
+    c->del_int = del_is_int ? 1 : 0;
+    for (int i = 0; i < noptions; ++i)
+        if (!sed_opts_set(*o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    return SED_OK;
+}
+
+extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                 int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
+                                 int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
+                                 uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return rc;
+    sed_join_f64_plan_t p;
+    rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
+                              nullptr);
+    if (rc != SED_OK) return rc;
+    const double v[] = {0.0, (double)SED_JOIN_KERNEL_F64, p.waves, p.scope, p.run, p.cells};
+    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}
+
+extern "C" int sed_join_f64_keep(double ins, double del, double max_dist, uint64_t *keep) {
+    if (!keep || !(std::isfinite(ins) && ins >= 0) || !(std::isfinite(del) && del >= 0) || std::isnan(max_dist) || max_dist < 0)
+        return SED_E_ARG;
+    sed_join_f64_keep_rule(ins + 0.0, del + 0.0, max_dist, keep);
+    return SED_OK;
+}
+
+extern "C" int sed_join_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                              int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows,
+                              const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
+                              uint32_t col_codes_seen, double max_dist, char *why, int why_len) {
+    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
+    if (why_len) why[0] = 0;
+    sed_costs c;
+    sed_opts o;
+    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return rc;
+    sed_join_plan_t p;
+    std::string e_int, e_f64;
+    if ((rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
+                               &e_int)) == SED_OK)
+        return SED_JOIN_ROUTE_INT;
+    if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
+    sed_join_f64_plan_t pf;
+    rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &pf,
+                              &e_f64);
+    const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
+    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
+    return rc == SED_OK ? SED_JOIN_ROUTE_F64 : rc;
 }
 
 extern "C" int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,

@@ -31,3 +31,29 @@ int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *
 int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
                      int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
                      sed_join_plan_t *plan, std::string *err);
+
+// The fp64 route (include/sed.h: sed_join_self_f64, sed_join_search_f64; kernel: sed_join_f64.hip): any table of finite
+// costs >= 0 over at most SED_JOIN_F64_MAXK symbols.  There is no scale: a cell's value is the oracle's.
+#define SED_JOIN_KERNEL_F64 3
+struct sed_join_f64_plan_t {
+    double ins = 0, del = 0;     // -0.0 normalised to +0.0, as sub
+    double sub[SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK] = {};  // row a = row symbol a, zeros past K
+    double max_dist = 0;
+    uint64_t keep[SED_JOIN_MAXLEN + 1] = {};  // keep[n] bit m: a row of n and a column of m symbols are computed
+    int64_t launch_rows = 0;     // as sed_join_plan_t's
+    double waves = 0, scope = 0, run = 0, cells = 0;
+};
+// The table alone: K <= SED_JOIN_F64_MAXK, every cost finite and >= 0; fills ins, del, sub.  Anything else: SED_E_RANGE,
+// *err names the bound or the cost.
+int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::string *err);
+// The length skip under rounding.  The oracle's D of a row of n and a column of m symbols is a
+// sequentially rounded sum; with k = |m - n| and c = insert (m > n) or delete (n > m),
+//     D >= k c (1 - 2^-53)^(n + m) > fl(k c) (1 - 2^-46),
+// so the pair is left out exactly when n, m, k >= 1, max_dist is finite, p = fl(k c) is finite and >= 2^-900, and
+// fl(p - p 2^-40) > max_dist.  With n = 0 or m = 0, D is the product fl(m insert) or fl(n delete) itself and the exact
+// compare decides.  keep[n] bit m = the pair is computed.  ins, del >= +0, max_dist >= 0 or +inf.
+void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t keep[SED_JOIN_MAXLEN + 1]);
+// The whole plan: sed_join_plan_of's arguments, checks (in its order) and counts under the rule above.
+int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows,
+                         const int32_t *len_cols, int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes,
+                         double max_dist, sed_join_f64_plan_t *plan, std::string *err);

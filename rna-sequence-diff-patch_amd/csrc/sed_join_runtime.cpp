@@ -1,6 +1,6 @@
 // sed_join_runtime.cpp — the similarity join's entry points of the C-ABI (include/sed.h): sed_join_index_* and
-// sed_join_self / sed_join_search over a resident index of short sequences.  What a join runs is the join planner's
-// decision (sed_join_plan.cpp), the kernels are sed_join.hip; here: pack, reserve, upload, launch, download, sort,
+// sed_join_self / sed_join_search and their _f64 siblings over a resident index of short sequences.  What a join runs is
+// the join planner's decision (sed_join_plan.cpp), the kernels are sed_join.hip and sed_join_f64.hip; here: pack, reserve, upload, launch, download, sort,
 // decode, on the context's stream (sed_runtime.h).
 #include "sed_join_plan.h"
 #include "sed_runtime.h"
@@ -26,9 +26,11 @@ struct JoinTimer {  // the events around a call's launches, created on first use
     }
 };
 struct JoinRec {  // one record of the device hit list (sed_internal.h: sed_join_args)
-    uint32_t row, col, D, zero;
+    uint32_t row, col, D, zero;  // (the fp64 route: D, zero = the distance's low and high words)
 };
 const size_t REC = SED_JOIN_MAXLEN, SPARE = 16;  // a sequence record, and the spare bytes that end a record buffer
+
+const size_t F64_TAB = SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK;  // the fp64 table's doubles
 
 uint32_t code_bit(uint8_t c) { return 1u << (c < 31 ? c : 31); }
 }  // namespace
@@ -44,6 +46,8 @@ struct sed_join_index {
     DevBuf d_rows, d_row_len, d_cols, d_col_len, d_col_orig, d_query;
     DevBuf d_tab, d_hits, d_count;
     uint32_t h_tab[16] = {};       // the cost rows of the call under way (the upload's source)
+    DevBuf d_f64;                  // the fp64 route's table and keep words, and their upload's source
+    uint64_t h_f64[F64_TAB + SED_JOIN_MAXLEN + 1] = {};
     std::vector<uint8_t> h_query;
     std::vector<JoinRec> h_hits;
     PinBuf pin;                    // the two counters' download
@@ -52,45 +56,72 @@ struct sed_join_index {
     ~sed_join_index() {
         pin.release();
         d_rows.release(); d_row_len.release(); d_cols.release(); d_col_len.release(); d_col_orig.release();
-        d_query.release(); d_tab.release(); d_hits.release(); d_count.release();
+        d_query.release(); d_tab.release(); d_f64.release(); d_hits.release(); d_count.release();
     }
 };
 
-// What both joins share once their rows are on the device: the plan's launches, the counters, the hit list.
-// a holds the rows and columns; nrows rows from a.row0 on.
-static int join_run(sed_join_index *ix, const sed_join_plan_t &plan, sed_join_args a, int32_t nrows, sed_join_hit *out,
-                    int64_t cap, int64_t *found) {
+// What a call runs: the integer plan or the fp64 plan (exactly one is set)
+struct JoinCall {
+    const sed_join_plan_t *pi = nullptr;
+    const sed_join_f64_plan_t *pf = nullptr;
+    int64_t launch_rows() const { return pi ? pi->launch_rows : pf->launch_rows; }
+};
+
+// What all joins share once their rows are on the device: the plan's launches, the counters, the hit list.
+// a holds the rows (rows, row_len, row0, self); nrows rows from a.row0 on.
+static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_args a, int32_t nrows, sed_join_hit *out, int64_t cap,
+                    int64_t *found) {
     sed_ctx *c = ix->ctx;
-    if ((uint64_t)cap > SIZE_MAX / sizeof(JoinRec) || !ix->d_count.reserve(16) || !ix->d_tab.reserve(sizeof ix->h_tab) ||
+    if ((uint64_t)cap > SIZE_MAX / sizeof(JoinRec) || !ix->d_count.reserve(16) ||
+        !(k.pi ? ix->d_tab.reserve(sizeof ix->h_tab) : ix->d_f64.reserve(sizeof ix->h_f64)) ||
         !ix->d_hits.reserve(std::max<size_t>((size_t)cap * sizeof(JoinRec), sizeof(JoinRec))) || !ix->pin.reserve(16, 64))
         return c->fail(SED_E_OOM, "device allocation failed (join, room for %lld hits)", (long long)cap);
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
-    memcpy(ix->h_tab, plan.sp.row, sizeof ix->h_tab);
-    if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(ix->d_tab.p, ix->h_tab, sizeof ix->h_tab, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-        return c->hipfail(e, "upload (join)");
+    if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess) return c->hipfail(e, "upload (join)");
     a.cols = ix->d_cols.p;
     a.col_len = (const int32_t *)ix->d_col_len.p;
     a.col_orig = (const int32_t *)ix->d_col_orig.p;
     a.ncols = ix->nseqs;
-    a.tab = (const uint2 *)ix->d_tab.p;
-    a.ins = plan.sp.ins;
-    a.del = plan.sp.del;
-    a.umap = plan.sp.umap;
-    a.shift = plan.scale_log2;
-    a.cut = plan.cut;
     a.hits = (uint4 *)ix->d_hits.p;
     a.count = (unsigned long long *)ix->d_count.p;
     a.cap = (unsigned long long)cap;
+    sed_join_f64_args f{};
+    if (k.pi) {
+        const sed_join_plan_t &plan = *k.pi;
+        memcpy(ix->h_tab, plan.sp.row, sizeof ix->h_tab);
+        e = hipMemcpyAsync(ix->d_tab.p, ix->h_tab, sizeof ix->h_tab, hipMemcpyHostToDevice, c->stream);
+        a.tab = (const uint2 *)ix->d_tab.p;
+        a.ins = plan.sp.ins;
+        a.del = plan.sp.del;
+        a.umap = plan.sp.umap;
+        a.shift = plan.scale_log2;
+        a.cut = plan.cut;
+    } else {  // one block: [the table | the keep words]
+        const sed_join_f64_plan_t &plan = *k.pf;
+        static_assert(sizeof ix->h_f64 == sizeof plan.sub + sizeof plan.keep, "the upload's layout");
+        memcpy(ix->h_f64, plan.sub, sizeof plan.sub);
+        memcpy(ix->h_f64 + F64_TAB, plan.keep, sizeof plan.keep);
+        e = hipMemcpyAsync(ix->d_f64.p, ix->h_f64, sizeof ix->h_f64, hipMemcpyHostToDevice, c->stream);
+        f.rows = a.rows; f.row_len = a.row_len; f.self = a.self;
+        f.cols = a.cols; f.col_len = a.col_len; f.col_orig = a.col_orig; f.ncols = a.ncols;
+        f.sub = (const double *)ix->d_f64.p;
+        f.keep = (const unsigned long long *)ix->d_f64.p + F64_TAB;
+        f.ins = plan.ins;
+        f.del = plan.del;
+        f.max_dist = plan.max_dist;
+        f.hits = a.hits; f.count = a.count; f.cap = a.cap;
+    }
+    if (e != hipSuccess) return c->hipfail(e, "upload (join)");
     const int32_t first = a.row0;
-    for (int64_t r = 0; r < nrows; r += plan.launch_rows) {  // the events bracket the launches
-        a.row0 = first + (int32_t)r;
-        a.nrows = (int32_t)std::min<int64_t>(plan.launch_rows, nrows - r);
-        if ((e = sed_launch_join(c->stream, r == 0 ? ix->timer.ev[0] : nullptr,
-                                 r + plan.launch_rows >= nrows ? ix->timer.ev[1] : nullptr, a,
-                                 plan.kernel == SED_JOIN_KERNEL_BITPAR)) != hipSuccess)
-            return c->hipfail(e, "join kernel launch");
+    const int64_t step = k.launch_rows();
+    for (int64_t r = 0; r < nrows; r += step) {  // the events bracket the launches
+        a.row0 = f.row0 = first + (int32_t)r;
+        a.nrows = f.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
+        hipEvent_t e0 = r == 0 ? ix->timer.ev[0] : nullptr, e1 = r + step >= nrows ? ix->timer.ev[1] : nullptr;
+        e = k.pi ? sed_launch_join(c->stream, e0, e1, a, k.pi->kernel == SED_JOIN_KERNEL_BITPAR)
+                 : sed_launch_join_f64(c->stream, e0, e1, f);
+        if (e != hipSuccess) return c->hipfail(e, "join kernel launch");
     }
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (join)");
@@ -110,13 +141,23 @@ static int join_run(sed_join_index *ix, const sed_join_plan_t &plan, sed_join_ar
         return c->hipfail(e, "download (join hits)");
     std::sort(ix->h_hits.begin(), ix->h_hits.end(),
               [](const JoinRec &x, const JoinRec &y) { return x.row != y.row ? x.row < y.row : x.col < y.col; });
-    const double inv = std::ldexp(1.0, -plan.scale_log2);
+    const double inv = k.pi ? std::ldexp(1.0, -k.pi->scale_log2) : 0.0;
     for (size_t i = 0; i < (size_t)n; ++i) {
         const JoinRec &r = ix->h_hits[i];
-        if (r.row < (uint32_t)first || r.row >= (uint32_t)first + (uint32_t)nrows || r.col >= (uint32_t)ix->nseqs ||
-            r.D > (uint32_t)plan.cut || (i > 0 && ix->h_hits[i - 1].row == r.row && ix->h_hits[i - 1].col == r.col))
+        double dist;
+        bool within;
+        if (k.pi) {
+            within = r.D <= (uint32_t)k.pi->cut;
+            dist = (double)r.D * inv;
+        } else {  // (D, zero) = the double's low and high words, copied, not scaled; NaN fails the compare
+            const uint64_t bits = (uint64_t)r.D | ((uint64_t)r.zero << 32);
+            memcpy(&dist, &bits, sizeof dist);
+            within = dist <= k.pf->max_dist;
+        }
+        if (r.row < (uint32_t)first || r.row >= (uint32_t)first + (uint32_t)nrows || r.col >= (uint32_t)ix->nseqs || !within ||
+            (i > 0 && ix->h_hits[i - 1].row == r.row && ix->h_hits[i - 1].col == r.col))
             return c->fail(SED_E_DEVICE, "join: record %zu from the device is no hit (row %u, column %u)", i, r.row, r.col);
-        out[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, (double)r.D * inv};
+        out[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, dist};
     }
     return SED_OK;
 }
@@ -192,16 +233,32 @@ void sed_join_index_destroy(sed_join_index *ix) {
 
 int32_t sed_join_index_seqs(const sed_join_index *ix) { return ix ? ix->nseqs : SED_E_ARG; }
 
-int sed_join_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
-                  int64_t *found) {
+}  // extern "C"
+
+// The plan of a call under either route (f64: the fp64 planner), the refusal's text in the context
+static int join_plan_call(sed_ctx *c, bool f64, const int32_t *len_rows, int32_t nrows, const sed_join_index *ix, bool self,
+                          uint32_t row_codes, double max_dist, sed_join_plan_t *pi, sed_join_f64_plan_t *pf, JoinCall *k) {
+    if (f64) {
+        k->pf = pf;
+        return sed_join_f64_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes,
+                                    max_dist, pf, &c->err);
+    }
+    k->pi = pi;
+    return sed_join_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes, max_dist,
+                            pi, &c->err);
+}
+
+static int join_self(sed_join_index *ix, bool f64, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
+                     int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
     int rc = join_enter(c, 0 <= row_lo && row_lo <= row_hi && row_hi <= ix->nseqs && cap >= 0 && (cap == 0 || out) && found);
     if (rc != SED_OK) return rc;
-    sed_join_plan_t plan;
+    sed_join_plan_t pi;
+    sed_join_f64_plan_t pf;
+    JoinCall k;
     const int32_t nrows = row_hi - row_lo;
-    rc = sed_join_plan_of(c->costs, c->opt, ix->len.data() + row_lo, nrows, ix->len.data(), ix->nseqs, true, ix->codes,
-                          ix->codes, max_dist, &plan, &c->err);
+    rc = join_plan_call(c, f64, ix->len.data() + row_lo, nrows, ix, true, ix->codes, max_dist, &pi, &pf, &k);
     if (rc != SED_OK) return rc;
     *found = 0;
     ix->pairs_run = 0;
@@ -211,11 +268,11 @@ int sed_join_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max
     a.row_len = (const int32_t *)ix->d_row_len.p;
     a.row0 = row_lo;
     a.self = 1;
-    return join_run(ix, plan, a, nrows, out, cap, found);
+    return join_run(ix, k, a, nrows, out, cap, found);
 }
 
-int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
-                    int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+static int join_search(sed_join_index *ix, bool f64, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                       int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
     int rc = join_enter(c, (nqueries == 0 || (nqueries > 0 && codes_q && off_q && len_q)) && cap >= 0 && (cap == 0 || out) &&
@@ -232,9 +289,10 @@ int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *o
         for (int j = 0; j < len_q[q]; ++j) qcodes |= code_bit(ix->h_query[REC * (size_t)q + j] = codes_q[off_q[q] + j]);
     }
     if (nqueries) memcpy(&ix->h_query[o_len], len_q, sizeof(int32_t) * (size_t)nqueries);
-    sed_join_plan_t plan;
-    rc = sed_join_plan_of(c->costs, c->opt, len_q, nqueries, ix->len.data(), ix->nseqs, false, qcodes, ix->codes, max_dist,
-                          &plan, &c->err);
+    sed_join_plan_t pi;
+    sed_join_f64_plan_t pf;
+    JoinCall k;
+    rc = join_plan_call(c, f64, len_q, nqueries, ix, false, qcodes, max_dist, &pi, &pf, &k);
     if (rc != SED_OK) return rc;
     *found = 0;
     ix->pairs_run = 0;
@@ -247,7 +305,29 @@ int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *o
     a.row_len = (const int32_t *)((const uint8_t *)ix->d_query.p + o_len);
     a.row0 = 0;
     a.self = 0;
-    return join_run(ix, plan, a, nqueries, out, cap, found);
+    return join_run(ix, k, a, nqueries, out, cap, found);
+}
+
+extern "C" {
+
+int sed_join_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
+                  int64_t *found) {
+    return join_self(ix, false, row_lo, row_hi, max_dist, out, cap, found);
+}
+
+int sed_join_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
+                      int64_t *found) {
+    return join_self(ix, true, row_lo, row_hi, max_dist, out, cap, found);
+}
+
+int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                    int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_search(ix, false, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+}
+
+int sed_join_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                        int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_search(ix, true, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_last_time(const sed_join_index *ix, float *kernel_ms) {

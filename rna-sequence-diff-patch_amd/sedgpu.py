@@ -196,6 +196,17 @@ SIGNATURES = [
     ("sed_join_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                 _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
                                 _f64p, C.c_int]),
+    ("sed_join_self_f64", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                    C.POINTER(C.c_int64)]),
+    ("sed_join_search_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                      C.POINTER(C.c_int64)]),
+    ("sed_join_f64_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                    _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
+                                    _f64p, C.c_int]),
+    ("sed_join_f64_keep", C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
+    ("sed_join_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                 _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
+                                 C.c_char_p, C.c_int]),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -696,19 +707,30 @@ class JoinIndex:
                 self._hit_room = max(self._hit_room, room)
             return out[:self.found]
 
-    def self_join(self, max_dist, rows=None, cap=None):
+    def self_join(self, max_dist, rows=None, cap=None, _call="sed_join_self"):
         """Every (i, j), i != j, i in rows = (lo, hi) (default: every sequence), with distance(seq i -> seq j) <=
         max_dist (sed_join_self).  cap = the records to make room for: more hits raise SedError (the index stays
         usable; found has the count; cap=0 is a count query).  cap=None retries once with room, so it returns every hit."""
         lo, hi = (0, self.nseqs) if rows is None else rows
-        return self._hits("sed_join_self", lambda out, room, found: self._lib.sed_join_self(
+        fn = getattr(self._lib, _call)
+        return self._hits(_call, lambda out, room, found: fn(
             self.ptr, int(lo), int(hi), float(max_dist), out, room, found), cap)
 
-    def search(self, packed, max_dist, cap=None):
+    def search(self, packed, max_dist, cap=None, _call="sed_join_search"):
         """Every (q, j) with distance(query q -> seq j) <= max_dist (sed_join_search); packed: the queries as side a of
         a PackedPairs, 0..32 symbols each.  cap as for self_join."""
-        return self._hits("sed_join_search", lambda out, room, found: self._lib.sed_join_search(
+        fn = getattr(self._lib, _call)
+        return self._hits(_call, lambda out, room, found: fn(
             self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.npairs, float(max_dist), out, room, found), cap)
+
+    def self_join_f64(self, max_dist, rows=None, cap=None):
+        """self_join() through the fp64 kernel (sed_join_self_f64): the tables and alphabets (up to 16 symbols)
+        self_join() refuses, on the same resident sequences; dist is the oracle's double, bit for bit."""
+        return self.self_join(max_dist, rows, cap, "sed_join_self_f64")
+
+    def search_f64(self, packed, max_dist, cap=None):
+        """search() through the fp64 kernel (sed_join_search_f64)."""
+        return self.search(packed, max_dist, cap, "sed_join_search_f64")
 
     def last_ms(self):
         """Device time of the last join's kernel(s) (ms, HIP events)."""
@@ -724,7 +746,8 @@ class JoinIndex:
 
 
 JOIN_PLAN_FIELDS = ("scale", "kernel", "waves", "scope", "run", "cells")
-JOIN_KERNELS = {1: "dp", 2: "bitpar"}
+JOIN_KERNELS = {1: "dp", 2: "bitpar", 3: "f64"}
+JOIN_ROUTES = {0: "int", 1: "f64"}  # SED_JOIN_ROUTE_*
 
 
 def codes_seen(codes):
@@ -735,24 +758,63 @@ def codes_seen(codes):
     return mask
 
 
-def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
-    """What JoinIndex.self_join / search would decide, without a device (sed_join_plan): {field: number} over
-    JOIN_PLAN_FIELDS.  costs and options as plan_routes takes them; row_codes / col_codes from codes_seen.  Raises
-    SedError carrying the SED_E_* code (.code) the join would fail with."""
+def _join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
     K, sub, sub_int, ins, ins_int, dele, del_int = costs
     opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
     lr = np.ascontiguousarray(len_rows if len(len_rows) else [0], np.int32)
     lc = np.ascontiguousarray(len_cols if len(len_cols) else [0], np.int32)
+    return (int(K), np.ascontiguousarray(sub, np.float64).ravel(), np.ascontiguousarray(sub_int, np.uint8).ravel(),
+            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options), lr, len(len_rows), lc, len(len_cols),
+            int(bool(self_join)), int(row_codes), int(col_codes), float(max_dist))
+
+
+def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist, _call="sed_join_plan"):
+    """What JoinIndex.self_join / search would decide, without a device (sed_join_plan): {field: number} over
+    JOIN_PLAN_FIELDS.  costs and options as plan_routes takes them; row_codes / col_codes from codes_seen.  Raises
+    SedError carrying the SED_E_* code (.code) the join would fail with."""
     out = np.zeros(len(JOIN_PLAN_FIELDS), np.float64)
-    rc = load().sed_join_plan(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
-                              np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
-                              int(del_int), opts, len(options), lr, len(len_rows), lc, len(len_cols), int(bool(self_join)),
-                              int(row_codes), int(col_codes), float(max_dist), out, len(out))
+    rc = getattr(load(), _call)(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                                out, len(out))
     if rc != 0:
-        err = SedError("sed_join_plan failed (%d)" % rc)
+        err = SedError("%s failed (%d)" % (_call, rc))
         err.code = rc
         raise err
     return {k: (float(v) if k in ("scale", "cells") else int(v)) for k, v in zip(JOIN_PLAN_FIELDS, out)}
+
+
+def join_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
+    """What JoinIndex.self_join_f64 / search_f64 would decide, without a device (sed_join_f64_plan): join_plan's fields
+    with scale = 0 (fp64 has none) and kernel = 3.  Arguments and errors as join_plan."""
+    return join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist, "sed_join_f64_plan")
+
+
+def join_f64_keep(ins, dele, max_dist):
+    """The fp64 route's length skip (sed_join_f64_keep): a 33 x 33 bool array, [n, m] true when a row of n and a column
+    of m symbols are computed under these costs and cutoff."""
+    keep = (C.c_uint64 * 33)()
+    rc = load().sed_join_f64_keep(float(ins), float(dele), float(max_dist), keep)
+    if rc != 0:
+        err = SedError("sed_join_f64_keep failed (%d)" % rc)
+        err.code = rc
+        raise err
+    return np.array([[(int(keep[n]) >> m) & 1 for m in range(33)] for n in range(33)], bool)
+
+
+def join_route(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
+    """Which route serves the join join_plan's arguments describe, without a device (sed_join_route): (route, why).
+    route = "int" (self_join / search serve it), "f64" (only self_join_f64 / search_f64 do; why = the integer route's
+    refusal) or None (neither; why = both refusals).  Bad arguments raise SedError as join_plan does."""
+    why = C.create_string_buffer(1024)
+    rc = load().sed_join_route(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                               why, len(why))
+    text = why.value.decode()
+    if rc in JOIN_ROUTES:
+        return JOIN_ROUTES[rc], text
+    if rc == SED_E_RANGE:
+        return None, text
+    err = SedError("sed_join_route failed (%d)" % rc)
+    err.code = rc
+    raise err
 
 
 def unpack_ops(ops_words, ops_off, p, length):

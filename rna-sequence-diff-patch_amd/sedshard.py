@@ -62,26 +62,36 @@ def all_vs_all(seqs, userCosts=False, world=1, rank=0, device=None, distance_fn=
     return got[0].cpu().numpy().reshape(len(seqs), len(seqs))
 
 
-def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, join_fn=None):
+def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, join_fn=None, route="int"):
     """Every ordered pair (i, j), i != j, of the short sequences seqs (0..32 symbols) whose distance from seqs[i] to
     seqs[j] is <= max_dist, as a numpy record array (row, col, dist) sorted by (row, col), on rank 0 (None on other
     ranks).  Rank r joins its block of rows, shard_range(len(seqs), world, r), against every sequence on its own GPU
     (StringEditDistance.join_index; every rank holds the whole collection, which is small: 32 bytes a sequence), and
     only its hits travel, once, to rank 0; the blocks are contiguous, so their concatenation is sorted.
+    route: "int" (the default) runs the integer kernels, "f64" the fp64 kernel (any table of costs >= 0 over at most 16
+    symbols: IUPAC collections under costs.json), "auto" the integer call whenever it serves this rank's rows
+    (StringEditDistance.join_route), as wfsearch.JoinIndex takes it.
     join_fn(seqs, lo, hi, max_dist, userCosts) -> [(i, j, dist)] sorted replaces the engine (the CPU tests inject the
-    oracle to check the sharding and reassembly)."""
+    oracle to check the sharding and reassembly); the fp64 route calls it with f64=True as a further, keyword argument."""
     import torch
-    if join_fn is None:
+    if route not in ("int", "f64", "auto"):
+        raise ValueError("route must be one of int, f64, auto, not %r" % (route,))
+    if join_fn is None or route == "auto":
         import StringEditDistance as SED
-
-        def join_fn(seqs, lo, hi, max_dist, userCosts):
-            ix = SED.join_index(seqs, userCosts)
+    if join_fn is None:
+        def join_fn(seqs, lo, hi, max_dist, userCosts, f64=False):
+            ix = SED.join_index(seqs, userCosts, f64=route != "int")
             try:
-                return ix.self_join(max_dist, (lo, hi))
+                return (ix.self_join_f64 if f64 else ix.self_join)(max_dist, (lo, hi))
             finally:
                 ix.close()
     lo, hi = shard_range(len(seqs), world, rank)
-    hits = list(join_fn(seqs, lo, hi, max_dist, userCosts)) if hi > lo else []
+    if hi <= lo:
+        hits = []
+    elif (SED.join_route(seqs[lo:hi], seqs, max_dist, userCosts) if route == "auto" else route) == "f64":
+        hits = list(join_fn(seqs, lo, hi, max_dist, userCosts, f64=True))
+    else:
+        hits = list(join_fn(seqs, lo, hi, max_dist, userCosts))
     dtype = np.dtype([("row", np.int32), ("col", np.int32), ("dist", np.float64)])
     rows = np.array([h[0] for h in hits], np.int32)
     cols = np.array([h[1] for h in hits], np.int32)

@@ -338,33 +338,57 @@ class JoinIndex:
 
     Rows (i, the queries) are str1 and columns (j, the documents) str2, the direction of wf_score(query, doc).
     index_fn(sequences, user_cost) -> an object with self_join(max_dist, rows) -> [(i, j, d)] and
-    search(queries, max_dist) -> [(q, j, d)], both sorted, and close(), replaces the engine (CPU tests).  Not cached."""
+    search(queries, max_dist) -> [(q, j, d)], both sorted, and close(), replaces the engine (CPU tests).  Not cached.
 
-    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None):
+    route (the constructor's, and per call on neighbors, search_many, search; None = the constructor's): "int" (the
+    default) runs the integer kernels, which serve dyadic cost tables over at most 8 symbols and raise SedError
+    otherwise; "f64" runs the fp64 kernel, which serves any table of costs >= 0 over at most 16 symbols (IUPAC
+    collections under costs.json); "auto" takes the integer call whenever it serves the join
+    (StringEditDistance.join_route), so only a refusal turns into a result.  An index whose constructor route is "f64"
+    or "auto" is built with f64=True (up to 16 symbols; index_fn is called with that keyword) and serves integer calls
+    too; one built under the default keeps the 8-symbol bound, whatever route a later call names.  The fp64 route calls
+    the index's self_join_f64 / search_f64."""
+
+    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None, route="int"):
+        if route not in ROUTES:
+            raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
         self.seqs = _sequences(seqs_or_collection)
         self.user_cost = user_cost
-        self._ix = (index_fn or SED.join_index)(self.seqs, user_cost) if self.seqs else None
+        self.route = route
+        make = index_fn or SED.join_index
+        self._ix = (make(self.seqs, user_cost) if route == "int" else make(self.seqs, user_cost, f64=True)) \
+            if self.seqs else None
 
-    def neighbors(self, max_dist, rows=None):
+    def _f64(self, route, rows, max_dist):
+        """whether the fp64 calls serve these rows under route"""
+        route = self.route if route is None else route
+        if route not in ROUTES:
+            raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
+        return (SED.join_route(rows, self.seqs, max_dist, self.user_cost) if route == "auto" else route) == "f64"
+
+    def neighbors(self, max_dist, rows=None, route=None):
         """[(i, j, 1 / (1 + d))] sorted by (i, j): every ordered pair i != j, i in rows = (lo, hi) (default: all), whose
         distance d from sequence i to sequence j is <= max_dist."""
         if self._ix is None:
             return []
-        return [(i, j, 1 / (1 + d)) for i, j, d in self._ix.self_join(max_dist, rows)]
+        lo, hi = (0, len(self.seqs)) if rows is None else rows
+        call = self._ix.self_join_f64 if self._f64(route, self.seqs[lo:hi], max_dist) else self._ix.self_join
+        return [(i, j, 1 / (1 + d)) for i, j, d in call(max_dist, rows)]
 
-    def search_many(self, queries, max_dist):
+    def search_many(self, queries, max_dist, route=None):
         """Per query, [(sequence, 1 / (1 + d))] for the documents within max_dist, in collection order: what
         search_within(query, seqs, max_dist, user_cost) returns, for all the queries from one engine call."""
         queries = list(queries)
         out = [[] for _ in queries]
         if self._ix is None or not queries:
             return out
-        for q, j, d in self._ix.search(queries, max_dist):
+        call = self._ix.search_f64 if self._f64(route, queries, max_dist) else self._ix.search
+        for q, j, d in call(queries, max_dist):
             out[q].append((self.seqs[j], 1 / (1 + d)))
         return out
 
-    def search(self, query, max_dist):
-        return self.search_many([query], max_dist)[0]
+    def search(self, query, max_dist, route=None):
+        return self.search_many([query], max_dist, route)[0]
 
     def close(self):
         if self._ix is not None:
@@ -372,9 +396,9 @@ class JoinIndex:
         self._ix = None
 
 
-def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None):
+def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None, route="int"):
     """JoinIndex.neighbors in one shot: builds an index over the sequences, joins it with itself and closes it."""
-    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn)
+    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, route=route)
     try:
         return ix.neighbors(max_dist)
     finally:
