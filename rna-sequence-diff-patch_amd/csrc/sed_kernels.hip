@@ -164,7 +164,7 @@ void sed_wf_i32_kernel(const sed_pair_desc *__restrict__ pd, int npairs, const i
         if (lane == 0) {
             const uint32_t D = (n == 0) ? (uint32_t)m * prm.ins : (uint32_t)n * prm.del;
             res[pair].dist = (double)D;
-            res[pair].len = n + m;
+            res[pair].len = (LEN || CK) ? n + m : -1;  // (as i32_decode: no length without LEN or checkpoints)
             res[pair].is_int = (D == 0);
             res[pair].err = 0;
         }

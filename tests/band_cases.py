@@ -185,14 +185,17 @@ FAMILIES = {"random": random_family, "low_complexity": low_complexity, "rearrang
 FAMILY_N = {"random": 600, "low_complexity": 619, "rearranged": 700, "edges": 0, "drift": 0}
 
 
-def _seed(*parts):
+def seed(*parts):
+    """A seed of its own for every named input (shared with tests/cut_cases.py)."""
     return sum(ord(ch) * (i + 1) for i, ch in enumerate("/".join(map(str, parts))))
 
 
-def family_pairs(table, family, R, n=None):
-    """(A, B) of one family under one table's delta, from a seed of its own."""
-    n = FAMILY_N[family] if n is None else n
-    return FAMILIES[family](np.random.default_rng(_seed(table, family, R, n)), n, R, DELTA[table])
+def family_pairs(table, family, R, n=None, families=None, family_n=None, delta=None):
+    """(A, B) of one family under one table's delta, from a seed of its own.  families, family_n and delta stand in for
+    FAMILIES, FAMILY_N and DELTA (tests/cut_cases.py adds families of its own)."""
+    n = (family_n or FAMILY_N)[family] if n is None else n
+    return (families or FAMILIES)[family](np.random.default_rng(seed(table, family, R, n)), n, R,
+                                          (delta or DELTA)[table])
 
 
 # ---- the reference of the CPU model tests: forward + backward DP in numpy (integer costs: exact in float64) ----

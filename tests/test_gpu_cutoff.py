@@ -2,7 +2,8 @@
 oracle: distance D <= T gives the same value and int flag as without a cutoff, D > T gives (inf, flag 0, len -1).  The
 windowed distance-only stripe kernel (R = 4, 8, 16) is reached by batches of a few long pairs with the two-pairs-per-wave
 packing, CHAIN and SPLIT off, and under default options by a batch that leaves the two-pairs-per-wave route for it; the
-other routes (fp64, two pairs per wave, lane kernels, SPLIT) only compare."""
+other routes (fp64, two pairs per wave, lane kernels, SPLIT) only compare.  tests/test_gpu_cut_envelope.py runs the same
+contract over the tables, families and cutoffs of tests/cut_cases.py."""
 import importlib
 import math
 import os
