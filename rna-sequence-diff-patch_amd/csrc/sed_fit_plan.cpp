@@ -1,9 +1,9 @@
 // sed_fit_plan.cpp — the fit planner (sed_fit_plan.h): scale, update addends, window, chunk length, lanes and the
-// cutoff of a fit search, from the cost model, the options and the lengths.  No HIP call.  Also the device-free fit
-// entry points of include/sed.h (sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes,
+// cutoff of a fit search, from the route, the cost model, the options and the lengths.  No HIP call.  Also the
+// device-free fit entry points of include/sed.h (sed_fit_plan, sed_fit_lanes, sed_fit_index_plan, sed_fit_index_lanes,
 // sed_fit_index_long_plan, sed_fit_index_long_lanes, sed_fit_cutoff_scaled, sed_fit_f64_plan, sed_fit_f64_lanes,
 // sed_fit_index_f64_plan, sed_fit_index_f64_lanes, sed_fit_route, sed_fit_index_long_f64_plan,
-// sed_fit_index_long_f64_lanes, sed_fit_long_route).
+// sed_fit_index_long_f64_lanes, sed_fit_long_route): each is its route handed to one of a few shared bodies.
 #include "sed_fit_plan.h"
 
 #include <algorithm>
@@ -20,6 +20,14 @@
 #define SED_FIT_TARGET_WAVES 4
 #define SED_FIT_MAX_SPAN 65535  // columns of one lane, border column included: the 16-bit start field
 
+static const FitRoute FIT_ROUTES[] = {
+    {SED_LANE_MAXM, 64, 0, false},       // FIT_SHORT_KEYS
+    {SED_FIT_LONG_MAXP, 1, 128, false},  // FIT_LONG_KEYS (128 = sed_fit_dp.h: FIT_REBASE)
+    {SED_LANE_MAXM, 64, 0, true},        // FIT_F64
+    {SED_FIT_LONG_MAXP, 1, 0, true},     // FIT_LONG_F64: the waves, no key field to share
+};
+const FitRoute &sed_fit_route_of(FitKind kind) { return FIT_ROUTES[kind]; }
+
 // What the plan takes from the pairs through sums alone (a batch of listed pairs and an index search's cross product
 // fill it their own ways): the pairs, the longest pattern, sum (n + 1) and the longest text.
 struct FitSums {
@@ -29,26 +37,8 @@ struct FitSums {
     int64_t nmax = -1;
 };
 
-// How a kernel family lays a pair out, as far as the rule cares: the short kernels run one pair's chunk in a lane, 64 to
-// a wave, and their P <= 32 keeps the D field's rebase room out of the envelope; the long kernels (sed_fit_long.hip)
-// run it in a whole wave, and P delete S shares the 16-bit D field with the FIT_REBASE insert S a key carries at most
-// between rebases.
-struct FitLayout {
-    int pmax;            // patterns of 1..pmax symbols
-    int units_per_wave;  // (pair, chunk) units a wave runs
-    int rebase_cols;     // columns of insert the D-field condition adds to P delete; 0: none
-};
-static const FitLayout FIT_SHORT = {SED_LANE_MAXM, 64, 0};
-static const FitLayout FIT_LONG = {SED_FIT_LONG_MAXP, 1, 128};  // (128 = sed_fit_dp.h: FIT_REBASE)
-static const FitLayout FIT_LONG_F64 = {SED_FIT_LONG_MAXP, 1, 0};  // sed_fit_long_f64.hip: the waves, no key field to share
-
-// The one rule every caller shares: scale, update addends and W from the costs and the longest pattern, then the chunk
-// length and the span check.  *chunk_out = the chunk every text is cut by (0: one lane per text); plan->chunk = the
-// chunk the plan reports, which cuts them the same way (it is 0 only where no text has more columns than the chunk).
-// *span_fail_cols > 0 (a span refusal) = the columns n + 1 from which a text fails, for the caller to name one.
-static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &sm, const FitLayout &lay, sed_fit_plan_t *plan,
-                         std::string *err, int64_t *chunk_out, int64_t *span_fail_cols) {
-    const int pmax = sm.pmax;
+// The integer routes' cost envelope: scale, update addends and W from the costs and the longest pattern.
+static int fit_keys_envelope(const sed_costs &c, int pmax, const FitRoute &r, sed_fit_plan_t *plan, std::string *err) {
     // the smallest S = 2^k, k <= 8, that makes every cost an integer in 0..255
     int k = 0;
     for (;; ++k) {
@@ -66,9 +56,9 @@ static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &s
     const double insS = c.ins * S, delS = c.del * S;
     if ((double)pmax * delS > 65535.0)
         return sed_plan_fail(err, SED_E_RANGE, "fit search: P * delete * S = %d * %g exceeds 65535", pmax, delS);
-    if (lay.rebase_cols && (double)pmax * delS + (double)lay.rebase_cols * insS > 65535.0)
+    if (r.rebase_cols && (double)pmax * delS + (double)r.rebase_cols * insS > 65535.0)
         return sed_plan_fail(err, SED_E_RANGE, "fit search: P * delete * S + %d * insert * S = %d * %g + %d * %g exceeds 65535",
-                             lay.rebase_cols, pmax, delS, lay.rebase_cols, insS);
+                             r.rebase_cols, pmax, delS, r.rebase_cols, insS);
     if (delS > 255.0) return sed_plan_fail(err, SED_E_RANGE, "fit search: delete * S = %g exceeds 255", delS);
     if (insS + delS > 255.0)
         return sed_plan_fail(err, SED_E_RANGE, "fit search: (insert + delete) * S = %g exceeds 255 (the update addend's byte)",
@@ -84,136 +74,11 @@ static int fit_plan_rule(const sed_costs &c, const sed_opts &o, const FitSums &s
             plan->fp.row[a][b >> 2] |= (ins + del - v) << (8 * (b & 3));
         }
     plan->W = ins ? pmax + (int64_t)pmax * del / ins : -1;
-    // the chunk length
-    int64_t chunk = 0;
-    if (ins && o.fit_chunk > 0)
-        chunk = o.fit_chunk;
-    else if (ins && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * lay.units_per_wave) {
-        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * lay.units_per_wave));
-        chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
-    }
-    // texts too long for one lane's start field are always split
-    if (ins && o.fit_chunk == 0 && sm.nmax + 1 > SED_FIT_MAX_SPAN && (chunk == 0 || chunk + plan->W + 3 > SED_FIT_MAX_SPAN))
-        chunk = SED_FIT_MAX_SPAN - plan->W - 3;
-    // a text of ncol columns runs in more than one lane when ncol > chunk > 0, each spanning chunk + W + 3 at most;
-    // else in one lane of ncol
-    const bool split = chunk > 0 && sm.nmax + 1 > chunk;
-    *span_fail_cols = 0;
-    if (split && chunk + plan->W + 3 > SED_FIT_MAX_SPAN)
-        *span_fail_cols = std::min<int64_t>(chunk, SED_FIT_MAX_SPAN) + 1;
-    else if (!split && sm.nmax + 1 > SED_FIT_MAX_SPAN)
-        *span_fail_cols = SED_FIT_MAX_SPAN + 1;
-    plan->chunk = split || o.fit_chunk > 0 ? (int32_t)std::min<int64_t>(chunk, INT_MAX) : 0;
-    *chunk_out = chunk;
-    return SED_OK;
-}
-static int fit_span_fail(std::string *err, const char *what, int64_t idx, bool ins) {
-    return sed_plan_fail(err, SED_E_RANGE, "fit search: %s %lld: a lane would span more than %d text columns%s", what,
-                         (long long)idx, SED_FIT_MAX_SPAN, ins ? "" : " (insert = 0: a text runs as one chunk)");
-}
-// the lanes of one text under the rule's chunk, and the columns they compute (warm-up included)
-static inline int64_t fit_text_lanes(int64_t chunk, int64_t W, int64_t n, double *computed) {
-    const int64_t ncol = n + 1;
-    const int64_t nl = chunk > 0 ? (ncol + chunk - 1) / chunk : 1;
-    if (computed)
-        for (int64_t l = 0; l < nl; ++l) {
-            const int64_t c0 = l * chunk, c1 = nl > 1 ? std::min(ncol, c0 + chunk) : ncol;
-            *computed += (double)(c1 - 1 - (c0 - sed_fit_lead(W, c0)));
-        }
-    return nl;
-}
-
-int sed_fit_plan_batch(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
-                       sed_fit_plan_t *plan, std::string *err) {
-    if (npairs < 0 || (npairs > 0 && (!len_p || !len_t))) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
-    if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
-    FitSums sm;
-    sm.npairs = npairs;
-    for (int p = 0; p < npairs; ++p) {
-        if (len_t[p] < 0) return sed_plan_fail(err, SED_E_ARG, "pair %d: negative text length", p);
-        if (len_p[p] < 1 || len_p[p] > SED_LANE_MAXM)
-            return sed_plan_fail(err, SED_E_RANGE, "fit search: pair %d: pattern length %d outside 1..%d", p, len_p[p],
-                                 SED_LANE_MAXM);
-        sm.pmax = std::max(sm.pmax, len_p[p]);
-        sm.cols += (double)len_t[p] + 1;
-        sm.nmax = std::max<int64_t>(sm.nmax, len_t[p]);
-    }
-    int64_t chunk = 0, span_cols = 0;
-    const int rc = fit_plan_rule(c, o, sm, FIT_SHORT, plan, err, &chunk, &span_cols);
-    if (rc != SED_OK) return rc;
-    plan->first.assign((size_t)npairs + 1, 0);
-    plan->cells = plan->nominal = 0;
-    for (int p = 0; p < npairs; ++p) {
-        if (span_cols && (int64_t)len_t[p] + 1 >= span_cols) return fit_span_fail(err, "pair", p, plan->fp.ins != 0);
-        double computed = 0;
-        plan->first[p + 1] = plan->first[p] + fit_text_lanes(chunk, plan->W, len_t[p], &computed);
-        plan->cells += (double)len_p[p] * computed;
-        plan->nominal += (double)len_p[p] * (double)len_t[p];
-    }
-    plan->lanes = plan->first[npairs];
-    if (plan->lanes > INT_MAX) return sed_plan_fail(err, SED_E_RANGE, "fit search: %lld lanes", (long long)plan->lanes);
     return SED_OK;
 }
 
-// The plan of an index search under either layout; rows (the long layout's, may be null) = each query's R.
-static int fit_plan_index_of(const sed_costs &c, const sed_opts &o, const FitLayout &lay, const int32_t *len_p, int32_t nqueries,
-                             const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err) {
-    if (nqueries < 0 || (nqueries > 0 && !len_p) || tx.ntexts < 0) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
-    if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
-    FitSums sm;
-    double psum = 0;
-    // the refusals of the cross product's pairs, query-major: pair (0, 0)'s text, then its pattern, then the other
-    // texts (pairs (0, d)), then the other patterns; an empty cross product has no pair to refuse
-    for (int q = 0; q < nqueries && tx.ntexts > 0; ++q) {
-        if (tx.first_negative >= 0 && (q == 0 ? tx.first_negative == 0 : q == 1))
-            return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
-        if (len_p[q] < 1 || len_p[q] > lay.pmax)
-            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q],
-                                 lay.pmax);
-        if (lay.units_per_wave == 1 && o.fit_rows && len_p[q] > 64 * o.fit_rows)  // (the wave layout reads the option)
-            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d exceeds the 64 * %d rows of SED_OPT_FIT_ROWS",
-                                 q, len_p[q], o.fit_rows);
-        sm.pmax = std::max(sm.pmax, len_p[q]);
-        psum += (double)len_p[q];
-    }
-    if (nqueries == 1 && tx.ntexts > 0 && tx.first_negative >= 0)
-        return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
-    if (nqueries > 0 && tx.ntexts > 0) {
-        sm.npairs = (int64_t)nqueries * tx.ntexts;
-        sm.cols = (double)nqueries * tx.cols;
-        sm.nmax = tx.nmax;
-    }
-    int64_t chunk = 0, span_cols = 0;
-    const int rc = fit_plan_rule(c, o, sm, lay, plan, err, &chunk, &span_cols);
-    if (rc != SED_OK) return rc;
-    if (span_cols) return fit_span_fail(err, "a text of length", tx.nmax, plan->fp.ins != 0);
-    plan->first.clear();
-    plan->lanes = 0;
-    plan->cells = 0;
-    plan->nominal = psum * (tx.cols - (double)tx.ntexts);
-    if (rows) {
-        rows->resize((size_t)nqueries);
-        for (int q = 0; q < nqueries; ++q) (*rows)[q] = o.fit_rows ? o.fit_rows : sed_fit_long_rows(len_p[q]);
-    }
-    return SED_OK;
-}
-
-int sed_fit_plan_index(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
-                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
-    return fit_plan_index_of(c, o, FIT_SHORT, len_p, nqueries, tx, plan, nullptr, err);
-}
-
-int sed_fit_plan_index_long(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
-                            const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err) {
-    return fit_plan_index_of(c, o, FIT_LONG, len_p, nqueries, tx, plan, rows, err);
-}
-
-// ---- the fp64 route ----
-// The rule of the fp64 plans: the envelope, the table the kernels read, W and the chunk.  The chunk rule is
-// fit_plan_rule's under the layout (FIT_SHORT: 64 lanes a wave; FIT_LONG_F64: one unit a wave; its two wave constants
-// carried over, measured for neither fp64 kernel), without the span limit.
-static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSums &sm, const FitLayout &lay, sed_fit_plan_t *plan,
-                             std::string *err, int64_t *chunk_out) {
+// The fp64 routes' cost envelope: the symbols, the table the kernels read, W and why there is none.
+static int fit_f64_envelope(const sed_costs &c, int pmax, sed_fit_plan_t *plan, std::string *err) {
     if (c.K > SED_FIT_F64_MAXK)
         return sed_plan_fail(err, SED_E_RANGE, "fit search (fp64): the batch has %d symbols (at most %d)", c.K, SED_FIT_F64_MAXK);
     auto cost_ok = [](double v) { return std::isfinite(v) && v >= 0; };  // (-0.0 >= 0)
@@ -233,8 +98,7 @@ static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSum
     // W = P + Y, Y = floor(P delete / insert) + 2, under the hypotheses of DESIGN.md 3.6i: insert, and delete unless 0,
     // within 2^-900 .. 2^900 (no product here under- or overflows), P delete / insert <= 2^20, and, checked as
     // computed, (Y - 1) insert >= P delete (1 + 2^-30).  Anything else: one lane per text.  The argument holds for the
-    // long layout's P <= 2048 as it stands (the straight-down path's (1 + u)^2047 is below 1 + 2^-42).
-    const int pmax = sm.pmax;
+    // wave layout's P <= 2048 as it stands (the straight-down path's (1 + u)^2047 is below 1 + 2^-42).
     const double ins = plan->f64_ins, del = plan->f64_del, lo = std::ldexp(1.0, -900), hi = std::ldexp(1.0, 900);
     plan->W = -1;
     plan->one_lane = ins == 0 ? SED_FIT_F64_INSERT_ZERO : SED_FIT_F64_NO_WINDOW;
@@ -248,39 +112,86 @@ static int fit_plan_rule_f64(const sed_costs &c, const sed_opts &o, const FitSum
             }
         }
     }
-    int64_t chunk = 0;
-    if (plan->W >= 0 && o.fit_chunk > 0)
-        chunk = o.fit_chunk;
-    else if (plan->W >= 0 && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * lay.units_per_wave) {
-        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * lay.units_per_wave));
-        chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
-    }
-    const bool split = chunk > 0 && sm.nmax + 1 > chunk;
-    plan->chunk = split || (plan->W >= 0 && o.fit_chunk > 0) ? (int32_t)std::min<int64_t>(chunk, INT_MAX) : 0;
-    *chunk_out = chunk;
     return SED_OK;
 }
 
-int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
-                           sed_fit_plan_t *plan, std::string *err) {
+// The one rule every caller shares: the route's envelope (scale or table, and W: a finite window exists when W >= 0),
+// then the chunk length under the route's layout (its two wave constants were measured for the integer lane layout and
+// are carried over to the others) and, on the integer routes, the span check.  *chunk_out = the chunk every text is
+// cut by (0: one lane per text); plan->chunk = the chunk the plan reports, which cuts them the same way (it is 0 only
+// where no text has more columns than the chunk, or no window exists).  *span_fail_cols > 0 (a span refusal) = the
+// columns n + 1 from which a text fails, for the caller to name one.
+static int fit_plan_rule(const FitRoute &r, const sed_costs &c, const sed_opts &o, const FitSums &sm, sed_fit_plan_t *plan,
+                         std::string *err, int64_t *chunk_out, int64_t *span_fail_cols) {
+    const int rc = r.f64 ? fit_f64_envelope(c, sm.pmax, plan, err) : fit_keys_envelope(c, sm.pmax, r, plan, err);
+    if (rc != SED_OK) return rc;
+    const bool window = plan->W >= 0, span_limit = !r.f64;
+    int64_t chunk = 0;
+    if (window && o.fit_chunk > 0)
+        chunk = o.fit_chunk;
+    else if (window && sm.npairs > 0 && sm.npairs < SED_FIT_ENOUGH_WAVES * SED_FIT_SIMDS * r.units_per_wave) {
+        chunk = (int64_t)std::ceil(sm.cols / (double)(SED_FIT_TARGET_WAVES * SED_FIT_SIMDS * r.units_per_wave));
+        chunk = std::max<int64_t>((chunk + 3) & ~(int64_t)3, plan->W);
+    }
+    // texts too long for one lane's start field are always split
+    if (span_limit && window && o.fit_chunk == 0 && sm.nmax + 1 > SED_FIT_MAX_SPAN &&
+        (chunk == 0 || chunk + plan->W + 3 > SED_FIT_MAX_SPAN))
+        chunk = SED_FIT_MAX_SPAN - plan->W - 3;
+    // a text of ncol columns runs in more than one lane when ncol > chunk > 0, each spanning chunk + W + 3 at most;
+    // else in one lane of ncol
+    const bool split = chunk > 0 && sm.nmax + 1 > chunk;
+    *span_fail_cols = 0;
+    if (span_limit && split && chunk + plan->W + 3 > SED_FIT_MAX_SPAN)
+        *span_fail_cols = std::min<int64_t>(chunk, SED_FIT_MAX_SPAN) + 1;
+    else if (span_limit && !split && sm.nmax + 1 > SED_FIT_MAX_SPAN)
+        *span_fail_cols = SED_FIT_MAX_SPAN + 1;
+    plan->chunk = split || (window && o.fit_chunk > 0) ? (int32_t)std::min<int64_t>(chunk, INT_MAX) : 0;
+    *chunk_out = chunk;
+    return SED_OK;
+}
+static int fit_span_fail(std::string *err, const char *what, int64_t idx, bool ins) {
+    return sed_plan_fail(err, SED_E_RANGE, "fit search: %s %lld: a lane would span more than %d text columns%s", what,
+                         (long long)idx, SED_FIT_MAX_SPAN, ins ? "" : " (insert = 0: a text runs as one chunk)");
+}
+// the integer routes' refusal of a table over more than 8 symbols, which comes before any look at the lengths (the fp64
+// routes' own, fit_f64_envelope's, comes after them)
+static int fit_keys_symbols_fail(const sed_costs &c, std::string *err) {
+    return sed_plan_fail(err, SED_E_RANGE, "fit search: the batch has %d symbols (at most 8)", c.K);
+}
+// the lanes of one text under the rule's chunk, and the columns they compute (warm-up included)
+static inline int64_t fit_text_lanes(int64_t chunk, int64_t W, int64_t n, double *computed) {
+    const int64_t ncol = n + 1;
+    const int64_t nl = chunk > 0 ? (ncol + chunk - 1) / chunk : 1;
+    if (computed)
+        for (int64_t l = 0; l < nl; ++l) {
+            const int64_t c0 = l * chunk, c1 = nl > 1 ? std::min(ncol, c0 + chunk) : ncol;
+            *computed += (double)(c1 - 1 - (c0 - sed_fit_lead(W, c0)));
+        }
+    return nl;
+}
+
+int sed_fit_plan_batch(FitKind kind, const sed_costs &c, const sed_opts &o, const int32_t *len_p, const int32_t *len_t,
+                       int32_t npairs, sed_fit_plan_t *plan, std::string *err) {
+    const FitRoute &r = sed_fit_route_of(kind);
     if (npairs < 0 || (npairs > 0 && (!len_p || !len_t))) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
+    if (!r.f64 && c.K > 8) return fit_keys_symbols_fail(c, err);
     FitSums sm;
     sm.npairs = npairs;
     for (int p = 0; p < npairs; ++p) {
         if (len_t[p] < 0) return sed_plan_fail(err, SED_E_ARG, "pair %d: negative text length", p);
-        if (len_p[p] < 1 || len_p[p] > SED_LANE_MAXM)
-            return sed_plan_fail(err, SED_E_RANGE, "fit search: pair %d: pattern length %d outside 1..%d", p, len_p[p],
-                                 SED_LANE_MAXM);
+        if (len_p[p] < 1 || len_p[p] > r.pmax)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: pair %d: pattern length %d outside 1..%d", p, len_p[p], r.pmax);
         sm.pmax = std::max(sm.pmax, len_p[p]);
         sm.cols += (double)len_t[p] + 1;
         sm.nmax = std::max<int64_t>(sm.nmax, len_t[p]);
     }
-    int64_t chunk = 0;
-    const int rc = fit_plan_rule_f64(c, o, sm, FIT_SHORT, plan, err, &chunk);
+    int64_t chunk = 0, span_cols = 0;
+    const int rc = fit_plan_rule(r, c, o, sm, plan, err, &chunk, &span_cols);
     if (rc != SED_OK) return rc;
     plan->first.assign((size_t)npairs + 1, 0);
     plan->cells = plan->nominal = 0;
     for (int p = 0; p < npairs; ++p) {
+        if (span_cols && (int64_t)len_t[p] + 1 >= span_cols) return fit_span_fail(err, "pair", p, plan->fp.ins != 0);
         double computed = 0;
         plan->first[p + 1] = plan->first[p] + fit_text_lanes(chunk, plan->W, len_t[p], &computed);
         plan->cells += (double)len_p[p] * computed;
@@ -291,21 +202,21 @@ int sed_fit_plan_batch_f64(const sed_costs &c, const sed_opts &o, const int32_t 
     return SED_OK;
 }
 
-// The fp64 plan of an index search under either layout; rows (the wave layout's, may be null) = each query's R.
-static int fit_plan_index_f64_of(const sed_costs &c, const sed_opts &o, const FitLayout &lay, const int32_t *len_p,
-                                 int32_t nqueries, const sed_fit_index_sums &tx, sed_fit_plan_t *plan,
-                                 std::vector<int32_t> *rows, std::string *err) {
+int sed_fit_plan_index(FitKind kind, const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
+                       const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows, std::string *err) {
+    const FitRoute &r = sed_fit_route_of(kind);
     if (nqueries < 0 || (nqueries > 0 && !len_p) || tx.ntexts < 0) return sed_plan_fail(err, SED_E_ARG, "bad fit arguments");
+    if (!r.f64 && c.K > 8) return fit_keys_symbols_fail(c, err);
     FitSums sm;
     double psum = 0;
-    // the cross product's refusals in sed_fit_plan_batch_f64's order (fit_plan_index_of)
+    // the refusals of the cross product's pairs, query-major, in sed_fit_plan_batch's order: pair (0, 0)'s text, then its
+    // pattern, then the other texts (pairs (0, d)), then the other patterns; an empty cross product has no pair to refuse
     for (int q = 0; q < nqueries && tx.ntexts > 0; ++q) {
         if (tx.first_negative >= 0 && (q == 0 ? tx.first_negative == 0 : q == 1))
             return sed_plan_fail(err, SED_E_ARG, "text %d: negative text length", tx.first_negative);
-        if (len_p[q] < 1 || len_p[q] > lay.pmax)
-            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q],
-                                 lay.pmax);
-        if (lay.units_per_wave == 1 && o.fit_rows && len_p[q] > 64 * o.fit_rows)  // (the wave layout reads the option)
+        if (len_p[q] < 1 || len_p[q] > r.pmax)
+            return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d outside 1..%d", q, len_p[q], r.pmax);
+        if (r.waves() && o.fit_rows && len_p[q] > 64 * o.fit_rows)  // (the wave layout reads the option)
             return sed_plan_fail(err, SED_E_RANGE, "fit search: query %d: pattern length %d exceeds the 64 * %d rows of SED_OPT_FIT_ROWS",
                                  q, len_p[q], o.fit_rows);
         sm.pmax = std::max(sm.pmax, len_p[q]);
@@ -318,29 +229,19 @@ static int fit_plan_index_f64_of(const sed_costs &c, const sed_opts &o, const Fi
         sm.cols = (double)nqueries * tx.cols;
         sm.nmax = tx.nmax;
     }
-    int64_t chunk = 0;
-    const int rc = fit_plan_rule_f64(c, o, sm, lay, plan, err, &chunk);
+    int64_t chunk = 0, span_cols = 0;
+    const int rc = fit_plan_rule(r, c, o, sm, plan, err, &chunk, &span_cols);
     if (rc != SED_OK) return rc;
+    if (span_cols) return fit_span_fail(err, "a text of length", tx.nmax, plan->fp.ins != 0);
     plan->first.clear();
     plan->lanes = 0;
     plan->cells = 0;
     plan->nominal = psum * (tx.cols - (double)tx.ntexts);
     if (rows) {
-        rows->resize((size_t)nqueries);
-        for (int q = 0; q < nqueries; ++q) (*rows)[q] = o.fit_rows ? o.fit_rows : sed_fit_long_rows(len_p[q]);
+        rows->resize(r.waves() ? (size_t)nqueries : 0);
+        for (size_t q = 0; q < rows->size(); ++q) (*rows)[q] = o.fit_rows ? o.fit_rows : sed_fit_long_rows(len_p[q]);
     }
     return SED_OK;
-}
-
-int sed_fit_plan_index_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
-                           const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::string *err) {
-    return fit_plan_index_f64_of(c, o, FIT_SHORT, len_p, nqueries, tx, plan, nullptr, err);
-}
-
-int sed_fit_plan_index_long_f64(const sed_costs &c, const sed_opts &o, const int32_t *len_p, int32_t nqueries,
-                                const sed_fit_index_sums &tx, sed_fit_plan_t *plan, std::vector<int32_t> *rows,
-                                std::string *err) {
-    return fit_plan_index_f64_of(c, o, FIT_LONG_F64, len_p, nqueries, tx, plan, rows, err);
 }
 
 int64_t sed_fit_build_chunks(const sed_fit_plan_t &plan, const int32_t *len_t, int32_t ntexts,
@@ -385,27 +286,113 @@ void sed_fit_build_lanes(const sed_fit_plan_t &plan, const int32_t *len_p, const
     }
 }
 
-extern "C" {
+// ---- the device-free exports: a few bodies, each taking the route ----
+// The cost model and options as every export takes them, gathered where the C function is entered.
+struct FitCArgs {
+    int K;
+    const double *sub;
+    const uint8_t *sub_int;
+    double ins;
+    int ins_is_int;
+    double del;
+    int del_is_int;
+    const int32_t *options;
+    int noptions;
+};
+#define FIT_C_ARGS (FitCArgs{K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions})
 
-// the cost model and options of the device-free fit exports, from their C arguments
-static int fit_costs_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                        int del_is_int, const int32_t *options, int noptions, sed_costs *c, sed_opts *o) {
-    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options)) return SED_E_ARG;
-    if (!std::isfinite(ins) || !std::isfinite(del)) return SED_E_ARG;
+static int fit_costs_of(const FitCArgs &a, sed_costs *c, sed_opts *o) {
+    const int K = a.K;
+    if (K < 1 || K > 255 || !a.sub || a.noptions < 0 || (a.noptions && !a.options)) return SED_E_ARG;
+    if (!std::isfinite(a.ins) || !std::isfinite(a.del)) return SED_E_ARG;
     for (int e = 0; e < K * K; ++e)
-        if (!std::isfinite(sub[e])) return SED_E_ARG;
+        if (!std::isfinite(a.sub[e])) return SED_E_ARG;
     c->K = K;
-    c->sub.assign(sub, sub + K * K);
-    if (sub_int) c->sub_int.assign(sub_int, sub_int + K * K);
-    c->ins = ins;
-    c->del = del;
-    c->ins_int = ins_is_int ? 1 : 0;
-    c->del_int = del_is_int ? 1 : 0;
-    for (int i = 0; i < noptions; ++i)
-        if (!sed_opts_set(*o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
+    c->sub.assign(a.sub, a.sub + K * K);
+    if (a.sub_int) c->sub_int.assign(a.sub_int, a.sub_int + K * K);
+    c->ins = a.ins;
+    c->del = a.del;
+    c->ins_int = a.ins_is_int ? 1 : 0;
+    c->del_int = a.del_is_int ? 1 : 0;
+    for (int i = 0; i < a.noptions; ++i)
+        if (!sed_opts_set(*o, a.options[2 * i], a.options[2 * i + 1], true)) return SED_E_ARG;
     return SED_OK;
 }
+// the texts' sums as an index keeps them, from their lengths
+static sed_fit_index_sums fit_text_sums(const int32_t *len_t, int32_t ntexts) {
+    sed_fit_index_sums tx;
+    tx.ntexts = ntexts;
+    for (int d = 0; d < ntexts; ++d) {
+        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
+        tx.cols += (double)len_t[d] + 1;
+        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
+    }
+    return tx;
+}
+static bool fit_index_lengths_ok(int32_t nqueries, const int32_t *len_t, int32_t ntexts) {
+    return nqueries >= 0 && ntexts >= 0 && (ntexts == 0 || len_t);
+}
+
+// the plan of listed pairs from the C arguments
+static int fit_pairs_plan_of(FitKind kind, const FitCArgs &a, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                             sed_fit_plan_t *p) {
+    sed_costs c;
+    sed_opts o;
+    const int rc = fit_costs_of(a, &c, &o);
+    return rc != SED_OK ? rc : sed_fit_plan_batch(kind, c, o, len_p, len_t, npairs, p, nullptr);
+}
+// the plan of a cross product from the C arguments, the chunk table (may be null) and the sums the plan reports
+static int fit_index_plan_of(FitKind kind, const FitCArgs &a, const int32_t *len_p, int32_t nqueries, const int32_t *len_t,
+                             int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks, std::vector<int32_t> *rows) {
+    if (!fit_index_lengths_ok(nqueries, len_t, ntexts)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    const int rc0 = fit_costs_of(a, &c, &o);
+    if (rc0 != SED_OK) return rc0;
+    const int rc = sed_fit_plan_index(kind, c, o, len_p, nqueries, fit_text_sums(len_t, ntexts), p, rows, nullptr);
+    if (rc != SED_OK) return rc;
+    double computed = 0, psum = 0;
+    const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
+    for (int q = 0; q < nqueries && ntexts > 0; ++q) psum += (double)len_p[q];
+    p->lanes = nqueries * nchunks;
+    p->cells = psum * computed;
+    return p->lanes > INT_MAX ? SED_E_RANGE : SED_OK;
+}
+
+// What the _plan exports report of a plan that stands (rc = its planning's result, handed through): FIT_PLAN_FIELDS of
+// sedgpu.py; the fp64 routes have no scale (0.0) and add one_lane.
+static int fit_plan_out(FitKind kind, int rc, const sed_fit_plan_t &p, double *out, int nout) {
+    if (rc != SED_OK) return rc;
+    const bool f64 = sed_fit_route_of(kind).f64;
+    const double v[] = {f64 ? 0.0 : std::ldexp(1.0, p.scale_log2), (double)p.W, (double)p.chunk, (double)p.lanes, p.cells,
+                        p.nominal, (double)p.one_lane};
+    for (int i = 0; i < nout && i < (f64 ? 7 : 6); ++i) out[i] = v[i];
+    return SED_OK;
+}
+static int fit_pairs_plan_export(FitKind kind, const FitCArgs &a, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                                 double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    return fit_plan_out(kind, fit_pairs_plan_of(kind, a, len_p, len_t, npairs, &p), p, out, nout);
+}
+static int fit_index_plan_export(FitKind kind, const FitCArgs &a, const int32_t *len_p, int32_t nqueries, const int32_t *len_t,
+                                 int32_t ntexts, double *out, int nout, int32_t *out_rows) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    std::vector<int32_t> rows;
+    const int rc = fit_plan_out(kind, fit_index_plan_of(kind, a, len_p, nqueries, len_t, ntexts, &p, nullptr, &rows), p, out, nout);
+    if (rc == SED_OK && out_rows && !rows.empty()) std::memcpy(out_rows, rows.data(), rows.size() * sizeof(int32_t));
+    return rc;
+}
+
+// The _lanes exports: the records, and on the integer routes the kernel's parameter words (out_params; the fp64
+// exports have none and pass null).
+static_assert(sizeof(sed_fit_lane) == 8 * sizeof(int32_t), "a lane record is eight 32-bit words");
+static bool fit_lanes_args_ok(FitKind kind, const int32_t *out_lanes, int64_t max_lanes, const uint32_t *out_params) {
+    return max_lanes >= 0 && (max_lanes == 0 || out_lanes) && (sed_fit_route_of(kind).f64 || out_params);
+}
 static void fit_params_out(const sed_fit_params &fp, uint32_t *out_params) {
+    if (!out_params) return;
     for (int a = 0; a < 8; ++a) {
         out_params[2 * a] = fp.row[a][0];
         out_params[2 * a + 1] = fp.row[a][1];
@@ -413,31 +400,82 @@ static void fit_params_out(const sed_fit_params &fp, uint32_t *out_params) {
     out_params[16] = fp.ins;
     out_params[17] = fp.del;
 }
-// what sed_fit_plan and sed_fit_index_plan report of a plan that stands (rc = its planning's result, handed through)
-static int fit_plan_out(int rc, const sed_fit_plan_t &p, double *out, int nout) {
+static int fit_pairs_lanes_export(FitKind kind, const FitCArgs &a, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                                  int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    if (!fit_lanes_args_ok(kind, out_lanes, max_lanes, out_params)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    const int rc = fit_pairs_plan_of(kind, a, len_p, len_t, npairs, &p);
     if (rc != SED_OK) return rc;
-    const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal};
-    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    std::vector<sed_fit_lane> lanes;
+    sed_fit_build_lanes(p, len_p, len_t, npairs, lanes);
+    if (!lanes.empty()) std::memcpy(out_lanes, lanes.data(), lanes.size() * sizeof(sed_fit_lane));
+    fit_params_out(p.fp, out_params);
+    return SED_OK;
+}
+static int fit_index_lanes_export(FitKind kind, const FitCArgs &a, const int32_t *len_p, int32_t nqueries, const int32_t *len_t,
+                                  int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    if (!fit_lanes_args_ok(kind, out_lanes, max_lanes, out_params)) return SED_E_ARG;
+    sed_fit_plan_t p;
+    std::vector<sed_fit_chunk> chunks;
+    std::vector<int32_t> rows;
+    const int rc = fit_index_plan_of(kind, a, len_p, nqueries, len_t, ntexts, &p, &chunks, &rows);
+    if (rc != SED_OK) return rc;
+    if (p.lanes > max_lanes) return SED_E_ARG;
+    sed_fit_lane *out = (sed_fit_lane *)out_lanes;
+    for (int q = 0; q < nqueries; ++q)  // the kernel's own derivation, with each text at word 0
+        for (const sed_fit_chunk &ck : chunks) {
+            sed_fit_lane ln = sed_fit_derive_lane(ck, sed_fit_text{0u, len_t[ck.text]}, p.chunk, len_p[q], p.W);
+            ln.pair = q * ntexts + ck.text;
+            *out++ = ln;
+        }
+    fit_params_out(p.fp, out_params);
     return SED_OK;
 }
 
-// sed_fit_plan's and sed_fit_lanes' common half: the plan of the C arguments
-static int fit_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                       int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
-                       int32_t npairs, sed_fit_plan_t *p) {
+// The route exports: plan(kind, costs, options, err) = the planner's answer for the call's lengths.  The integer route
+// when it serves; else, when its refusal is one of range (bad arguments are bad for both), the fp64 route or both
+// refusals, the integer one's first.
+template <class Plan>
+static int fit_route_export(const FitCArgs &a, bool lengths_ok, FitKind keys, FitKind f64, char *why, int why_len, Plan plan) {
+    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
+    if (why_len) why[0] = 0;
+    if (!lengths_ok) return SED_E_ARG;
     sed_costs c;
     sed_opts o;
-    const int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    return rc != SED_OK ? rc : sed_fit_plan_batch(c, o, len_p, len_t, npairs, p, nullptr);
+    int rc = fit_costs_of(a, &c, &o);
+    if (rc != SED_OK) return rc;
+    std::string e_int, e_f64;
+    if ((rc = plan(keys, c, o, &e_int)) == SED_OK) return SED_FIT_ROUTE_INT;
+    if (rc != SED_E_RANGE) return rc;
+    rc = plan(f64, c, o, &e_f64);
+    const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
+    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
+    return rc == SED_OK ? SED_FIT_ROUTE_F64 : rc;
 }
+
+extern "C" {
 
 int sed_fit_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
                  const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
                  double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    return fit_plan_out(fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p),
-                        p, out, nout);
+    return fit_pairs_plan_export(FIT_SHORT_KEYS, FIT_C_ARGS, len_p, len_t, npairs, out, nout);
+}
+int sed_fit_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                     const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                     double *out, int nout) {
+    return fit_pairs_plan_export(FIT_F64, FIT_C_ARGS, len_p, len_t, npairs, out, nout);
+}
+
+int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                  const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                  int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
+    return fit_pairs_lanes_export(FIT_SHORT_KEYS, FIT_C_ARGS, len_p, len_t, npairs, out_lanes, max_lanes, out_params);
+}
+int sed_fit_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
+                      const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
+                      int32_t *out_lanes, int64_t max_lanes) {
+    return fit_pairs_lanes_export(FIT_F64, FIT_C_ARGS, len_p, len_t, npairs, out_lanes, max_lanes, nullptr);
 }
 
 int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
@@ -445,7 +483,7 @@ int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, doub
                           int32_t npairs, double max_dist, int64_t *out) {
     if (!out) return SED_E_ARG;
     sed_fit_plan_t p;
-    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
+    const int rc = fit_pairs_plan_of(FIT_SHORT_KEYS, FIT_C_ARGS, len_p, len_t, npairs, &p);
     if (rc != SED_OK) return rc;
     int32_t cut = 0;
     const int rc2 = sed_fit_cutoff_rule(p, max_dist, &cut, nullptr);
@@ -453,287 +491,68 @@ int sed_fit_cutoff_scaled(int K, const double *sub, const uint8_t *sub_int, doub
     return rc2;
 }
 
-int sed_fit_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
-                  const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
-                  int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
-    if (max_lanes < 0 || (max_lanes && !out_lanes) || !out_params) return SED_E_ARG;
-    sed_fit_plan_t p;
-    const int rc = fit_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
-    if (rc != SED_OK) return rc;
-    if (p.lanes > max_lanes) return SED_E_ARG;
-    std::vector<sed_fit_lane> lanes;
-    sed_fit_build_lanes(p, len_p, len_t, npairs, lanes);
-    static_assert(sizeof(sed_fit_lane) == 8 * sizeof(int32_t), "a lane record is eight 32-bit words");
-    if (!lanes.empty()) std::memcpy(out_lanes, lanes.data(), lanes.size() * sizeof(sed_fit_lane));
-    fit_params_out(p.fp, out_params);
-    return SED_OK;
-}
-
-// sed_fit_index_plan's and sed_fit_index_lanes' common half: the plan of the cross product from the C arguments, the
-// chunk table and the sums the plan reports
-static int fit_index_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                             const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks,
-                             std::vector<int32_t> *long_rows = nullptr) {
-    if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
-    sed_costs c;
-    sed_opts o;
-    const int rc0 = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc0 != SED_OK) return rc0;
-    sed_fit_index_sums tx;
-    tx.ntexts = ntexts;
-    for (int d = 0; d < ntexts; ++d) {
-        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
-        tx.cols += (double)len_t[d] + 1;
-        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
-    }
-    const int rc = long_rows ? sed_fit_plan_index_long(c, o, len_p, nqueries, tx, p, long_rows, nullptr)
-                             : sed_fit_plan_index(c, o, len_p, nqueries, tx, p, nullptr);
-    if (rc != SED_OK) return rc;
-    double computed = 0, psum = 0;
-    const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
-    for (int q = 0; q < nqueries && ntexts > 0; ++q) psum += (double)len_p[q];
-    p->lanes = nqueries * nchunks;
-    p->cells = psum * computed;
-    return p->lanes > INT_MAX ? SED_E_RANGE : SED_OK;
-}
-
 int sed_fit_index_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                        int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
                        const int32_t *len_t, int32_t ntexts, double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    return fit_plan_out(fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
-                                          len_t, ntexts, &p, nullptr),
-                        p, out, nout);
+    return fit_index_plan_export(FIT_SHORT_KEYS, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out, nout, nullptr);
 }
-
-// sed_fit_index_lanes' and sed_fit_index_long_lanes' common half (long_rows: the long layout's plan)
-static int fit_index_lanes_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                              int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                              const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params,
-                              std::vector<int32_t> *long_rows) {
-    if (max_lanes < 0 || (max_lanes && !out_lanes) || !out_params) return SED_E_ARG;
-    sed_fit_plan_t p;
-    std::vector<sed_fit_chunk> chunks;
-    const int rc = fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
-                                     len_t, ntexts, &p, &chunks, long_rows);
-    if (rc != SED_OK) return rc;
-    if (p.lanes > max_lanes) return SED_E_ARG;
-    sed_fit_lane *out = (sed_fit_lane *)out_lanes;
-    for (int q = 0; q < nqueries; ++q)  // the kernel's own derivation, with each text at word 0
-        for (const sed_fit_chunk &ck : chunks) {
-            sed_fit_lane ln = sed_fit_derive_lane(ck, sed_fit_text{0u, len_t[ck.text]}, p.chunk, len_p[q], p.W);
-            ln.pair = q * ntexts + ck.text;
-            *out++ = ln;
-        }
-    fit_params_out(p.fp, out_params);
-    return SED_OK;
+int sed_fit_index_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                           int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                           const int32_t *len_t, int32_t ntexts, double *out, int nout) {
+    return fit_index_plan_export(FIT_F64, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out, nout, nullptr);
+}
+int sed_fit_index_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                            int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                            const int32_t *len_t, int32_t ntexts, double *out, int nout, int32_t *out_rows) {
+    return fit_index_plan_export(FIT_LONG_KEYS, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out, nout, out_rows);
+}
+int sed_fit_index_long_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
+                                const int32_t *len_t, int32_t ntexts, double *out, int nout, int32_t *out_rows) {
+    return fit_index_plan_export(FIT_LONG_F64, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out, nout, out_rows);
 }
 
 int sed_fit_index_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                         int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
                         const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes, uint32_t *out_params) {
-    return fit_index_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
-                              ntexts, out_lanes, max_lanes, out_params, nullptr);
+    return fit_index_lanes_export(FIT_SHORT_KEYS, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out_lanes, max_lanes, out_params);
 }
-
-int sed_fit_index_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                            const int32_t *len_t, int32_t ntexts, double *out, int nout, int32_t *out_rows) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    std::vector<int32_t> rows;
-    const int rc = fit_plan_out(fit_index_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p,
-                                                  nqueries, len_t, ntexts, &p, nullptr, &rows),
-                                p, out, nout);
-    if (rc == SED_OK && out_rows && !rows.empty()) std::memcpy(out_rows, rows.data(), rows.size() * sizeof(int32_t));
-    return rc;
+                            const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
+    return fit_index_lanes_export(FIT_F64, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out_lanes, max_lanes, nullptr);
 }
-
 int sed_fit_index_long_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                              int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
                              const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes,
                              uint32_t *out_params) {
-    std::vector<int32_t> rows;
-    return fit_index_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
-                              ntexts, out_lanes, max_lanes, out_params, &rows);
+    return fit_index_lanes_export(FIT_LONG_KEYS, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out_lanes, max_lanes, out_params);
 }
-
-// ---- the fp64 route's device-free exports ----
-static int fit_f64_plan_out(int rc, const sed_fit_plan_t &p, double *out, int nout) {
-    if (rc != SED_OK) return rc;
-    const double v[] = {0.0, (double)p.W, (double)p.chunk, (double)p.lanes, p.cells, p.nominal, (double)p.one_lane};
-    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
-    return SED_OK;
-}
-static int fit_f64_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                           int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t,
-                           int32_t npairs, sed_fit_plan_t *p, std::string *err = nullptr) {
-    sed_costs c;
-    sed_opts o;
-    const int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    return rc != SED_OK ? rc : sed_fit_plan_batch_f64(c, o, len_p, len_t, npairs, p, err);
-}
-// sed_fit_index_f64_plan's and sed_fit_index_f64_lanes' common half (fit_index_plan_of for the fp64 plan)
-static int fit_index_f64_plan_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                                 int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                                 const int32_t *len_t, int32_t ntexts, sed_fit_plan_t *p, std::vector<sed_fit_chunk> *chunks,
-                                 std::vector<int32_t> *long_rows = nullptr) {
-    if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
-    sed_costs c;
-    sed_opts o;
-    const int rc0 = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc0 != SED_OK) return rc0;
-    sed_fit_index_sums tx;
-    tx.ntexts = ntexts;
-    for (int d = 0; d < ntexts; ++d) {
-        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
-        tx.cols += (double)len_t[d] + 1;
-        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
-    }
-    const int rc = long_rows ? sed_fit_plan_index_long_f64(c, o, len_p, nqueries, tx, p, long_rows, nullptr)
-                             : sed_fit_plan_index_f64(c, o, len_p, nqueries, tx, p, nullptr);
-    if (rc != SED_OK) return rc;
-    double computed = 0, psum = 0;
-    const int64_t nchunks = nqueries > 0 ? sed_fit_build_chunks(*p, len_t, ntexts, chunks, &computed) : 0;
-    for (int q = 0; q < nqueries && ntexts > 0; ++q) psum += (double)len_p[q];
-    p->lanes = nqueries * nchunks;
-    p->cells = psum * computed;
-    return p->lanes > INT_MAX ? SED_E_RANGE : SED_OK;
-}
-
-int sed_fit_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
-                     const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
-                     double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    return fit_f64_plan_out(fit_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t,
-                                            npairs, &p),
-                            p, out, nout);
-}
-
-int sed_fit_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
-                      const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs,
-                      int32_t *out_lanes, int64_t max_lanes) {
-    if (max_lanes < 0 || (max_lanes && !out_lanes)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    const int rc = fit_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, len_t, npairs, &p);
-    if (rc != SED_OK) return rc;
-    if (p.lanes > max_lanes) return SED_E_ARG;
-    std::vector<sed_fit_lane> lanes;
-    sed_fit_build_lanes(p, len_p, len_t, npairs, lanes);
-    if (!lanes.empty()) std::memcpy(out_lanes, lanes.data(), lanes.size() * sizeof(sed_fit_lane));
-    return SED_OK;
-}
-
-int sed_fit_index_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                           int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                           const int32_t *len_t, int32_t ntexts, double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    return fit_f64_plan_out(fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p,
-                                                  nqueries, len_t, ntexts, &p, nullptr),
-                            p, out, nout);
-}
-
-// sed_fit_index_f64_lanes' and sed_fit_index_long_f64_lanes' common half (long_rows: the wave layout's plan)
-static int fit_index_f64_lanes_of(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                                  const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes,
-                                  std::vector<int32_t> *long_rows) {
-    if (max_lanes < 0 || (max_lanes && !out_lanes)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    std::vector<sed_fit_chunk> chunks;
-    const int rc = fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries,
-                                         len_t, ntexts, &p, &chunks, long_rows);
-    if (rc != SED_OK) return rc;
-    if (p.lanes > max_lanes) return SED_E_ARG;
-    sed_fit_lane *out = (sed_fit_lane *)out_lanes;
-    for (int q = 0; q < nqueries; ++q)  // the kernel's own derivation, with each text at word 0
-        for (const sed_fit_chunk &ck : chunks) {
-            sed_fit_lane ln = sed_fit_derive_lane(ck, sed_fit_text{0u, len_t[ck.text]}, p.chunk, len_p[q], p.W);
-            ln.pair = q * ntexts + ck.text;
-            *out++ = ln;
-        }
-    return SED_OK;
-}
-
-int sed_fit_index_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                            int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                            const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
-    return fit_index_f64_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
-                                  ntexts, out_lanes, max_lanes, nullptr);
-}
-
-int sed_fit_index_long_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                                int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
-                                const int32_t *len_t, int32_t ntexts, double *out, int nout, int32_t *out_rows) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_fit_plan_t p;
-    std::vector<int32_t> rows;
-    const int rc = fit_f64_plan_out(fit_index_f64_plan_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions,
-                                                          len_p, nqueries, len_t, ntexts, &p, nullptr, &rows),
-                                    p, out, nout);
-    if (rc == SED_OK && out_rows && !rows.empty()) std::memcpy(out_rows, rows.data(), rows.size() * sizeof(int32_t));
-    return rc;
-}
-
 int sed_fit_index_long_f64_lanes(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
                                  const int32_t *len_t, int32_t ntexts, int32_t *out_lanes, int64_t max_lanes) {
-    std::vector<int32_t> rows;
-    return fit_index_f64_lanes_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_p, nqueries, len_t,
-                                  ntexts, out_lanes, max_lanes, &rows);
+    return fit_index_lanes_export(FIT_LONG_F64, FIT_C_ARGS, len_p, nqueries, len_t, ntexts, out_lanes, max_lanes, nullptr);
 }
 
 int sed_fit_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,
                   const int32_t *options, int noptions, const int32_t *len_p, const int32_t *len_t, int32_t npairs, char *why,
                   int why_len) {
-    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
-    if (why_len) why[0] = 0;
-    sed_costs c;
-    sed_opts o;
-    int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc != SED_OK) return rc;
-    sed_fit_plan_t p;
-    std::string e_int, e_f64;
-    if ((rc = sed_fit_plan_batch(c, o, len_p, len_t, npairs, &p, &e_int)) == SED_OK) return SED_FIT_ROUTE_INT;
-    if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
-    sed_fit_plan_t pf;
-    rc = sed_fit_plan_batch_f64(c, o, len_p, len_t, npairs, &pf, &e_f64);
-    const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
-    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
-    return rc == SED_OK ? SED_FIT_ROUTE_F64 : rc;
+    return fit_route_export(FIT_C_ARGS, true, FIT_SHORT_KEYS, FIT_F64, why, why_len,
+                            [&](FitKind kind, const sed_costs &c, const sed_opts &o, std::string *err) {
+                                sed_fit_plan_t p;
+                                return sed_fit_plan_batch(kind, c, o, len_p, len_t, npairs, &p, err);
+                            });
 }
-
 int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                        int del_is_int, const int32_t *options, int noptions, const int32_t *len_p, int32_t nqueries,
                        const int32_t *len_t, int32_t ntexts, char *why, int why_len) {
-    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
-    if (why_len) why[0] = 0;
-    if (nqueries < 0 || ntexts < 0 || (ntexts > 0 && !len_t)) return SED_E_ARG;
-    sed_costs c;
-    sed_opts o;
-    int rc = fit_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc != SED_OK) return rc;
-    sed_fit_index_sums tx;
-    tx.ntexts = ntexts;
-    for (int d = 0; d < ntexts; ++d) {
-        if (len_t[d] < 0 && tx.first_negative < 0) tx.first_negative = d;
-        tx.cols += (double)len_t[d] + 1;
-        tx.nmax = std::max<int64_t>(tx.nmax, len_t[d]);
-    }
-    sed_fit_plan_t p;
-    std::vector<int32_t> rows;
-    std::string e_int, e_f64;
-    if ((rc = sed_fit_plan_index_long(c, o, len_p, nqueries, tx, &p, &rows, &e_int)) == SED_OK) return SED_FIT_ROUTE_INT;
-    if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
-    sed_fit_plan_t pf;
-    rc = sed_fit_plan_index_long_f64(c, o, len_p, nqueries, tx, &pf, &rows, &e_f64);
-    const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
-    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
-    return rc == SED_OK ? SED_FIT_ROUTE_F64 : rc;
+    const bool ok = fit_index_lengths_ok(nqueries, len_t, ntexts);
+    const sed_fit_index_sums tx = ok ? fit_text_sums(len_t, ntexts) : sed_fit_index_sums{};
+    return fit_route_export(FIT_C_ARGS, ok, FIT_LONG_KEYS, FIT_LONG_F64, why, why_len,
+                            [&](FitKind kind, const sed_costs &c, const sed_opts &o, std::string *err) {
+                                sed_fit_plan_t p;
+                                return sed_fit_plan_index(kind, c, o, len_p, nqueries, tx, &p, nullptr, err);
+                            });
 }
 
 }  // extern "C"

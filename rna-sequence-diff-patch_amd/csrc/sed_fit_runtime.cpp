@@ -101,8 +101,7 @@ static int fit_search_of(sed_ctx *c, bool f64, const uint8_t *codes_p, const int
                                           out_start && out_end));
     if (rc != SED_OK) return rc;
     sed_fit_plan_t plan;
-    rc = f64 ? sed_fit_plan_batch_f64(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err)
-             : sed_fit_plan_batch(c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err);
+    rc = sed_fit_plan_batch(f64 ? FIT_F64 : FIT_SHORT_KEYS, c->costs, c->opt, len_p, len_t, npairs, &plan, &c->err);
     if (rc != SED_OK || npairs == 0) return rc;
     const int K = c->costs.K;
     struct Span {
@@ -331,6 +330,91 @@ static int fit_index_stage(sed_fit_index *ix, const sed_fit_plan_t &plan, const 
     return SED_OK;
 }
 
+// One R group's share of a long call's arguments
+static sed_fit_index_args fit_long_group_args(const sed_fit_index_args &a, const FitLongGroups::Group &g) {
+    sed_fit_index_args ga = a;
+    ga.pats = (const uint8_t *)a.pats + g.at;
+    ga.nqueries = g.count;
+    return ga;
+}
+
+// What the kernels of one index call take besides the staged arguments: the plan's parameter words or the fp64 cost
+// table, a search's per-lane records (fp64) and, for a hits call, the list, its counter and room, and the cutoff on the
+// route's own scale.
+struct FitIndexCall {
+    FitKind kind;
+    bool hits;
+    const sed_fit_plan_t *plan;
+    sed_fit_f64_costs fc;
+    unsigned long long cap;
+    int32_t cut;
+    double max_dist;
+};
+static const char *const FIT_INDEX_LAUNCH_FAILS[2][4] = {  // [hits][kind]
+    {"fit index kernel launch", "fit index long kernel launch", "fit index fp64 kernel launch",
+     "fit index long fp64 kernel launch"},
+    {"fit index hits kernel launch", "fit index long hits kernel launch", "fit index fp64 hits kernel launch",
+     "fit index long fp64 hits kernel launch"}};
+// The launches of an index call, best-hit or hits, on any route: the lane layouts' one launch, or the wave layouts' R
+// groups (each group: its waves, then, best-hit, its reduce), the timer's events bracketing them.
+static hipError_t fit_index_launch(sed_fit_index *ix, const FitIndexCall &k, FitTimer &timer, const sed_fit_index_args &a,
+                                   const FitLongGroups &lg) {
+    hipStream_t s = ix->ctx->stream;
+    unsigned long long *count = (unsigned long long *)ix->d_count.p;
+    sed_fit_f64_best *rec = (sed_fit_f64_best *)ix->d_rec.p, *best = (sed_fit_f64_best *)ix->d_out.p;
+    sed_fit_f64_hit *hits64 = (sed_fit_f64_hit *)ix->d_hits.p;
+    const sed_fit_params &fp = k.plan->fp;
+    auto one = [&](hipEvent_t e0, hipEvent_t e1, const sed_fit_index_args &ga, const int32_t *qlist, int rows) {
+        switch (k.kind) {
+        case FIT_SHORT_KEYS:
+            return k.hits ? sed_launch_fit_index_hits(s, e0, e1, ga, ix->d_hits.p, count, k.cap, k.cut, fp)
+                          : sed_launch_fit_index(s, e0, e1, ga, fp);
+        case FIT_F64:
+            return k.hits ? sed_launch_fit_index_f64_hits(s, e0, e1, ga, hits64, count, k.cap, k.max_dist, k.fc)
+                          : sed_launch_fit_index_f64(s, e0, e1, ga, rec, best, k.fc);
+        case FIT_LONG_KEYS:
+            return k.hits ? sed_launch_fit_index_long_hits(s, e0, e1, ga, qlist, rows, ix->d_hits.p, count, k.cap, k.cut, fp)
+                          : sed_launch_fit_index_long(s, e0, e1, ga, qlist, rows, fp);
+        default:
+            return k.hits ? sed_launch_fit_index_long_f64_hits(s, e0, e1, ga, qlist, rows, hits64, count, k.cap, k.max_dist, k.fc)
+                          : sed_launch_fit_index_long_f64(s, e0, e1, ga, qlist, rows, rec, best, k.fc);
+        }
+    };
+    if (!sed_fit_route_of(k.kind).waves()) return one(timer.ev[0], timer.ev[1], a, nullptr, 0);
+    hipError_t e = hipSuccess;
+    for (size_t g = 0; g < lg.groups.size() && e == hipSuccess; ++g)
+        e = one(g == 0 ? timer.ev[0] : nullptr, g + 1 == lg.groups.size() ? timer.ev[1] : nullptr,
+                fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first, lg.groups[g].rows);
+    return e;
+}
+
+// The tail of a hits search over either record type: download the n records the kernels appended, sort them by
+// (pair, end) - unique keys -, check each and decode it.  read(record, &start, &dist) = whether the record's own fields
+// are those of a hit within the cutoff, and its start and distance.
+template <class Rec, class Read>
+static int fit_hits_decode(sed_fit_index *ix, std::vector<Rec> &recs, size_t n, int32_t nqueries, sed_fit_hit *out, Read read) {
+    sed_ctx *c = ix->ctx;
+    const uint32_t ntexts = (uint32_t)ix->sums.ntexts;
+    recs.resize(n);
+    hipError_t e = hipSuccess;
+    if ((e = hipMemcpyAsync(recs.data(), ix->d_hits.p, n * sizeof(Rec), hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+        return c->hipfail(e, "download (fit index hits)");
+    std::sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) { return x.pair != y.pair ? x.pair < y.pair : x.end < y.end; });
+    for (size_t i = 0; i < n; ++i) {
+        const Rec &r = recs[i];
+        const uint32_t q = r.pair / ntexts, d = r.pair % ntexts;
+        int32_t start = 0;
+        double dist = 0;
+        if (q >= (uint32_t)nqueries || r.end > (uint32_t)ix->len_t[d] || !read(r, &start, &dist) ||
+            (i > 0 && recs[i - 1].pair == r.pair && recs[i - 1].end == r.end))
+            return c->fail(SED_E_DEVICE, "fit hits: record %zu from the device is no hit (query %u, text %u, end %u)", i, q, d,
+                           r.end);
+        out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, start, (int32_t)r.end, dist};
+    }
+    return SED_OK;
+}
+
 extern "C" {
 
 sed_fit_index *sed_fit_index_create(sed_ctx *c, const uint8_t *codes_t, const int64_t *off_t, const int32_t *len_t,
@@ -397,26 +481,8 @@ void sed_fit_index_destroy(sed_fit_index *ix) {
 int32_t sed_fit_index_texts(const sed_fit_index *ix) { return ix ? ix->sums.ntexts : SED_E_ARG; }
 int64_t sed_fit_index_symbols(const sed_fit_index *ix) { return ix ? ix->symbols : SED_E_ARG; }
 
-// One R group's share of a long call's arguments
-static sed_fit_index_args fit_long_group_args(const sed_fit_index_args &a, const FitLongGroups::Group &g) {
-    sed_fit_index_args ga = a;
-    ga.pats = (const uint8_t *)a.pats + g.at;
-    ga.nqueries = g.count;
-    return ga;
-}
-
 // sed_fit_index_search, sed_fit_index_search_long, sed_fit_index_search_f64 and sed_fit_index_search_long_f64: the plan,
-// the launches and the result records differ, nothing else
-enum FitKind { FIT_SHORT_KEYS, FIT_LONG_KEYS, FIT_F64, FIT_LONG_F64 };
-static inline bool fit_kind_long(FitKind k) { return k == FIT_LONG_KEYS || k == FIT_LONG_F64; }
-static inline bool fit_kind_f64(FitKind k) { return k == FIT_F64 || k == FIT_LONG_F64; }
-static int fit_index_plan_kind(sed_ctx *c, FitKind kind, const int32_t *len_p, int32_t nqueries, const sed_fit_index_sums &sums,
-                               sed_fit_plan_t *plan, std::vector<int32_t> *rows) {
-    return kind == FIT_LONG_KEYS  ? sed_fit_plan_index_long(c->costs, c->opt, len_p, nqueries, sums, plan, rows, &c->err)
-           : kind == FIT_LONG_F64 ? sed_fit_plan_index_long_f64(c->costs, c->opt, len_p, nqueries, sums, plan, rows, &c->err)
-           : kind == FIT_F64      ? sed_fit_plan_index_f64(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err)
-                                  : sed_fit_plan_index(c->costs, c->opt, len_p, nqueries, sums, plan, &c->err);
-}
+// the launches and the result records differ with the route (sed_fit_plan.h: FitKind), nothing else
 static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                                int32_t nqueries, double *out_dist, int32_t *out_start, int32_t *out_end) {
     if (!ix) return SED_E_ARG;
@@ -428,8 +494,8 @@ static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *c
     sed_fit_plan_t plan;
     std::vector<int32_t> rows;
     FitLongGroups lg;
-    const bool lng = fit_kind_long(kind), f64 = fit_kind_f64(kind);
-    rc = fit_index_plan_kind(c, kind, len_p, nqueries, ix->sums, &plan, &rows);
+    const bool lng = sed_fit_route_of(kind).waves(), f64 = sed_fit_route_of(kind).f64;
+    rc = sed_fit_plan_index(kind, c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &rows, &c->err);
     if (rc != SED_OK || nqueries == 0 || ntexts == 0) return rc;
     const size_t nres = (size_t)nqueries * (size_t)ntexts, resbytes = (f64 ? sizeof(sed_fit_f64_best) : 8) * nres;
     sed_fit_index_args a{};
@@ -445,24 +511,8 @@ static int fit_index_search_of(sed_fit_index *ix, FitKind kind, const uint8_t *c
         return c->hipfail(e, "upload (fit index search)");
     sed_fit_f64_costs fc{};
     if (f64 && (e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess) return c->hipfail(e, "upload (fit index costs)");
-    if (kind == FIT_F64 && (e = sed_launch_fit_index_f64(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, (sed_fit_f64_best *)ix->d_rec.p,
-                                                         (sed_fit_f64_best *)ix->d_out.p, fc)) != hipSuccess)
-        return c->hipfail(e, "fit index fp64 kernel launch");
-    if (kind == FIT_SHORT_KEYS && (e = sed_launch_fit_index(c->stream, ix->timer.ev[0], ix->timer.ev[1], a, plan.fp)) != hipSuccess)
-        return c->hipfail(e, "fit index kernel launch");
-    for (size_t g = 0; kind == FIT_LONG_F64 && g < lg.groups.size(); ++g)  // each group: its waves, then its reduce
-        if ((e = sed_launch_fit_index_long_f64(c->stream, g == 0 ? ix->timer.ev[0] : nullptr,
-                                               g + 1 == lg.groups.size() ? ix->timer.ev[1] : nullptr,
-                                               fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
-                                               lg.groups[g].rows, (sed_fit_f64_best *)ix->d_rec.p,
-                                               (sed_fit_f64_best *)ix->d_out.p, fc)) != hipSuccess)
-            return c->hipfail(e, "fit index long fp64 kernel launch");
-    for (size_t g = 0; kind == FIT_LONG_KEYS && g < lg.groups.size(); ++g)  // the events bracket the groups' launches
-        if ((e = sed_launch_fit_index_long(c->stream, g == 0 ? ix->timer.ev[0] : nullptr,
-                                           g + 1 == lg.groups.size() ? ix->timer.ev[1] : nullptr,
-                                           fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
-                                           lg.groups[g].rows, plan.fp)) != hipSuccess)
-            return c->hipfail(e, "fit index long kernel launch");
+    if ((e = fit_index_launch(ix, FitIndexCall{kind, false, &plan, fc, 0, 0, 0.0}, ix->timer, a, lg)) != hipSuccess)
+        return c->hipfail(e, FIT_INDEX_LAUNCH_FAILS[0][kind]);
     const uint64_t *keys = (const uint64_t *)ix->pin.p;
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_out.p, resbytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (fit index search)");
@@ -502,7 +552,7 @@ int sed_fit_index_last_time(const sed_fit_index *ix, float *kernel_ms) {
 
 // Every hit within max_dist (include/sed.h).  The search's plan, chunk table and queries (fit_index_stage); the kernel
 // appends its records in whatever order the waves' atomic adds land, and counts on past `cap`.  The host reads the
-// count, then the records when they all fit, sorts them by (pair, end) - unique keys - and decodes them.
+// count, then the records when they all fit (fit_hits_decode).
 static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,
                              int32_t nqueries, double max_dist, sed_fit_hit *out, int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
@@ -513,8 +563,8 @@ static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *cod
     sed_fit_plan_t plan;
     std::vector<int32_t> rows;
     FitLongGroups lg;
-    const bool lng = fit_kind_long(kind), f64 = fit_kind_f64(kind);
-    rc = fit_index_plan_kind(c, kind, len_p, nqueries, ix->sums, &plan, &rows);
+    const bool lng = sed_fit_route_of(kind).waves(), f64 = sed_fit_route_of(kind).f64;
+    rc = sed_fit_plan_index(kind, c->costs, c->opt, len_p, nqueries, ix->sums, &plan, &rows, &c->err);
     int32_t cut = 0;
     if (rc == SED_OK) rc = sed_fit_cutoff_rule(plan, max_dist, &cut, &c->err);  // (fp64: its check of max_dist alone)
     if (rc != SED_OK) return rc;
@@ -531,28 +581,8 @@ static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *cod
     if ((e = hipMemsetAsync(ix->d_count.p, 0, 8, c->stream)) != hipSuccess) return c->hipfail(e, "upload (fit index hits)");
     sed_fit_f64_costs fc{};
     if (f64 && (e = fit_f64_costs_upload(c, plan, ix->d_tab, &fc)) != hipSuccess) return c->hipfail(e, "upload (fit index costs)");
-    if (kind == FIT_F64 && (e = sed_launch_fit_index_f64_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a,
-                                                              (sed_fit_f64_hit *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
-                                                              (unsigned long long)cap, max_dist, fc)) != hipSuccess)
-        return c->hipfail(e, "fit index fp64 hits kernel launch");
-    for (size_t g = 0; kind == FIT_LONG_F64 && g < lg.groups.size(); ++g)
-        if ((e = sed_launch_fit_index_long_f64_hits(c->stream, g == 0 ? ix->hits_timer.ev[0] : nullptr,
-                                                    g + 1 == lg.groups.size() ? ix->hits_timer.ev[1] : nullptr,
-                                                    fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
-                                                    lg.groups[g].rows, (sed_fit_f64_hit *)ix->d_hits.p,
-                                                    (unsigned long long *)ix->d_count.p, (unsigned long long)cap, max_dist,
-                                                    fc)) != hipSuccess)
-            return c->hipfail(e, "fit index long fp64 hits kernel launch");
-    if (kind == FIT_SHORT_KEYS && (e = sed_launch_fit_index_hits(c->stream, ix->hits_timer.ev[0], ix->hits_timer.ev[1], a, ix->d_hits.p,
-                                               (unsigned long long *)ix->d_count.p, (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
-        return c->hipfail(e, "fit index hits kernel launch");
-    for (size_t g = 0; kind == FIT_LONG_KEYS && g < lg.groups.size(); ++g)
-        if ((e = sed_launch_fit_index_long_hits(c->stream, g == 0 ? ix->hits_timer.ev[0] : nullptr,
-                                                g + 1 == lg.groups.size() ? ix->hits_timer.ev[1] : nullptr,
-                                                fit_long_group_args(a, lg.groups[g]), lg.d_qlist + lg.groups[g].first,
-                                                lg.groups[g].rows, ix->d_hits.p, (unsigned long long *)ix->d_count.p,
-                                                (unsigned long long)cap, cut, plan.fp)) != hipSuccess)
-            return c->hipfail(e, "fit index long hits kernel launch");
+    const FitIndexCall call{kind, true, &plan, fc, (unsigned long long)cap, cut, max_dist};
+    if ((e = fit_index_launch(ix, call, ix->hits_timer, a, lg)) != hipSuccess) return c->hipfail(e, FIT_INDEX_LAUNCH_FAILS[1][kind]);
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
         return c->hipfail(e, "download (fit index hits)");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "fit index hits kernel execution");
@@ -563,46 +593,18 @@ static int fit_index_hits_of(sed_fit_index *ix, FitKind kind, const uint8_t *cod
         return c->fail(SED_E_RANGE, "fit hits: found %lld hits, cap %lld: call again with room for them", (long long)n,
                        (long long)cap);
     if (n == 0) return SED_OK;
-    if (f64) {  // the same steps over the wider records: download, sort by (pair, end), check, decode
-        ix->h_hits64.resize((size_t)n);
-        if ((e = hipMemcpyAsync(ix->h_hits64.data(), ix->d_hits.p, (size_t)n * sizeof(sed_fit_f64_hit), hipMemcpyDeviceToHost,
-                                c->stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-            return c->hipfail(e, "download (fit index hits)");
-        std::sort(ix->h_hits64.begin(), ix->h_hits64.end(), [](const sed_fit_f64_hit &x, const sed_fit_f64_hit &y) {
-            return x.pair != y.pair ? x.pair < y.pair : x.end < y.end;
+    if (f64)
+        return fit_hits_decode(ix, ix->h_hits64, (size_t)n, nqueries, out, [&](const sed_fit_f64_hit &r, int32_t *start, double *dist) {
+            *start = r.start;
+            *dist = r.D;
+            return r.start >= 0 && (uint32_t)r.start <= r.end && r.D >= 0 && r.D <= max_dist;
         });
-        for (size_t i = 0; i < (size_t)n; ++i) {
-            const sed_fit_f64_hit &r = ix->h_hits64[i];
-            const uint32_t q = r.pair / (uint32_t)ntexts, d = r.pair % (uint32_t)ntexts;
-            if (q >= (uint32_t)nqueries || r.end > (uint32_t)ix->len_t[d] || r.start < 0 || (uint32_t)r.start > r.end ||
-                !(r.D >= 0 && r.D <= max_dist) ||
-                (i > 0 && ix->h_hits64[i - 1].pair == r.pair && ix->h_hits64[i - 1].end == r.end))
-                return c->fail(SED_E_DEVICE, "fit hits: record %zu from the device is no hit (query %u, text %u, end %u)", i, q,
-                               d, r.end);
-            out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, r.start, (int32_t)r.end, r.D};
-        }
-        return SED_OK;
-    }
-    ix->h_hits.resize((size_t)n);
-    if ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(sed_fit_hit_rec), hipMemcpyDeviceToHost,
-                            c->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (fit index hits)");
-    std::sort(ix->h_hits.begin(), ix->h_hits.end(), [](const sed_fit_hit_rec &x, const sed_fit_hit_rec &y) {
-        return x.pair != y.pair ? x.pair < y.pair : x.end < y.end;
-    });
     const double inv = std::ldexp(1.0, -plan.scale_log2);
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        const sed_fit_hit_rec &r = ix->h_hits[i];
-        const uint32_t q = r.pair / (uint32_t)ntexts, d = r.pair % (uint32_t)ntexts;
-        if (q >= (uint32_t)nqueries || r.end > (uint32_t)ix->len_t[d] || r.len > r.end || r.D > (uint32_t)cut ||
-            (i > 0 && ix->h_hits[i - 1].pair == r.pair && ix->h_hits[i - 1].end == r.end))
-            return c->fail(SED_E_DEVICE, "fit hits: record %zu from the device is no hit (query %u, text %u, end %u)", i, q, d,
-                           r.end);
-        out[i] = sed_fit_hit{(int32_t)q, (int32_t)d, (int32_t)(r.end - r.len), (int32_t)r.end, (double)r.D * inv};
-    }
-    return SED_OK;
+    return fit_hits_decode(ix, ix->h_hits, (size_t)n, nqueries, out, [&](const sed_fit_hit_rec &r, int32_t *start, double *dist) {
+        *start = (int32_t)(r.end - r.len);
+        *dist = (double)r.D * inv;
+        return r.len <= r.end && r.D <= (uint32_t)cut;
+    });
 }
 
 int sed_fit_index_hits(sed_fit_index *ix, const uint8_t *codes_p, const int64_t *off_p, const int32_t *len_p,

@@ -1,6 +1,6 @@
 // sed_join_plan.cpp — the join planner (sed_join_plan.h): scale and cost rows, the kernel variant, the cutoff on the
-// integer scale, the launches and the pair counts of a similarity join.  No HIP call.  Also the device-free entry point
-// sed_join_plan of include/sed.h.
+// integer scale, the launches and the pair counts of a similarity join.  No HIP call.  Also the device-free entry points
+// sed_join_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route of include/sed.h.
 #include "sed_join_plan.h"
 
 #include <algorithm>
@@ -64,13 +64,17 @@ static bool join_unit_costs(const sed_costs &c, uint32_t row_codes, uint32_t col
     return true;
 }
 
-int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
-                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
-                     sed_join_plan_t *plan, std::string *err) {
+// What the plans of both routes share: the checks in their one order - the arguments, max_dist, the route's costs rule
+// (rule(): it also derives whatever keep reads), the code set, the rows, the columns - then the launches and the counts
+// under keep(n, m) = a row of n and a column of m symbols are computed.
+template <class Rule, class Keep>
+static int join_plan_shared(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
+                            int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
+                            sed_join_counts *plan, std::string *err, Rule rule, Keep keep) {
     if (nrows < 0 || ncols < 0 || (nrows && !len_rows) || (ncols && !len_cols) || (self && nrows > ncols))
         return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
     if (std::isnan(max_dist) || max_dist < 0) return sed_plan_fail(err, SED_E_ARG, "join: max_dist is NaN or negative");
-    int rc = sed_join_costs_rule(c, plan, err);
+    const int rc = rule();
     if (rc != SED_OK) return rc;
     const uint32_t seen = row_codes | col_codes;
     if (c.K < 32 && (seen >> c.K) != 0) {
@@ -90,12 +94,6 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
             return sed_plan_fail(err, SED_E_ARG, "join: column %d has %d symbols (0..%d)", j, len_cols[j], SED_JOIN_MAXLEN);
         hc[len_cols[j]] += 1;
     }
-    uint32_t umap = 0;
-    plan->kernel = o.join_dp != 2 && join_unit_costs(c, row_codes, col_codes, &umap) ? SED_JOIN_KERNEL_BITPAR : SED_JOIN_KERNEL_DP;
-    plan->sp.umap = umap;
-    // floor(max_dist S): S is a power of two, so the product is exact (or overflows to +inf, which the clamp takes)
-    const double cs = std::floor(std::ldexp(max_dist, plan->scale_log2));
-    plan->cut = cs >= SED_JOIN_CUT_ALL ? SED_JOIN_CUT_ALL : (int32_t)cs;
     plan->launch_rows = o.join_rows > 0 ? o.join_rows : (int64_t)SED_JOIN_MAX_GROUPS * SED_JOIN_G;
     const double blocks = (ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK;
     double groups = 0;
@@ -106,16 +104,36 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
     plan->run = plan->cells = 0;
     for (int n = 0; n <= SED_JOIN_MAXLEN; ++n)
         for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
-            const uint32_t lb = m > n ? (uint32_t)(m - n) * plan->sp.ins : (uint32_t)(n - m) * plan->sp.del;
-            if (lb > (uint32_t)plan->cut) continue;
+            if (!keep(n, m)) continue;
             plan->run += hr[n] * hc[m];
             plan->cells += hr[n] * hc[m] * n * m;
         }
-    if (self) {  // every (i, i) has bound 0 and was counted
+    if (self) {  // every (i, i) has n = m, which both routes' rules compute, and was counted
         plan->run -= nrows;
         plan->cells -= own_cells;
     }
     return SED_OK;
+}
+
+int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
+                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
+                     sed_join_plan_t *plan, std::string *err) {
+    auto rule = [&]() -> int {
+        const int rc = sed_join_costs_rule(c, plan, err);
+        if (rc != SED_OK) return rc;
+        uint32_t umap = 0;
+        plan->kernel = o.join_dp != 2 && join_unit_costs(c, row_codes, col_codes, &umap) ? SED_JOIN_KERNEL_BITPAR : SED_JOIN_KERNEL_DP;
+        plan->sp.umap = umap;
+        // floor(max_dist S): S is a power of two, so the product is exact (or overflows to +inf, which the clamp takes)
+        const double cs = std::floor(std::ldexp(max_dist, plan->scale_log2));
+        plan->cut = cs >= SED_JOIN_CUT_ALL ? SED_JOIN_CUT_ALL : (int32_t)cs;
+        return SED_OK;
+    };
+    auto keep = [&](int n, int m) {  // the length bound within the cutoff
+        const uint32_t lb = m > n ? (uint32_t)(m - n) * plan->sp.ins : (uint32_t)(n - m) * plan->sp.del;
+        return lb <= (uint32_t)plan->cut;
+    };
+    return join_plan_shared(c, o, len_rows, nrows, len_cols, ncols, self, row_codes, col_codes, max_dist, plan, err, rule, keep);
 }
 
 // ---- the fp64 route ----
@@ -158,50 +176,15 @@ void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t ke
 int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows,
                          const int32_t *len_cols, int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes,
                          double max_dist, sed_join_f64_plan_t *plan, std::string *err) {
-    if (nrows < 0 || ncols < 0 || (nrows && !len_rows) || (ncols && !len_cols) || (self && nrows > ncols))
-        return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
-    if (std::isnan(max_dist) || max_dist < 0) return sed_plan_fail(err, SED_E_ARG, "join: max_dist is NaN or negative");
-    int rc = sed_join_f64_costs_rule(c, plan, err);
-    if (rc != SED_OK) return rc;
-    const uint32_t seen = row_codes | col_codes;
-    if ((seen >> c.K) != 0) {  // (K <= 16)
-        const bool in_cols = (col_codes >> c.K) != 0;
-        return sed_plan_fail(err, SED_E_ARG, "join: a %s code is outside the alphabet (K=%d)", in_cols ? "column" : "row", c.K);
-    }
-    double hr[SED_JOIN_MAXLEN + 1] = {}, hc[SED_JOIN_MAXLEN + 1] = {};
-    double own_cells = 0;  // sum n n over the rows: the (i, i) pairs a self join leaves out
-    for (int i = 0; i < nrows; ++i) {
-        if (len_rows[i] < 0 || len_rows[i] > SED_JOIN_MAXLEN)
-            return sed_plan_fail(err, SED_E_ARG, "join: row %d has %d symbols (0..%d)", i, len_rows[i], SED_JOIN_MAXLEN);
-        hr[len_rows[i]] += 1;
-        own_cells += (double)len_rows[i] * len_rows[i];
-    }
-    for (int j = 0; j < ncols; ++j) {
-        if (len_cols[j] < 0 || len_cols[j] > SED_JOIN_MAXLEN)
-            return sed_plan_fail(err, SED_E_ARG, "join: column %d has %d symbols (0..%d)", j, len_cols[j], SED_JOIN_MAXLEN);
-        hc[len_cols[j]] += 1;
-    }
-    plan->max_dist = max_dist;
-    sed_join_f64_keep_rule(plan->ins, plan->del, max_dist, plan->keep);
-    plan->launch_rows = o.join_rows > 0 ? o.join_rows : (int64_t)SED_JOIN_MAX_GROUPS * SED_JOIN_G;
-    const double blocks = (ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK;
-    double groups = 0;
-    for (int64_t r = 0; r < nrows; r += plan->launch_rows)
-        groups += (double)((std::min<int64_t>(plan->launch_rows, nrows - r) + SED_JOIN_G - 1) / SED_JOIN_G);
-    plan->waves = ncols > 0 ? blocks * groups * (SED_JOIN_BLOCK / 64) : 0;
-    plan->scope = (double)nrows * ncols - (self ? nrows : 0);
-    plan->run = plan->cells = 0;
-    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n)
-        for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
-            if (!((plan->keep[n] >> m) & 1u)) continue;
-            plan->run += hr[n] * hc[m];
-            plan->cells += hr[n] * hc[m] * n * m;
-        }
-    if (self) {  // every (i, i) has n = m, which the rule always computes, and was counted
-        plan->run -= nrows;
-        plan->cells -= own_cells;
-    }
-    return SED_OK;
+    auto rule = [&]() -> int {
+        const int rc = sed_join_f64_costs_rule(c, plan, err);
+        if (rc != SED_OK) return rc;
+        plan->max_dist = max_dist;
+        sed_join_f64_keep_rule(plan->ins, plan->del, max_dist, plan->keep);
+        return SED_OK;
+    };
+    auto keep = [&](int n, int m) { return ((plan->keep[n] >> m) & 1u) != 0; };
+    return join_plan_shared(c, o, len_rows, nrows, len_cols, ncols, self, row_codes, col_codes, max_dist, plan, err, rule, keep);
 }
 
 // sed_join_plan's, sed_join_f64_plan's and sed_join_route's arguments as the planner's costs and options
@@ -220,6 +203,27 @@ static int join_costs_of(int K, const double *sub, const uint8_t *sub_int, doubl
     return SED_OK;
 }
 
+// what sed_join_plan and sed_join_f64_plan report: JOIN_PLAN_FIELDS of sedgpu.py
+static int join_plan_out(double scale, int kernel, const sed_join_counts &p, double *out, int nout) {
+    const double v[] = {scale, (double)kernel, p.waves, p.scope, p.run, p.cells};
+    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
+    return SED_OK;
+}
+
+extern "C" int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows,
+                             const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
+                             uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return SED_E_ARG;
+    sed_costs c;
+    sed_opts o;
+    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return rc;
+    sed_join_plan_t p;
+    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p, nullptr);
+    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, nout);
+}
+
 extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
                                  int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
@@ -232,10 +236,7 @@ extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_in
     sed_join_f64_plan_t p;
     rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
                               nullptr);
-    if (rc != SED_OK) return rc;
-    const double v[] = {0.0, (double)SED_JOIN_KERNEL_F64, p.waves, p.scope, p.run, p.cells};
-    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
-    return SED_OK;
+    return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, nout);
 }
 
 extern "C" int sed_join_f64_keep(double ins, double del, double max_dist, uint64_t *keep) {
@@ -267,29 +268,4 @@ extern "C" int sed_join_route(int K, const double *sub, const uint8_t *sub_int, 
     const std::string text = rc == SED_OK ? e_int : e_int + "; " + e_f64;
     if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
     return rc == SED_OK ? SED_JOIN_ROUTE_F64 : rc;
-}
-
-extern "C" int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows,
-                             const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
-                             uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    if (K < 1 || K > 255 || !sub || noptions < 0 || (noptions && !options) || nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_costs c;
-    sed_opts o;
-    c.K = K;
-    c.sub.assign(sub, sub + K * K);
-    if (sub_int) c.sub_int.assign(sub_int, sub_int + K * K);
-    c.ins = ins;
-    c.del = del;
-    c.ins_int = ins_is_int ? 1 : 0;
-    c.del_int = del_is_int ? 1 : 0;
-    for (int i = 0; i < noptions; ++i)
-        if (!sed_opts_set(o, options[2 * i], options[2 * i + 1], true)) return SED_E_ARG;
-    sed_join_plan_t p;
-    const int rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen,
-                                    max_dist, &p, nullptr);
-    if (rc != SED_OK) return rc;
-    const double v[] = {std::ldexp(1.0, p.scale_log2), (double)p.kernel, p.waves, p.scope, p.run, p.cells};
-    for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
-    return SED_OK;
 }

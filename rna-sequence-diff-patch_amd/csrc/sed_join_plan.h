@@ -1,7 +1,7 @@
 // sed_join_plan.h — the device-free half of the similarity join (include/sed.h: sed_join_self, sed_join_search): what a
 // join decides from the cost model, the options, the lengths, the codes seen and the cutoff.  sed_join_plan.cpp calls no
 // HIP API (it shares sed_costs, sed_opts and sed_plan_fail with the batch planner, sed_plan.h, and nothing else); its
-// export sed_join_plan runs, and is tested, without a device.
+// exports sed_join_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route run, and are tested, without a device.
 #pragma once
 #include "sed_plan.h"
 
@@ -9,15 +9,18 @@
 #define SED_JOIN_KERNEL_BITPAR 2
 #define SED_JOIN_CUT_ALL 65535  // no scaled distance of two sequences of <= 32 symbols exceeds 64 * 255
 
-struct sed_join_plan_t {
+// What a plan of either route counts, from the lengths and the route's rule of which (n, m) are computed
+struct sed_join_counts {
+    int64_t launch_rows = 0;     // rows one launch takes: SED_JOIN_MAX_GROUPS groups, or SED_OPT_JOIN_ROWS
+    double waves = 0;            // the 64-lane waves of every launch: 4 per block
+    double scope = 0;            // the pairs the call is about: rows x columns, less the (i, i) of a self join
+    double run = 0, cells = 0;   // those the route's length rule computes, and their n m
+};
+struct sed_join_plan_t : sed_join_counts {  // run: the pairs whose length bound is within the cutoff
     int scale_log2 = 0;          // S = 2^scale_log2
     int kernel = SED_JOIN_KERNEL_DP;
     sed_scaled_params sp{};      // the cost rows, insert and delete on the integer scale, umap (bit-parallel variant)
     int32_t cut = 0;             // min(floor(max_dist S), SED_JOIN_CUT_ALL)
-    int64_t launch_rows = 0;     // rows one launch takes: SED_JOIN_MAX_GROUPS groups, or SED_OPT_JOIN_ROWS
-    double waves = 0;            // the 64-lane waves of every launch: 4 per block
-    double scope = 0;            // the pairs the call is about: rows x columns, less the (i, i) of a self join
-    double run = 0, cells = 0;   // those whose length bound is within the cutoff, and their n m
 };
 
 // The table alone: the smallest S = 2^k, k <= 8, that makes insert, delete and every substitution cost integral, with
@@ -27,7 +30,8 @@ struct sed_join_plan_t {
 int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *err);
 // The whole plan.  len_rows / len_cols = the lengths (0..32 each, else SED_E_ARG); self: the rows are nrows of the ncols
 // columns, and each row's own column is out of scope; row_codes / col_codes = bit c set when code c occurs (bit 31: any
-// code >= 31).  A code >= K: SED_E_ARG; NaN or negative max_dist: SED_E_ARG.
+// code >= 31).  A code >= K: SED_E_ARG; NaN or negative max_dist: SED_E_ARG.  Both routes' plans refuse in one order:
+// the arguments, max_dist, the route's costs rule, the code set, the rows, the columns.
 int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
                      int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
                      sed_join_plan_t *plan, std::string *err);
@@ -35,13 +39,11 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
 // The fp64 route (include/sed.h: sed_join_self_f64, sed_join_search_f64; kernel: sed_join_f64.hip): any table of finite
 // costs >= 0 over at most SED_JOIN_F64_MAXK symbols.  There is no scale: a cell's value is the oracle's.
 #define SED_JOIN_KERNEL_F64 3
-struct sed_join_f64_plan_t {
+struct sed_join_f64_plan_t : sed_join_counts {
     double ins = 0, del = 0;     // -0.0 normalised to +0.0, as sub
     double sub[SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK] = {};  // row a = row symbol a, zeros past K
     double max_dist = 0;
     uint64_t keep[SED_JOIN_MAXLEN + 1] = {};  // keep[n] bit m: a row of n and a column of m symbols are computed
-    int64_t launch_rows = 0;     // as sed_join_plan_t's
-    double waves = 0, scope = 0, run = 0, cells = 0;
 };
 // The table alone: K <= SED_JOIN_F64_MAXK, every cost finite and >= 0; fills ins, del, sub.  Anything else: SED_E_RANGE,
 // *err names the bound or the cost.
@@ -53,7 +55,7 @@ int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::
 // fl(p - p 2^-40) > max_dist.  With n = 0 or m = 0, D is the product fl(m insert) or fl(n delete) itself and the exact
 // compare decides.  keep[n] bit m = the pair is computed.  ins, del >= +0, max_dist >= 0 or +inf.
 void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t keep[SED_JOIN_MAXLEN + 1]);
-// The whole plan: sed_join_plan_of's arguments, checks (in its order) and counts under the rule above.
+// The whole plan: sed_join_plan_of's arguments, checks and counts, under the rule above.
 int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows,
                          const int32_t *len_cols, int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes,
                          double max_dist, sed_join_f64_plan_t *plan, std::string *err);

@@ -759,13 +759,8 @@ def codes_seen(codes):
 
 
 def _join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
-    K, sub, sub_int, ins, ins_int, dele, del_int = costs
-    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
-    lr = np.ascontiguousarray(len_rows if len(len_rows) else [0], np.int32)
-    lc = np.ascontiguousarray(len_cols if len(len_cols) else [0], np.int32)
-    return (int(K), np.ascontiguousarray(sub, np.float64).ravel(), np.ascontiguousarray(sub_int, np.uint8).ravel(),
-            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options), lr, len(len_rows), lc, len(len_cols),
-            int(bool(self_join)), int(row_codes), int(col_codes), float(max_dist))
+    return _plan_args(costs, options) + (_lengths(len_rows), len(len_rows), _lengths(len_cols), len(len_cols),
+                                         int(bool(self_join)), int(row_codes), int(col_codes), float(max_dist))
 
 
 def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist, _call="sed_join_plan"):
@@ -776,9 +771,7 @@ def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_code
     rc = getattr(load(), _call)(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
                                 out, len(out))
     if rc != 0:
-        err = SedError("%s failed (%d)" % (_call, rc))
-        err.code = rc
-        raise err
+        raise _fit_fail(_call, rc)
     return {k: (float(v) if k in ("scale", "cells") else int(v)) for k, v in zip(JOIN_PLAN_FIELDS, out)}
 
 
@@ -794,9 +787,7 @@ def join_f64_keep(ins, dele, max_dist):
     keep = (C.c_uint64 * 33)()
     rc = load().sed_join_f64_keep(float(ins), float(dele), float(max_dist), keep)
     if rc != 0:
-        err = SedError("sed_join_f64_keep failed (%d)" % rc)
-        err.code = rc
-        raise err
+        raise _fit_fail("sed_join_f64_keep", rc)
     return np.array([[(int(keep[n]) >> m) & 1 for m in range(33)] for n in range(33)], bool)
 
 
@@ -804,17 +795,8 @@ def join_route(costs, options, len_rows, len_cols, self_join, row_codes, col_cod
     """Which route serves the join join_plan's arguments describe, without a device (sed_join_route): (route, why).
     route = "int" (self_join / search serve it), "f64" (only self_join_f64 / search_f64 do; why = the integer route's
     refusal) or None (neither; why = both refusals).  Bad arguments raise SedError as join_plan does."""
-    why = C.create_string_buffer(1024)
-    rc = load().sed_join_route(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
-                               why, len(why))
-    text = why.value.decode()
-    if rc in JOIN_ROUTES:
-        return JOIN_ROUTES[rc], text
-    if rc == SED_E_RANGE:
-        return None, text
-    err = SedError("sed_join_route failed (%d)" % rc)
-    err.code = rc
-    raise err
+    return _route_call("sed_join_route", _join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                       JOIN_ROUTES)
 
 
 def unpack_ops(ops_words, ops_off, p, length):
@@ -1455,84 +1437,29 @@ def plan_schedule(costs, options, packed, flags, cut_on=False, cut_win=False):
 
 
 FIT_PLAN_FIELDS = ("scale", "W", "chunk", "lanes", "cells", "nominal_cells")
-
-
-def fit_plan(costs, options, len_p, len_t):
-    """What Context.fit would decide, without a device (sed_fit_plan): {field: number} over FIT_PLAN_FIELDS.  costs and
-    options as plan_routes takes them; len_p / len_t = the pairs' pattern and text lengths.  Raises SedError carrying
-    the SED_E_* code (.code) the search would fail with."""
-    K, sub, sub_int, ins, ins_int, dele, del_int = costs
-    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
-    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
-    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
-    out = np.zeros(len(FIT_PLAN_FIELDS), np.float64)
-    rc = load().sed_fit_plan(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
-                             np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
-                             int(del_int), opts, len(options), lp, lt, len(len_p), out, len(out))
-    if rc != 0:
-        err = SedError("sed_fit_plan failed (%d)" % rc)
-        err.code = rc
-        raise err
-    return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
-
-
-def fit_cutoff_scaled(costs, options, len_p, len_t, max_dist):
-    """The cutoff FitIndex.hits hands its kernel, without a device (sed_fit_cutoff_scaled): min(floor(max_dist * S),
-    65535) under the scale S of fit_plan's plan for the same arguments.  Raises SedError carrying the code (.code):
-    fit_plan's for these arguments, else SED_E_ARG for a NaN or negative max_dist."""
-    K, sub, sub_int, ins, ins_int, dele, del_int = costs
-    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
-    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
-    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
-    out = C.c_int64(0)
-    rc = load().sed_fit_cutoff_scaled(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
-                                      np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int),
-                                      float(dele), int(del_int), opts, len(options), lp, lt, len(len_p), float(max_dist),
-                                      C.byref(out))
-    if rc != 0:
-        err = SedError("sed_fit_cutoff_scaled failed (%d)" % rc)
-        err.code = rc
-        raise err
-    return int(out.value)
-
-
-FIT_LANE_FIELDS = ("tw", "pair", "pat", "plen", "nsteps", "lead", "cnt", "c0")
-
-
-def fit_lanes(costs, options, len_p, len_t):
-    """The lane records Context.fit would run, without a device (sed_fit_lanes): (lanes, params).  lanes = {field:
-    int64[nlanes]} over FIT_LANE_FIELDS, tw in 4-symbol words from the pair's own text start; params = {"row":
-    u32[8][2] update addend bytes, "ins", "del": the scaled insert and delete}.  Arguments and errors as fit_plan."""
-    nl = fit_plan(costs, options, len_p, len_t)["lanes"]
-    K, sub, sub_int, ins, ins_int, dele, del_int = costs
-    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
-    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
-    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
-    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
-    par = np.zeros(18, np.uint32)
-    rc = load().sed_fit_lanes(int(K), np.ascontiguousarray(sub, np.float64).ravel(),
-                              np.ascontiguousarray(sub_int, np.uint8).ravel(), float(ins), int(ins_int), float(dele),
-                              int(del_int), opts, len(options), lp, lt, len(len_p), rec.ravel(), nl, par)
-    if rc != 0:
-        err = SedError("sed_fit_lanes failed (%d)" % rc)
-        err.code = rc
-        raise err
-    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
-    lanes["tw"] &= 0xFFFFFFFF
-    return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
-
-
 FIT_F64_PLAN_FIELDS = FIT_PLAN_FIELDS + ("one_lane",)
+FIT_LANE_FIELDS = ("tw", "pair", "pat", "plen", "nsteps", "lead", "cnt", "c0")
 FIT_ROUTES = {0: "int", 1: "f64"}
 
 
-def _fit_pair_args(costs, options, len_p, len_t):
+def _plan_args(costs, options):
+    """The cost model and the options as every device-free export takes them."""
     K, sub, sub_int, ins, ins_int, dele, del_int = costs
     opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
-    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
-    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
     return (int(K), np.ascontiguousarray(sub, np.float64).ravel(), np.ascontiguousarray(sub_int, np.uint8).ravel(),
-            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options), lp, lt, len(len_p))
+            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options))
+
+
+def _lengths(lens):
+    return np.ascontiguousarray(lens if len(lens) else [0], np.int32)
+
+
+def _fit_pair_args(costs, options, len_p, len_t):
+    return _plan_args(costs, options) + (_lengths(len_p), _lengths(len_t), len(len_p))
+
+
+def _fit_index_args(costs, options, len_p, len_t):
+    return _plan_args(costs, options) + (_lengths(len_p), len(len_p), _lengths(len_t), len(len_t))
 
 
 def _fit_fail(name, rc):
@@ -1541,178 +1468,151 @@ def _fit_fail(name, rc):
     return err
 
 
-def _fit_f64_plan_dict(out):
-    return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_F64_PLAN_FIELDS, out)}
+def _fit_plan_call(name, args, fields=FIT_PLAN_FIELDS, nrows=None):
+    """The plan dict of one _plan export over `fields`; nrows = the queries of a long plan, which adds "rows"."""
+    out = np.zeros(len(fields), np.float64)
+    rows = () if nrows is None else (np.zeros(max(nrows, 1), np.int32),)
+    rc = getattr(load(), name)(*args, out, len(out), *rows)
+    if rc != 0:
+        raise _fit_fail(name, rc)
+    plan = {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(fields, out)}
+    if rows:
+        plan["rows"] = rows[0][:nrows]
+    return plan
+
+
+def _fit_lanes_call(name, args, nl, params):
+    """The lane dict of one _lanes export of nl records; params: the integer routes' (lanes, params), else lanes alone."""
+    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
+    par = (np.zeros(18, np.uint32),) if params else ()
+    rc = getattr(load(), name)(*args, rec.ravel(), nl, *par)
+    if rc != 0:
+        raise _fit_fail(name, rc)
+    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
+    lanes["tw"] &= 0xFFFFFFFF
+    if not params:
+        return lanes
+    return lanes, {"row": par[0][:16].reshape(8, 2).copy(), "ins": int(par[0][16]), "del": int(par[0][17])}
+
+
+def _route_call(name, args, routes):
+    """(route, why) of one _route export: a name of `routes`, or None when the refusal is both routes'."""
+    why = C.create_string_buffer(1024)
+    rc = getattr(load(), name)(*args, why, len(why))
+    text = why.value.decode()
+    if rc in routes:
+        return routes[rc], text
+    if rc == SED_E_RANGE:
+        return None, text
+    raise _fit_fail(name, rc)
+
+
+def fit_plan(costs, options, len_p, len_t):
+    """What Context.fit would decide, without a device (sed_fit_plan): {field: number} over FIT_PLAN_FIELDS.  costs and
+    options as plan_routes takes them; len_p / len_t = the pairs' pattern and text lengths.  Raises SedError carrying
+    the SED_E_* code (.code) the search would fail with."""
+    return _fit_plan_call("sed_fit_plan", _fit_pair_args(costs, options, len_p, len_t))
+
+
+def fit_cutoff_scaled(costs, options, len_p, len_t, max_dist):
+    """The cutoff FitIndex.hits hands its kernel, without a device (sed_fit_cutoff_scaled): min(floor(max_dist * S),
+    65535) under the scale S of fit_plan's plan for the same arguments.  Raises SedError carrying the code (.code):
+    fit_plan's for these arguments, else SED_E_ARG for a NaN or negative max_dist."""
+    out = C.c_int64(0)
+    rc = load().sed_fit_cutoff_scaled(*_fit_pair_args(costs, options, len_p, len_t), float(max_dist), C.byref(out))
+    if rc != 0:
+        raise _fit_fail("sed_fit_cutoff_scaled", rc)
+    return int(out.value)
+
+
+def fit_lanes(costs, options, len_p, len_t):
+    """The lane records Context.fit would run, without a device (sed_fit_lanes): (lanes, params).  lanes = {field:
+    int64[nlanes]} over FIT_LANE_FIELDS, tw in 4-symbol words from the pair's own text start; params = {"row":
+    u32[8][2] update addend bytes, "ins", "del": the scaled insert and delete}.  Arguments and errors as fit_plan."""
+    nl = fit_plan(costs, options, len_p, len_t)["lanes"]
+    return _fit_lanes_call("sed_fit_lanes", _fit_pair_args(costs, options, len_p, len_t), nl, True)
 
 
 def fit_f64_plan(costs, options, len_p, len_t):
     """What Context.fit_f64 would decide, without a device (sed_fit_f64_plan): fit_plan's fields with scale = 0 (fp64)
     and "one_lane": 0, or why every text runs as one lane (1 insert = 0, 2 the window argument's conditions fail).
     Arguments and errors as fit_plan."""
-    out = np.zeros(len(FIT_F64_PLAN_FIELDS), np.float64)
-    rc = load().sed_fit_f64_plan(*_fit_pair_args(costs, options, len_p, len_t), out, len(out))
-    if rc != 0:
-        raise _fit_fail("sed_fit_f64_plan", rc)
-    return _fit_f64_plan_dict(out)
+    return _fit_plan_call("sed_fit_f64_plan", _fit_pair_args(costs, options, len_p, len_t), FIT_F64_PLAN_FIELDS)
 
 
 def fit_f64_lanes(costs, options, len_p, len_t):
     """The lane records Context.fit_f64 would run, without a device (sed_fit_f64_lanes): {field: int64[nlanes]} over
     FIT_LANE_FIELDS, as fit_lanes' first result."""
     nl = fit_f64_plan(costs, options, len_p, len_t)["lanes"]
-    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
-    rc = load().sed_fit_f64_lanes(*_fit_pair_args(costs, options, len_p, len_t), rec.ravel(), nl)
-    if rc != 0:
-        raise _fit_fail("sed_fit_f64_lanes", rc)
-    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
-    lanes["tw"] &= 0xFFFFFFFF
-    return lanes
+    return _fit_lanes_call("sed_fit_f64_lanes", _fit_pair_args(costs, options, len_p, len_t), nl, False)
 
 
 def fit_index_f64_plan(costs, options, len_p, len_t):
     """What FitIndex.search_f64 would decide, without a device (sed_fit_index_f64_plan): fit_f64_plan's fields for the
     queries x texts cross product."""
-    out = np.zeros(len(FIT_F64_PLAN_FIELDS), np.float64)
-    rc = load().sed_fit_index_f64_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out))
-    if rc != 0:
-        raise _fit_fail("sed_fit_index_f64_plan", rc)
-    return _fit_f64_plan_dict(out)
+    return _fit_plan_call("sed_fit_index_f64_plan", _fit_index_args(costs, options, len_p, len_t), FIT_F64_PLAN_FIELDS)
 
 
 def fit_index_f64_lanes(costs, options, len_p, len_t):
     """The lane records FitIndex.search_f64 / hits_f64 would run, without a device (sed_fit_index_f64_lanes), query-major,
     pair = query * len(len_t) + text."""
     nl = fit_index_f64_plan(costs, options, len_p, len_t)["lanes"]
-    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
-    rc = load().sed_fit_index_f64_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl)
-    if rc != 0:
-        raise _fit_fail("sed_fit_index_f64_lanes", rc)
-    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
-    lanes["tw"] &= 0xFFFFFFFF
-    return lanes
+    return _fit_lanes_call("sed_fit_index_f64_lanes", _fit_index_args(costs, options, len_p, len_t), nl, False)
 
 
 def fit_route(costs, options, len_p, len_t):
     """Which route serves the search fit_plan's arguments describe, without a device (sed_fit_route): (route, why).
     route = "int" (Context.fit serves it), "f64" (only Context.fit_f64 does; why = the integer route's refusal) or
     None (neither; why = both refusals).  Bad arguments raise SedError as fit_plan does."""
-    why = C.create_string_buffer(1024)
-    rc = load().sed_fit_route(*_fit_pair_args(costs, options, len_p, len_t), why, len(why))
-    text = why.value.decode()
-    if rc in FIT_ROUTES:
-        return FIT_ROUTES[rc], text
-    if rc == SED_E_RANGE:
-        return None, text
-    raise _fit_fail("sed_fit_route", rc)
-
-
-def _fit_index_args(costs, options, len_p, len_t):
-    K, sub, sub_int, ins, ins_int, dele, del_int = costs
-    opts = np.array([x for kv in options.items() for x in kv] or [0, 0], np.int32)
-    lp = np.ascontiguousarray(len_p if len(len_p) else [0], np.int32)
-    lt = np.ascontiguousarray(len_t if len(len_t) else [0], np.int32)
-    return (int(K), np.ascontiguousarray(sub, np.float64).ravel(), np.ascontiguousarray(sub_int, np.uint8).ravel(),
-            float(ins), int(ins_int), float(dele), int(del_int), opts, len(options), lp, len(len_p), lt, len(len_t))
+    return _route_call("sed_fit_route", _fit_pair_args(costs, options, len_p, len_t), FIT_ROUTES)
 
 
 def fit_index_plan(costs, options, len_p, len_t):
     """What FitIndex.search would decide for queries of lengths len_p against texts of lengths len_t, without a device
     (sed_fit_index_plan): fit_plan's fields for the queries x texts cross product.  Errors as fit_plan."""
-    out = np.zeros(len(FIT_PLAN_FIELDS), np.float64)
-    rc = load().sed_fit_index_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out))
-    if rc != 0:
-        err = SedError("sed_fit_index_plan failed (%d)" % rc)
-        err.code = rc
-        raise err
-    return {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
+    return _fit_plan_call("sed_fit_index_plan", _fit_index_args(costs, options, len_p, len_t))
 
 
 def fit_index_lanes(costs, options, len_p, len_t):
     """The lane records FitIndex.search would run, without a device (sed_fit_index_lanes): (lanes, params) as fit_lanes
     returns them, query-major, pair = query * len(len_t) + text."""
     nl = fit_index_plan(costs, options, len_p, len_t)["lanes"]
-    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
-    par = np.zeros(18, np.uint32)
-    rc = load().sed_fit_index_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl, par)
-    if rc != 0:
-        err = SedError("sed_fit_index_lanes failed (%d)" % rc)
-        err.code = rc
-        raise err
-    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
-    lanes["tw"] &= 0xFFFFFFFF
-    return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
+    return _fit_lanes_call("sed_fit_index_lanes", _fit_index_args(costs, options, len_p, len_t), nl, True)
 
 
 def fit_index_long_plan(costs, options, len_p, len_t):
     """What FitIndex.search_long would decide, without a device (sed_fit_index_long_plan): fit_index_plan's fields
     (lanes = the waves) and "rows": int32[queries], the pattern rows per lane each query runs with.  Errors as
     fit_plan."""
-    out = np.zeros(len(FIT_PLAN_FIELDS), np.float64)
-    rows = np.zeros(max(len(len_p), 1), np.int32)
-    rc = load().sed_fit_index_long_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out), rows)
-    if rc != 0:
-        err = SedError("sed_fit_index_long_plan failed (%d)" % rc)
-        err.code = rc
-        raise err
-    plan = {k: (float(v) if k in ("scale", "cells", "nominal_cells") else int(v)) for k, v in zip(FIT_PLAN_FIELDS, out)}
-    plan["rows"] = rows[:len(len_p)]
-    return plan
+    return _fit_plan_call("sed_fit_index_long_plan", _fit_index_args(costs, options, len_p, len_t), nrows=len(len_p))
 
 
 def fit_index_long_lanes(costs, options, len_p, len_t):
     """The wave records FitIndex.search_long would run, without a device (sed_fit_index_long_lanes): (lanes, params) as
     fit_index_lanes returns them, one record per (query, chunk record), query-major."""
     nl = fit_index_long_plan(costs, options, len_p, len_t)["lanes"]
-    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
-    par = np.zeros(18, np.uint32)
-    rc = load().sed_fit_index_long_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl, par)
-    if rc != 0:
-        err = SedError("sed_fit_index_long_lanes failed (%d)" % rc)
-        err.code = rc
-        raise err
-    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
-    lanes["tw"] &= 0xFFFFFFFF
-    return lanes, {"row": par[:16].reshape(8, 2).copy(), "ins": int(par[16]), "del": int(par[17])}
+    return _fit_lanes_call("sed_fit_index_long_lanes", _fit_index_args(costs, options, len_p, len_t), nl, True)
 
 
 def fit_index_long_f64_plan(costs, options, len_p, len_t):
     """What FitIndex.search_long_f64 would decide, without a device (sed_fit_index_long_f64_plan): fit_index_f64_plan's
     fields (lanes = the waves) and "rows": int32[queries], as fit_index_long_plan."""
-    out = np.zeros(len(FIT_F64_PLAN_FIELDS), np.float64)
-    rows = np.zeros(max(len(len_p), 1), np.int32)
-    rc = load().sed_fit_index_long_f64_plan(*_fit_index_args(costs, options, len_p, len_t), out, len(out), rows)
-    if rc != 0:
-        raise _fit_fail("sed_fit_index_long_f64_plan", rc)
-    plan = _fit_f64_plan_dict(out)
-    plan["rows"] = rows[:len(len_p)]
-    return plan
+    return _fit_plan_call("sed_fit_index_long_f64_plan", _fit_index_args(costs, options, len_p, len_t), FIT_F64_PLAN_FIELDS,
+                          nrows=len(len_p))
 
 
 def fit_index_long_f64_lanes(costs, options, len_p, len_t):
     """The wave records FitIndex.search_long_f64 / hits_long_f64 would run, without a device
     (sed_fit_index_long_f64_lanes): as fit_index_f64_lanes, one record per (query, chunk record), query-major."""
     nl = fit_index_long_f64_plan(costs, options, len_p, len_t)["lanes"]
-    rec = np.zeros((max(nl, 1), len(FIT_LANE_FIELDS)), np.int32)
-    rc = load().sed_fit_index_long_f64_lanes(*_fit_index_args(costs, options, len_p, len_t), rec.ravel(), nl)
-    if rc != 0:
-        raise _fit_fail("sed_fit_index_long_f64_lanes", rc)
-    lanes = {k: rec[:nl, i].astype(np.int64) for i, k in enumerate(FIT_LANE_FIELDS)}
-    lanes["tw"] &= 0xFFFFFFFF
-    return lanes
+    return _fit_lanes_call("sed_fit_index_long_f64_lanes", _fit_index_args(costs, options, len_p, len_t), nl, False)
 
 
 def fit_long_route(costs, options, len_p, len_t):
     """fit_route for the long calls, over fit_index_long_plan's arguments (sed_fit_long_route): (route, why).  route =
     "int" whenever FitIndex.search_long serves the search, "f64" when only search_long_f64 does (why = the integer
     route's refusal), None when neither does (why = both refusals)."""
-    why = C.create_string_buffer(1024)
-    rc = load().sed_fit_long_route(*_fit_index_args(costs, options, len_p, len_t), why, len(why))
-    text = why.value.decode()
-    if rc in FIT_ROUTES:
-        return FIT_ROUTES[rc], text
-    if rc == SED_E_RANGE:
-        return None, text
-    raise _fit_fail("sed_fit_long_route", rc)
+    return _route_call("sed_fit_long_route", _fit_index_args(costs, options, len_p, len_t), FIT_ROUTES)
 
 
 def band_bounds(n, m, ins, dele, ub):

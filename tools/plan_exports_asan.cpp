@@ -1,0 +1,112 @@
+// plan_exports_asan.cpp — every device-free fit and join export of include/sed.h called once on a case it serves and once
+// on a case it refuses (sizes from tests/plan_snapshot_cases.py), for a run of the planners' host code under the address
+// and undefined-behaviour sanitizers.  No device, no Python:
+//
+//   cd rna-sequence-diff-patch_amd/csrc && g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I. ../../tools/plan_exports_asan.cpp sed_fit_plan.cpp sed_join_plan.cpp \
+//       sed_plan.cpp -o /tmp/plan_exports_asan && /tmp/plan_exports_asan
+//
+// Exit status 0 and "ok" = every call answered the code expected of it and the sanitizers reported nothing.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "../include/sed.h"
+
+static int failures = 0;
+static void expect(const char *what, int got, int want) {
+    if (got != want) {
+        std::printf("%s: %d, expected %d\n", what, got, want);
+        ++failures;
+    }
+}
+
+struct Table {
+    int K;
+    std::vector<double> sub;
+    std::vector<uint8_t> sub_int;
+    double ins, del;
+    Table(int K_, double ins_, double del_) : K(K_), sub((size_t)K_ * K_, 1.0), sub_int((size_t)K_ * K_, 0), ins(ins_), del(del_) {
+        for (int a = 0; a < K; ++a) sub[(size_t)a * K + a] = 0.0, sub_int[(size_t)a * K + a] = 1;
+    }
+};
+// the nine leading arguments of every export
+#define COSTS(t, opts, nopts) (t).K, (t).sub.data(), (t).sub_int.data(), (t).ins, 0, (t).del, 0, opts, nopts
+
+int main() {
+    const Table unit(4, 1.0, 1.0), k9(9, 1.0, 1.0), k17(17, 1.0, 1.0);
+    const int32_t chunk16[] = {SED_OPT_FIT_CHUNK, 16}, rows2[] = {SED_OPT_FIT_ROWS, 2};
+    const int32_t lp[] = {7, 32, 1, 12}, lt[] = {0, 5, 70, 150};          // pairs, and 4 queries x 4 texts
+    const int32_t lp_long[] = {33, 129, 2048}, lt_long[] = {0, 150, 300};
+    const int32_t lp_bad[] = {5, 0}, lt_neg[] = {5, -1};
+    double out[8];
+    int32_t rows[4];
+    uint32_t params[18];
+    std::vector<int32_t> lanes((size_t)8 * 4096);
+    const int64_t room = (int64_t)lanes.size() / 8;
+    char why[256];
+    int64_t cut = 0;
+
+    // ---- listed pairs ----
+    expect("sed_fit_plan", sed_fit_plan(COSTS(unit, chunk16, 1), lp, lt, 4, out, 6), SED_OK);
+    expect("sed_fit_plan K=9", sed_fit_plan(COSTS(k9, nullptr, 0), lp_bad, lt, 2, out, 6), SED_E_RANGE);
+    expect("sed_fit_lanes", sed_fit_lanes(COSTS(unit, chunk16, 1), lp, lt, 4, lanes.data(), room, params), SED_OK);
+    expect("sed_fit_lanes text < 0", sed_fit_lanes(COSTS(unit, nullptr, 0), lp, lt_neg, 2, lanes.data(), room, params), SED_E_ARG);
+    expect("sed_fit_f64_plan", sed_fit_f64_plan(COSTS(k9, chunk16, 1), lp, lt, 4, out, 7), SED_OK);
+    expect("sed_fit_f64_plan K=17", sed_fit_f64_plan(COSTS(k17, nullptr, 0), lp, lt, 4, out, 7), SED_E_RANGE);
+    expect("sed_fit_f64_lanes", sed_fit_f64_lanes(COSTS(k9, chunk16, 1), lp, lt, 4, lanes.data(), room), SED_OK);
+    expect("sed_fit_f64_lanes P=0", sed_fit_f64_lanes(COSTS(k9, nullptr, 0), lp_bad, lt, 2, lanes.data(), room), SED_E_RANGE);
+    expect("sed_fit_cutoff_scaled", sed_fit_cutoff_scaled(COSTS(unit, nullptr, 0), lp, lt, 4, 1.5, &cut), SED_OK);
+    expect("sed_fit_cutoff_scaled NaN", sed_fit_cutoff_scaled(COSTS(unit, nullptr, 0), lp, lt, 4, std::nan(""), &cut), SED_E_ARG);
+    expect("sed_fit_route int", sed_fit_route(COSTS(unit, nullptr, 0), lp, lt, 4, why, sizeof why), SED_FIT_ROUTE_INT);
+    expect("sed_fit_route f64", sed_fit_route(COSTS(k9, nullptr, 0), lp, lt, 4, why, sizeof why), SED_FIT_ROUTE_F64);
+    expect("sed_fit_route neither", sed_fit_route(COSTS(k17, nullptr, 0), lp_bad, lt, 2, why, 8), SED_E_RANGE);  // (why cut short)
+
+    // ---- the index forms: the lane layouts, then the wave layouts ----
+    expect("sed_fit_index_plan", sed_fit_index_plan(COSTS(unit, chunk16, 1), lp, 4, lt, 4, out, 6), SED_OK);
+    expect("sed_fit_index_plan P=33", sed_fit_index_plan(COSTS(unit, nullptr, 0), lp_long, 3, lt, 4, out, 6), SED_E_RANGE);
+    expect("sed_fit_index_lanes", sed_fit_index_lanes(COSTS(unit, chunk16, 1), lp, 4, lt, 4, lanes.data(), room, params), SED_OK);
+    expect("sed_fit_index_lanes room", sed_fit_index_lanes(COSTS(unit, chunk16, 1), lp, 4, lt, 4, lanes.data(), 3, params), SED_E_ARG);
+    expect("sed_fit_index_f64_plan", sed_fit_index_f64_plan(COSTS(k9, chunk16, 1), lp, 4, lt, 4, out, 7), SED_OK);
+    expect("sed_fit_index_f64_plan text < 0", sed_fit_index_f64_plan(COSTS(k9, nullptr, 0), lp, 2, lt_neg, 2, out, 7), SED_E_ARG);
+    expect("sed_fit_index_f64_lanes", sed_fit_index_f64_lanes(COSTS(k9, chunk16, 1), lp, 4, lt, 4, lanes.data(), room), SED_OK);
+    expect("sed_fit_index_f64_lanes K=17", sed_fit_index_f64_lanes(COSTS(k17, nullptr, 0), lp, 4, lt, 4, lanes.data(), room), SED_E_RANGE);
+    expect("sed_fit_index_long_plan", sed_fit_index_long_plan(COSTS(unit, chunk16, 1), lp_long, 3, lt_long, 3, out, 6, rows), SED_OK);
+    expect("sed_fit_index_long_plan rows", sed_fit_index_long_plan(COSTS(unit, rows2, 1), lp_long, 3, lt_long, 3, out, 6, rows), SED_E_RANGE);
+    expect("sed_fit_index_long_lanes",
+           sed_fit_index_long_lanes(COSTS(unit, chunk16, 1), lp_long, 3, lt_long, 3, lanes.data(), room, params), SED_OK);
+    expect("sed_fit_index_long_lanes K=9",
+           sed_fit_index_long_lanes(COSTS(k9, nullptr, 0), lp_long, 3, lt_long, 3, lanes.data(), room, params), SED_E_RANGE);
+    expect("sed_fit_index_long_f64_plan", sed_fit_index_long_f64_plan(COSTS(k9, chunk16, 1), lp_long, 3, lt_long, 3, out, 7, rows), SED_OK);
+    expect("sed_fit_index_long_f64_plan P=0", sed_fit_index_long_f64_plan(COSTS(k9, nullptr, 0), lp_bad, 2, lt_long, 3, out, 7, rows),
+           SED_E_RANGE);
+    expect("sed_fit_index_long_f64_lanes",
+           sed_fit_index_long_f64_lanes(COSTS(k9, chunk16, 1), lp_long, 3, lt_long, 3, lanes.data(), room), SED_OK);
+    expect("sed_fit_index_long_f64_lanes no texts", sed_fit_index_long_f64_lanes(COSTS(k9, nullptr, 0), lp_long, 3, nullptr, 0, nullptr, 0),
+           SED_OK);
+    expect("sed_fit_index_long_f64_lanes K=17",
+           sed_fit_index_long_f64_lanes(COSTS(k17, nullptr, 0), lp_long, 3, lt_long, 3, lanes.data(), room), SED_E_RANGE);
+    expect("sed_fit_long_route int", sed_fit_long_route(COSTS(unit, nullptr, 0), lp_long, 3, lt_long, 3, why, sizeof why), SED_FIT_ROUTE_INT);
+    expect("sed_fit_long_route f64", sed_fit_long_route(COSTS(k9, nullptr, 0), lp_long, 3, lt_long, 3, why, sizeof why), SED_FIT_ROUTE_F64);
+    expect("sed_fit_long_route neither", sed_fit_long_route(COSTS(k17, nullptr, 0), lp_long, 3, lt_long, 3, why, sizeof why), SED_E_RANGE);
+    expect("sed_fit_long_route text < 0", sed_fit_long_route(COSTS(unit, nullptr, 0), lp, 2, lt_neg, 2, why, sizeof why), SED_E_ARG);
+
+    // ---- the join ----
+    const int32_t jr[] = {0, 1, 9, 20, 32, 20, 31}, jc[] = {0, 1, 9, 20, 32, 20, 31, 5, 5, 18}, jbad[] = {3, 65};
+    const int32_t join_rows3[] = {SED_OPT_JOIN_ROWS, 3};
+    uint64_t keep[33];
+    expect("sed_join_plan", sed_join_plan(COSTS(unit, join_rows3, 1), jc, 10, jc, 10, 1, 0xF, 0xF, 2.0, out, 6), SED_OK);
+    expect("sed_join_plan length", sed_join_plan(COSTS(unit, nullptr, 0), jbad, 2, jc, 10, 0, 0xF, 0xF, 2.0, out, 6), SED_E_ARG);
+    expect("sed_join_plan K=9", sed_join_plan(COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 2.0, out, 6), SED_E_RANGE);
+    expect("sed_join_f64_plan", sed_join_f64_plan(COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0x1FF, 0xF, 1.5, out, 6), SED_OK);
+    expect("sed_join_f64_plan code", sed_join_f64_plan(COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0x200, 1.5, out, 6), SED_E_ARG);
+    expect("sed_join_f64_keep", sed_join_f64_keep(0.1, 0.2, 0.3, keep), SED_OK);
+    expect("sed_join_f64_keep NaN", sed_join_f64_keep(1.0, 1.0, std::nan(""), keep), SED_E_ARG);
+    expect("sed_join_route int", sed_join_route(COSTS(unit, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, INFINITY, why, sizeof why), SED_JOIN_ROUTE_INT);
+    expect("sed_join_route f64", sed_join_route(COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 0.0, why, sizeof why), SED_JOIN_ROUTE_F64);
+    expect("sed_join_route neither", sed_join_route(COSTS(k17, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 2.0, why, sizeof why), SED_E_RANGE);
+
+    std::printf(failures ? "%d calls answered another code\n" : "ok\n", failures);
+    return failures != 0;
+}
