@@ -121,7 +121,7 @@ enum {
                                    calls) only: pattern rows per lane, 0 auto (each query the smallest R of 2, 4, 8, 16,
                                    32 with 64 R >= P), else that R for every query (tests and A/Bs; a query of P > 64 R:
                                    SED_E_RANGE).  sed_plan_routes refuses it */
-#define SED_OPT_JOIN_DP 20      /* the similarity join (sed_join_self, sed_join_search, sed_join_plan) only: 0 auto (the
+#define SED_OPT_JOIN_DP 20      /* the similarity join (sed_join_self, sed_join_search, sed_join_plan, sed_join_long_*) only: 0 auto (the
                                    bit-parallel kernel when the codes present have unit costs), 2 the scaled DP kernel always
                                    (tests and A/Bs).  sed_plan_routes refuses it */
 #define SED_OPT_JOIN_ROWS 21    /* the similarity join only, for tests: the rows one launch takes, 0 auto (the grid's limit,
@@ -619,8 +619,9 @@ int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double 
  * scaled DP; SED_OPT_JOIN_DP forces the DP.  A pair whose length bound insert * (m - n)+ + delete * (n - m)+ exceeds
  * max_dist is never computed, and a wave whose 64 columns all fail it skips the row.  More rows than one launch takes
  * (65535 groups of sed_join_rows_per_group rows; SED_OPT_JOIN_ROWS) run as further launches of the same call.
- * Not served: tables the conditions refuse (IUPAC: the _f64 calls below serve them), sequences over 32 symbols, edit
- * scripts of the hits, k-nearest lists, the i < j half alone for symmetric tables, a per-tile mix of the two variants. */
+ * Not served: tables the conditions refuse (IUPAC: the _f64 calls below serve them), sequences over 32 symbols (the
+ * sed_join_long_ calls below serve up to 128), edit scripts of the hits, k-nearest lists, the i < j half alone for
+ * symmetric tables, a per-tile mix of the two variants. */
 typedef struct sed_join_index sed_join_index;
 typedef struct { int32_t row, col; double dist; } sed_join_hit;
 sed_join_index *sed_join_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
@@ -688,6 +689,54 @@ int sed_join_route(int K, const double *sub, const uint8_t *sub_int, double ins,
                    double del, int del_is_int, const int32_t *options, int noptions,
                    const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
                    uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, char *why, int why_len);
+
+/* The similarity join over sequences of 0..128 symbols (tRNA, pre-miRNA hairpins, snoRNA, 5S rRNA): sed_join_self /
+ * sed_join_search with a longer record, through the integer route.  It batches the same reference lines:
+ * wf_score(query, doc) over a whole collection, IRMethods.py:435-440 inside search_collection's loop,
+ * IRMethods.py:443-477, each a full wagnerFisher(str1, str2), StringEditDistance.py:133-224.
+ * A sed_join_long_index is a type of its own, because its device records differ (128 byte codes a sequence); it is
+ * created, used and destroyed as a sed_join_index is, holds nseqs sequences of 0..sed_join_long_max_len() = 128 symbols
+ * each (129, a negative length or offset, NULL: SED_E_ARG, the text names the number of symbols), and belongs to its
+ * context.  Unchanged from sed_join_self / sed_join_search: rows are str1 and columns str2; the hit record, dist = D / S
+ * and the rule D <= floor(max_dist * S); the (row, col) sort; the cap protocol (*found always set, SED_E_RANGE naming
+ * both numbers, the index stays usable, the count query with cap = 0 and out = NULL); the state errors; +inf admits
+ * every pair (no scaled distance of two sequences of <= 128 symbols exceeds 128 * 255 < 65535); NaN or a negative
+ * max_dist: SED_E_ARG; the cost models served and their refusals, condition for condition (for such tables D / S is the
+ * reference's value bit for bit); a row or column code >= K: SED_E_ARG; bit-parallel under the same conditions, else
+ * the scaled DP, and SED_OPT_JOIN_DP forces the DP; the length skip by wave; SED_OPT_JOIN_ROWS and the limit of 65535
+ * groups of sed_join_rows_per_group rows a launch.
+ * A wave runs a row over the columns 1 .. 32 * ceil(longest / 32) of its 64 columns (stored sorted by length), so a
+ * collection of 40-symbol sequences pays for 64 cells a row, not 128; sequences of at most 32 symbols are served, and
+ * faster by sed_join_index.  sed_join_long_plan's out[6] counts the cells executed.
+ * Not served: tables the conditions refuse (there is no fp64 route for this index yet), sequences over 128 symbols, edit
+ * scripts of the hits, k-nearest lists, the i < j half alone for symmetric tables, a per-tile mix of the two variants. */
+typedef struct sed_join_long_index sed_join_long_index;
+sed_join_long_index *sed_join_long_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
+                                                int32_t nseqs);
+void sed_join_long_index_destroy(sed_join_long_index *ix);
+int32_t sed_join_long_index_seqs(const sed_join_long_index *ix);
+int sed_join_long_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
+                       int64_t cap, int64_t *found);
+int sed_join_long_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                         int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+/* sed_join_last_time and sed_join_pairs_run for this index type. */
+int sed_join_long_last_time(const sed_join_long_index *ix, float *kernel_ms);
+int sed_join_long_pairs_run(const sed_join_long_index *ix, int64_t *pairs);
+/* The longest sequence a sed_join_long_index holds: 128. */
+int32_t sed_join_long_max_len(void);
+/* What the long calls would decide, without a device: sed_join_plan's arguments, order of refusals and out[] slots 0..5,
+ * with lengths 0..128 accepted (129 or a negative length: SED_E_ARG); for lengths all <= 32 slots 0..5 are
+ * sed_join_plan's.  out[6] = the cells the waves execute: for every wave (64 columns in sorted order; the last wave's
+ * spare lanes run too) and every row it runs (one of its columns passes the length bound; a self join's own pairs are
+ * not taken out here), 64 * n * 32 * ceil(the wave's longest column / 32).  Beside out[5] it shows what the padding of a
+ * collection costs: the bit-parallel variant skips words by the same rule. */
+int sed_join_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                       double del, int del_is_int, const int32_t *options, int noptions,
+                       const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                       uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
+/* The text of this thread's last sed_join_long_plan refusal (the one the long calls leave in sed_last_error for the same
+ * inputs: it names the failed condition, or the row or column and its number of symbols); "" after a plan that passed. */
+const char *sed_join_long_plan_error(void);
 
 /* Full DP matrix of one pair (the dp object the GUI renders, StringEditDistance.py:143-224):
  * D[i*(m+1)+j] = dp[i][j].value, M[...] = optimal incoming edges (1 insert, 2 delete,

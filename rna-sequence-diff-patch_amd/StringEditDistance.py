@@ -904,15 +904,16 @@ def fit_index(texts, userCosts=False, alphabet=None, engine=None, f64=False):
 
 
 JOIN_MAX_LEN = 32  # the join's longest sequence (include/sed.h: sed_join_index_create)
+JOIN_LONG_MAX_LEN = 128  # the long join's (include/sed.h: sed_join_long_index_create)
 JOIN_F64_SYMBOLS = 16  # the fp64 route's table bound (include/sed.h: sed_join_self_f64)
 
 
 class _EngineJoin:
     """The device half of a JoinIndex: the sequences' codes resident on the process's engine (sedgpu.JoinIndex)."""
 
-    def __init__(self, codes, off, lens):
+    def __init__(self, codes, off, lens, long_seqs=False):
         self.ctx = sedgpu.context()
-        self.ix = self.ctx.join_index(codes, off, lens)
+        self.ix = (self.ctx.join_long_index if long_seqs else self.ctx.join_index)(codes, off, lens)
 
     def self_join(self, plan, max_dist, rows):
         self.ctx.set_costs(plan)
@@ -943,18 +944,24 @@ class JoinIndex:
     cost tables over at most 8 symbols and raises SedError otherwise.  f64=True builds the index for the fp64 route
     instead: the bound is 16 symbols (the refusal names the bound in force; the default's text is unchanged), and
     self_join_f64 / search_f64 serve any table of costs >= 0 (self_join / search still run the integer kernels and
-    refuse what those refuse).  The cost table is read at every call, and the
-    KeyErrors are the reference's for the first offending (row, column) in row-major order."""
+    refuse what those refuse).  long_seqs=True builds the index for sequences and queries of 0..128 symbols
+    (include/sed.h: sed_join_long_self, sed_join_long_search): the integer route only, so with f64=True it is a
+    ValueError; the engine is then called with long_seqs=True as a further, keyword argument.  The cost table is read at
+    every call, and the KeyErrors are the reference's for the first offending (row, column) in row-major order."""
 
-    def __init__(self, seqs, userCosts=False, alphabet=None, engine=None, f64=False):
+    def __init__(self, seqs, userCosts=False, alphabet=None, engine=None, f64=False, long_seqs=False):
         self.seqs = list(seqs)
         self.userCosts = userCosts
         self.f64 = bool(f64)
+        self.long_seqs = bool(long_seqs)
+        if self.f64 and self.long_seqs:
+            raise ValueError("the long join has no fp64 route yet: long_seqs=True takes f64=False")
+        self.max_len = JOIN_LONG_MAX_LEN if self.long_seqs else JOIN_MAX_LEN
         self.max_symbols = JOIN_F64_SYMBOLS if self.f64 else 8
         for i, s in enumerate(self.seqs):
-            if len(s) > JOIN_MAX_LEN:
+            if len(s) > self.max_len:
                 raise sedgpu.SedError("join index: sequence %d has %d symbols (the join serves at most %d)"
-                                      % (i, len(s), JOIN_MAX_LEN))
+                                      % (i, len(s), self.max_len))
         used = sedcost.distinct_many(self.seqs) if sedcost._all_str(self.seqs) else \
             list(dict.fromkeys(c for t in self.seqs for c in t))
         self._used = used
@@ -968,7 +975,8 @@ class JoinIndex:
         off = np.zeros(len(lens), np.int64)
         if len(lens):
             off[1:] = np.cumsum(lens[:-1], dtype=np.int64)
-        self._dev = (engine or _EngineJoin)(codes, off, lens)
+        self._dev = (engine or _EngineJoin)(codes, off, lens, long_seqs=True) if self.long_seqs else \
+            (engine or _EngineJoin)(codes, off, lens)
 
     def plan(self, rows):
         """The reference's KeyError for the first offending (row, sequence), if any, then the call's CostPlan: the
@@ -1009,8 +1017,8 @@ class JoinIndex:
     def search(self, queries, max_dist, _dev="search"):
         queries = list(queries)
         for q, s in enumerate(queries):
-            if len(s) > JOIN_MAX_LEN:
-                raise sedgpu.SedError("join: query %d has %d symbols (the join serves at most %d)" % (q, len(s), JOIN_MAX_LEN))
+            if len(s) > self.max_len:
+                raise sedgpu.SedError("join: query %d has %d symbols (the join serves at most %d)" % (q, len(s), self.max_len))
         plan = self.plan(queries)
         if not queries or not self.seqs:
             return []
@@ -1023,12 +1031,13 @@ class JoinIndex:
         self._dev.close()
 
 
-def join_index(seqs, userCosts=False, alphabet=None, engine=None, f64=False):
-    """A JoinIndex over seqs (0..32 symbols each): every pair within a distance, for clustering, de-duplication,
-    neighbour graphs, or many queries against one collection.  engine(codes, off, lens) -> an object with
-    self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), their self_join_f64 / search_f64, all returning
-    sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU tests)."""
-    return JoinIndex(seqs, userCosts, alphabet, engine, f64)
+def join_index(seqs, userCosts=False, alphabet=None, engine=None, f64=False, long_seqs=False):
+    """A JoinIndex over seqs (0..32 symbols each; long_seqs=True: 0..128, the integer route only): every pair within a
+    distance, for clustering, de-duplication, neighbour graphs, or many queries against one collection.  engine(codes,
+    off, lens) -> an object with self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), their
+    self_join_f64 / search_f64, all returning sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU
+    tests); under long_seqs=True it is called with that keyword."""
+    return JoinIndex(seqs, userCosts, alphabet, engine, f64, long_seqs)
 
 
 def join_route(rows, seqs, max_dist, userCosts=False):

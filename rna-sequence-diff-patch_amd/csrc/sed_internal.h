@@ -366,6 +366,16 @@ struct sed_join_args {
     unsigned long long cap;
 };
 hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar);
+// The integer join over sequences of 0..SED_JOIN_LONG_MAXLEN symbols (sed_join_long.hip; include/sed.h: sed_join_long_self,
+// sed_join_long_search): sed_join_args, the grid, the counters, the self rule and the hit records of the kernel above.
+// What differs is the record: SED_JOIN_LONG_MAXLEN byte codes, zero padded, 32 words.  The row loads are wave-uniform and
+// read up to two words past a record (word 33 of a row of 128 symbols), so both record buffers end with 16 spare bytes.
+// The scaled DP keeps V[0 .. 128] and the column's 32 code words in registers and runs a row in blocks of
+// SED_JOIN_LONG_BLOCK columns, the bit-parallel variant keeps four 32-bit words of state; a block or word above the
+// wave's longest column is not run.
+#define SED_JOIN_LONG_MAXLEN 128
+#define SED_JOIN_LONG_BLOCK 32
+hipError_t sed_launch_join_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar);
 // The fp64 route of the join (sed_join_f64.hip; include/sed.h: sed_join_self_f64, sed_join_search_f64): the same records,
 // grid, counters and self rule.
 //   sub      = SED_JOIN_F64_MAXK x SED_JOIN_F64_MAXK doubles on the device, row a = row symbol a, zeros past K;

@@ -8,32 +8,16 @@
 // for all 64 lanes.  The cells are sed_lane_dp.h's, shared with the lane kernels, so the scaled distance D * S is the
 // lane kernels' number.
 //
-// Length skip: insert (m - n)+ + delete (n - m)+ bounds the distance from below.  The columns are sorted by length, so
-// the 64 columns of a wave have nearly one length, and a wave none of whose lanes can be within the cutoff for the
-// current row leaves that row out.  count[1] counts the pairs whose bound passed: the pairs of the waves that ran.
+// The walk over the rows - the self rule, the length skip by ballot, the two counters - and the append are
+// sed_join_dev.h's, shared with the kernel for longer sequences (sed_join_long.hip).  The columns are sorted by length,
+// so the 64 columns of a wave have nearly one length, and the skip leaves out whole waves.
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
 #include "sed_lane_dp.h"
+#include "sed_join_dev.h"
 
 namespace {
-
-// One hit per lane, decided for the whole wave (sed_fit_dp.h: sed_fit_append): the first hitting lane takes popcount
-// slots with one atomic add, every hitting lane stores at the first slot + its rank among them; slots >= cap only count.
-__device__ __forceinline__ void join_append(const sed_join_args &a, bool hit, int32_t row, int32_t col, uint32_t D) {
-    const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
-    if (b == 0) return;
-    if (hit) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        unsigned long long base = 0;
-        if (rank == 0) base = atomicAdd(a.count, (unsigned long long)__popcll(b));
-        // (the first active lane here is the hitting lane of rank 0)
-        const unsigned long long slot =
-            (((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-             __builtin_amdgcn_readfirstlane((uint32_t)base)) + rank;
-        if (slot < a.cap) a.hits[slot] = make_uint4((uint32_t)row, (uint32_t)col, D, 0u);
-    }
-}
 
 template <bool BITPAR>
 __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t *__restrict__ rows,
@@ -65,19 +49,9 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
 #pragma unroll
         for (int j = 0; j < MM; ++j) sel[j] = sed_scaled_sel(bw[j >> 2] >> (8 * (j & 3)));
     }
-    const int rbeg = a.row0 + (int)blockIdx.y * SED_JOIN_G;
-    const int rend = min(rbeg + SED_JOIN_G, a.row0 + a.nrows);
-    uint32_t ran = 0;
-    for (int r = rbeg; r < rend; ++r) {
-        const int n = row_len[r];  // (uniform: a scalar load)
-        const uint32_t lb = m > n ? (uint32_t)(m - n) * a.ins : (uint32_t)(n - m) * a.del;
-        const bool go = valid && !(a.self && orig == r) && lb <= (uint32_t)a.cut;
-        const unsigned long long gb = __builtin_amdgcn_ballot_w64(go);
-        if (gb == 0) continue;  // no column of this wave can be within the cutoff of row r
-        ran += (uint32_t)__popcll(gb);
+    sed_join_rows(row_len, a, valid, m, orig, [&](int r, int n) -> uint32_t {
         const uint32_t *pr = rows + 8 * (size_t)r;
         uint32_t w0 = pr[0], w1 = pr[1];  // rows 0..3 and 4..7 (the buffer ends with spare words)
-        uint32_t D;
         if constexpr (BITPAR) {
             uint32_t Pv = ~0u, Mv = 0u;
             for (int i = 0; i < n; ++i) {
@@ -88,7 +62,7 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
                 }
                 sed_bitpar_step(Pv, Mv, sed_bitpar_tq(E0, E1, __builtin_amdgcn_ubfe(a.umap, 2 * c, 2)));
             }
-            D = sed_bitpar_sink(n, m, Pv, Mv) << a.shift;
+            return sed_bitpar_sink(n, m, Pv, Mv) << a.shift;
         } else {
             uint32_t V[MM + 1];
 #pragma unroll
@@ -107,11 +81,9 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
             uint32_t cap = V[0];  // m = 0: the border column
 #pragma unroll
             for (int j = 1; j <= MM; ++j) cap = (j == m) ? V[j] : cap;
-            D = sed_scaled_decode(cap, n, m, a.ins, a.del);
+            return sed_scaled_decode(cap, n, m, a.ins, a.del);
         }
-        join_append(a, go && D <= (uint32_t)a.cut, r, orig, D);
-    }
-    if (ran != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.count + 1, (unsigned long long)ran);
+    });
 }
 
 }  // namespace

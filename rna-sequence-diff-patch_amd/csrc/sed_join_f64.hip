@@ -31,7 +31,7 @@ namespace {
 
 constexpr int JF_K = SED_JOIN_F64_MAXK;
 
-// sed_join.hip's join_append with D as 64 bits: the first hitting lane takes popcount slots with one atomic add, every
+// sed_join_dev.h's sed_join_append with D as 64 bits: the first hitting lane takes popcount slots with one atomic add, every
 // hitting lane stores at the first slot + its rank among them; slots >= cap only count.
 __device__ __forceinline__ void join_f64_append(const sed_join_f64_args &a, bool hit, int32_t row, int32_t col, double D) {
     const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);

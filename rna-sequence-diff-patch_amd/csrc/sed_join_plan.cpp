@@ -1,13 +1,14 @@
 // sed_join_plan.cpp — the join planner (sed_join_plan.h): scale and cost rows, the kernel variant, the cutoff on the
 // integer scale, the launches and the pair counts of a similarity join.  No HIP call.  Also the device-free entry points
-// sed_join_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route of include/sed.h.
+// sed_join_plan, sed_join_long_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route of include/sed.h.
 #include "sed_join_plan.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <vector>
 
-int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *err) {
+int sed_join_costs_rule(const sed_costs &c, int maxlen, sed_join_plan_t *plan, std::string *err) {
     if (c.K > 8) return sed_plan_fail(err, SED_E_RANGE, "join: %d symbols (the scaled cost rows hold at most 8)", c.K);
     auto finite = [](double v) { return std::isfinite(v) && v >= 0; };
     bool ok = finite(c.ins) && finite(c.del);
@@ -33,6 +34,10 @@ int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *
     if ((c.ins + c.del) * S > 255)
         return sed_plan_fail(err, SED_E_RANGE, "join: (insert + delete) * S = %g exceeds 255 (the update addend's byte)",
                              (c.ins + c.del) * S);
+    // the keys' room (sed_join_plan.h): a key's high half-word sinks by at most maxlen (insert + delete) S
+    if ((c.ins + c.del) * S * maxlen > SED_JOIN_CUT_ALL)
+        return sed_plan_fail(err, SED_E_RANGE, "join: (insert + delete) * S * %d = %g exceeds %d (the key's half-word)", maxlen,
+                             (c.ins + c.del) * S * maxlen, SED_JOIN_CUT_ALL);
     plan->scale_log2 = k;
     sed_scaled_params &sp = plan->sp;
     sp = sed_scaled_params{};
@@ -66,10 +71,10 @@ static bool join_unit_costs(const sed_costs &c, uint32_t row_codes, uint32_t col
 
 // What the plans of both routes share: the checks in their one order - the arguments, max_dist, the route's costs rule
 // (rule(): it also derives whatever keep reads), the code set, the rows, the columns - then the launches and the counts
-// under keep(n, m) = a row of n and a column of m symbols are computed.
+// under keep(n, m) = a row of n and a column of m symbols are computed.  maxlen = the route's longest sequence.
 template <class Rule, class Keep>
 static int join_plan_shared(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
-                            int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
+                            int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist, int maxlen,
                             sed_join_counts *plan, std::string *err, Rule rule, Keep keep) {
     if (nrows < 0 || ncols < 0 || (nrows && !len_rows) || (ncols && !len_cols) || (self && nrows > ncols))
         return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
@@ -81,17 +86,17 @@ static int join_plan_shared(const sed_costs &c, const sed_opts &o, const int32_t
         const bool in_cols = (col_codes >> c.K) != 0;
         return sed_plan_fail(err, SED_E_ARG, "join: a %s code is outside the alphabet (K=%d)", in_cols ? "column" : "row", c.K);
     }
-    double hr[SED_JOIN_MAXLEN + 1] = {}, hc[SED_JOIN_MAXLEN + 1] = {};
+    double hr[SED_JOIN_LONG_MAXLEN + 1] = {}, hc[SED_JOIN_LONG_MAXLEN + 1] = {};
     double own_cells = 0;  // sum n n over the rows: the (i, i) pairs a self join leaves out
     for (int i = 0; i < nrows; ++i) {
-        if (len_rows[i] < 0 || len_rows[i] > SED_JOIN_MAXLEN)
-            return sed_plan_fail(err, SED_E_ARG, "join: row %d has %d symbols (0..%d)", i, len_rows[i], SED_JOIN_MAXLEN);
+        if (len_rows[i] < 0 || len_rows[i] > maxlen)
+            return sed_plan_fail(err, SED_E_ARG, "join: row %d has %d symbols (0..%d)", i, len_rows[i], maxlen);
         hr[len_rows[i]] += 1;
         own_cells += (double)len_rows[i] * len_rows[i];
     }
     for (int j = 0; j < ncols; ++j) {
-        if (len_cols[j] < 0 || len_cols[j] > SED_JOIN_MAXLEN)
-            return sed_plan_fail(err, SED_E_ARG, "join: column %d has %d symbols (0..%d)", j, len_cols[j], SED_JOIN_MAXLEN);
+        if (len_cols[j] < 0 || len_cols[j] > maxlen)
+            return sed_plan_fail(err, SED_E_ARG, "join: column %d has %d symbols (0..%d)", j, len_cols[j], maxlen);
         hc[len_cols[j]] += 1;
     }
     plan->launch_rows = o.join_rows > 0 ? o.join_rows : (int64_t)SED_JOIN_MAX_GROUPS * SED_JOIN_G;
@@ -102,8 +107,8 @@ static int join_plan_shared(const sed_costs &c, const sed_opts &o, const int32_t
     plan->waves = ncols > 0 ? blocks * groups * (SED_JOIN_BLOCK / 64) : 0;
     plan->scope = (double)nrows * ncols - (self ? nrows : 0);
     plan->run = plan->cells = 0;
-    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n)
-        for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
+    for (int n = 0; n <= maxlen; ++n)
+        for (int m = 0; m <= maxlen; ++m) {
             if (!keep(n, m)) continue;
             plan->run += hr[n] * hc[m];
             plan->cells += hr[n] * hc[m] * n * m;
@@ -112,14 +117,35 @@ static int join_plan_shared(const sed_costs &c, const sed_opts &o, const int32_t
         plan->run -= nrows;
         plan->cells -= own_cells;
     }
+    // What the waves execute: the columns sorted by length, 64 to a wave (the last wave's spare lanes take the longest
+    // column); a wave runs a row when keep() holds for one of its columns, over every block of `block` columns up to
+    // its longest.  (block = 0: the route does not count them.)
+    plan->lane_cells = 0;
+    if (plan->block > 0 && ncols > 0) {
+        std::vector<int32_t> sorted(len_cols, len_cols + ncols);
+        std::sort(sorted.begin(), sorted.end());
+        for (int32_t w = 0; w < ncols; w += 64) {
+            const int32_t end = std::min(w + 64, ncols);
+            const int longest = end - w < 64 ? sorted[ncols - 1] : sorted[end - 1];
+            const double width = (double)((longest + plan->block - 1) / plan->block) * plan->block;
+            for (int n = 0; n <= maxlen; ++n) {
+                if (hr[n] == 0) continue;
+                bool runs = false;
+                for (int32_t t = w; t < end && !runs; ++t) runs = (t == w || sorted[t] != sorted[t - 1]) && keep(n, sorted[t]);
+                if (runs) plan->lane_cells += hr[n] * 64.0 * n * width;
+            }
+        }
+    }
     return SED_OK;
 }
 
 int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
-                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
+                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist, int maxlen,
                      sed_join_plan_t *plan, std::string *err) {
+    if (maxlen != SED_JOIN_MAXLEN && maxlen != SED_JOIN_LONG_MAXLEN) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    plan->block = maxlen == SED_JOIN_LONG_MAXLEN ? SED_JOIN_LONG_BLOCK : 0;
     auto rule = [&]() -> int {
-        const int rc = sed_join_costs_rule(c, plan, err);
+        const int rc = sed_join_costs_rule(c, maxlen, plan, err);
         if (rc != SED_OK) return rc;
         uint32_t umap = 0;
         plan->kernel = o.join_dp != 2 && join_unit_costs(c, row_codes, col_codes, &umap) ? SED_JOIN_KERNEL_BITPAR : SED_JOIN_KERNEL_DP;
@@ -133,7 +159,8 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
         const uint32_t lb = m > n ? (uint32_t)(m - n) * plan->sp.ins : (uint32_t)(n - m) * plan->sp.del;
         return lb <= (uint32_t)plan->cut;
     };
-    return join_plan_shared(c, o, len_rows, nrows, len_cols, ncols, self, row_codes, col_codes, max_dist, plan, err, rule, keep);
+    return join_plan_shared(c, o, len_rows, nrows, len_cols, ncols, self, row_codes, col_codes, max_dist, maxlen, plan, err, rule,
+                            keep);
 }
 
 // ---- the fp64 route ----
@@ -184,7 +211,8 @@ int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *l
         return SED_OK;
     };
     auto keep = [&](int n, int m) { return ((plan->keep[n] >> m) & 1u) != 0; };
-    return join_plan_shared(c, o, len_rows, nrows, len_cols, ncols, self, row_codes, col_codes, max_dist, plan, err, rule, keep);
+    return join_plan_shared(c, o, len_rows, nrows, len_cols, ncols, self, row_codes, col_codes, max_dist, SED_JOIN_MAXLEN, plan,
+                            err, rule, keep);
 }
 
 // sed_join_plan's, sed_join_f64_plan's and sed_join_route's arguments as the planner's costs and options
@@ -205,24 +233,49 @@ static int join_costs_of(int K, const double *sub, const uint8_t *sub_int, doubl
 
 // what sed_join_plan and sed_join_f64_plan report: JOIN_PLAN_FIELDS of sedgpu.py
 static int join_plan_out(double scale, int kernel, const sed_join_counts &p, double *out, int nout) {
-    const double v[] = {scale, (double)kernel, p.waves, p.scope, p.run, p.cells};
+    const double v[] = {scale, (double)kernel, p.waves, p.scope, p.run, p.cells, p.lane_cells};
     for (int i = 0; i < nout && i < (int)(sizeof v / sizeof *v); ++i) out[i] = v[i];
     return SED_OK;
+}
+
+static thread_local std::string long_plan_error;  // sed_join_long_plan_error's text
+
+// sed_join_plan and sed_join_long_plan: the integer plan for sequences of up to maxlen symbols, nslots slots of it; *err
+// (may be NULL) gets a refusal's text
+static int join_plan_export(int maxlen, int nslots, std::string *err, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                            double del, int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
+                            int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
+                            uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    if (nout < 0 || (nout && !out)) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    sed_costs c;
+    sed_opts o;
+    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return sed_plan_fail(err, rc, "bad join arguments");
+    sed_join_plan_t p;
+    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, maxlen, &p,
+                          err);
+    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, std::min(nout, nslots));
 }
 
 extern "C" int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                              int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows,
                              const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
                              uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_costs c;
-    sed_opts o;
-    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc != SED_OK) return rc;
-    sed_join_plan_t p;
-    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p, nullptr);
-    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, nout);
+    return join_plan_export(SED_JOIN_MAXLEN, 6, nullptr, K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_rows,
+                            nrows, len_cols, ncols, self, row_codes_seen, col_codes_seen, max_dist, out, nout);
 }
+
+extern "C" int sed_join_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
+                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
+                                  int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
+                                  uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    long_plan_error.clear();
+    return join_plan_export(SED_JOIN_LONG_MAXLEN, 7, &long_plan_error, K, sub, sub_int, ins, ins_is_int, del, del_is_int,
+                            options, noptions, len_rows, nrows, len_cols, ncols, self, row_codes_seen, col_codes_seen, max_dist,
+                            out, nout);
+}
+
+extern "C" const char *sed_join_long_plan_error(void) { return long_plan_error.c_str(); }
 
 extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
@@ -236,7 +289,7 @@ extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_in
     sed_join_f64_plan_t p;
     rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
                               nullptr);
-    return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, nout);
+    return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, std::min(nout, 6));
 }
 
 extern "C" int sed_join_f64_keep(double ins, double del, double max_dist, uint64_t *keep) {
@@ -258,8 +311,8 @@ extern "C" int sed_join_route(int K, const double *sub, const uint8_t *sub_int, 
     if (rc != SED_OK) return rc;
     sed_join_plan_t p;
     std::string e_int, e_f64;
-    if ((rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
-                               &e_int)) == SED_OK)
+    if ((rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist,
+                               SED_JOIN_MAXLEN, &p, &e_int)) == SED_OK)
         return SED_JOIN_ROUTE_INT;
     if (rc != SED_E_RANGE) return rc;  // (bad arguments are bad for both)
     sed_join_f64_plan_t pf;

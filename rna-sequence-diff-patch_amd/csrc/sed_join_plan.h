@@ -1,13 +1,18 @@
 // sed_join_plan.h — the device-free half of the similarity join (include/sed.h: sed_join_self, sed_join_search): what a
 // join decides from the cost model, the options, the lengths, the codes seen and the cutoff.  sed_join_plan.cpp calls no
 // HIP API (it shares sed_costs, sed_opts and sed_plan_fail with the batch planner, sed_plan.h, and nothing else); its
-// exports sed_join_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route run, and are tested, without a device.
+// exports sed_join_plan, sed_join_long_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route run, and are tested,
+// without a device.  The integer rule takes its longest sequence as a parameter: SED_JOIN_MAXLEN for sed_join_self /
+// sed_join_search, SED_JOIN_LONG_MAXLEN for sed_join_long_self / sed_join_long_search (kernel: sed_join_long.hip).
 #pragma once
 #include "sed_plan.h"
 
 #define SED_JOIN_KERNEL_DP 1
 #define SED_JOIN_KERNEL_BITPAR 2
-#define SED_JOIN_CUT_ALL 65535  // no scaled distance of two sequences of <= 32 symbols exceeds 64 * 255
+// No scaled distance of two sequences of <= 128 symbols exceeds 128 * 255 = 32640 (every cost <= insert + delete, so
+// max(n, m) updates and |n - m| indels bound it), so this cutoff admits every pair.  The same product is what a key's
+// high half-word sinks by at most, and its low half-word sinks by at most 128 below 0xFFFC (sed_lane_dp.h).
+#define SED_JOIN_CUT_ALL 65535
 
 // What a plan of either route counts, from the lengths and the route's rule of which (n, m) are computed
 struct sed_join_counts {
@@ -15,6 +20,9 @@ struct sed_join_counts {
     double waves = 0;            // the 64-lane waves of every launch: 4 per block
     double scope = 0;            // the pairs the call is about: rows x columns, less the (i, i) of a self join
     double run = 0, cells = 0;   // those the route's length rule computes, and their n m
+    int block = 0;               // the columns of a block the kernel runs or skips as one (0: lane_cells is not counted)
+    double lane_cells = 0;       // the cells the waves execute: per wave and row it runs, 64 lanes x n x the blocks of
+                                 // columns up to the wave's longest column (padding and spare lanes included)
 };
 struct sed_join_plan_t : sed_join_counts {  // run: the pairs whose length bound is within the cutoff
     int scale_log2 = 0;          // S = 2^scale_log2
@@ -26,14 +34,16 @@ struct sed_join_plan_t : sed_join_counts {  // run: the pairs whose length bound
 // The table alone: the smallest S = 2^k, k <= 8, that makes insert, delete and every substitution cost integral, with
 // insert S, delete S >= 1, every cost <= insert + delete and (insert + delete) S <= 255 over at most 8 symbols
 // (sed_plan.cpp: scaled_costs' conditions without the lane block's n <= 512 and without its typing); fills scale_log2 and
-// sp's rows, ins, del and inv_scale.  Anything else: SED_E_RANGE, *err names the failed condition.
-int sed_join_costs_rule(const sed_costs &c, sed_join_plan_t *plan, std::string *err);
-// The whole plan.  len_rows / len_cols = the lengths (0..32 each, else SED_E_ARG); self: the rows are nrows of the ncols
+// sp's rows, ins, del and inv_scale.  Anything else: SED_E_RANGE, *err names the failed condition.  maxlen = the longest
+// sequence the keys must hold: maxlen (insert + delete) S <= 65535, which the conditions give for every maxlen <= 128.
+int sed_join_costs_rule(const sed_costs &c, int maxlen, sed_join_plan_t *plan, std::string *err);
+// The whole plan.  len_rows / len_cols = the lengths (0..maxlen each, else SED_E_ARG; maxlen = SED_JOIN_MAXLEN or
+// SED_JOIN_LONG_MAXLEN, and with the latter lane_cells counts SED_JOIN_LONG_BLOCK columns a block); self: the rows are nrows of the ncols
 // columns, and each row's own column is out of scope; row_codes / col_codes = bit c set when code c occurs (bit 31: any
 // code >= 31).  A code >= K: SED_E_ARG; NaN or negative max_dist: SED_E_ARG.  Both routes' plans refuse in one order:
 // the arguments, max_dist, the route's costs rule, the code set, the rows, the columns.
 int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
-                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist,
+                     int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist, int maxlen,
                      sed_join_plan_t *plan, std::string *err);
 
 // The fp64 route (include/sed.h: sed_join_self_f64, sed_join_search_f64; kernel: sed_join_f64.hip): any table of finite

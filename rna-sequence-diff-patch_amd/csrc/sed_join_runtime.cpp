@@ -1,7 +1,8 @@
 // sed_join_runtime.cpp — the similarity join's entry points of the C-ABI (include/sed.h): sed_join_index_* and
-// sed_join_self / sed_join_search and their _f64 siblings over a resident index of short sequences.  What a join runs is
-// the join planner's decision (sed_join_plan.cpp), the kernels are sed_join.hip and sed_join_f64.hip; here: pack, reserve, upload, launch, download, sort,
-// decode, on the context's stream (sed_runtime.h).
+// sed_join_self / sed_join_search and their _f64 siblings over a resident index of short sequences, and sed_join_long_*
+// over one of sequences of up to 128 symbols.  What a join runs is the join planner's decision (sed_join_plan.cpp), the
+// kernels are sed_join.hip, sed_join_f64.hip and sed_join_long.hip; here: pack, reserve, upload, launch, download, sort,
+// decode, on the context's stream (sed_runtime.h).  The two index types differ in one number, the record's length.
 #include "sed_join_plan.h"
 #include "sed_runtime.h"
 
@@ -28,7 +29,7 @@ struct JoinTimer {  // the events around a call's launches, created on first use
 struct JoinRec {  // one record of the device hit list (sed_internal.h: sed_join_args)
     uint32_t row, col, D, zero;  // (the fp64 route: D, zero = the distance's low and high words)
 };
-const size_t REC = SED_JOIN_MAXLEN, SPARE = 16;  // a sequence record, and the spare bytes that end a record buffer
+const size_t SPARE = 16;  // the spare bytes that end a record buffer (the kernels' row loads reach two words past a record)
 
 const size_t F64_TAB = SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK;  // the fp64 table's doubles
 
@@ -37,6 +38,7 @@ uint32_t code_bit(uint8_t c) { return 1u << (c < 31 ? c : 31); }
 
 struct sed_join_index {
     sed_ctx *ctx = nullptr;
+    int32_t maxlen = SED_JOIN_MAXLEN;  // the longest sequence = the bytes of a record: SED_JOIN_MAXLEN or SED_JOIN_LONG_MAXLEN
     int32_t nseqs = 0;
     uint32_t codes = 0;            // bit c: code c occurs (bit 31: any code >= 31)
     std::vector<int32_t> len;      // in the caller's order: the rows of a self join
@@ -59,6 +61,8 @@ struct sed_join_index {
         d_query.release(); d_tab.release(); d_f64.release(); d_hits.release(); d_count.release();
     }
 };
+
+struct sed_join_long_index : sed_join_index {};  // (a type of its own in the C-ABI: its records are 128 bytes)
 
 // What a call runs: the integer plan or the fp64 plan (exactly one is set)
 struct JoinCall {
@@ -119,8 +123,9 @@ static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_args a, int3
         a.row0 = f.row0 = first + (int32_t)r;
         a.nrows = f.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
         hipEvent_t e0 = r == 0 ? ix->timer.ev[0] : nullptr, e1 = r + step >= nrows ? ix->timer.ev[1] : nullptr;
-        e = k.pi ? sed_launch_join(c->stream, e0, e1, a, k.pi->kernel == SED_JOIN_KERNEL_BITPAR)
-                 : sed_launch_join_f64(c->stream, e0, e1, f);
+        e = !k.pi ? sed_launch_join_f64(c->stream, e0, e1, f)
+            : ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long(c->stream, e0, e1, a, k.pi->kernel == SED_JOIN_KERNEL_BITPAR)
+                                                 : sed_launch_join(c->stream, e0, e1, a, k.pi->kernel == SED_JOIN_KERNEL_BITPAR);
         if (e != hipSuccess) return c->hipfail(e, "join kernel launch");
     }
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
@@ -171,26 +176,28 @@ static int join_enter(sed_ctx *c, bool args_ok) {
     return SED_OK;
 }
 
-extern "C" {
-
-sed_join_index *sed_join_index_create(sed_ctx *c, const uint8_t *codes, const int64_t *off, const int32_t *len,
-                                      int32_t nseqs) {
+// sed_join_index_create and sed_join_long_index_create: Index = the type made, of sequences of up to maxlen symbols
+template <class Index>
+static Index *join_index_create(sed_ctx *c, int32_t maxlen, const uint8_t *codes, const int64_t *off, const int32_t *len,
+                                int32_t nseqs) {
     if (!c) return nullptr;
+    const size_t REC = (size_t)maxlen;
     if (nseqs < 0 || (nseqs > 0 && (!codes || !off || !len))) {
         c->fail(SED_E_ARG, "bad join index arguments");
         return nullptr;
     }
     for (int i = 0; i < nseqs; ++i)
-        if (len[i] < 0 || len[i] > SED_JOIN_MAXLEN || off[i] < 0) {
+        if (len[i] < 0 || len[i] > maxlen || off[i] < 0) {
             if (off[i] < 0 || len[i] < 0)
                 c->fail(SED_E_ARG, "join index: sequence %d: negative %s", i, len[i] < 0 ? "length" : "offset");
             else
-                c->fail(SED_E_ARG, "join index: sequence %d has %d symbols (at most %d)", i, len[i], SED_JOIN_MAXLEN);
+                c->fail(SED_E_ARG, "join index: sequence %d has %d symbols (at most %d)", i, len[i], maxlen);
             return nullptr;
         }
     (void)hipSetDevice(c->device);
-    sed_join_index *ix = new sed_join_index;
+    Index *ix = new Index;
     ix->ctx = c;
+    ix->maxlen = maxlen;
     ix->nseqs = nseqs;
     ix->len.assign(len, len + nseqs);
     std::vector<int32_t> order((size_t)nseqs);
@@ -225,13 +232,32 @@ sed_join_index *sed_join_index_create(sed_ctx *c, const uint8_t *codes, const in
     return nullptr;
 }
 
-void sed_join_index_destroy(sed_join_index *ix) {
+template <class Index>
+static void join_index_destroy(Index *ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->ctx->device);
     delete ix;
 }
 
+extern "C" {
+
+sed_join_index *sed_join_index_create(sed_ctx *c, const uint8_t *codes, const int64_t *off, const int32_t *len,
+                                      int32_t nseqs) {
+    return join_index_create<sed_join_index>(c, SED_JOIN_MAXLEN, codes, off, len, nseqs);
+}
+
+sed_join_long_index *sed_join_long_index_create(sed_ctx *c, const uint8_t *codes, const int64_t *off, const int32_t *len,
+                                                int32_t nseqs) {
+    return join_index_create<sed_join_long_index>(c, SED_JOIN_LONG_MAXLEN, codes, off, len, nseqs);
+}
+
+void sed_join_index_destroy(sed_join_index *ix) { join_index_destroy(ix); }
+
+void sed_join_long_index_destroy(sed_join_long_index *ix) { join_index_destroy(ix); }
+
 int32_t sed_join_index_seqs(const sed_join_index *ix) { return ix ? ix->nseqs : SED_E_ARG; }
+
+int32_t sed_join_long_index_seqs(const sed_join_long_index *ix) { return ix ? ix->nseqs : SED_E_ARG; }
 
 }  // extern "C"
 
@@ -245,7 +271,7 @@ static int join_plan_call(sed_ctx *c, bool f64, const int32_t *len_rows, int32_t
     }
     k->pi = pi;
     return sed_join_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes, max_dist,
-                            pi, &c->err);
+                            ix->maxlen, pi, &c->err);
 }
 
 static int join_self(sed_join_index *ix, bool f64, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
@@ -279,13 +305,14 @@ static int join_search(sed_join_index *ix, bool f64, const uint8_t *codes_q, con
                                found);
     if (rc != SED_OK) return rc;
     // the queries' records and lengths, one block: [records | spare | lengths]
+    const size_t REC = (size_t)ix->maxlen;
     const size_t o_len = REC * (size_t)nqueries + SPARE, qbytes = o_len + sizeof(int32_t) * (size_t)nqueries;
     ix->h_query.assign(qbytes, 0);
     uint32_t qcodes = 0;
     for (int q = 0; q < nqueries; ++q) {
         if (off_q[q] < 0) return c->fail(SED_E_ARG, "query %d: negative offset", q);
-        if (len_q[q] < 0 || len_q[q] > SED_JOIN_MAXLEN)
-            return c->fail(SED_E_ARG, "query %d has %d symbols (0..%d)", q, len_q[q], SED_JOIN_MAXLEN);
+        if (len_q[q] < 0 || len_q[q] > ix->maxlen)
+            return c->fail(SED_E_ARG, "query %d has %d symbols (0..%d)", q, len_q[q], ix->maxlen);
         for (int j = 0; j < len_q[q]; ++j) qcodes |= code_bit(ix->h_query[REC * (size_t)q + j] = codes_q[off_q[q] + j]);
     }
     if (nqueries) memcpy(&ix->h_query[o_len], len_q, sizeof(int32_t) * (size_t)nqueries);
@@ -344,5 +371,22 @@ int sed_join_pairs_run(const sed_join_index *ix, int64_t *pairs) {
 }
 
 int32_t sed_join_rows_per_group(void) { return SED_JOIN_G; }
+
+// ---- sequences of up to 128 symbols: the calls above over the other index type (the integer route only) ----
+int sed_join_long_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
+                       int64_t cap, int64_t *found) {
+    return join_self(ix, false, row_lo, row_hi, max_dist, out, cap, found);
+}
+
+int sed_join_long_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                         int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_search(ix, false, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+}
+
+int sed_join_long_last_time(const sed_join_long_index *ix, float *kernel_ms) { return sed_join_last_time(ix, kernel_ms); }
+
+int sed_join_long_pairs_run(const sed_join_long_index *ix, int64_t *pairs) { return sed_join_pairs_run(ix, pairs); }
+
+int32_t sed_join_long_max_len(void) { return SED_JOIN_LONG_MAXLEN; }
 
 }  // extern "C"

@@ -207,6 +207,20 @@ SIGNATURES = [
     ("sed_join_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                  _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
                                  C.c_char_p, C.c_int]),
+    ("sed_join_long_index_create", C.c_void_p, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32]),
+    ("sed_join_long_index_destroy", None, [C.c_void_p]),
+    ("sed_join_long_index_seqs", C.c_int32, [C.c_void_p]),
+    ("sed_join_long_self", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                     C.POINTER(C.c_int64)]),
+    ("sed_join_long_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                       C.POINTER(C.c_int64)]),
+    ("sed_join_long_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("sed_join_long_pairs_run", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("sed_join_long_max_len", C.c_int32, []),
+    ("sed_join_long_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
+                                     _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
+                                     _f64p, C.c_int]),
+    ("sed_join_long_plan_error", C.c_char_p, []),
     ("sed_selftest", C.c_int, [C.c_void_p]),
     ("sed_full_matrix", C.c_int, [C.c_void_p, _u8p, C.c_int32, _u8p, C.c_int32, _f64p, _u8p]),
 ]
@@ -390,6 +404,10 @@ class Context:
         """A resident index of short sequences for the similarity join (sed_join_index_create): sequence i =
         codes[off[i] : off[i] + lens[i]], 0..32 symbols, uploaded once."""
         return JoinIndex(self, codes, off, lens)
+
+    def join_long_index(self, codes, off, lens):
+        """join_index for sequences of 0..128 symbols (sed_join_long_index_create): the integer route only."""
+        return LongJoinIndex(self, codes, off, lens)
 
     def run_pair(self, codes_a, codes_b, want_script, no_len=False):
         """One pair (codes as bytes): (dist, is_int, len, ops u32[] | None) through sed_run_pair, the per-call path of
@@ -655,6 +673,8 @@ class JoinIndex:
     self_join() / search() return every (row, col) pair within a distance as a JOIN_HIT_DTYPE array sorted by (row, col),
     under the context's costs and options of that moment.  Rows are str1, columns str2."""
 
+    _PREFIX = "sed_join_"  # the entry points' names: _PREFIX + index_create, self, search, last_time, pairs_run, ...
+
     def __init__(self, ctx, codes, off, lens):
         self.ctx = ctx
         self.found = 0       # the last call's total count
@@ -665,11 +685,12 @@ class JoinIndex:
         self.nseqs = len(lens)
         codes = np.ascontiguousarray(codes, np.uint8)
         one = lambda a, t: a if len(a) else np.zeros(1, t)
-        self.ptr = self._lib.sed_join_index_create(ctx.ptr, one(codes, np.uint8), one(off, np.int64), one(lens, np.int32),
-                                                   self.nseqs)
+        create = self._PREFIX + "index_create"
+        self.ptr = getattr(self._lib, create)(ctx.ptr, one(codes, np.uint8), one(off, np.int64), one(lens, np.int32),
+                                              self.nseqs)
         if not self.ptr:
             msg = self._lib.sed_last_error(ctx.ptr)
-            raise SedError("sed_join_index_create failed: %s" % (msg.decode() if msg else ""))
+            raise SedError("%s failed: %s" % (create, msg.decode() if msg else ""))
 
     @classmethod
     def from_seqs(cls, ctx, seqs):
@@ -681,7 +702,7 @@ class JoinIndex:
 
     def close(self):
         if self.ptr and self.ctx.ptr and self.ctx._pid == os.getpid():
-            self._lib.sed_join_index_destroy(self.ptr)
+            getattr(self._lib, self._PREFIX + "index_destroy")(self.ptr)
         self.ptr = None
 
     def __del__(self):
@@ -707,18 +728,20 @@ class JoinIndex:
                 self._hit_room = max(self._hit_room, room)
             return out[:self.found]
 
-    def self_join(self, max_dist, rows=None, cap=None, _call="sed_join_self"):
+    def self_join(self, max_dist, rows=None, cap=None, _call=None):
         """Every (i, j), i != j, i in rows = (lo, hi) (default: every sequence), with distance(seq i -> seq j) <=
         max_dist (sed_join_self).  cap = the records to make room for: more hits raise SedError (the index stays
         usable; found has the count; cap=0 is a count query).  cap=None retries once with room, so it returns every hit."""
         lo, hi = (0, self.nseqs) if rows is None else rows
+        _call = _call or self._PREFIX + "self"
         fn = getattr(self._lib, _call)
         return self._hits(_call, lambda out, room, found: fn(
             self.ptr, int(lo), int(hi), float(max_dist), out, room, found), cap)
 
-    def search(self, packed, max_dist, cap=None, _call="sed_join_search"):
+    def search(self, packed, max_dist, cap=None, _call=None):
         """Every (q, j) with distance(query q -> seq j) <= max_dist (sed_join_search); packed: the queries as side a of
         a PackedPairs, 0..32 symbols each.  cap as for self_join."""
+        _call = _call or self._PREFIX + "search"
         fn = getattr(self._lib, _call)
         return self._hits(_call, lambda out, room, found: fn(
             self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.npairs, float(max_dist), out, room, found), cap)
@@ -735,14 +758,33 @@ class JoinIndex:
     def last_ms(self):
         """Device time of the last join's kernel(s) (ms, HIP events)."""
         ms = C.c_float()
-        self.ctx._check(self._lib.sed_join_last_time(self.ptr, C.byref(ms)), "sed_join_last_time")
+        self.ctx._check(getattr(self._lib, self._PREFIX + "last_time")(self.ptr, C.byref(ms)), self._PREFIX + "last_time")
         return ms.value
 
     def pairs_run(self):
         """The pairs the last join's waves ran, counted on the device (sed_join_pairs_run): join_plan's "run"."""
         n = C.c_int64()
-        self.ctx._check(self._lib.sed_join_pairs_run(self.ptr, C.byref(n)), "sed_join_pairs_run")
+        self.ctx._check(getattr(self._lib, self._PREFIX + "pairs_run")(self.ptr, C.byref(n)), self._PREFIX + "pairs_run")
         return int(n.value)
+
+
+def join_long_max_len():
+    """The longest sequence a LongJoinIndex holds (sed_join_long_max_len): 128."""
+    return int(load().sed_join_long_max_len())
+
+
+class LongJoinIndex(JoinIndex):
+    """JoinIndex for sequences of 0..128 symbols each (sed_join_long_*): the same calls, records, sort and cap protocol
+    through the integer route's long kernel; the queries of search() have 0..128 symbols too.  There is no fp64 route
+    for it yet."""
+
+    _PREFIX = "sed_join_long_"
+
+    def self_join_f64(self, max_dist, rows=None, cap=None):
+        raise SedError("the long join has no fp64 route yet (sed_join_long_self serves the integer route's tables)")
+
+    def search_f64(self, packed, max_dist, cap=None):
+        raise SedError("the long join has no fp64 route yet (sed_join_long_search serves the integer route's tables)")
 
 
 JOIN_PLAN_FIELDS = ("scale", "kernel", "waves", "scope", "run", "cells")
@@ -773,6 +815,21 @@ def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_code
     if rc != 0:
         raise _fit_fail(_call, rc)
     return {k: (float(v) if k in ("scale", "cells") else int(v)) for k, v in zip(JOIN_PLAN_FIELDS, out)}
+
+
+def join_long_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
+    """What LongJoinIndex.self_join / search would decide, without a device (sed_join_long_plan): join_plan's fields for
+    lengths 0..128, and "lane_cells", the cells the waves execute with their blocks of 32 columns and their spare lanes.
+    Arguments and errors as join_plan; the SedError also carries the refusal's text (sed_join_long_plan_error)."""
+    fields = JOIN_PLAN_FIELDS + ("lane_cells",)
+    out = np.zeros(len(fields), np.float64)
+    rc = load().sed_join_long_plan(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                                   out, len(out))
+    if rc != 0:
+        err = SedError("sed_join_long_plan failed (%d): %s" % (rc, load().sed_join_long_plan_error().decode()))
+        err.code = rc
+        raise err
+    return {k: (float(v) if k in ("scale", "cells", "lane_cells") else int(v)) for k, v in zip(fields, out)}
 
 
 def join_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
@@ -1120,6 +1177,10 @@ class EngineClient:
     def join_index(self, codes, off, lens):
         raise SedError("join_index: a forked child's engine proxy does not serve resident indexes (its sequences would "
                        "live in the serving process); build the index in the process that owns the device")
+
+    def join_long_index(self, codes, off, lens):
+        raise SedError("join_long_index: a forked child's engine proxy does not serve resident indexes (its sequences "
+                       "would live in the serving process); build the index in the process that owns the device")
 
 
 class _PlanArgs:

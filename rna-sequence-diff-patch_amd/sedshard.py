@@ -62,7 +62,8 @@ def all_vs_all(seqs, userCosts=False, world=1, rank=0, device=None, distance_fn=
     return got[0].cpu().numpy().reshape(len(seqs), len(seqs))
 
 
-def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, join_fn=None, route="int"):
+def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, join_fn=None, route="int",
+              long_sequences=False):
     """Every ordered pair (i, j), i != j, of the short sequences seqs (0..32 symbols) whose distance from seqs[i] to
     seqs[j] is <= max_dist, as a numpy record array (row, col, dist) sorted by (row, col), on rank 0 (None on other
     ranks).  Rank r joins its block of rows, shard_range(len(seqs), world, r), against every sequence on its own GPU
@@ -72,15 +73,20 @@ def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, joi
     symbols: IUPAC collections under costs.json), "auto" the integer call whenever it serves this rank's rows
     (StringEditDistance.join_route), as wfsearch.JoinIndex takes it.
     join_fn(seqs, lo, hi, max_dist, userCosts) -> [(i, j, dist)] sorted replaces the engine (the CPU tests inject the
-    oracle to check the sharding and reassembly); the fp64 route calls it with f64=True as a further, keyword argument."""
+    oracle to check the sharding and reassembly); the fp64 route calls it with f64=True as a further, keyword argument.
+    long_sequences=True serves sequences of 0..128 symbols through the integer route's long kernel
+    (StringEditDistance.join_index(..., long_seqs=True); 128 bytes a sequence on every rank); join_fn is then called with
+    long_seqs=True as a further, keyword argument.  It has no fp64 route yet: "f64" and "auto" raise ValueError."""
     import torch
     if route not in ("int", "f64", "auto"):
         raise ValueError("route must be one of int, f64, auto, not %r" % (route,))
+    if long_sequences and route != "int":
+        raise ValueError("the long join has no fp64 route yet: long_sequences=True takes route=\"int\", not %r" % (route,))
     if join_fn is None or route == "auto":
         import StringEditDistance as SED
     if join_fn is None:
-        def join_fn(seqs, lo, hi, max_dist, userCosts, f64=False):
-            ix = SED.join_index(seqs, userCosts, f64=route != "int")
+        def join_fn(seqs, lo, hi, max_dist, userCosts, f64=False, long_seqs=False):
+            ix = SED.join_index(seqs, userCosts, f64=route != "int", long_seqs=long_seqs)
             try:
                 return (ix.self_join_f64 if f64 else ix.self_join)(max_dist, (lo, hi))
             finally:
@@ -88,6 +94,8 @@ def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, joi
     lo, hi = shard_range(len(seqs), world, rank)
     if hi <= lo:
         hits = []
+    elif long_sequences:
+        hits = list(join_fn(seqs, lo, hi, max_dist, userCosts, long_seqs=True))
     elif (SED.join_route(seqs[lo:hi], seqs, max_dist, userCosts) if route == "auto" else route) == "f64":
         hits = list(join_fn(seqs, lo, hi, max_dist, userCosts, f64=True))
     else:

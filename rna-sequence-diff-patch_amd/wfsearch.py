@@ -347,23 +347,37 @@ class JoinIndex:
     (StringEditDistance.join_route), so only a refusal turns into a result.  An index whose constructor route is "f64"
     or "auto" is built with f64=True (up to 16 symbols; index_fn is called with that keyword) and serves integer calls
     too; one built under the default keeps the 8-symbol bound, whatever route a later call names.  The fp64 route calls
-    the index's self_join_f64 / search_f64."""
+    the index's self_join_f64 / search_f64.
 
-    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None, route="int"):
+    long_sequences=True serves sequences and queries of 0..128 symbols (tRNA, pre-miRNA hairpins, 5S rRNA) through the
+    integer route's long kernel (StringEditDistance.join_index(..., long_seqs=True); index_fn is called with
+    long_seqs=True).  It has no fp64 route yet: "f64" and "auto" raise ValueError, at the constructor and per call."""
+
+    def __init__(self, seqs_or_collection, user_cost=False, index_fn=None, route="int", long_sequences=False):
         if route not in ROUTES:
             raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
+        self.long_sequences = bool(long_sequences)
+        self._no_f64(route)
         self.seqs = _sequences(seqs_or_collection)
         self.user_cost = user_cost
         self.route = route
         make = index_fn or SED.join_index
+        if self.long_sequences:
+            self._ix = make(self.seqs, user_cost, long_seqs=True) if self.seqs else None
+            return
         self._ix = (make(self.seqs, user_cost) if route == "int" else make(self.seqs, user_cost, f64=True)) \
             if self.seqs else None
+
+    def _no_f64(self, route):
+        if self.long_sequences and route != "int":
+            raise ValueError("the long join has no fp64 route yet: long_sequences=True takes route=\"int\", not %r" % (route,))
 
     def _f64(self, route, rows, max_dist):
         """whether the fp64 calls serve these rows under route"""
         route = self.route if route is None else route
         if route not in ROUTES:
             raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
+        self._no_f64(route)
         return (SED.join_route(rows, self.seqs, max_dist, self.user_cost) if route == "auto" else route) == "f64"
 
     def neighbors(self, max_dist, rows=None, route=None):
@@ -396,9 +410,9 @@ class JoinIndex:
         self._ix = None
 
 
-def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None, route="int"):
+def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None, route="int", long_sequences=False):
     """JoinIndex.neighbors in one shot: builds an index over the sequences, joins it with itself and closes it."""
-    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, route=route)
+    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, route=route, long_sequences=long_sequences)
     try:
         return ix.neighbors(max_dist)
     finally:
