@@ -129,6 +129,23 @@ template <int B, int E, class F> __device__ __forceinline__ void static_for(F &&
 
 template <bool B> struct BoolTag { static constexpr bool value = B; };
 
+// Slots of a device hit list for the hitting lanes of a wave, one atomic add a wave: the hitting lane of rank 0 adds
+// the wave's popcount to *count, every hitting lane's slot is the sum before + its rank among them.  True in the lanes
+// that hit (whose *slot is then set); the callers store their record where the slot is below their list's room, so
+// *count counts every hit, stored or not.  The one copy for the fit and join hit lists.
+__device__ __forceinline__ bool wave_claim_slot(unsigned long long *count, bool hit, unsigned long long *slot) {
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
+    if (b == 0) return false;
+    if (!hit) return false;
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    unsigned long long base = 0;
+    if (rank == 0) base = atomicAdd(count, (unsigned long long)__popcll(b));
+    // (the first active lane here is the hitting lane of rank 0, so readfirstlane hands every lane its sum)
+    *slot = (((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+             __builtin_amdgcn_readfirstlane((uint32_t)base)) + rank;
+    return true;
+}
+
 // Inter-workgroup hand-off of stripe bottom rows (SPLIT mode), per 16-step group and self-validating: every
 // bottom-row cell travels as one 64-bit word {tag, value}, stored with a relaxed agent-scope 64-bit atomic
 // (single-copy atomic, so a reader sees the tag and the value of one store together), tag = the run's epoch

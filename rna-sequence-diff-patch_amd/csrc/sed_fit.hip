@@ -30,6 +30,7 @@
 #include "sed_internal.h"
 #include "sed_dev.h"
 #include "sed_fit_dp.h"
+#include "sed_fit_index_dev.h"
 
 namespace {
 
@@ -46,23 +47,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_kernel(const sed_fit
     sed_fit_dp(ln, pats[2 * (size_t)ln.pat], pats[2 * (size_t)ln.pat + 1], tab, text, out, fp);
 }
 
-// The lane of thread t of an index kernel, and its query: blockIdx.y + q0 = the query, whose pattern record and length
-// are uniform across the block; t = blockIdx.x * 64 + threadIdx.x = the chunk record.  The lane derives its record
-// (sed_fit_derive_lane, the function the device-free sed_fit_index_lanes checks against the lane builder) for pair
-// query * ntexts + text.
-__device__ __forceinline__ sed_fit_lane sed_fit_index_lane(const sed_fit_chunk *__restrict__ chunks,
-                                                           const sed_fit_text *__restrict__ texts, int ntexts,
-                                                           const int32_t *__restrict__ plens, int q0, int32_t chunk, int32_t W,
-                                                           int t, int *q) {
-    *q = q0 + (int)blockIdx.y;
-    const sed_fit_chunk ck = chunks[t];
-    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[*q], W);
-    ln.pair = *q * ntexts + ck.text;
-    return ln;
-}
-
 // The same DP over a resident index (sed_internal.h: sed_fit_index_args): one lane per (query, chunk record)
-// (sed_fit_index_lane), which reports into out[query * ntexts + text].
+// (sed_fit_index_dev.h: sed_fit_index_lane), which reports into out[query * ntexts + text].
 __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_kernel(const sed_fit_chunk *__restrict__ chunks,
                                                                           int nchunks,
                                                                           const sed_fit_text *__restrict__ texts,
@@ -75,8 +61,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_kernel(const s
     sed_fit_fill_tab(tab, fp);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
-    int q;
-    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q0, chunk, W, t, &q);
+    const int q = q0 + (int)blockIdx.y;
+    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q, chunk, W, t);
     sed_fit_dp(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, out, fp);
 }
 
@@ -93,8 +79,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 4) void sed_fit_index_hits_kernel(
     sed_fit_fill_tab(tab, fp);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
-    int q;
-    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q0, chunk, W, t, &q);
+    const int q = q0 + (int)blockIdx.y;
+    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q, chunk, W, t);
     sed_fit_dp_hits(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, sed_fit_hit_list{hits, count, cap, cut}, fp);
 }
 
@@ -108,23 +94,17 @@ hipError_t sed_launch_fit(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, co
     return hipGetLastError();
 }
 
-#define SED_FIT_INDEX_MAXY 65535  // queries per launch (the grid's y limit); more run as further launches
-// An index kernel over all of a's queries: the arguments the index kernels share up to the text, then `tail`.  The
-// events bracket the whole search: the first launch starts ev0, the last stops ev1.
+// An index kernel over all of a's queries (sed_internal.h: sed_fit_each_query_group): the arguments the index kernels
+// share up to the text, then `tail`.
 template <typename Kernel, typename... Tail>
 static hipError_t fit_launch_queries(Kernel kernel, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
                                      const sed_fit_index_args &a, Tail... tail) {
-    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
     const unsigned gx = (unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK);
-    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_INDEX_MAXY) {
-        const int nq = a.nqueries - q0 < SED_FIT_INDEX_MAXY ? a.nqueries - q0 : SED_FIT_INDEX_MAXY;
-        hipExtLaunchKernelGGL(kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream, q0 == 0 ? ev0 : nullptr,
-                              q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts, a.ntexts,
-                              (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, tail...);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(kernel, dim3(gx, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream, e0, e1, 0, a.chunks, a.nchunks,
+                              a.texts, a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, tail...);
+        return hipGetLastError();
+    });
 }
 
 hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,

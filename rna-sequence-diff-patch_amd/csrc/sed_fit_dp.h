@@ -27,23 +27,12 @@ struct sed_fit_hit_list {
     int32_t cut;
 };
 
-// One hit of the lane, decided for the whole wave: the ballot's first lane takes popcount slots, every hitting lane
-// stores at the first slot + its rank among them.  tt = (D - P delete) << 16 | (end - start).
+// One hit of the lane, decided for the whole wave (sed_dev.h: wave_claim_slot).  tt = (D - P delete) << 16 | (end - start).
 __device__ __forceinline__ void sed_fit_append(const sed_fit_hit_list &hl, bool hit, int32_t pair, int32_t end, int32_t tt,
                                                uint32_t pdel) {
-    const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
-    if (b == 0) return;
-    if (hit) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        unsigned long long base = 0;
-        if (rank == 0) base = atomicAdd(hl.count, (unsigned long long)__popcll(b));
-        // (the first active lane here is the hitting lane of rank 0)
-        const unsigned long long slot =
-            (((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-             __builtin_amdgcn_readfirstlane((uint32_t)base)) + rank;
-        if (slot < hl.cap)
-            hl.rec[slot] = make_uint4((uint32_t)pair, (uint32_t)end, (uint32_t)tt & 0xFFFFu, (uint32_t)((tt >> 16) + (int32_t)pdel));
-    }
+    unsigned long long slot;
+    if (wave_claim_slot(hl.count, hit, &slot) && slot < hl.cap)
+        hl.rec[slot] = make_uint4((uint32_t)pair, (uint32_t)end, (uint32_t)tt & 0xFFFFu, (uint32_t)((tt >> 16) + (int32_t)pdel));
 }
 
 // q0, q1 = the pattern, right-aligned in 32 byte codes, code 8 in front of it (sed_fit_runtime.cpp: fit_pack_pattern).

@@ -25,12 +25,13 @@
 // to its own record; sed_fit_f64_reduce_kernel / sed_fit_index_f64_reduce_kernel take per pair the first strict minimum
 // over the pair's lanes in chunk order.  No atomic is involved: the result does not depend on any order of execution.
 // Hits: every owned column with sink D <= max_dist (a plain fp64 compare) is appended through the wave's ballot, one
-// atomic add per wave and column on the counter, as sed_fit_dp.h: sed_fit_append does it, the record carrying D as 64
-// bits and the start as 32; the host sorts the list.
+// atomic add per wave and column on the counter (sed_dev.h: wave_claim_slot), the record carrying D as 64 bits and the
+// start as 32; the host sorts the list.
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
 #include "sed_fit_f64_dp.h"
+#include "sed_fit_index_dev.h"
 
 namespace {
 
@@ -130,21 +131,7 @@ __global__ __launch_bounds__(SED_FIT_BLOCK) void sed_fit_f64_reduce_kernel(const
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nlanes || lanes[t].c0 != 0) return;
     const int32_t pair = lanes[t].pair;
-    sed_fit_f64_best b = rec[t];
-    for (int k = t + 1; k < nlanes && lanes[k].pair == pair; ++k)
-        if (rec[k].D < b.D) b = rec[k];
-    out[pair] = b;
-}
-
-// The index kernels' lane (sed_fit.hip: sed_fit_index_lane): query blockIdx.y + q0, chunk record t
-__device__ __forceinline__ sed_fit_lane fit_f64_index_lane(const sed_fit_chunk *__restrict__ chunks,
-                                                           const sed_fit_text *__restrict__ texts, int ntexts,
-                                                           const int32_t *__restrict__ plens, int q, int32_t chunk, int32_t W,
-                                                           int t) {
-    const sed_fit_chunk ck = chunks[t];
-    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
-    ln.pair = q * ntexts + ck.text;
-    return ln;
+    out[pair] = fit_f64_first_min(rec, t, nlanes, [&](int k) { return lanes[k].pair == pair; });
 }
 
 __global__ __launch_bounds__(SED_FIT_BLOCK, 2) void sed_fit_index_f64_kernel(
@@ -156,7 +143,7 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 2) void sed_fit_index_f64_kernel(
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
     const int q = q0 + (int)blockIdx.y;
-    const sed_fit_lane ln = fit_f64_index_lane(chunks, texts, ntexts, plens, q, chunk, W, t);
+    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q, chunk, W, t);
     fit_f64_dp<false>(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, rec + (size_t)q * nchunks + t,
                       fit_f64_hit_list{}, ins, del);
 }
@@ -169,11 +156,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK) void sed_fit_index_f64_reduce_kernel
     if (t >= nchunks || chunks[t].c0 != 0) return;
     const int q = q0 + (int)blockIdx.y;
     const int32_t d = chunks[t].text;
-    const sed_fit_f64_best *r = rec + (size_t)q * nchunks;
-    sed_fit_f64_best b = r[t];
-    for (int k = t + 1; k < nchunks && chunks[k].text == d; ++k)
-        if (r[k].D < b.D) b = r[k];
-    out[(size_t)q * ntexts + d] = b;
+    out[(size_t)q * ntexts + d] =
+        fit_f64_first_min(rec + (size_t)q * nchunks, t, nchunks, [&](int k) { return chunks[k].text == d; });
 }
 
 __global__ __launch_bounds__(SED_FIT_BLOCK, 2) void sed_fit_index_f64_hits_kernel(
@@ -186,7 +170,7 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, 2) void sed_fit_index_f64_hits_kerne
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nchunks) return;
     const int q = q0 + (int)blockIdx.y;
-    const sed_fit_lane ln = fit_f64_index_lane(chunks, texts, ntexts, plens, q, chunk, W, t);
+    const sed_fit_lane ln = sed_fit_index_lane(chunks, texts, ntexts, plens, q, chunk, W, t);
     fit_f64_dp<true>(ln, pats[2 * (size_t)q], pats[2 * (size_t)q + 1], tab, text, nullptr,
                      fit_f64_hit_list{hits, count, cap, max_dist}, ins, del);
 }
@@ -207,24 +191,15 @@ hipError_t sed_launch_fit_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1
     return hipGetLastError();
 }
 
-#define SED_FIT_INDEX_MAXY 65535  // queries per launch (the grid's y limit), as sed_fit.hip
-// launch(grid, q0, e0, e1) for every group of at most SED_FIT_INDEX_MAXY queries of a: it starts e0 with its first
-// kernel and stops e1 with its last (null but for the search's first and last group)
-template <typename Launch>
-static hipError_t fit_f64_each_group(hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a, Launch launch) {
-    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
-    const unsigned gx = (unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK);
-    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_INDEX_MAXY) {
-        const int nq = a.nqueries - q0 < SED_FIT_INDEX_MAXY ? a.nqueries - q0 : SED_FIT_INDEX_MAXY;
-        const hipError_t e = launch(dim3(gx, (unsigned)nq), q0, q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+// nq queries of an index search (sed_internal.h: sed_fit_each_query_group): one lane per (query, chunk record)
+static dim3 fit_f64_grid(const sed_fit_index_args &a, int nq) {
+    return dim3((unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK), (unsigned)nq);
 }
 
 hipError_t sed_launch_fit_index_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                     sed_fit_f64_best *rec, sed_fit_f64_best *out, const sed_fit_f64_costs &fc) {
-    return fit_f64_each_group(ev0, ev1, a, [&](dim3 grid, int q0, hipEvent_t e0, hipEvent_t e1) {
+    return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+        const dim3 grid = fit_f64_grid(a, nq);
         hipExtLaunchKernelGGL(sed_fit_index_f64_kernel, grid, dim3(SED_FIT_BLOCK), 0, stream, e0, nullptr, 0, a.chunks, a.nchunks,
                               a.texts, a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, rec, a.chunk,
                               a.W, fc.sub, fc.ins, fc.del);
@@ -239,8 +214,8 @@ hipError_t sed_launch_fit_index_f64(hipStream_t stream, hipEvent_t ev0, hipEvent
 hipError_t sed_launch_fit_index_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                          sed_fit_f64_hit *hits, unsigned long long *count, unsigned long long cap,
                                          double max_dist, const sed_fit_f64_costs &fc) {
-    return fit_f64_each_group(ev0, ev1, a, [&](dim3 grid, int q0, hipEvent_t e0, hipEvent_t e1) {
-        hipExtLaunchKernelGGL(sed_fit_index_f64_hits_kernel, grid, dim3(SED_FIT_BLOCK), 0, stream, e0, e1, 0, a.chunks, a.nchunks,
+    return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(sed_fit_index_f64_hits_kernel, fit_f64_grid(a, nq), dim3(SED_FIT_BLOCK), 0, stream, e0, e1, 0, a.chunks, a.nchunks,
                               a.texts, a.ntexts, (const uint4 *)a.pats, a.plens, q0, (const uint32_t *)a.text, hits, count, cap,
                               max_dist, a.chunk, a.W, fc.sub, fc.ins, fc.del);
         return hipGetLastError();

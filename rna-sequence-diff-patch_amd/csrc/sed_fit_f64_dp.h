@@ -1,6 +1,6 @@
 // sed_fit_f64_dp.h - what the fp64 fit kernels of sed_fit_f64.hip (one lane per chunk) and sed_fit_long_f64.hip (one
-// wave per chunk) share: the cost table in LDS, the lexicographic minimum of a cell, and the hit list's append.  One
-// copy of each; the cell loops themselves differ (where the rows live) and stay in their units.
+// wave per chunk) share: the cost table in LDS, the lexicographic minimum of a cell, the hit list's append and the
+// best-hit reduce.  One copy of each; the cell loops themselves differ (where the rows live) and stay in their units.
 #pragma once
 #include "sed_internal.h"
 #include "sed_dev.h"
@@ -22,20 +22,23 @@ struct fit_f64_hit_list {
     double max_dist;
 };
 
-// One hit of the lane, decided for the whole wave (sed_fit_dp.h: sed_fit_append, with the wider record)
+// One hit of the lane, decided for the whole wave (sed_dev.h: wave_claim_slot)
 __device__ __forceinline__ void fit_f64_append(const fit_f64_hit_list &hl, bool hit, int32_t pair, int32_t end, int32_t start,
                                                double D) {
-    const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
-    if (b == 0) return;
-    if (hit) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        unsigned long long base = 0;
-        if (rank == 0) base = atomicAdd(hl.count, (unsigned long long)__popcll(b));
-        const unsigned long long slot =
-            (((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-             __builtin_amdgcn_readfirstlane((uint32_t)base)) + rank;
-        if (slot < hl.cap) hl.rec[slot] = sed_fit_f64_hit{(uint32_t)pair, (uint32_t)end, start, 0u, D};
-    }
+    unsigned long long slot;
+    if (wave_claim_slot(hl.count, hit, &slot) && slot < hl.cap)
+        hl.rec[slot] = sed_fit_f64_hit{(uint32_t)pair, (uint32_t)end, start, 0u, D};
+}
+
+// Best hit over a run of records: the first strict minimum of rec[t], rec[t + 1], ... while k < n and same(k), the
+// records that share rec[t]'s key (a pair's lanes, a text's chunk records) in chunk order.  The one copy for the three
+// reduce kernels, which find their records, their key and their output slot.
+template <class Same>
+__device__ __forceinline__ sed_fit_f64_best fit_f64_first_min(const sed_fit_f64_best *__restrict__ rec, int t, int n, Same same) {
+    sed_fit_f64_best b = rec[t];
+    for (int k = t + 1; k < n && same(k); ++k)
+        if (rec[k].D < b.D) b = rec[k];
+    return b;
 }
 
 // (d, s) <- the lexicographic minimum of (d, -s) and (cd, -cs)

@@ -29,6 +29,7 @@
 #include "sed_internal.h"
 #include "sed_dev.h"
 #include "sed_fit_dp.h"
+#include "sed_fit_index_dev.h"
 
 namespace {
 
@@ -118,29 +119,6 @@ __device__ __forceinline__ void sed_fit_long_dp_t(const sed_fit_lane &ln, const 
     atomicMin(out + ln.pair, ((unsigned long long)(uint32_t)bestd << 48) | ((unsigned long long)end << 16) | (bestt & 0xFFFFu));
 }
 
-// The wave's record and its lane's pattern codes: blockIdx.x = the chunk record, q0 + blockIdx.y = the query's place in
-// its group, whose record is pats[64 R place ...]; lane l reads bytes l R .. l R + R - 1 of it.
-template <int R>
-__device__ __forceinline__ sed_fit_lane sed_fit_long_lane(const sed_fit_chunk *__restrict__ chunks,
-                                                          const sed_fit_text *__restrict__ texts, int ntexts,
-                                                          const uint8_t *__restrict__ pats, const int32_t *__restrict__ plens,
-                                                          const int32_t *__restrict__ qlist, int q0, int32_t chunk, int32_t W,
-                                                          uint32_t (&pw)[(R + 3) / 4]) {
-    const int place = q0 + (int)blockIdx.y;
-    const int q = qlist[place];
-    const sed_fit_chunk ck = chunks[blockIdx.x];
-    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
-    ln.pair = q * ntexts + ck.text;
-    const uint8_t *rec = pats + (size_t)place * (64 * R) + threadIdx.x * R;
-    if constexpr (R == 2) {
-        pw[0] = *(const uint16_t *)rec;
-    } else {
-#pragma unroll
-        for (int i = 0; i < R / 4; ++i) pw[i] = ((const uint32_t *)rec)[i];
-    }
-    return ln;
-}
-
 template <int R> struct LongWaves { static constexpr int value = R <= 8 ? 8 : 4; };  // waves per SIMD the registers allow
 
 template <int R>
@@ -152,7 +130,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, LongWaves<R>::value) void sed_fit_in
     sed_fit_fill_tab(tab, fp);
     if ((int)blockIdx.x >= nchunks) return;
     uint32_t pw[(R + 3) / 4];
-    const sed_fit_lane ln = sed_fit_long_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw);
+    int q;  // (not used: these kernels report by ln.pair)
+    const sed_fit_lane ln = sed_fit_long_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw, &q);
     sed_fit_long_dp_t<R, false>(ln, pw, tab, text, out, sed_fit_hit_list{}, fp);
 }
 
@@ -166,50 +145,36 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, LongWaves<R>::value) void sed_fit_in
     sed_fit_fill_tab(tab, fp);
     if ((int)blockIdx.x >= nchunks) return;
     uint32_t pw[(R + 3) / 4];
-    const sed_fit_lane ln = sed_fit_long_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw);
+    int q;  // (not used: these kernels report by ln.pair)
+    const sed_fit_lane ln = sed_fit_long_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw, &q);
     sed_fit_long_dp_t<R, true>(ln, pw, tab, text, nullptr, sed_fit_hit_list{hits, count, cap, cut}, fp);
-}
-
-#define SED_FIT_LONG_MAXY 65535  // queries per launch (the grid's y limit); more run as further launches
-// One R group's launches: the arguments the two kernels share up to the text, then `tail`.
-template <typename Kernel, typename... Tail>
-hipError_t fit_long_launch(Kernel kernel, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
-                           const int32_t *qlist, Tail... tail) {
-    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
-    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_LONG_MAXY) {
-        const int nq = a.nqueries - q0 < SED_FIT_LONG_MAXY ? a.nqueries - q0 : SED_FIT_LONG_MAXY;
-        hipExtLaunchKernelGGL(kernel, dim3((unsigned)a.nchunks, (unsigned)nq), dim3(SED_FIT_BLOCK), 0, stream,
-                              q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr, 0, a.chunks, a.nchunks, a.texts,
-                              a.ntexts, (const uint8_t *)a.pats, a.plens, qlist, q0, (const uint32_t *)a.text, tail...);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
 }
 
 }  // namespace
 
+// One R group's launches (sed_internal.h: sed_fit_long_with_rows, sed_fit_each_query_group), as sed_fit_long_f64.hip's
 hipError_t sed_launch_fit_index_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                      const int32_t *qlist, int rows, const sed_fit_params &fp) {
-    switch (rows) {
-#define SED_FIT_LONG_CASE(R) \
-    case R: return fit_long_launch(sed_fit_index_long_kernel<R>, stream, ev0, ev1, a, qlist, a.out, a.chunk, a.W, fp);
-        SED_FIT_LONG_CASE(2) SED_FIT_LONG_CASE(4) SED_FIT_LONG_CASE(8) SED_FIT_LONG_CASE(16) SED_FIT_LONG_CASE(32)
-#undef SED_FIT_LONG_CASE
-    }
-    return hipErrorInvalidValue;
+    return sed_fit_long_with_rows(rows, [&](auto R) {
+        return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+            hipExtLaunchKernelGGL(sed_fit_index_long_kernel<decltype(R)::value>, dim3((unsigned)a.nchunks, (unsigned)nq),
+                                  dim3(SED_FIT_BLOCK), 0, stream, e0, e1, 0, a.chunks, a.nchunks, a.texts, a.ntexts,
+                                  (const uint8_t *)a.pats, a.plens, qlist, q0, (const uint32_t *)a.text, a.out, a.chunk, a.W, fp);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t sed_launch_fit_index_long_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                           const int32_t *qlist, int rows, void *hits, unsigned long long *count,
                                           unsigned long long cap, int32_t cut, const sed_fit_params &fp) {
-    switch (rows) {
-#define SED_FIT_LONG_CASE(R)                                                                                          \
-    case R:                                                                                                           \
-        return fit_long_launch(sed_fit_index_long_hits_kernel<R>, stream, ev0, ev1, a, qlist, (uint4 *)hits, count, cap, cut, \
-                               a.chunk, a.W, fp);
-        SED_FIT_LONG_CASE(2) SED_FIT_LONG_CASE(4) SED_FIT_LONG_CASE(8) SED_FIT_LONG_CASE(16) SED_FIT_LONG_CASE(32)
-#undef SED_FIT_LONG_CASE
-    }
-    return hipErrorInvalidValue;
+    return sed_fit_long_with_rows(rows, [&](auto R) {
+        return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+            hipExtLaunchKernelGGL(sed_fit_index_long_hits_kernel<decltype(R)::value>, dim3((unsigned)a.nchunks, (unsigned)nq),
+                                  dim3(SED_FIT_BLOCK), 0, stream, e0, e1, 0, a.chunks, a.nchunks, a.texts, a.ntexts,
+                                  (const uint8_t *)a.pats, a.plens, qlist, q0, (const uint32_t *)a.text, (uint4 *)hits, count, cap,
+                                  cut, a.chunk, a.W, fp);
+            return hipGetLastError();
+        });
+    });
 }

@@ -22,11 +22,13 @@
 //     wave owns goes to the wave's record rec[query * nchunks + chunk record]; sed_fit_index_long_f64_reduce_kernel
 //     takes per (query, text) the first strict minimum over the text's records in chunk order.  No atomic takes part.
 //     Hits: every owned column with sink D <= max_dist goes through fit_f64_append (one hitting lane a wave and step).
+//     The lane's record (sed_fit_index_dev.h), the reduce's walk and the append (sed_fit_f64_dp.h) are the one copies.
 // The block is one wave (SED_FIT_BLOCK = 64): blockIdx.x = the chunk record, blockIdx.y = the query within its R group.
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
 #include "sed_fit_f64_dp.h"
+#include "sed_fit_index_dev.h"
 
 namespace {
 
@@ -121,29 +123,6 @@ __device__ __forceinline__ void fit_long_f64_dp(const sed_fit_lane &ln, const ui
     if (!HITS && lane == 63) *best = sed_fit_f64_best{bD, bS, bE};
 }
 
-// The wave's record, its query and its lane's pattern codes (sed_fit_long.hip: sed_fit_long_lane)
-template <int R>
-__device__ __forceinline__ sed_fit_lane fit_long_f64_lane(const sed_fit_chunk *__restrict__ chunks,
-                                                          const sed_fit_text *__restrict__ texts, int ntexts,
-                                                          const uint8_t *__restrict__ pats, const int32_t *__restrict__ plens,
-                                                          const int32_t *__restrict__ qlist, int q0, int32_t chunk, int32_t W,
-                                                          uint32_t (&pw)[(R + 3) / 4], int *query) {
-    const int place = q0 + (int)blockIdx.y;
-    const int q = qlist[place];
-    const sed_fit_chunk ck = chunks[blockIdx.x];
-    sed_fit_lane ln = sed_fit_derive_lane(ck, texts[ck.text], chunk, plens[q], W);
-    ln.pair = q * ntexts + ck.text;
-    *query = q;
-    const uint8_t *rec = pats + (size_t)place * (64 * R) + threadIdx.x * R;
-    if constexpr (R == 2) {
-        pw[0] = *(const uint16_t *)rec;
-    } else {
-#pragma unroll
-        for (int i = 0; i < R / 4; ++i) pw[i] = ((const uint32_t *)rec)[i];
-    }
-    return ln;
-}
-
 template <int R> struct LongF64Waves { static constexpr int value = R <= 4 ? 8 : R == 8 ? 5 : R == 16 ? 3 : 2; };
 
 template <int R>
@@ -157,7 +136,7 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, LongF64Waves<R>::value) void sed_fit
     if ((int)blockIdx.x >= nchunks) return;
     uint32_t pw[(R + 3) / 4];
     int q;
-    const sed_fit_lane ln = fit_long_f64_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw, &q);
+    const sed_fit_lane ln = sed_fit_long_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw, &q);
     fit_long_f64_dp<R, false>(ln, pw, tab, text, rec + (size_t)q * nchunks + blockIdx.x, fit_f64_hit_list{}, ins, del);
 }
 
@@ -169,11 +148,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK) void sed_fit_index_long_f64_reduce_k
     if (t >= nchunks || chunks[t].c0 != 0) return;
     const int q = qlist[q0 + (int)blockIdx.y];
     const int32_t d = chunks[t].text;
-    const sed_fit_f64_best *r = rec + (size_t)q * nchunks;
-    sed_fit_f64_best b = r[t];
-    for (int k = t + 1; k < nchunks && chunks[k].text == d; ++k)
-        if (r[k].D < b.D) b = r[k];
-    out[(size_t)q * ntexts + d] = b;
+    out[(size_t)q * ntexts + d] =
+        fit_f64_first_min(rec + (size_t)q * nchunks, t, nchunks, [&](int k) { return chunks[k].text == d; });
 }
 
 template <int R>
@@ -188,49 +164,8 @@ __global__ __launch_bounds__(SED_FIT_BLOCK, LongF64Waves<R>::value) void sed_fit
     if ((int)blockIdx.x >= nchunks) return;
     uint32_t pw[(R + 3) / 4];
     int q;
-    const sed_fit_lane ln = fit_long_f64_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw, &q);
+    const sed_fit_lane ln = sed_fit_long_lane<R>(chunks, texts, ntexts, pats, plens, qlist, q0, chunk, W, pw, &q);
     fit_long_f64_dp<R, true>(ln, pw, tab, text, nullptr, fit_f64_hit_list{hits, count, cap, max_dist}, ins, del);
-}
-
-#define SED_FIT_LONG_MAXY 65535  // queries per launch (the grid's y limit); more run as further launches
-// launch(nq, q0, e0, e1) for every 65535 queries of one R group (sed_fit_f64.hip: fit_f64_each_group)
-template <typename Launch>
-hipError_t fit_long_f64_each(hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a, Launch launch) {
-    if (a.nchunks <= 0 || a.nqueries <= 0) return hipSuccess;
-    for (int q0 = 0; q0 < a.nqueries; q0 += SED_FIT_LONG_MAXY) {
-        const int nq = a.nqueries - q0 < SED_FIT_LONG_MAXY ? a.nqueries - q0 : SED_FIT_LONG_MAXY;
-        const hipError_t e = launch((unsigned)nq, q0, q0 == 0 ? ev0 : nullptr, q0 + nq == a.nqueries ? ev1 : nullptr);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <int R>
-hipError_t fit_long_f64_search(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
-                               const int32_t *qlist, sed_fit_f64_best *rec, sed_fit_f64_best *out, const sed_fit_f64_costs &fc) {
-    return fit_long_f64_each(ev0, ev1, a, [&](unsigned nq, int q0, hipEvent_t e0, hipEvent_t e1) {
-        hipExtLaunchKernelGGL(sed_fit_index_long_f64_kernel<R>, dim3((unsigned)a.nchunks, nq), dim3(SED_FIT_BLOCK), 0, stream, e0,
-                              nullptr, 0, a.chunks, a.nchunks, a.texts, a.ntexts, (const uint8_t *)a.pats, a.plens, qlist, q0,
-                              (const uint32_t *)a.text, rec, a.chunk, a.W, fc.sub, fc.ins, fc.del);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        const dim3 grid((unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK), nq);
-        hipExtLaunchKernelGGL(sed_fit_index_long_f64_reduce_kernel, grid, dim3(SED_FIT_BLOCK), 0, stream, nullptr, e1, 0,
-                              a.chunks, a.nchunks, a.ntexts, qlist, q0, (const sed_fit_f64_best *)rec, out);
-        return hipGetLastError();
-    });
-}
-
-template <int R>
-hipError_t fit_long_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
-                             const int32_t *qlist, sed_fit_f64_hit *hits, unsigned long long *count, unsigned long long cap,
-                             double max_dist, const sed_fit_f64_costs &fc) {
-    return fit_long_f64_each(ev0, ev1, a, [&](unsigned nq, int q0, hipEvent_t e0, hipEvent_t e1) {
-        hipExtLaunchKernelGGL(sed_fit_index_long_f64_hits_kernel<R>, dim3((unsigned)a.nchunks, nq), dim3(SED_FIT_BLOCK), 0, stream,
-                              e0, e1, 0, a.chunks, a.nchunks, a.texts, a.ntexts, (const uint8_t *)a.pats, a.plens, qlist, q0,
-                              (const uint32_t *)a.text, hits, count, cap, max_dist, a.chunk, a.W, fc.sub, fc.ins, fc.del);
-        return hipGetLastError();
-    });
 }
 
 }  // namespace
@@ -238,23 +173,32 @@ hipError_t fit_long_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
 hipError_t sed_launch_fit_index_long_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                          const int32_t *qlist, int rows, sed_fit_f64_best *rec, sed_fit_f64_best *out,
                                          const sed_fit_f64_costs &fc) {
-    switch (rows) {
-#define SED_FIT_LONG_CASE(R) \
-    case R: return fit_long_f64_search<R>(stream, ev0, ev1, a, qlist, rec, out, fc);
-        SED_FIT_LONG_CASE(2) SED_FIT_LONG_CASE(4) SED_FIT_LONG_CASE(8) SED_FIT_LONG_CASE(16) SED_FIT_LONG_CASE(32)
-#undef SED_FIT_LONG_CASE
-    }
-    return hipErrorInvalidValue;
+    return sed_fit_long_with_rows(rows, [&](auto R) {
+        return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+            hipExtLaunchKernelGGL(sed_fit_index_long_f64_kernel<decltype(R)::value>, dim3((unsigned)a.nchunks, (unsigned)nq),
+                                  dim3(SED_FIT_BLOCK), 0, stream, e0, nullptr, 0, a.chunks, a.nchunks, a.texts, a.ntexts,
+                                  (const uint8_t *)a.pats, a.plens, qlist, q0, (const uint32_t *)a.text, rec, a.chunk, a.W, fc.sub,
+                                  fc.ins, fc.del);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+            const dim3 grid((unsigned)((a.nchunks + SED_FIT_BLOCK - 1) / SED_FIT_BLOCK), (unsigned)nq);
+            hipExtLaunchKernelGGL(sed_fit_index_long_f64_reduce_kernel, grid, dim3(SED_FIT_BLOCK), 0, stream, nullptr, e1, 0,
+                                  a.chunks, a.nchunks, a.ntexts, qlist, q0, (const sed_fit_f64_best *)rec, out);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t sed_launch_fit_index_long_f64_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                               const int32_t *qlist, int rows, sed_fit_f64_hit *hits, unsigned long long *count,
                                               unsigned long long cap, double max_dist, const sed_fit_f64_costs &fc) {
-    switch (rows) {
-#define SED_FIT_LONG_CASE(R) \
-    case R: return fit_long_f64_hits<R>(stream, ev0, ev1, a, qlist, hits, count, cap, max_dist, fc);
-        SED_FIT_LONG_CASE(2) SED_FIT_LONG_CASE(4) SED_FIT_LONG_CASE(8) SED_FIT_LONG_CASE(16) SED_FIT_LONG_CASE(32)
-#undef SED_FIT_LONG_CASE
-    }
-    return hipErrorInvalidValue;
+    return sed_fit_long_with_rows(rows, [&](auto R) {
+        return sed_fit_each_query_group(a.nchunks, a.nqueries, ev0, ev1, [&](int q0, int nq, hipEvent_t e0, hipEvent_t e1) {
+            hipExtLaunchKernelGGL(sed_fit_index_long_f64_hits_kernel<decltype(R)::value>, dim3((unsigned)a.nchunks, (unsigned)nq),
+                                  dim3(SED_FIT_BLOCK), 0, stream, e0, e1, 0, a.chunks, a.nchunks, a.texts, a.ntexts,
+                                  (const uint8_t *)a.pats, a.plens, qlist, q0, (const uint32_t *)a.text, hits, count, cap, max_dist,
+                                  a.chunk, a.W, fc.sub, fc.ins, fc.del);
+            return hipGetLastError();
+        });
+    });
 }

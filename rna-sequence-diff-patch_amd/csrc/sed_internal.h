@@ -2,7 +2,9 @@
 // are in one section ("Fit search" below), read by sed_fit.hip, sed_fit_dp.h, sed_fit_plan.h and sed_fit_runtime.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define SED_MAX_K 32
 
@@ -266,6 +268,22 @@ struct sed_fit_index_args {
     int32_t chunk;
     int32_t W;
 };
+// A search's launches (every index launcher of the four fit units): the queries are a grid's y, so they run in groups of
+// at most SED_FIT_MAX_QUERIES.  launch(q0, nq, e0, e1) runs queries [q0, q0 + nq) and returns its error, the first of
+// which ends the search; it starts e0 with its first kernel and stops e1 with its last.  The events bracket the whole
+// search: ev0 goes to the first group, ev1 to the last, the others get null.  Host code without a kernel in it:
+// tools/fit_groups_check.cpp runs it with a recording callback.
+#define SED_FIT_MAX_QUERIES 65535  // a grid's y extent
+template <class Launch>
+inline hipError_t sed_fit_each_query_group(int nchunks, int nqueries, hipEvent_t ev0, hipEvent_t ev1, Launch launch) {
+    if (nchunks <= 0 || nqueries <= 0) return hipSuccess;
+    for (int q0 = 0; q0 < nqueries; q0 += SED_FIT_MAX_QUERIES) {
+        const int nq = nqueries - q0 < SED_FIT_MAX_QUERIES ? nqueries - q0 : SED_FIT_MAX_QUERIES;
+        const hipError_t e = launch(q0, nq, q0 == 0 ? ev0 : nullptr, q0 + nq == nqueries ? ev1 : nullptr);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 hipError_t sed_launch_fit_index(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                 const sed_fit_params &fp);
 // The same lanes, reporting every owned column whose sink distance * S is <= cut (sed_fit.hip:
@@ -285,6 +303,17 @@ __host__ __device__ inline int sed_fit_long_rows(int P) {  // the smallest R wit
     int R = 2;
     while (64 * R < P) R *= 2;
     return R;
+}
+// `rows` as a compile-time R for the long launchers: f(std::integral_constant<int, R>), or an error for no such R
+template <class F> inline hipError_t sed_fit_long_with_rows(int rows, F f) {
+    switch (rows) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    case 16: return f(std::integral_constant<int, 16>{});
+    case 32: return f(std::integral_constant<int, 32>{});
+    }
+    return hipErrorInvalidValue;
 }
 hipError_t sed_launch_fit_index_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                      const int32_t *qlist, int rows, const sed_fit_params &fp);
@@ -349,7 +378,7 @@ hipError_t sed_launch_fit_index_long_f64_hits(hipStream_t stream, hipEvent_t ev0
 #define SED_JOIN_BLOCK 256
 #define SED_JOIN_MAXLEN 32
 #define SED_JOIN_MAX_GROUPS 65535  // a grid's y extent
-struct sed_join_args {
+struct sed_join_sides {  // the two sides of a launch, the same for every route: s of sed_join_args and sed_join_f64_args
     const void *rows;
     const int32_t *row_len;
     int32_t row0, nrows;
@@ -357,13 +386,19 @@ struct sed_join_args {
     const int32_t *col_len, *col_orig;
     int32_t ncols;
     int32_t self;
+};
+struct sed_join_list {  // the hit list and the two counters, the same for every route: out of both
+    uint4 *hits;
+    unsigned long long *count;
+    unsigned long long cap;
+};
+struct sed_join_args {
+    sed_join_sides s;
     const uint2 *tab;
     uint32_t ins, del, umap;
     int32_t shift;  // log2 S: the bit-parallel variant's D << shift is the scaled distance
     int32_t cut;
-    uint4 *hits;
-    unsigned long long *count;
-    unsigned long long cap;
+    sed_join_list out;
 };
 hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar);
 // The integer join over sequences of 0..SED_JOIN_LONG_MAXLEN symbols (sed_join_long.hip; include/sed.h: sed_join_long_self,
@@ -385,20 +420,32 @@ hipError_t sed_launch_join_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t e
 //   hits     = 16-byte records (row, original column, D's low word, D's high word).
 #define SED_JOIN_F64_MAXK 16
 struct sed_join_f64_args {
-    const void *rows;
-    const int32_t *row_len;
-    int32_t row0, nrows;
-    const void *cols;
-    const int32_t *col_len, *col_orig;
-    int32_t ncols;
-    int32_t self;
+    sed_join_sides s;
     const double *sub;
     const unsigned long long *keep;
     double ins, del, max_dist;
-    uint4 *hits;
-    unsigned long long *count;
-    unsigned long long cap;
+    sed_join_list out;
 };
+// The kernels take both structs by value, so their layout is part of the code objects: every field where it was when
+// each struct spelled its own copy of s and out.
+#define SED_JOIN_AT(T, field, at) static_assert(offsetof(T, field) == at, #T "." #field " moved")
+#define SED_JOIN_SIDES_AT(T)                                                                                         \
+    SED_JOIN_AT(T, s.rows, 0); SED_JOIN_AT(T, s.row_len, 8); SED_JOIN_AT(T, s.row0, 16); SED_JOIN_AT(T, s.nrows, 20); \
+    SED_JOIN_AT(T, s.cols, 24); SED_JOIN_AT(T, s.col_len, 32); SED_JOIN_AT(T, s.col_orig, 40);                       \
+    SED_JOIN_AT(T, s.ncols, 48); SED_JOIN_AT(T, s.self, 52)
+SED_JOIN_SIDES_AT(sed_join_args);
+SED_JOIN_AT(sed_join_args, tab, 56); SED_JOIN_AT(sed_join_args, ins, 64); SED_JOIN_AT(sed_join_args, del, 68);
+SED_JOIN_AT(sed_join_args, umap, 72); SED_JOIN_AT(sed_join_args, shift, 76); SED_JOIN_AT(sed_join_args, cut, 80);
+SED_JOIN_AT(sed_join_args, out.hits, 88); SED_JOIN_AT(sed_join_args, out.count, 96); SED_JOIN_AT(sed_join_args, out.cap, 104);
+static_assert(sizeof(sed_join_args) == 112, "sed_join_args");
+SED_JOIN_SIDES_AT(sed_join_f64_args);
+SED_JOIN_AT(sed_join_f64_args, sub, 56); SED_JOIN_AT(sed_join_f64_args, keep, 64); SED_JOIN_AT(sed_join_f64_args, ins, 72);
+SED_JOIN_AT(sed_join_f64_args, del, 80); SED_JOIN_AT(sed_join_f64_args, max_dist, 88);
+SED_JOIN_AT(sed_join_f64_args, out.hits, 96); SED_JOIN_AT(sed_join_f64_args, out.count, 104);
+SED_JOIN_AT(sed_join_f64_args, out.cap, 112);
+static_assert(sizeof(sed_join_f64_args) == 120, "sed_join_f64_args");
+#undef SED_JOIN_SIDES_AT
+#undef SED_JOIN_AT
 hipError_t sed_launch_join_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_f64_args &a);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first

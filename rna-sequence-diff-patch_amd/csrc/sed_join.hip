@@ -9,7 +9,8 @@
 // lane kernels' number.
 //
 // The walk over the rows - the self rule, the length skip by ballot, the two counters - and the append are
-// sed_join_dev.h's, shared with the kernel for longer sequences (sed_join_long.hip).  The columns are sorted by length,
+// sed_join_dev.h's, shared with the kernel for longer sequences (sed_join_long.hip); the append and the launch also with
+// the fp64 route (sed_join_f64.hip).  The columns are sorted by length,
 // so the 64 columns of a wave have nearly one length, and the skip leaves out whole waves.
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
@@ -28,12 +29,12 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
     constexpr int MM = SED_JOIN_MAXLEN;
     static_assert(MM == 32, "a record is two 16-byte words; the bit-parallel state is one 32-bit word");
     const int t = blockIdx.x * SED_JOIN_BLOCK + threadIdx.x;
-    const bool valid = t < a.ncols;
-    const int tc = valid ? t : a.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
-    const uint4 *pc = reinterpret_cast<const uint4 *>(a.cols) + 2 * (size_t)tc;
+    const bool valid = t < a.s.ncols;
+    const int tc = valid ? t : a.s.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
+    const uint4 *pc = reinterpret_cast<const uint4 *>(a.s.cols) + 2 * (size_t)tc;
     const uint4 q0 = pc[0], q1 = pc[1];
-    const int m = a.col_len[tc];
-    const int orig = a.col_orig[tc];
+    const int m = a.s.col_len[tc];
+    const int orig = a.s.col_orig[tc];
     const uint32_t bw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
     // what the lane keeps of its column
     uint32_t sel[BITPAR ? 1 : MM];
@@ -89,14 +90,6 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
 }  // namespace
 
 hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar) {
-    if (a.nrows <= 0 || a.ncols <= 0) return hipSuccess;
-    const dim3 grid((a.ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK, (a.nrows + SED_JOIN_G - 1) / SED_JOIN_G);
-    if (grid.y > SED_JOIN_MAX_GROUPS) return hipErrorInvalidValue;
-    if (bitpar)
-        hipExtLaunchKernelGGL(sed_join_kernel<true>, grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0,
-                              (const uint32_t *)a.rows, a.row_len, a.tab, a);
-    else
-        hipExtLaunchKernelGGL(sed_join_kernel<false>, grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0,
-                              (const uint32_t *)a.rows, a.row_len, a.tab, a);
-    return hipGetLastError();
+    return bitpar ? sed_join_launch(sed_join_kernel<true>, stream, ev0, ev1, a, a.tab)
+                  : sed_join_launch(sed_join_kernel<false>, stream, ev0, ev1, a, a.tab);
 }

@@ -23,31 +23,16 @@
 // (DESIGN.md 3.6l), and the kernel tests the bit: no floating point is involved in skipping.  A wave none of whose lanes
 // has its bit set for the current row leaves that row out; count[1] counts the pairs whose bit was set.
 // A hit is D <= max_dist, a plain fp64 compare; its record is (row, original column, D's low word, D's high word).
+// The append and the launch are sed_join_dev.h's; the row loop is this kernel's own copy of sed_join_rows there (the
+// shared walk, given the keep bit and the fp64 distance as parameters, compiled to another schedule).
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
+#include "sed_join_dev.h"
 
 namespace {
 
 constexpr int JF_K = SED_JOIN_F64_MAXK;
-
-// sed_join_dev.h's sed_join_append with D as 64 bits: the first hitting lane takes popcount slots with one atomic add, every
-// hitting lane stores at the first slot + its rank among them; slots >= cap only count.
-__device__ __forceinline__ void join_f64_append(const sed_join_f64_args &a, bool hit, int32_t row, int32_t col, double D) {
-    const unsigned long long b = __builtin_amdgcn_ballot_w64(hit);
-    if (b == 0) return;
-    if (hit) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        unsigned long long base = 0;
-        if (rank == 0) base = atomicAdd(a.count, (unsigned long long)__popcll(b));
-        // (the first active lane here is the hitting lane of rank 0)
-        const unsigned long long slot =
-            (((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
-             __builtin_amdgcn_readfirstlane((uint32_t)base)) + rank;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(D);
-        if (slot < a.cap) a.hits[slot] = make_uint4((uint32_t)row, (uint32_t)col, (uint32_t)bits, (uint32_t)(bits >> 32));
-    }
-}
 
 __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint32_t *__restrict__ rows,
                                                                       const int32_t *__restrict__ row_len,
@@ -62,25 +47,25 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint
     for (int e = threadIdx.x; e < JF_K * JF_K; e += SED_JOIN_BLOCK) tab[e] = sub[e];
     __syncthreads();
     const int t = blockIdx.x * SED_JOIN_BLOCK + threadIdx.x;
-    const bool valid = t < a.ncols;
-    const int tc = valid ? t : a.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
-    const uint4 *pc = reinterpret_cast<const uint4 *>(a.cols) + 2 * (size_t)tc;
+    const bool valid = t < a.s.ncols;
+    const int tc = valid ? t : a.s.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
+    const uint4 *pc = reinterpret_cast<const uint4 *>(a.s.cols) + 2 * (size_t)tc;
     const uint4 q0 = pc[0], q1 = pc[1];
-    const int m = a.col_len[tc];
-    const int orig = a.col_orig[tc];
+    const int m = a.s.col_len[tc];
+    const int orig = a.s.col_orig[tc];
     // the column's codes as byte offsets into a table row: 8 b_j, four to a word (b_j < 16: the planner's check)
     uint32_t bw[8] = {(q0.x & 0x0F0F0F0Fu) << 3, (q0.y & 0x0F0F0F0Fu) << 3, (q0.z & 0x0F0F0F0Fu) << 3,
                             (q0.w & 0x0F0F0F0Fu) << 3, (q1.x & 0x0F0F0F0Fu) << 3, (q1.y & 0x0F0F0F0Fu) << 3,
                             (q1.z & 0x0F0F0F0Fu) << 3, (q1.w & 0x0F0F0F0Fu) << 3};
     const char *tb = reinterpret_cast<const char *>(tab);
     const double ins = a.ins, del = a.del;
-    const int rbeg = a.row0 + (int)blockIdx.y * SED_JOIN_G;
-    const int rend = min(rbeg + SED_JOIN_G, a.row0 + a.nrows);
+    const int rbeg = a.s.row0 + (int)blockIdx.y * SED_JOIN_G;
+    const int rend = min(rbeg + SED_JOIN_G, a.s.row0 + a.s.nrows);
     uint32_t ran = 0;
     for (int r = rbeg; r < rend; ++r) {
         const int n = row_len[r];  // (uniform: a scalar load)
         const unsigned long long kn = keep[n];
-        const bool go = valid && !(a.self && orig == r) && ((kn >> m) & 1ull) != 0;
+        const bool go = valid && !(a.s.self && orig == r) && ((kn >> m) & 1ull) != 0;
         const unsigned long long gb = __builtin_amdgcn_ballot_w64(go);
         if (gb == 0) continue;  // no column of this wave can be within the cutoff of row r
         ran += (uint32_t)__popcll(gb);
@@ -119,18 +104,14 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint
 #pragma unroll
             for (int j = 0; j < MM; j += 2 * s) V[j] = (m & s) ? V[j + s] : V[j];
         const double D = m == MM ? V[MM] : V[0];
-        join_f64_append(a, go && D <= a.max_dist, r, orig, D);
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(D);
+        sed_join_append(a.out, go && D <= a.max_dist, r, orig, (uint32_t)bits, (uint32_t)(bits >> 32));
     }
-    if (ran != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.count + 1, (unsigned long long)ran);
+    if (ran != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.out.count + 1, (unsigned long long)ran);
 }
 
 }  // namespace
 
 hipError_t sed_launch_join_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_f64_args &a) {
-    if (a.nrows <= 0 || a.ncols <= 0) return hipSuccess;
-    const dim3 grid((a.ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK, (a.nrows + SED_JOIN_G - 1) / SED_JOIN_G);
-    if (grid.y > SED_JOIN_MAX_GROUPS) return hipErrorInvalidValue;
-    hipExtLaunchKernelGGL(sed_join_f64_kernel, grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0, (const uint32_t *)a.rows,
-                          a.row_len, a.sub, a.keep, a);
-    return hipGetLastError();
+    return sed_join_launch(sed_join_f64_kernel, stream, ev0, ev1, a, a.sub, a.keep);
 }

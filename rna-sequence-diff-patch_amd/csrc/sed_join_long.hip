@@ -37,9 +37,9 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uin
     constexpr int MM = SED_JOIN_LONG_MAXLEN, BL = SED_JOIN_LONG_BLOCK, NW = MM / 4, NB = MM / BL;
     static_assert(BL == 32 && NB == 4, "a block of columns is one word of bit-parallel state; four of them a record");
     const int t = blockIdx.x * SED_JOIN_BLOCK + threadIdx.x;
-    const bool valid = t < a.ncols;
-    const int tc = valid ? t : a.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
-    const uint4 *pc = reinterpret_cast<const uint4 *>(a.cols) + (NW / 4) * (size_t)tc;
+    const bool valid = t < a.s.ncols;
+    const int tc = valid ? t : a.s.ncols - 1;  // (lanes past the last column stay in the wave and report nothing)
+    const uint4 *pc = reinterpret_cast<const uint4 *>(a.s.cols) + (NW / 4) * (size_t)tc;
     uint32_t cw[NW];  // the column's byte codes, four a word
 #pragma unroll
     for (int k = 0; k < NW / 4; ++k) {
@@ -47,8 +47,8 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uin
         cw[4 * k] = q.x & 0x07070707u, cw[4 * k + 1] = q.y & 0x07070707u;
         cw[4 * k + 2] = q.z & 0x07070707u, cw[4 * k + 3] = q.w & 0x07070707u;
     }
-    const int m = a.col_len[tc];
-    const int orig = a.col_orig[tc];
+    const int m = a.s.col_len[tc];
+    const int orig = a.s.col_orig[tc];
     // the blocks of columns (the words of state) the wave's longest column reaches: uniform, 0..4
     int nblk = 0;
 #pragma unroll
@@ -144,14 +144,6 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uin
 }  // namespace
 
 hipError_t sed_launch_join_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar) {
-    if (a.nrows <= 0 || a.ncols <= 0) return hipSuccess;
-    const dim3 grid((a.ncols + SED_JOIN_BLOCK - 1) / SED_JOIN_BLOCK, (a.nrows + SED_JOIN_G - 1) / SED_JOIN_G);
-    if (grid.y > SED_JOIN_MAX_GROUPS) return hipErrorInvalidValue;
-    if (bitpar)
-        hipExtLaunchKernelGGL((sed_join_long_kernel<true, false>), grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0,
-                              (const uint32_t *)a.rows, a.row_len, a.tab, a);
-    else
-        hipExtLaunchKernelGGL((sed_join_long_kernel<false, kSelRegs>), grid, dim3(SED_JOIN_BLOCK), 0, stream, ev0, ev1, 0,
-                              (const uint32_t *)a.rows, a.row_len, a.tab, a);
-    return hipGetLastError();
+    return bitpar ? sed_join_launch(sed_join_long_kernel<true, false>, stream, ev0, ev1, a, a.tab)
+                  : sed_join_launch(sed_join_long_kernel<false, kSelRegs>, stream, ev0, ev1, a, a.tab);
 }

@@ -72,8 +72,8 @@ struct JoinCall {
 };
 
 // What all joins share once their rows are on the device: the plan's launches, the counters, the hit list.
-// a holds the rows (rows, row_len, row0, self); nrows rows from a.row0 on.
-static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_args a, int32_t nrows, sed_join_hit *out, int64_t cap,
+// s holds the rows (rows, row_len, row0, self); nrows rows from s.row0 on.
+static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
                     int64_t *found) {
     sed_ctx *c = ix->ctx;
     if ((uint64_t)cap > SIZE_MAX / sizeof(JoinRec) || !ix->d_count.reserve(16) ||
@@ -83,13 +83,12 @@ static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_args a, int3
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess) return c->hipfail(e, "upload (join)");
-    a.cols = ix->d_cols.p;
-    a.col_len = (const int32_t *)ix->d_col_len.p;
-    a.col_orig = (const int32_t *)ix->d_col_orig.p;
-    a.ncols = ix->nseqs;
-    a.hits = (uint4 *)ix->d_hits.p;
-    a.count = (unsigned long long *)ix->d_count.p;
-    a.cap = (unsigned long long)cap;
+    s.cols = ix->d_cols.p;
+    s.col_len = (const int32_t *)ix->d_col_len.p;
+    s.col_orig = (const int32_t *)ix->d_col_orig.p;
+    s.ncols = ix->nseqs;
+    const sed_join_list list{(uint4 *)ix->d_hits.p, (unsigned long long *)ix->d_count.p, (unsigned long long)cap};
+    sed_join_args a{};  // (one of a and f is filled and launched: the call's route)
     sed_join_f64_args f{};
     if (k.pi) {
         const sed_join_plan_t &plan = *k.pi;
@@ -101,31 +100,36 @@ static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_args a, int3
         a.umap = plan.sp.umap;
         a.shift = plan.scale_log2;
         a.cut = plan.cut;
+        a.out = list;
     } else {  // one block: [the table | the keep words]
         const sed_join_f64_plan_t &plan = *k.pf;
         static_assert(sizeof ix->h_f64 == sizeof plan.sub + sizeof plan.keep, "the upload's layout");
         memcpy(ix->h_f64, plan.sub, sizeof plan.sub);
         memcpy(ix->h_f64 + F64_TAB, plan.keep, sizeof plan.keep);
         e = hipMemcpyAsync(ix->d_f64.p, ix->h_f64, sizeof ix->h_f64, hipMemcpyHostToDevice, c->stream);
-        f.rows = a.rows; f.row_len = a.row_len; f.self = a.self;
-        f.cols = a.cols; f.col_len = a.col_len; f.col_orig = a.col_orig; f.ncols = a.ncols;
         f.sub = (const double *)ix->d_f64.p;
         f.keep = (const unsigned long long *)ix->d_f64.p + F64_TAB;
         f.ins = plan.ins;
         f.del = plan.del;
         f.max_dist = plan.max_dist;
-        f.hits = a.hits; f.count = a.count; f.cap = a.cap;
+        f.out = list;
     }
     if (e != hipSuccess) return c->hipfail(e, "upload (join)");
-    const int32_t first = a.row0;
+    const int32_t first = s.row0;
     const int64_t step = k.launch_rows();
     for (int64_t r = 0; r < nrows; r += step) {  // the events bracket the launches
-        a.row0 = f.row0 = first + (int32_t)r;
-        a.nrows = f.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
+        s.row0 = first + (int32_t)r;
+        s.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
         hipEvent_t e0 = r == 0 ? ix->timer.ev[0] : nullptr, e1 = r + step >= nrows ? ix->timer.ev[1] : nullptr;
-        e = !k.pi ? sed_launch_join_f64(c->stream, e0, e1, f)
-            : ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long(c->stream, e0, e1, a, k.pi->kernel == SED_JOIN_KERNEL_BITPAR)
-                                                 : sed_launch_join(c->stream, e0, e1, a, k.pi->kernel == SED_JOIN_KERNEL_BITPAR);
+        if (!k.pi) {
+            f.s = s;
+            e = sed_launch_join_f64(c->stream, e0, e1, f);
+        } else {
+            a.s = s;
+            const bool bitpar = k.pi->kernel == SED_JOIN_KERNEL_BITPAR;
+            e = ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long(c->stream, e0, e1, a, bitpar)
+                                                   : sed_launch_join(c->stream, e0, e1, a, bitpar);
+        }
         if (e != hipSuccess) return c->hipfail(e, "join kernel launch");
     }
     if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
@@ -289,12 +293,12 @@ static int join_self(sed_join_index *ix, bool f64, int32_t row_lo, int32_t row_h
     *found = 0;
     ix->pairs_run = 0;
     if (nrows == 0) return SED_OK;
-    sed_join_args a{};
-    a.rows = ix->d_rows.p;
-    a.row_len = (const int32_t *)ix->d_row_len.p;
-    a.row0 = row_lo;
-    a.self = 1;
-    return join_run(ix, k, a, nrows, out, cap, found);
+    sed_join_sides s{};
+    s.rows = ix->d_rows.p;
+    s.row_len = (const int32_t *)ix->d_row_len.p;
+    s.row0 = row_lo;
+    s.self = 1;
+    return join_run(ix, k, s, nrows, out, cap, found);
 }
 
 static int join_search(sed_join_index *ix, bool f64, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
@@ -327,12 +331,12 @@ static int join_search(sed_join_index *ix, bool f64, const uint8_t *codes_q, con
     if (!ix->d_query.reserve(qbytes)) return c->fail(SED_E_OOM, "device allocation failed (join, %d queries)", nqueries);
     hipError_t e = hipMemcpyAsync(ix->d_query.p, ix->h_query.data(), qbytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) return c->hipfail(e, "upload (join queries)");
-    sed_join_args a{};
-    a.rows = ix->d_query.p;
-    a.row_len = (const int32_t *)((const uint8_t *)ix->d_query.p + o_len);
-    a.row0 = 0;
-    a.self = 0;
-    return join_run(ix, k, a, nqueries, out, cap, found);
+    sed_join_sides s{};
+    s.rows = ix->d_query.p;
+    s.row_len = (const int32_t *)((const uint8_t *)ix->d_query.p + o_len);
+    s.row0 = 0;
+    s.self = 0;
+    return join_run(ix, k, s, nqueries, out, cap, found);
 }
 
 extern "C" {
