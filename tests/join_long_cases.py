@@ -1,7 +1,8 @@
 """The similarity join over sequences of 0..128 symbols (sed_join_long_self / sed_join_long_search):
 the sequence sets, the planner's recount and the two lanes of sed_join_long.hip restated word for word, shared by the
-CPU tests (tests/test_join_long_host.py) and the GPU tests (tests/test_gpu_join_long.py).  No device is needed here.
-The reference is join_cases.oracle_matrix throughout."""
+CPU tests (tests/test_join_long_host.py) and the GPU tests (tests/test_gpu_join_long.py, and across the envelope - code
+maps and shifts, row and column geometry, the last query's look-ahead, code positions, the cutoff clamp -
+tests/test_gpu_join_long_envelope.py).  No device is needed here.  The reference is join_cases.oracle_matrix throughout."""
 import math
 
 import numpy as np
@@ -121,6 +122,111 @@ def random_set(seed=2024, count=300):
     return seqs[:count]
 
 
+# ---- the envelope's sets: code maps and shifts, code positions, the last query, column geometry ----
+
+EDGE_LENGTHS = (0, 1, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128)  # the word (block) edges and their neighbours
+
+
+def near_set_long(seed, symbols, count):
+    """`count` near-prefixes of one 128-mer over `symbols`: every EDGE_LENGTHS length as the exact prefix and once more
+    as a variant, a second exact copy of 32, 96 and 128 symbols (pairs at distance 0), and random lengths 0..128; a
+    variant has 0..3 substitutions, or is the prefix of one more symbol with one deletion.  Shuffled."""
+    rng = np.random.default_rng(seed)
+    base = jc.random_seq(rng, symbols, MAXLEN)
+    exact = list(EDGE_LENGTHS) + [32, 96, 128]
+    assert count >= len(exact) + len(EDGE_LENGTHS)
+    lens = list(EDGE_LENGTHS) + [int(x) for x in rng.integers(0, MAXLEN + 1, size=count - len(exact) - len(EDGE_LENGTHS))]
+    seqs = [base[:n] for n in exact]
+    for n in lens:
+        kind = int(rng.integers(5))
+        if kind == 4 and n < MAXLEN:
+            p = int(rng.integers(n + 1))
+            seqs.append(base[:p] + base[p + 1:n + 1])
+        else:
+            s = list(base[:n])
+            for _ in range(min(kind, 3) if n else 0):
+                s[int(rng.integers(n))] = jc.random_seq(rng, symbols, 1)
+            seqs.append("".join(s))
+    return [seqs[i] for i in rng.permutation(len(seqs))]
+
+
+def bitpar_long_sets():
+    """name -> (plan, S, rows, columns) over je.bitpar_tables(): S > 1 and, but for "costs ACGUN", a code map that is not
+    the identity.  The two square sets (rows is columns) are near_set_longs of 100; "one way" has 30 queries over codes
+    {0, 1} and one more, the last, carrying a fifth code (which plans the DP), against 70 columns over codes {6, 7}."""
+    out = {}
+    for name, (plan, S, symbols) in je.bitpar_tables().items():
+        if symbols is None:
+            rows = near_set_long(11, je.ALPHA[0:2], 30)
+            q = max(rows, key=len)
+            out[name] = (plan, S, rows + [q[:5] + je.ALPHA[2] + q[5:100]], near_set_long(12, je.ALPHA[6:8], 70))
+        else:
+            seqs = near_set_long(13 + S, symbols, 100)
+            out[name] = (plan, S, seqs, seqs)
+    return out
+
+
+def code_position_set():
+    """40 sequences over the eight codes: the rotations of ALPHA[:8] * 16 by 0..7 (code (j + r) % 8 at position j, so
+    every code stands at every j & 3 of a code word in every block of 32 columns), each once more with one
+    substitution, and the rotations' prefixes of 96, 64 and 32 symbols."""
+    rng = np.random.default_rng(8)
+    al = je.ALPHA[:8]
+    rot = [(al[r:] + al[:r]) * (MAXLEN // 8) for r in range(8)]
+    sub = []
+    for s in rot:
+        p = int(rng.integers(MAXLEN))
+        sub.append(s[:p] + al[(al.index(s[p]) + 1 + int(rng.integers(7))) % 8] + s[p + 1:])
+    return rot + sub + [s[:n] for n in (96, 64, 32) for s in rot]
+
+
+def code_positions(seqs):
+    """{(code, j & 3, j >> 5)} over the 128-symbol sequences of seqs."""
+    return {(je.ALPHA.index(c), j & 3, j >> 5) for s in seqs if len(s) == MAXLEN for j, c in enumerate(s)}
+
+
+def last_query_sets():
+    """(plan, S, columns, query lists, a larger query list) under je's "unit block" table (the bit-parallel variant
+    through a code map that is not the identity; the DP when forced).  Every list ends with one 128-symbol query, and
+    one list is that query alone: its record is the last of the upload [records | spare | lengths], so the row reader's
+    look-ahead past it reads the spare bytes.  The query's last four symbols are the block's four codes, all different
+    and nonzero; the columns hold it once exactly and once with two substitutions, among a near_set_long of 40."""
+    plan, S, symbols = je.bitpar_tables()["unit block"]
+    rng = np.random.default_rng(33)
+    head = jc.random_seq(rng, symbols, MAXLEN - 4)
+    q128 = head + symbols[2] + symbols[0] + symbols[3] + symbols[1]
+    near = q128[:40] + symbols[(symbols.index(q128[40]) + 1) % 4] + q128[41:126] + q128[127] + q128[127]
+    cols = near_set_long(34, symbols, 40) + [q128, near]
+    other = near_set_long(35, symbols, 30)
+    lists = [[q128], other[:3] + [q128], ["", q128[:127], other[5], q128[1:], q128]]
+    return plan, S, cols, lists, other[:20]
+
+
+def column_geometry_set():
+    """257 sequences over ACGU for the prefixes seqs[:N], N = 1, 2, 63, 64, 65, 255, 256, 257: the first has 128 symbols
+    and every other at most 96, so in each prefix the sorted columns end with that one in the last wave, beside columns
+    that stop at or below the 96 / 97 block edge it crosses, and (N & 63 != 0) beside spare lanes that copy it.
+    Near-prefixes of one 128-mer, so small cutoffs keep some pairs."""
+    rng = np.random.default_rng(257)
+    base = jc.random_seq(rng, "ACGU", MAXLEN)
+    seqs = [base]
+    while len(seqs) < 257:
+        s = list(base[:int(rng.integers(0, 97))])
+        for _ in range(int(rng.integers(0, 3)) if s else 0):
+            s[int(rng.integers(len(s)))] = jc.random_seq(rng, "ACGU", 1)
+        seqs.append("".join(s))
+    return seqs
+
+
+COLUMN_COUNTS = (1, 2, 63, 64, 65, 255, 256, 257)
+
+
+def waves_of(nrows, ncols, launch_rows, G=4, block=256):
+    """sed_join_plan's "waves": the column blocks x the row groups of every launch x the block's waves."""
+    groups = sum((min(launch_rows, nrows - r) + G - 1) // G for r in range(0, nrows, launch_rows))
+    return ((ncols + block - 1) // block) * groups * (block // 64) if ncols else 0
+
+
 # ---- the planner's counts, from their definition ----
 
 def lane_cells(len_rows, len_cols, keep):
@@ -237,6 +343,78 @@ def bitpar_distance(x, y, words=None):
         keep = M32 if bits >= 32 else (1 << bits) - 1
         D += bin(Pv[k] & keep).count("1") - bin(Mv[k] & keep).count("1")
     return D & M32
+
+
+# ---- the bit-parallel kernel's lane under the planner's code map (sed_join_long_kernel<true, ...>), word for word ----
+
+SPARE = 16  # sed_join_runtime.cpp: the spare bytes that end a record buffer
+
+
+def record_words(seqs):
+    """[records | spare] as the runtime uploads byte codes (128 zero-padded bytes a sequence), as 32-bit words."""
+    buf = np.zeros(MAXLEN * len(seqs) + SPARE, np.uint8)
+    for r, c in enumerate(seqs):
+        buf[MAXLEN * r:MAXLEN * r + len(c)] = c
+    return buf.view("<u4").astype(np.int64)
+
+
+def popcount(x):
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    x = (x + (x >> 4)) & 0x0F0F0F0F
+    return ((x * 0x01010101) & M32) >> 24
+
+
+def bitpar_lane_matrix(umap, shift, rows, cols, words=0):
+    """D S of every (row, column) pair of byte-code arrays through the bit-parallel kernel's lane, side by side in numpy
+    with 32-bit words held in int64: the column's 128 zero-padded codes through ubfe(umap, 2 code, 2) into two bit
+    planes over four words (the padding maps through umap's field 0); the row reader (w0, w1 and the look-ahead
+    pr[(i >> 2) + 2] over [records | spare]); the row symbol through umap; every word k < nblk, nblk = the larger of
+    the column's own count and `words` (what a wave with a longer column runs); the sink over m bits; D << shift."""
+    NW = MAXLEN // 4
+    R, Cn = len(rows), len(cols)
+    n = np.array([len(s) for s in rows], np.int64)
+    m = np.array([len(s) for s in cols], np.int64)
+    pr = record_words(rows)
+    base = NW * np.arange(R)
+    cw = record_words(cols)[:NW * Cn].reshape(Cn, NW) & 0x07070707
+    E0, E1 = np.zeros((Cn, 4), np.int64), np.zeros((Cn, 4), np.int64)
+    for j in range(MAXLEN):
+        u = (umap >> (2 * ((cw[:, j >> 2] >> (8 * (j & 3))) & 7))) & 3
+        E0[:, j >> 5] |= (u & 1) << (j & 31)
+        E1[:, j >> 5] |= (u >> 1) << (j & 31)
+    nblk = np.maximum((m + BLOCK - 1) // BLOCK, words)
+    assert words <= MAXLEN // BLOCK
+    Pv = [np.full((R, Cn), M32, np.int64) for _ in range(4)]
+    Mv = [np.zeros((R, Cn), np.int64) for _ in range(4)]
+    w0, w1 = pr[base], pr[base + 1]
+    for i in range(int(n.max()) if R else 0):
+        live = i < n
+        c = (w0 >> (8 * (i & 3))) & 7
+        if (i & 3) == 3:
+            w0 = np.where(live, w1, w0)
+            w1 = np.where(live, pr[base + (i >> 2) + 2], w1)
+        u = (umap >> (2 * c)) & 3
+        f0, f1 = np.where(u & 1, M32, 0)[:, None], np.where(u >> 1, M32, 0)[:, None]
+        cadd, cph, cmh = np.zeros((R, Cn), np.int64), np.ones((R, Cn), np.int64), np.zeros((R, Cn), np.int64)
+        for k in range(4):
+            run = live[:, None] & (k < nblk)[None, :]
+            tq = (E0[None, :, k] ^ f0) | (E1[None, :, k] ^ f1)
+            P, M, cadd, cph, cmh = bitpar_word(Pv[k], Mv[k], tq, cadd, cph, cmh)
+            Pv[k], Mv[k] = np.where(run, P, Pv[k]), np.where(run, M, Mv[k])
+    D = np.broadcast_to(n[:, None], (R, Cn)).copy()
+    for k in range(4):
+        bits = np.clip(m - BLOCK * k, 0, 32)
+        keep = ((np.int64(1) << bits) - 1)[None, :]
+        D += np.where((k < nblk)[None, :], popcount(Pv[k] & keep) - popcount(Mv[k] & keep), 0)
+    return (D << shift) & M32
+
+
+def mapped_matrix(plan, S, rows, cols, words=0):
+    """bitpar_lane_matrix of sequences under the planner's map (je.unit_map restates join_unit_costs) and shift log2 S."""
+    umap = je.unit_map(plan, jc.codes_mask(plan, rows), jc.codes_mask(plan, cols))
+    assert umap is not None
+    return bitpar_lane_matrix(umap, S.bit_length() - 1, jc.encode(plan, rows), jc.encode(plan, cols), words)
 
 
 # ---- an oracle-backed engine for the Python layers ----

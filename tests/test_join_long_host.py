@@ -1,6 +1,8 @@
 """CPU: the long similarity join (sequences of 0..128 symbols): its planner (sed_join_long_plan), the two lanes of
 sed_join_long.hip as word-for-word models against the C oracle across their numeric envelope, and the Python layers
-(wfsearch.JoinIndex / neighbors, sedshard.neighbors with long_sequences=True) over an oracle-backed engine."""
+(wfsearch.JoinIndex / neighbors, sedshard.neighbors with long_sequences=True) over an oracle-backed engine; and the cases
+of tests/test_gpu_join_long_envelope.py proved before a device sees them: the planner's choice, the bit-parallel lane
+under a code map and a shift, what each set claims to hold, and the planner's counts of every call made there."""
 import math
 import os
 import socket
@@ -364,3 +366,176 @@ def test_sharded_long_neighbors_world_1_and_2():
         p.join(timeout=60)
         assert p.exitcode == 0
     assert got == (one["row"].tolist(), one["col"].tolist(), one["dist"].tolist())
+
+
+# ---- the envelope's cases, proved before tests/test_gpu_join_long_envelope.py runs them on a device ----
+
+_ENV = {}  # computed once, shared, never changed
+IDENTITY_MAP = 0b11100100  # ubfe(umap, 2 c, 2) = c for c = 0..3
+
+
+def bitpar_case(name):
+    """(plan, S, rows, columns, the oracle's D) of jl.bitpar_long_sets()[name]."""
+    if name not in _ENV:
+        plan, S, rows, cols = jl.bitpar_long_sets()[name]
+        D = jc.oracle_matrix(plan, rows, cols)
+        D.setflags(write=False)
+        _ENV[name] = (plan, S, rows, cols, D)
+    return _ENV[name]
+
+
+def _plan_of(plan, rows, cols, T, self_join=False, options=None):
+    return sedgpu.join_long_plan(jc.costs_of(plan), options or {}, [len(s) for s in rows], [len(s) for s in cols], self_join,
+                                 jc.codes_mask(plan, rows), jc.codes_mask(plan, cols), T)
+
+
+@pytest.mark.parametrize("name", list(je.bitpar_tables()))
+def test_bitpar_cases_plan_the_bit_parallel_kernel(name):
+    plan, S, rows, cols, _ = bitpar_case(name)
+    forced = {sedgpu.SED_OPT_JOIN_DP: 2}
+    assert S > 1 and je.scale_of(plan) == S
+    if name == "one way":
+        queries = rows[:-1]
+        assert (jc.codes_mask(plan, queries), jc.codes_mask(plan, rows), jc.codes_mask(plan, cols)) == (0b11, 0b111, 0b11000000)
+        assert len(queries) == 30 and len(cols) == 70 and len(rows[-1]) > 96
+        assert _plan_of(plan, rows, cols, 1.0)["kernel"] == 1  # the fifth code
+        assert _plan_of(plan, cols, queries, 1.0)["kernel"] == 1  # the other way costs 0.5
+        rows = queries
+    else:
+        assert rows is cols
+    for self_join in ((False,) if name == "one way" else (False, True)):
+        for T in je.BITPAR_CUTOFFS:
+            p = _plan_of(plan, rows, cols, T, self_join)
+            assert (p["scale"], p["kernel"]) == (S, 2), (name, T)
+            assert _plan_of(plan, rows, cols, T, self_join, forced)["kernel"] == 1
+    umap = je.unit_map(plan, jc.codes_mask(plan, rows), jc.codes_mask(plan, cols))
+    assert (umap == IDENTITY_MAP) == (name == "costs ACGUN")
+
+
+@pytest.mark.parametrize("name", list(je.bitpar_tables()))
+def test_bitpar_lane_model_under_the_code_map(name):
+    """The kernel's umap step on both sides (the columns' zero padding included), its row reader and its << shift
+    against oracle * S: on every pair of the set, under every count of words a wave could run for a column (words = 0:
+    the column's own; 1..4: at least that many, as beside a longer column)."""
+    plan, S, rows, cols, D = bitpar_case(name)
+    square = rows is cols
+    if name == "one way":
+        rows, D = rows[:-1], D[:-1]
+    want = D * S
+    assert np.array_equal(want, np.floor(want)) and (want.max() > 100 * S or name == "one way")
+    for words in range(5):
+        DS = jl.mapped_matrix(plan, S, rows, cols, words)
+        assert np.array_equal(DS, want.astype(np.int64)), (name, words)
+    for T in je.BITPAR_CUTOFFS:
+        got = je.hits_of_scaled(DS, je.planner_cut(T, S), S, square)
+        assert jc.same_hits(got, je.expected_hits(D, T, S, square)), (name, T)
+    if not square:
+        assert not np.array_equal(D, jc.oracle_matrix(plan, cols, rows).T)  # the other way costs 0.5
+
+
+def test_bitpar_lane_matrix_is_the_scalar_model_under_the_identity_map():
+    rng = np.random.default_rng(44)
+    rows = [rng.integers(0, 4, size=n).astype(np.uint8) for n in (0, 1, 5, 33, 97, 128)]
+    cols = [rng.integers(0, 4, size=m).astype(np.uint8) for m in (0, 2, 32, 64, 65, 128)]
+    for words in (0, 4):
+        DS = jl.bitpar_lane_matrix(IDENTITY_MAP, 3, rows, cols, words)
+        for i, x in enumerate(rows):
+            for j, y in enumerate(cols):
+                assert DS[i, j] == jl.bitpar_distance(x.tolist(), y.tolist(), words or None) << 3
+
+
+@pytest.mark.parametrize("name", ["costs ACGUN", "unit block"])
+def test_square_sets_are_split_by_every_cutoff(name):
+    plan, S, seqs, _, D = bitpar_case(name)
+    symbols = je.bitpar_tables()[name][2]
+    lens = {len(s) for s in seqs}
+    assert len(seqs) == 100 and not set("".join(seqs)) - set(symbols)
+    assert set(jl.EDGE_LENGTHS) <= lens and len(lens) > 40 and max(lens) == 128 and min(lens) == 0
+    counts = [len(je.expected_hits(D, T, S, True)) for T in je.BITPAR_CUTOFFS]
+    assert 0 < counts[0] < counts[1] == counts[2] == counts[3] < counts[4] < counts[5] == 100 * 99
+    # distances 0, 1 and 2 among sequences of 95 symbols and more: all four words are live where the cutoffs split
+    long = [i for i, s in enumerate(seqs) if len(s) >= 95]
+    assert {0.0, 1.0, 2.0} <= set(D[np.ix_(long, long)][~np.eye(len(long), dtype=bool)].tolist())
+
+
+def test_code_position_set_covers_every_position():
+    seqs = jl.code_position_set()
+    assert len(seqs) == 40 and sorted({len(s) for s in seqs}) == [32, 64, 96, 128]
+    assert jl.code_positions(seqs[:8]) == {(c, p, b) for c in range(8) for p in range(4) for b in range(4)}
+    assert len(jl.code_positions(seqs)) == 8 * 4 * 4
+    assert all(sum(a != b for a, b in zip(seqs[r], seqs[8 + r])) == 1 for r in range(8))
+    for name in ("i127_d128", "unit block"):
+        plan = je.limit_tables()[name][0] if name == "i127_d128" else je.unit_block_table()
+        assert plan.K == 8 and jc.codes_mask(plan, seqs) == 0xFF
+        assert _plan_of(plan, seqs, seqs, 1.0, True)["kernel"] == 1  # eight codes: the DP
+        D = jc.oracle_matrix(plan, seqs[:16], seqs[:16])
+        assert len(np.unique(D)) > 4, name
+
+
+def test_last_query_sets_end_with_the_128_symbol_query():
+    plan, S, cols, lists, larger = jl.last_query_sets()
+    q128 = lists[0][0]
+    assert lists[0] == [q128] and len(q128) == 128 and all(q[-1] == q128 for q in lists)
+    assert len(larger) > max(len(q) for q in lists) and all(len(q) >= 2 for q in lists[1:])
+    last4 = [int(c) for c in plan.encode(q128[-4:])]
+    assert len(set(last4)) == 4 and 0 not in last4
+    assert S == 64 and max(len(s) for s in cols) == 128
+    D = jc.oracle_matrix(plan, [q128], cols)[0]
+    assert (D[-2], D[-1]) == (0.0, 2.0) and sorted(D.tolist())[2] > 3.0  # the planted copies, and nothing else near
+    assert _plan_of(plan, lists[2], cols, 3.0)["kernel"] == 2
+    # the model reads the look-ahead words past the last record from the spare bytes: pr[32] and pr[33]
+    assert len(jl.record_words([plan.encode(q128)])) == 32 + jl.SPARE // 4 >= 34
+    for q in lists:
+        Dq = jc.oracle_matrix(plan, q, cols)
+        assert np.array_equal(jl.mapped_matrix(plan, S, q, cols, 4), (Dq * S).astype(np.int64))
+
+
+def test_column_geometry_set_ends_every_prefix_with_the_longest_column():
+    seqs = jl.column_geometry_set()
+    lens = [len(s) for s in seqs]
+    assert len(seqs) == 257 and lens[0] == 128 and max(lens[1:]) <= 96 and min(lens) == 0 and set("".join(seqs)) == set("ACGU")
+    for N in jl.COLUMN_COUNTS:
+        col = je.sorted_lengths(seqs[:N])
+        last = col[64 * ((N - 1) // 64):]
+        assert last[-1] == 128 and all(m <= 96 for m in last[:-1]) and len(last) == (N - 1) % 64 + 1
+    assert max(je.sorted_lengths(seqs[:65])[:64]) <= 96  # N = 65: a wave of three blocks, then the one column of four
+
+
+@pytest.mark.parametrize("which", ["unit", "user"])
+def test_counts_of_the_geometry_cases(which):
+    """scope, run, cells, lane_cells and waves of the calls the GPU envelope makes: the column counts around the wave
+    and block edges, rows=(lo, hi) ranges and query counts around a row group, and more rows than one launch."""
+    G = sedgpu.join_rows_per_group()
+    plan, S = jl.unit_plan() if which == "unit" else jl.user_plan()
+    ins, dele = float(plan.ins), float(plan.dele)
+    one_launch = 65535 * G
+
+    def check(len_rows, len_cols, T, self_rows=None, options=None, launch_rows=one_launch):
+        p = _long(plan, len_rows, len_cols, T, self_rows is not None, options=options)
+        assert p["scope"] == len(len_rows) * len(len_cols) - (len(len_rows) if self_rows is not None else 0)
+        assert (p["run"], p["cells"]) == jc.lower_bound_count(len_rows, len_cols, ins, dele, T, S, self_rows=self_rows)
+        assert p["lane_cells"] == jl.lane_cells(len_rows, len_cols, jl.keep_rule(ins, dele, T, S))
+        assert p["waves"] == jl.waves_of(len(len_rows), len(len_cols), launch_rows, G)
+        return p
+
+    lens = [len(s) for s in jl.column_geometry_set()]
+    for N in jl.COLUMN_COUNTS:
+        for T in (2.0, INF):
+            p = check(lens[:N], lens[:N], T, list(range(N)))
+            assert (p["run"] == N * (N - 1)) == (T == INF or N == 1)
+            check([lens[3 % N], lens[0], lens[N - 1]], lens[:N], T)
+    grid = [len(s) for s in jl.near_grid(1, "ACGU")]
+    N = 70
+    for R in (G - 1, G, G + 1, 2 * G + 1):
+        for T in (2.0, INF):
+            for lo in (0, 5, N - R):
+                check(grid[lo:lo + R], grid[:N], T, list(range(lo, lo + R)))
+            check(grid[N:N + R], grid[:N], T)
+    N = 2 * (G + 1) + 3
+    rows_opt = {sedgpu.SED_OPT_JOIN_ROWS: G + 1}
+    for T in (1.0, INF):
+        p = check(grid[:N], grid[:N], T, list(range(N)), rows_opt, G + 1)
+        assert p["waves"] == 4 * (2 + 2 + 1)
+        q = check(grid[:N], grid[:N], T, list(range(N)))
+        assert q["waves"] == 4 * 4 and {k: p[k] for k in p if k != "waves"} == {k: q[k] for k in q if k != "waves"}
+        check(grid[20:20 + N], grid[:N], T, None, rows_opt, G + 1)
