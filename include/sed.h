@@ -620,8 +620,9 @@ int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double 
  * max_dist is never computed, and a wave whose 64 columns all fail it skips the row.  More rows than one launch takes
  * (65535 groups of sed_join_rows_per_group rows; SED_OPT_JOIN_ROWS) run as further launches of the same call.
  * Not served: tables the conditions refuse (IUPAC: the _f64 calls below serve them), sequences over 32 symbols (the
- * sed_join_long_ calls below serve up to 128), edit scripts of the hits, k-nearest lists, the i < j half alone for
- * symmetric tables, a per-tile mix of the two variants. */
+ * sed_join_long_ calls below serve up to 128), edit scripts of the hits, the i < j half alone for symmetric tables, a
+ * per-tile mix of the two variants; of the k-nearest calls below: an fp64 route (their selection works on integer
+ * keys) and k > 64. */
 typedef struct sed_join_index sed_join_index;
 typedef struct { int32_t row, col; double dist; } sed_join_hit;
 sed_join_index *sed_join_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
@@ -648,6 +649,54 @@ int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, 
                   double del, int del_is_int, const int32_t *options, int noptions,
                   const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
                   uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
+
+/* The k nearest columns of every row (an extension; it batches the same reference lines as the join: wf_score(query,
+ * doc) over a whole collection, IRMethods.py:435-440 inside search_collection's loop, IRMethods.py:443-477, each a full
+ * wagnerFisher(str1, str2), StringEditDistance.py:133-224, followed by the sort that shows the best few): for every row
+ * in the scope of sed_join_self / sed_join_search, the k columns of smallest distance, exact and deterministic, through
+ * the integer route's kernels (both variants).
+ *   Scope: sed_join_self's or sed_join_search's; a self join never reports (i, i); duplicates are ordinary columns.
+ *   Order within a row: by (scaled distance D, original column index); the result is the first min(k, the in-scope
+ *   columns with D <= floor(max_dist * S)) of them.  max_dist = +inf: no cap; NaN or negative: SED_E_ARG.
+ *   k = 1..64 (a wave selects among its 64 lanes); anything else: SED_E_ARG, the text names k.
+ *   out: sed_join_hit records sorted by (row, dist, col): each row's neighbours together, nearest first; dist = D / S as
+ *   for the join, the reference's wagnerFisher(...).value bit for bit for the tables served.
+ * Everything else is the integer join's: the cap protocol (*found = the records of the result, always set; SED_E_RANGE
+ * names both numbers; cap = 0 with out = NULL counts; the index stays usable), the state errors, the cost models served
+ * and the order of refusals (k is checked with the arguments), a code >= K: SED_E_ARG, SED_OPT_JOIN_DP,
+ * SED_OPT_JOIN_ROWS and the 65535-group limit handled by further launches.
+ * Two passes over the rows, no wave waits for another: pass 1 keeps a bound for every row, starting at floor(max_dist * S)
+ * and lowered to the k-th smallest distance any wave of 64 columns finds among its own; pass 2 is the join with the row's
+ * bound as the cutoff, so it appends the k nearest and every tie at the k-th place, at most what sed_join_self appends at
+ * max_dist; the host keeps each row's first k (sed_join_knn_trim).  The device list is sized for the untrimmed candidates
+ * and grows when pass 2 overflows it (pass 2 then runs once more).
+ * sed_join_last_time and sed_join_pairs_run report these calls too: the device time from the first pass 1 to the last
+ * pass 2 (a second pass 2 and the wait before it included), and the pairs both passes ran (a second pass 2 not counted). */
+int sed_join_knn_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist, sed_join_hit *out,
+                      int64_t cap, int64_t *found);
+int sed_join_knn_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                        int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+/* The last k-nearest call's per-row bounds after pass 1, on the integer scale (D * S): bounds[i] belongs to row row_lo + i
+ * (query i), n = the call's rows exactly (else SED_E_ARG).  A call that launched nothing (no rows, or no columns) reports
+ * floor(max_dist * S), clamped to 65535, for every row.  SED_E_STATE before the first k-nearest call that got past its plan. */
+int sed_join_knn_bounds(const sed_join_index *ix, int32_t *bounds, int32_t n);
+/* The hits its pass 2 appended, before the trim.  SED_E_STATE as above. */
+int sed_join_knn_candidates(const sed_join_index *ix, int64_t *n);
+/* Device time of pass 1 of its first launch (ms); with one launch, the usual case, sed_join_last_time less this is pass 2.
+ * SED_E_STATE unless the last call that launched a kernel was a k-nearest one. */
+int sed_join_knn_bound_time(const sed_join_index *ix, float *kernel_ms);
+/* The trim and the sort alone, in place, without a device: hits[0 .. n) in any order -> sorted by (row, dist, col), each
+ * row's first k; *kept = the records left.  k outside 1..64, n < 0, a NULL or a NaN dist: SED_E_ARG. */
+int sed_join_knn_trim(sed_join_hit *hits, int64_t n, int32_t k, int64_t *kept);
+/* What a k-nearest call would decide, without a device: k, then sed_join_plan's arguments (long_index != 0: those of
+ * sed_join_long_plan, with its out[6]).  k outside 1..64: SED_E_ARG before anything else is looked at; then
+ * sed_join_plan's refusals in their order.  out[]: the plan of the join at max_dist, which bounds each pass from above.
+ * sed_join_knn_plan_error: the text of this thread's last refusal, "" after a plan that passed. */
+int sed_join_knn_plan(int long_index, int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                      double del, int del_is_int, const int32_t *options, int noptions,
+                      const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                      uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
+const char *sed_join_knn_plan_error(void);
 
 /* The fp64 route of the similarity join: sed_join_self / sed_join_search for the cost tables and alphabets their scaled
  * integer cells refuse (the 15-symbol IUPAC table of costs.json among them).  Arguments, hit records, sort order, cap
@@ -709,7 +758,8 @@ int sed_join_route(int K, const double *sub, const uint8_t *sub_int, double ins,
  * collection of 40-symbol sequences pays for 64 cells a row, not 128; sequences of at most 32 symbols are served, and
  * faster by sed_join_index.  sed_join_long_plan's out[6] counts the cells executed.
  * Not served: tables the conditions refuse (there is no fp64 route for this index yet), sequences over 128 symbols, edit
- * scripts of the hits, k-nearest lists, the i < j half alone for symmetric tables, a per-tile mix of the two variants. */
+ * scripts of the hits, the i < j half alone for symmetric tables, a per-tile mix of the two variants; of the k-nearest
+ * calls below: an fp64 route (their selection works on integer keys) and k > 64. */
 typedef struct sed_join_long_index sed_join_long_index;
 sed_join_long_index *sed_join_long_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
                                                 int32_t nseqs);
@@ -722,6 +772,16 @@ int sed_join_long_search(sed_join_long_index *ix, const uint8_t *codes_q, const 
 /* sed_join_last_time and sed_join_pairs_run for this index type. */
 int sed_join_long_last_time(const sed_join_long_index *ix, float *kernel_ms);
 int sed_join_long_pairs_run(const sed_join_long_index *ix, int64_t *pairs);
+/* sed_join_knn_self, sed_join_knn_search, sed_join_knn_bounds, sed_join_knn_candidates and sed_join_knn_bound_time for
+ * this index type (the same reference lines: IRMethods.py:435-440, 443-477; StringEditDistance.py:133-224): rows, columns
+ * and queries of 0..128 symbols, everything else as stated there. */
+int sed_join_long_knn_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist,
+                           sed_join_hit *out, int64_t cap, int64_t *found);
+int sed_join_long_knn_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                             int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+int sed_join_long_knn_bounds(const sed_join_long_index *ix, int32_t *bounds, int32_t n);
+int sed_join_long_knn_candidates(const sed_join_long_index *ix, int64_t *n);
+int sed_join_long_knn_bound_time(const sed_join_long_index *ix, float *kernel_ms);
 /* The longest sequence a sed_join_long_index holds: 128. */
 int32_t sed_join_long_max_len(void);
 /* What the long calls would decide, without a device: sed_join_plan's arguments, order of refusals and out[] slots 0..5,

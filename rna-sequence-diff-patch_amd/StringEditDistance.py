@@ -32,6 +32,7 @@ There is no CPU fallback for the DP: without libsed.so or a HIP device the
 functions raise sedgpu.SedError.
 """
 import json
+import math
 import sys
 from collections import deque
 
@@ -906,6 +907,7 @@ def fit_index(texts, userCosts=False, alphabet=None, engine=None, f64=False):
 JOIN_MAX_LEN = 32  # the join's longest sequence (include/sed.h: sed_join_index_create)
 JOIN_LONG_MAX_LEN = 128  # the long join's (include/sed.h: sed_join_long_index_create)
 JOIN_F64_SYMBOLS = 16  # the fp64 route's table bound (include/sed.h: sed_join_self_f64)
+JOIN_KNN_MAX_K = 64  # the k-nearest calls' largest k (include/sed.h: sed_join_knn_self)
 
 
 class _EngineJoin:
@@ -927,6 +929,14 @@ class _EngineJoin:
         self.ctx.set_costs(plan)
         return self.ix.self_join_f64(max_dist, rows)
 
+    def self_knn(self, plan, k, max_dist, rows):
+        self.ctx.set_costs(plan)
+        return self.ix.self_knn(k, max_dist, rows)
+
+    def search_knn(self, plan, packed, k, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.search_knn(packed, k, max_dist)
+
     def search_f64(self, plan, packed, max_dist):
         self.ctx.set_costs(plan)
         return self.ix.search_f64(packed, max_dist)
@@ -947,7 +957,11 @@ class JoinIndex:
     refuse what those refuse).  long_seqs=True builds the index for sequences and queries of 0..128 symbols
     (include/sed.h: sed_join_long_self, sed_join_long_search): the integer route only, so with f64=True it is a
     ValueError; the engine is then called with long_seqs=True as a further, keyword argument.  The cost table is read at
-    every call, and the KeyErrors are the reference's for the first offending (row, column) in row-major order."""
+    every call, and the KeyErrors are the reference's for the first offending (row, column) in row-major order.
+    self_nearest(k) and search_nearest(queries, k) return, for every row, its k nearest sequences instead (include/sed.h:
+    sed_join_knn_self, sed_join_knn_search): [(row, j, dist)] sorted by (row, dist, j), nearest first, ties going to the
+    lower j, at most k a row, k = 1..64; max_dist (None: no cap) leaves out what lies farther.  They run the integer
+    kernels, with long_seqs=True too, and on an index built f64=True refuse what those refuse."""
 
     def __init__(self, seqs, userCosts=False, alphabet=None, engine=None, f64=False, long_seqs=False):
         self.seqs = list(seqs)
@@ -1005,6 +1019,38 @@ class JoinIndex:
         h = getattr(self._dev, _dev)(plan, max_dist, (lo, hi))
         return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
 
+    @staticmethod
+    def check_k(k):
+        """k of the k-nearest calls, refused here as the engine refuses it, so that a call the engine is not reached for
+        (no rows, no queries, no sequences) refuses it too."""
+        if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= JOIN_KNN_MAX_K:
+            raise sedgpu.SedError("join: k = %r neighbours a row (1..%d)" % (k, JOIN_KNN_MAX_K))
+
+    def self_nearest(self, k, max_dist=None, rows=None):
+        self.check_k(k)
+        lo, hi = (0, len(self.seqs)) if rows is None else rows
+        if not 0 <= lo <= hi <= len(self.seqs):
+            raise ValueError("rows=(%r, %r) is no range of the index's %d sequences" % (lo, hi, len(self.seqs)))
+        plan = self.plan(self.seqs[lo:hi])
+        if lo == hi:
+            return []
+        h = self._dev.self_knn(plan, k, math.inf if max_dist is None else max_dist, (lo, hi))
+        return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
+
+    def search_nearest(self, queries, k, max_dist=None):
+        self.check_k(k)
+        queries = list(queries)
+        for q, s in enumerate(queries):
+            if len(s) > self.max_len:
+                raise sedgpu.SedError("join: query %d has %d symbols (the join serves at most %d)" % (q, len(s), self.max_len))
+        plan = self.plan(queries)
+        if not queries or not self.seqs:
+            return []
+        ca, la = plan.encode_many(queries)
+        packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
+        h = self._dev.search_knn(plan, packed, k, math.inf if max_dist is None else max_dist)
+        return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
+
     def self_join_f64(self, max_dist, rows=None):
         """self_join() through the fp64 kernel (include/sed.h: sed_join_self_f64): any table of costs >= 0; with an
         index built f64=True, up to 16 symbols."""
@@ -1035,8 +1081,9 @@ def join_index(seqs, userCosts=False, alphabet=None, engine=None, f64=False, lon
     """A JoinIndex over seqs (0..32 symbols each; long_seqs=True: 0..128, the integer route only): every pair within a
     distance, for clustering, de-duplication, neighbour graphs, or many queries against one collection.  engine(codes,
     off, lens) -> an object with self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), their
-    self_join_f64 / search_f64, all returning sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU
-    tests); under long_seqs=True it is called with that keyword."""
+    self_join_f64 / search_f64, self_knn(plan, k, max_dist, (lo, hi)) and search_knn(plan, packed, k, max_dist), all
+    returning sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU tests); under long_seqs=True it is
+    called with that keyword."""
     return JoinIndex(seqs, userCosts, alphabet, engine, f64, long_seqs)
 
 

@@ -446,6 +446,21 @@ SED_JOIN_AT(sed_join_f64_args, out.cap, 112);
 static_assert(sizeof(sed_join_f64_args) == 120, "sed_join_f64_args");
 #undef SED_JOIN_SIDES_AT
 #undef SED_JOIN_AT
+// The k nearest columns of every row (include/sed.h: sed_join_knn_self, sed_join_knn_search and their _long_ twins): the
+// integer join's kernels under two other walks over the rows (sed_join_dev.h).  j = the join's arguments as they are,
+// j.cut = the cap floor(max_dist S); bound[r], r = the row's index as the join counts it (j.s.row0 ..), starts at j.cut.
+// Pass 1 (emit = false) lowers bound[r] to the smallest k-th smallest in-scope distance any wave finds and appends
+// nothing; pass 2 (emit = true) is the join with bound[r] in place of j.cut.  Both add to count[1]; 1 <= k <= 64.
+#define SED_JOIN_KNN_MAXK 64
+struct sed_join_knn_args {
+    sed_join_args j;
+    uint32_t *bound;
+    int32_t k;
+};
+hipError_t sed_launch_join_knn(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_args &a, bool bitpar,
+                               bool emit);
+hipError_t sed_launch_join_long_knn(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_args &a,
+                                    bool bitpar, bool emit);
 hipError_t sed_launch_join_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_f64_args &a);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first

@@ -20,12 +20,16 @@
 
 namespace {
 
-template <bool BITPAR>
+// Walk = what is done with a row's distances (sed_join_dev.h): sed_join_walk_all is the join; the two sed_join_walk_knn
+// are the passes of the k-nearest calls, with arguments of their own around the join's.
+template <bool BITPAR, class Walk = sed_join_walk_all>
 __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t *__restrict__ rows,
                                                                   const int32_t *__restrict__ row_len,
-                                                                  const uint2 *__restrict__ tab, const sed_join_args a) {
+                                                                  const uint2 *__restrict__ tab,
+                                                                  const typename Walk::args wa) {
     // (rows, row_len, tab = a's, as restrict parameters: the hit list's stores cannot alias them, so their uniform
     // loads are scalar loads)
+    const sed_join_args &a = Walk::join(wa);
     constexpr int MM = SED_JOIN_MAXLEN;
     static_assert(MM == 32, "a record is two 16-byte words; the bit-parallel state is one 32-bit word");
     const int t = blockIdx.x * SED_JOIN_BLOCK + threadIdx.x;
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
 #pragma unroll
         for (int j = 0; j < MM; ++j) sel[j] = sed_scaled_sel(bw[j >> 2] >> (8 * (j & 3)));
     }
-    sed_join_rows(row_len, a, valid, m, orig, [&](int r, int n) -> uint32_t {
+    Walk::rows(row_len, wa, valid, m, orig, [&](int r, int n) -> uint32_t {
         const uint32_t *pr = rows + 8 * (size_t)r;
         uint32_t w0 = pr[0], w1 = pr[1];  // rows 0..3 and 4..7 (the buffer ends with spare words)
         if constexpr (BITPAR) {
@@ -92,4 +96,15 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_kernel(const uint32_t
 hipError_t sed_launch_join(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar) {
     return bitpar ? sed_join_launch(sed_join_kernel<true>, stream, ev0, ev1, a, a.tab)
                   : sed_join_launch(sed_join_kernel<false>, stream, ev0, ev1, a, a.tab);
+}
+
+hipError_t sed_launch_join_knn(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_args &a, bool bitpar,
+                               bool emit) {
+    using Bound = sed_join_walk_knn<false>;
+    using Emit = sed_join_walk_knn<true>;
+    if (bitpar)
+        return emit ? sed_join_launch(sed_join_kernel<true, Emit>, stream, ev0, ev1, a, a.j.tab)
+                    : sed_join_launch(sed_join_kernel<true, Bound>, stream, ev0, ev1, a, a.j.tab);
+    return emit ? sed_join_launch(sed_join_kernel<false, Emit>, stream, ev0, ev1, a, a.j.tab)
+                : sed_join_launch(sed_join_kernel<false, Bound>, stream, ev0, ev1, a, a.j.tab);
 }

@@ -28,12 +28,15 @@ constexpr bool kSelRegs = true;
 constexpr bool kSelRegs = false;
 #endif
 
-template <bool BITPAR, bool SELREGS>
+// Walk = what is done with a row's distances (sed_join_dev.h): the join, or a pass of the k-nearest calls.
+template <bool BITPAR, bool SELREGS, class Walk = sed_join_walk_all>
 __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uint32_t *__restrict__ rows,
                                                                        const int32_t *__restrict__ row_len,
-                                                                       const uint2 *__restrict__ tab, const sed_join_args a) {
+                                                                       const uint2 *__restrict__ tab,
+                                                                       const typename Walk::args wa) {
     // (rows, row_len, tab = a's, as restrict parameters: the hit list's stores cannot alias them, so their uniform
     // loads are scalar loads)
+    const sed_join_args &a = Walk::join(wa);
     constexpr int MM = SED_JOIN_LONG_MAXLEN, BL = SED_JOIN_LONG_BLOCK, NW = MM / 4, NB = MM / BL;
     static_assert(BL == 32 && NB == 4, "a block of columns is one word of bit-parallel state; four of them a record");
     const int t = blockIdx.x * SED_JOIN_BLOCK + threadIdx.x;
@@ -61,7 +64,7 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uin
             E0[j >> 5] |= (u & 1u) << (j & 31);
             E1[j >> 5] |= (u >> 1) << (j & 31);
         }
-        sed_join_rows(row_len, a, valid, m, orig, [&](int r, int n) -> uint32_t {
+        Walk::rows(row_len, wa, valid, m, orig, [&](int r, int n) -> uint32_t {
             const uint32_t *pr = rows + NW * (size_t)r;
             uint32_t w0 = pr[0], w1 = pr[1];  // rows 0..3 and 4..7 (the buffer ends with spare words)
             uint32_t Pv[NB], Mv[NB];
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uin
 #pragma unroll
             for (int j = 0; j < MM; ++j) sel[j] = sed_scaled_sel(cw[j >> 2] >> (8 * (j & 3)));
         }
-        sed_join_rows(row_len, a, valid, m, orig, [&](int r, int n) -> uint32_t {
+        Walk::rows(row_len, wa, valid, m, orig, [&](int r, int n) -> uint32_t {
             const uint32_t *pr = rows + NW * (size_t)r;
             uint32_t w0 = pr[0], w1 = pr[1];
             uint32_t V[MM + 1];
@@ -146,4 +149,15 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_long_kernel(const uin
 hipError_t sed_launch_join_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_args &a, bool bitpar) {
     return bitpar ? sed_join_launch(sed_join_long_kernel<true, false>, stream, ev0, ev1, a, a.tab)
                   : sed_join_launch(sed_join_long_kernel<false, kSelRegs>, stream, ev0, ev1, a, a.tab);
+}
+
+hipError_t sed_launch_join_long_knn(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_args &a,
+                                    bool bitpar, bool emit) {
+    using Bound = sed_join_walk_knn<false>;
+    using Emit = sed_join_walk_knn<true>;
+    if (bitpar)
+        return emit ? sed_join_launch(sed_join_long_kernel<true, false, Emit>, stream, ev0, ev1, a, a.j.tab)
+                    : sed_join_launch(sed_join_long_kernel<true, false, Bound>, stream, ev0, ev1, a, a.j.tab);
+    return emit ? sed_join_launch(sed_join_long_kernel<false, kSelRegs, Emit>, stream, ev0, ev1, a, a.j.tab)
+                : sed_join_launch(sed_join_long_kernel<false, kSelRegs, Bound>, stream, ev0, ev1, a, a.j.tab);
 }

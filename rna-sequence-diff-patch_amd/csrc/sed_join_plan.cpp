@@ -163,6 +163,31 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
                             keep);
 }
 
+int sed_join_knn_k_rule(int32_t k, std::string *err) {
+    if (k < 1 || k > SED_JOIN_KNN_MAXK)
+        return sed_plan_fail(err, SED_E_ARG, "join: k = %d neighbours a row (1..%d: a wave selects among its 64 lanes)", k,
+                             SED_JOIN_KNN_MAXK);
+    return SED_OK;
+}
+
+// The trim of the k-nearest calls, in place: hits in any order -> sorted by (row, dist, col), the first k of each row.
+// The order of (dist, col) is the kernels' (D, original column): dist = D / S with S a power of two.
+extern "C" int sed_join_knn_trim(sed_join_hit *hits, int64_t n, int32_t k, int64_t *kept) {
+    if (n < 0 || (n && !hits) || k < 1 || k > SED_JOIN_KNN_MAXK || !kept) return SED_E_ARG;
+    for (int64_t i = 0; i < n; ++i)
+        if (std::isnan(hits[i].dist)) return SED_E_ARG;  // (no order)
+    std::sort(hits, hits + n, [](const sed_join_hit &x, const sed_join_hit &y) {
+        return x.row != y.row ? x.row < y.row : x.dist != y.dist ? x.dist < y.dist : x.col < y.col;
+    });
+    int64_t w = 0, in_row = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        in_row = i > 0 && hits[i - 1].row == hits[i].row ? in_row + 1 : 0;
+        if (in_row < k) hits[w++] = hits[i];
+    }
+    *kept = w;
+    return SED_OK;
+}
+
 // ---- the fp64 route ----
 int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::string *err) {
     if (c.K > SED_JOIN_F64_MAXK)
@@ -276,6 +301,28 @@ extern "C" int sed_join_long_plan(int K, const double *sub, const uint8_t *sub_i
 }
 
 extern "C" const char *sed_join_long_plan_error(void) { return long_plan_error.c_str(); }
+
+static thread_local std::string knn_plan_error;  // sed_join_knn_plan_error's text
+
+extern "C" int sed_join_knn_plan(int long_index, int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins,
+                                 int ins_is_int, double del, int del_is_int, const int32_t *options, int noptions,
+                                 const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                                 uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    knn_plan_error.clear();
+    std::string *err = &knn_plan_error;
+    if (nout < 0 || (nout && !out)) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    sed_costs c;
+    sed_opts o;
+    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return sed_plan_fail(err, rc, "bad join arguments");
+    sed_join_plan_t p;
+    if ((rc = sed_join_knn_k_rule(k, err)) != SED_OK) return rc;
+    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist,
+                          long_index ? SED_JOIN_LONG_MAXLEN : SED_JOIN_MAXLEN, &p, err);
+    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, std::min(nout, long_index ? 7 : 6));
+}
+
+extern "C" const char *sed_join_knn_plan_error(void) { return knn_plan_error.c_str(); }
 
 extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,

@@ -1,7 +1,8 @@
 // sed_join_plan.h — the device-free half of the similarity join (include/sed.h: sed_join_self, sed_join_search): what a
 // join decides from the cost model, the options, the lengths, the codes seen and the cutoff.  sed_join_plan.cpp calls no
 // HIP API (it shares sed_costs, sed_opts and sed_plan_fail with the batch planner, sed_plan.h, and nothing else); its
-// exports sed_join_plan, sed_join_long_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route run, and are tested,
+// exports sed_join_plan, sed_join_long_plan, sed_join_knn_plan, sed_join_knn_trim, sed_join_f64_plan, sed_join_f64_keep and
+// sed_join_route run, and are tested,
 // without a device.  The integer rule takes its longest sequence as a parameter: SED_JOIN_MAXLEN for sed_join_self /
 // sed_join_search, SED_JOIN_LONG_MAXLEN for sed_join_long_self / sed_join_long_search (kernel: sed_join_long.hip).
 #pragma once
@@ -45,6 +46,11 @@ int sed_join_costs_rule(const sed_costs &c, int maxlen, sed_join_plan_t *plan, s
 int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols,
                      int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes, double max_dist, int maxlen,
                      sed_join_plan_t *plan, std::string *err);
+// The k-nearest calls (include/sed.h: sed_join_knn_self, sed_join_knn_search and their _long_ twins): k = 1 ..
+// SED_JOIN_KNN_MAXK, checked with the arguments by this one rule (anything else: SED_E_ARG, the text names k); their plan
+// is sed_join_plan_of as it is: plan->cut is the cap floor(max_dist S) every row's bound starts from, and run / cells /
+// lane_cells count what one pass runs at most (the bounds only take pairs away).
+int sed_join_knn_k_rule(int32_t k, std::string *err);
 
 // The fp64 route (include/sed.h: sed_join_self_f64, sed_join_search_f64; kernel: sed_join_f64.hip): any table of finite
 // costs >= 0 over at most SED_JOIN_F64_MAXK symbols.  There is no scale: a cell's value is the oracle's.

@@ -1,6 +1,6 @@
 // sed_join_runtime.cpp — the similarity join's entry points of the C-ABI (include/sed.h): sed_join_index_* and
-// sed_join_self / sed_join_search and their _f64 siblings over a resident index of short sequences, and sed_join_long_*
-// over one of sequences of up to 128 symbols.  What a join runs is the join planner's decision (sed_join_plan.cpp), the
+// sed_join_self / sed_join_search, their _f64 siblings and their k-nearest forms sed_join_knn_* over a resident index of
+// short sequences, and sed_join_long_* over one of sequences of up to 128 symbols.  What a join runs is the join planner's decision (sed_join_plan.cpp), the
 // kernels are sed_join.hip, sed_join_f64.hip and sed_join_long.hip; here: pack, reserve, upload, launch, download, sort,
 // decode, on the context's stream (sed_runtime.h).  The two index types differ in one number, the record's length.
 #include "sed_join_plan.h"
@@ -11,9 +11,10 @@
 #include <vector>
 
 namespace {
-struct JoinTimer {  // the events around a call's launches, created on first use
-    hipEvent_t ev[2] = {nullptr, nullptr};
+struct JoinTimer {  // the events around a call's launches, created on first use ([2]: a k-nearest call's first bound pass ends)
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool timed = false;
+    bool knn = false;  // the timed call was a k-nearest one: ev[2] was recorded
     ~JoinTimer() {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -47,6 +48,10 @@ struct sed_join_index {
     // their lengths and original indices (columns of every join); a search's query records and lengths
     DevBuf d_rows, d_row_len, d_cols, d_col_len, d_col_orig, d_query;
     DevBuf d_tab, d_hits, d_count;
+    DevBuf d_bound;                // the k-nearest calls' bound of every row, indexed as the rows are
+    std::vector<uint32_t> h_bound; // the last k-nearest call's bounds after pass 1, one a row of the call
+    std::vector<sed_join_hit> h_knn;  // its candidates, decoded, for the trim
+    int64_t knn_candidates = -1;   // the hits its pass 2 appended; -1 before the first k-nearest call
     uint32_t h_tab[16] = {};       // the cost rows of the call under way (the upload's source)
     DevBuf d_f64;                  // the fp64 route's table and keep words, and their upload's source
     uint64_t h_f64[F64_TAB + SED_JOIN_MAXLEN + 1] = {};
@@ -58,7 +63,7 @@ struct sed_join_index {
     ~sed_join_index() {
         pin.release();
         d_rows.release(); d_row_len.release(); d_cols.release(); d_col_len.release(); d_col_orig.release();
-        d_query.release(); d_tab.release(); d_f64.release(); d_hits.release(); d_count.release();
+        d_query.release(); d_tab.release(); d_f64.release(); d_hits.release(); d_count.release(); d_bound.release();
     }
 };
 
@@ -68,13 +73,126 @@ struct sed_join_long_index : sed_join_index {};  // (a type of its own in the C-
 struct JoinCall {
     const sed_join_plan_t *pi = nullptr;
     const sed_join_f64_plan_t *pf = nullptr;
+    int32_t knn = 0;  // k of a k-nearest call (the integer plan), 0: a join
     int64_t launch_rows() const { return pi ? pi->launch_rows : pf->launch_rows; }
 };
+
+// The integer route's arguments but for the sides: the cost rows' upload, the plan's numbers, the list
+static hipError_t join_int_args(sed_join_index *ix, const sed_join_plan_t &plan, const sed_join_list &list, sed_join_args *a) {
+    memcpy(ix->h_tab, plan.sp.row, sizeof ix->h_tab);
+    a->tab = (const uint2 *)ix->d_tab.p;
+    a->ins = plan.sp.ins;
+    a->del = plan.sp.del;
+    a->umap = plan.sp.umap;
+    a->shift = plan.scale_log2;
+    a->cut = plan.cut;
+    a->out = list;
+    return hipMemcpyAsync(ix->d_tab.p, ix->h_tab, sizeof ix->h_tab, hipMemcpyHostToDevice, ix->ctx->stream);
+}
+
+// The columns' side of every launch
+static void join_cols(const sed_join_index *ix, sed_join_sides *s) {
+    s->cols = ix->d_cols.p;
+    s->col_len = (const int32_t *)ix->d_col_len.p;
+    s->col_orig = (const int32_t *)ix->d_col_orig.p;
+    s->ncols = ix->nseqs;
+}
+
+// A k-nearest call once its rows are on the device (k.knn = k, k.pi the plan; s, nrows as join_run takes them): every
+// row's bound set to the plan's cut; per row launch pass 1 (the bounds) then pass 2 (the candidates {D <= bound[r]}) on
+// the one stream; the counters, the bounds and the candidates come down; the trim keeps each row's first k by (D, col).
+// The device list is sized for the candidates: when pass 2 overflows it, it grows to the count the device reports and
+// pass 2 alone runs once more (the bounds are final), which the pairs counted leave out and the time spans.
+static int join_knn_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
+                        int64_t *found) {
+    sed_ctx *c = ix->ctx;
+    const sed_join_plan_t &plan = *k.pi;
+    const int32_t first = s.row0;
+    const size_t nbound = (size_t)first + (size_t)nrows;
+    const size_t guess = 2 * (size_t)nrows * (size_t)k.knn + 1024;  // records: twice the answer and a little
+    if (!ix->d_count.reserve(16) || !ix->d_tab.reserve(sizeof ix->h_tab) || !ix->d_bound.reserve(nbound * sizeof(uint32_t)) ||
+        !ix->d_hits.reserve(guess * sizeof(JoinRec)) || !ix->pin.reserve(16, 64))
+        return c->fail(SED_E_OOM, "device allocation failed (k-nearest join, %d rows)", nrows);
+    hipError_t e = hipSuccess;
+    if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
+    join_cols(ix, &s);
+    sed_join_knn_args ka{};
+    ka.bound = (uint32_t *)ix->d_bound.p;
+    ka.k = k.knn;
+    const bool bitpar = plan.kernel == SED_JOIN_KERNEL_BITPAR;
+    const int64_t step = k.launch_rows();
+    ix->knn_candidates = -1;  // (a call that fails from here on leaves nothing to report)
+    ix->h_bound.assign((size_t)nrows, 0u);
+    uint64_t n = 0;
+    for (int run = 0; run < 2; ++run) {  // (run 1: pass 2 again with room for what run 0 counted)
+        const sed_join_list list{(uint4 *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
+                                 (unsigned long long)(ix->d_hits.cap / sizeof(JoinRec))};
+        if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess ||
+            (e = join_int_args(ix, plan, list, &ka.j)) != hipSuccess ||
+            (run == 0 && (e = hipMemsetD32Async((hipDeviceptr_t)(ka.bound + first), plan.cut, (size_t)nrows, c->stream)) !=
+                             hipSuccess))
+            return c->hipfail(e, "upload (k-nearest join)");
+        for (int64_t r = 0; r < nrows; r += step) {
+            s.row0 = first + (int32_t)r;
+            s.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
+            ka.j.s = s;
+            const bool head = r == 0, tail = r + step >= nrows;
+            for (int emit = run; emit < 2; ++emit) {
+                hipEvent_t e0 = run == 0 && head && !emit ? ix->timer.ev[0] : nullptr;
+                hipEvent_t e1 = emit ? (tail ? ix->timer.ev[1] : nullptr) : (run == 0 && head ? ix->timer.ev[2] : nullptr);
+                e = ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long_knn(c->stream, e0, e1, ka, bitpar, emit != 0)
+                                                       : sed_launch_join_knn(c->stream, e0, e1, ka, bitpar, emit != 0);
+                if (e != hipSuccess) return c->hipfail(e, "k-nearest join kernel launch");
+            }
+        }
+        if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+            (run == 0 && (e = hipMemcpyAsync(ix->h_bound.data(), ka.bound + first, (size_t)nrows * sizeof(uint32_t),
+                                             hipMemcpyDeviceToHost, c->stream)) != hipSuccess))
+            return c->hipfail(e, "download (k-nearest join)");
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "k-nearest join kernel execution");
+        ix->timer.timed = ix->timer.knn = true;
+        n = ((const uint64_t *)ix->pin.p)[0];
+        if (run == 0) ix->pairs_run = (int64_t)((const uint64_t *)ix->pin.p)[1];
+        if (n <= list.cap) break;
+        if (run == 1) return c->fail(SED_E_DEVICE, "k-nearest join: %llu candidates after room was made for them", (unsigned long long)n);
+        if (n > SIZE_MAX / sizeof(JoinRec) || !ix->d_hits.reserve((size_t)n * sizeof(JoinRec)))
+            return c->fail(SED_E_OOM, "device allocation failed (k-nearest join, room for %llu candidates)", (unsigned long long)n);
+    }
+    ix->knn_candidates = (int64_t)n;
+    ix->h_hits.resize((size_t)n);
+    if (n != 0 && ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(JoinRec), hipMemcpyDeviceToHost,
+                                       c->stream)) != hipSuccess ||
+                   (e = hipStreamSynchronize(c->stream)) != hipSuccess))
+        return c->hipfail(e, "download (k-nearest candidates)");
+    const double inv = std::ldexp(1.0, -plan.scale_log2);
+    ix->h_knn.resize((size_t)n);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        const JoinRec &r = ix->h_hits[i];
+        if (r.row < (uint32_t)first || r.row >= (uint32_t)first + (uint32_t)nrows || r.col >= (uint32_t)ix->nseqs ||
+            r.D > ix->h_bound[r.row - (uint32_t)first] || r.D > (uint32_t)plan.cut || (s.self && r.row == r.col))
+            return c->fail(SED_E_DEVICE, "k-nearest join: record %zu from the device is no candidate (row %u, column %u)", i,
+                           r.row, r.col);
+        ix->h_knn[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, (double)r.D * inv};
+    }
+    int64_t kept = 0;
+    if (sed_join_knn_trim(ix->h_knn.data(), (int64_t)n, k.knn, &kept) != SED_OK)
+        return c->fail(SED_E_DEVICE, "k-nearest join: the trim refused the device's records");
+    for (int64_t i = 1; i < kept; ++i)
+        if (ix->h_knn[i - 1].row == ix->h_knn[i].row && ix->h_knn[i - 1].col == ix->h_knn[i].col)
+            return c->fail(SED_E_DEVICE, "k-nearest join: row %d reports column %d twice", ix->h_knn[i].row, ix->h_knn[i].col);
+    *found = kept;
+    if (kept > cap)
+        return c->fail(SED_E_RANGE, "join: found %lld hits, cap %lld: call again with room for them", (long long)kept,
+                       (long long)cap);
+    if (kept) memcpy(out, ix->h_knn.data(), (size_t)kept * sizeof(sed_join_hit));
+    return SED_OK;
+}
 
 // What all joins share once their rows are on the device: the plan's launches, the counters, the hit list.
 // s holds the rows (rows, row_len, row0, self); nrows rows from s.row0 on.
 static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
                     int64_t *found) {
+    if (k.knn) return join_knn_run(ix, k, s, nrows, out, cap, found);
     sed_ctx *c = ix->ctx;
     if ((uint64_t)cap > SIZE_MAX / sizeof(JoinRec) || !ix->d_count.reserve(16) ||
         !(k.pi ? ix->d_tab.reserve(sizeof ix->h_tab) : ix->d_f64.reserve(sizeof ix->h_f64)) ||
@@ -83,24 +201,12 @@ static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess) return c->hipfail(e, "upload (join)");
-    s.cols = ix->d_cols.p;
-    s.col_len = (const int32_t *)ix->d_col_len.p;
-    s.col_orig = (const int32_t *)ix->d_col_orig.p;
-    s.ncols = ix->nseqs;
+    join_cols(ix, &s);
     const sed_join_list list{(uint4 *)ix->d_hits.p, (unsigned long long *)ix->d_count.p, (unsigned long long)cap};
     sed_join_args a{};  // (one of a and f is filled and launched: the call's route)
     sed_join_f64_args f{};
     if (k.pi) {
-        const sed_join_plan_t &plan = *k.pi;
-        memcpy(ix->h_tab, plan.sp.row, sizeof ix->h_tab);
-        e = hipMemcpyAsync(ix->d_tab.p, ix->h_tab, sizeof ix->h_tab, hipMemcpyHostToDevice, c->stream);
-        a.tab = (const uint2 *)ix->d_tab.p;
-        a.ins = plan.sp.ins;
-        a.del = plan.sp.del;
-        a.umap = plan.sp.umap;
-        a.shift = plan.scale_log2;
-        a.cut = plan.cut;
-        a.out = list;
+        e = join_int_args(ix, *k.pi, list, &a);
     } else {  // one block: [the table | the keep words]
         const sed_join_f64_plan_t &plan = *k.pf;
         static_assert(sizeof ix->h_f64 == sizeof plan.sub + sizeof plan.keep, "the upload's layout");
@@ -136,6 +242,7 @@ static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int
         return c->hipfail(e, "download (join)");
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "join kernel execution");
     ix->timer.timed = true;
+    ix->timer.knn = false;
     const uint64_t n = ((const uint64_t *)ix->pin.p)[0];
     ix->pairs_run = (int64_t)((const uint64_t *)ix->pin.p)[1];
     *found = (int64_t)n;
@@ -172,8 +279,10 @@ static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int
 }
 
 // What every join refuses first, in sed_fit_index_search's order
-static int join_enter(sed_ctx *c, bool args_ok) {
+// (knn: NULL for a join, else k of the k-nearest call, checked with the arguments by the planner's rule)
+static int join_enter(sed_ctx *c, bool args_ok, const int32_t *knn) {
     if (c->pair_pending) return c->fail(SED_E_STATE, "a submitted pair has not been waited for");
+    if (knn && sed_join_knn_k_rule(*knn, &c->err) != SED_OK) return SED_E_ARG;
     if (!args_ok) return c->fail(SED_E_ARG, "bad join arguments");
     if (!c->have_costs) return c->fail(SED_E_STATE, "sed_set_costs() was not called");
     (void)hipSetDevice(c->device);
@@ -278,20 +387,31 @@ static int join_plan_call(sed_ctx *c, bool f64, const int32_t *len_rows, int32_t
                             ix->maxlen, pi, &c->err);
 }
 
-static int join_self(sed_join_index *ix, bool f64, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
-                     int64_t cap, int64_t *found) {
+// A k-nearest call got past its plan: what sed_join_knn_bounds and sed_join_knn_candidates report until it has run
+static void join_knn_planned(sed_join_index *ix, const JoinCall &k, int32_t nrows) {
+    if (!k.knn) return;
+    ix->h_bound.assign((size_t)nrows, (uint32_t)k.pi->cut);
+    ix->knn_candidates = 0;
+}
+
+// (knn: NULL for a join, else k of the k-nearest call)
+static int join_self(sed_join_index *ix, bool f64, const int32_t *knn, int32_t row_lo, int32_t row_hi, double max_dist,
+                     sed_join_hit *out, int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
-    int rc = join_enter(c, 0 <= row_lo && row_lo <= row_hi && row_hi <= ix->nseqs && cap >= 0 && (cap == 0 || out) && found);
+    int rc = join_enter(c, 0 <= row_lo && row_lo <= row_hi && row_hi <= ix->nseqs && cap >= 0 && (cap == 0 || out) && found,
+                        knn);
     if (rc != SED_OK) return rc;
     sed_join_plan_t pi;
     sed_join_f64_plan_t pf;
     JoinCall k;
+    k.knn = knn ? *knn : 0;
     const int32_t nrows = row_hi - row_lo;
     rc = join_plan_call(c, f64, ix->len.data() + row_lo, nrows, ix, true, ix->codes, max_dist, &pi, &pf, &k);
     if (rc != SED_OK) return rc;
     *found = 0;
     ix->pairs_run = 0;
+    join_knn_planned(ix, k, nrows);
     if (nrows == 0) return SED_OK;
     sed_join_sides s{};
     s.rows = ix->d_rows.p;
@@ -301,12 +421,13 @@ static int join_self(sed_join_index *ix, bool f64, int32_t row_lo, int32_t row_h
     return join_run(ix, k, s, nrows, out, cap, found);
 }
 
-static int join_search(sed_join_index *ix, bool f64, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
-                       int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+static int join_search(sed_join_index *ix, bool f64, const int32_t *knn, const uint8_t *codes_q, const int64_t *off_q,
+                       const int32_t *len_q, int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap,
+                       int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
     int rc = join_enter(c, (nqueries == 0 || (nqueries > 0 && codes_q && off_q && len_q)) && cap >= 0 && (cap == 0 || out) &&
-                               found);
+                               found, knn);
     if (rc != SED_OK) return rc;
     // the queries' records and lengths, one block: [records | spare | lengths]
     const size_t REC = (size_t)ix->maxlen;
@@ -323,10 +444,12 @@ static int join_search(sed_join_index *ix, bool f64, const uint8_t *codes_q, con
     sed_join_plan_t pi;
     sed_join_f64_plan_t pf;
     JoinCall k;
+    k.knn = knn ? *knn : 0;
     rc = join_plan_call(c, f64, len_q, nqueries, ix, false, qcodes, max_dist, &pi, &pf, &k);
     if (rc != SED_OK) return rc;
     *found = 0;
     ix->pairs_run = 0;
+    join_knn_planned(ix, k, nqueries);
     if (nqueries == 0 || ix->nseqs == 0) return SED_OK;
     if (!ix->d_query.reserve(qbytes)) return c->fail(SED_E_OOM, "device allocation failed (join, %d queries)", nqueries);
     hipError_t e = hipMemcpyAsync(ix->d_query.p, ix->h_query.data(), qbytes, hipMemcpyHostToDevice, c->stream);
@@ -343,22 +466,22 @@ extern "C" {
 
 int sed_join_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
                   int64_t *found) {
-    return join_self(ix, false, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, false, nullptr, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
                       int64_t *found) {
-    return join_self(ix, true, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, true, nullptr, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                     int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, false, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, false, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                         int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, true, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, true, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_last_time(const sed_join_index *ix, float *kernel_ms) {
@@ -376,15 +499,63 @@ int sed_join_pairs_run(const sed_join_index *ix, int64_t *pairs) {
 
 int32_t sed_join_rows_per_group(void) { return SED_JOIN_G; }
 
+// ---- the k nearest columns of every row (the integer route of either index type) ----
+int sed_join_knn_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist, sed_join_hit *out,
+                      int64_t cap, int64_t *found) {
+    return join_self(ix, false, &k, row_lo, row_hi, max_dist, out, cap, found);
+}
+
+int sed_join_knn_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                        int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_search(ix, false, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+}
+
+int sed_join_knn_bounds(const sed_join_index *ix, int32_t *bounds, int32_t n) {
+    if (!ix || n < 0 || (n && !bounds)) return SED_E_ARG;
+    if (ix->knn_candidates < 0) return SED_E_STATE;
+    if ((size_t)n != ix->h_bound.size()) return SED_E_ARG;
+    for (int32_t i = 0; i < n; ++i) bounds[i] = (int32_t)ix->h_bound[(size_t)i];
+    return SED_OK;
+}
+
+int sed_join_knn_candidates(const sed_join_index *ix, int64_t *n) {
+    if (!ix || !n) return SED_E_ARG;
+    if (ix->knn_candidates < 0) return SED_E_STATE;
+    *n = ix->knn_candidates;
+    return SED_OK;
+}
+
+int sed_join_knn_bound_time(const sed_join_index *ix, float *kernel_ms) {
+    if (!ix || !kernel_ms) return SED_E_ARG;
+    if (!ix->timer.timed || !ix->timer.knn) return SED_E_STATE;
+    return hipEventElapsedTime(kernel_ms, ix->timer.ev[0], ix->timer.ev[2]) == hipSuccess ? SED_OK : SED_E_DEVICE;
+}
+
+int sed_join_long_knn_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist,
+                           sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_self(ix, false, &k, row_lo, row_hi, max_dist, out, cap, found);
+}
+
+int sed_join_long_knn_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                             int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_search(ix, false, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+}
+
+int sed_join_long_knn_bounds(const sed_join_long_index *ix, int32_t *bounds, int32_t n) { return sed_join_knn_bounds(ix, bounds, n); }
+
+int sed_join_long_knn_candidates(const sed_join_long_index *ix, int64_t *n) { return sed_join_knn_candidates(ix, n); }
+
+int sed_join_long_knn_bound_time(const sed_join_long_index *ix, float *kernel_ms) { return sed_join_knn_bound_time(ix, kernel_ms); }
+
 // ---- sequences of up to 128 symbols: the calls above over the other index type (the integer route only) ----
 int sed_join_long_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
                        int64_t cap, int64_t *found) {
-    return join_self(ix, false, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, false, nullptr, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_long_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                          int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, false, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, false, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_long_last_time(const sed_join_long_index *ix, float *kernel_ms) { return sed_join_last_time(ix, kernel_ms); }

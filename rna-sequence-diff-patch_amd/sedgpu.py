@@ -25,6 +25,7 @@ never touched by the child (not even by __del__).
 """
 import collections
 import ctypes as C
+import math
 import os
 import pickle
 import socket
@@ -196,6 +197,18 @@ SIGNATURES = [
     ("sed_join_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                 _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
                                 _f64p, C.c_int]),
+    ("sed_join_knn_self", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                    C.POINTER(C.c_int64)]),
+    ("sed_join_knn_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
+                                      C.c_int64, C.POINTER(C.c_int64)]),
+    ("sed_join_knn_bounds", C.c_int, [C.c_void_p, _i32p, C.c_int32]),
+    ("sed_join_knn_candidates", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("sed_join_knn_bound_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("sed_join_knn_trim", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    ("sed_join_knn_plan", C.c_int, [C.c_int, C.c_int32, C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int,
+                                    _i32p, C.c_int, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32,
+                                    C.c_double, _f64p, C.c_int]),
+    ("sed_join_knn_plan_error", C.c_char_p, []),
     ("sed_join_self_f64", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
                                     C.POINTER(C.c_int64)]),
     ("sed_join_search_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
@@ -216,6 +229,13 @@ SIGNATURES = [
                                        C.POINTER(C.c_int64)]),
     ("sed_join_long_last_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("sed_join_long_pairs_run", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("sed_join_long_knn_self", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64)]),
+    ("sed_join_long_knn_search", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
+                                           C.c_int64, C.POINTER(C.c_int64)]),
+    ("sed_join_long_knn_bounds", C.c_int, [C.c_void_p, _i32p, C.c_int32]),
+    ("sed_join_long_knn_candidates", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("sed_join_long_knn_bound_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("sed_join_long_max_len", C.c_int32, []),
     ("sed_join_long_plan", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                      _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
@@ -679,6 +699,7 @@ class JoinIndex:
         self.ctx = ctx
         self.found = 0       # the last call's total count
         self._hit_room = 0   # records the last cap=None call made room for: the next one starts there
+        self._knn_rows = 0   # the rows of the last self_knn / search_knn call
         self._lib = ctx._lib
         lens = np.ascontiguousarray(lens, np.int32)
         off = np.ascontiguousarray(off, np.int64)
@@ -755,6 +776,52 @@ class JoinIndex:
         """search() through the fp64 kernel (sed_join_search_f64)."""
         return self.search(packed, max_dist, cap, "sed_join_search_f64")
 
+    def self_knn(self, k, max_dist=math.inf, rows=None, cap=None):
+        """For every i in rows = (lo, hi) (default: every sequence), the k sequences j != i of smallest distance(seq i ->
+        seq j) among those within max_dist (sed_join_knn_self): JOIN_HIT_DTYPE records sorted by (row, dist, col), ties
+        going to the lower column.  k = 1..64; exact.  cap as for self_join (None: room for k a row, which suffices)."""
+        lo, hi = (0, self.nseqs) if rows is None else rows
+        _call = self._PREFIX + "knn_self"
+        fn = getattr(self._lib, _call)
+        self._knn_rows = max(int(hi) - int(lo), 0)
+        return self._hits(_call, lambda out, room, found: fn(
+            self.ptr, int(lo), int(hi), int(k), float(max_dist), out, room, found),
+            self._knn_rows * min(max(int(k), 0), 64) if cap is None else cap)
+
+    def search_knn(self, packed, k, max_dist=math.inf, cap=None):
+        """For every query q, the k sequences of smallest distance(query q -> seq j) among those within max_dist
+        (sed_join_knn_search); packed and cap as for search and self_knn."""
+        _call = self._PREFIX + "knn_search"
+        fn = getattr(self._lib, _call)
+        self._knn_rows = packed.npairs
+        return self._hits(_call, lambda out, room, found: fn(
+            self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.npairs, int(k), float(max_dist), out, room, found),
+            self._knn_rows * min(max(int(k), 0), 64) if cap is None else cap)
+
+    def knn_bounds(self):
+        """The last self_knn / search_knn call's bound of every row after its first pass, on the integer scale (D * S),
+        one per row of the call (sed_join_knn_bounds)."""
+        out = np.zeros(max(self._knn_rows, 1), np.int32)
+        name = self._PREFIX + "knn_bounds"
+        self.ctx._check(getattr(self._lib, name)(self.ptr, out, self._knn_rows), name)
+        return out[:self._knn_rows]
+
+    @property
+    def knn_candidates(self):
+        """The hits the last self_knn / search_knn call's second pass appended, before the trim (sed_join_knn_candidates)."""
+        n = C.c_int64()
+        name = self._PREFIX + "knn_candidates"
+        self.ctx._check(getattr(self._lib, name)(self.ptr, C.byref(n)), name)
+        return int(n.value)
+
+    def knn_bound_ms(self):
+        """Device time of the first pass of the last self_knn / search_knn call's first launch (ms, HIP events): with one
+        launch, last_ms() less this is the second pass."""
+        ms = C.c_float()
+        name = self._PREFIX + "knn_bound_time"
+        self.ctx._check(getattr(self._lib, name)(self.ptr, C.byref(ms)), name)
+        return ms.value
+
     def last_ms(self):
         """Device time of the last join's kernel(s) (ms, HIP events)."""
         ms = C.c_float()
@@ -830,6 +897,32 @@ def join_long_plan(costs, options, len_rows, len_cols, self_join, row_codes, col
         err.code = rc
         raise err
     return {k: (float(v) if k in ("scale", "cells", "lane_cells") else int(v)) for k, v in zip(fields, out)}
+
+
+def join_knn_trim(hits, k):
+    """The k-nearest calls' trim alone, without a device (sed_join_knn_trim): JOIN_HIT_DTYPE records in any order -> a
+    new array sorted by (row, dist, col) with each row's first k."""
+    out = np.array(hits, JOIN_HIT_DTYPE)
+    kept = C.c_int64()
+    rc = load().sed_join_knn_trim(out.ctypes.data if len(out) else None, len(out), int(k), C.byref(kept))
+    if rc != 0:
+        raise _fit_fail("sed_join_knn_trim", rc)
+    return out[:kept.value]
+
+
+def join_knn_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, k, max_dist, long_index=False):
+    """What JoinIndex.self_knn / search_knn (long_index: LongJoinIndex's) would decide, without a device
+    (sed_join_knn_plan): k outside 1..64 raises SedError (.code = SED_E_ARG, the text names k), then join_plan's (or
+    join_long_plan's) refusals; the fields are those of the join at max_dist, which bound each pass from above."""
+    fields = JOIN_PLAN_FIELDS + (("lane_cells",) if long_index else ())
+    out = np.zeros(len(fields), np.float64)
+    rc = load().sed_join_knn_plan(int(bool(long_index)), int(k), *_join_args(costs, options, len_rows, len_cols, self_join,
+                                                                            row_codes, col_codes, max_dist), out, len(out))
+    if rc != 0:
+        err = SedError("sed_join_knn_plan failed (%d): %s" % (rc, load().sed_join_knn_plan_error().decode()))
+        err.code = rc
+        raise err
+    return {f: (float(v) if f in ("scale", "cells", "lane_cells") else int(v)) for f, v in zip(fields, out)}
 
 
 def join_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):

@@ -100,6 +100,11 @@ def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, joi
         hits = list(join_fn(seqs, lo, hi, max_dist, userCosts, f64=True))
     else:
         hits = list(join_fn(seqs, lo, hi, max_dist, userCosts))
+    return _hits_to_rank0(hits, world, rank, device, torch)
+
+
+def _hits_to_rank0(hits, world, rank, device, torch):
+    """This rank's (row, col, dist) tuples, in the ranks' order, as one record array on rank 0 (None elsewhere)."""
     dtype = np.dtype([("row", np.int32), ("col", np.int32), ("dist", np.float64)])
     rows = np.array([h[0] for h in hits], np.int32)
     cols = np.array([h[1] for h in hits], np.int32)
@@ -113,3 +118,33 @@ def neighbors(seqs, max_dist, userCosts=False, world=1, rank=0, device=None, joi
     out = np.zeros(len(rows), dtype)
     out["row"], out["col"], out["dist"] = rows, cols, dist
     return out
+
+
+def nearest_neighbors(seqs, k, max_dist=None, userCosts=False, world=1, rank=0, device=None, join_fn=None,
+                      long_sequences=False):
+    """For every sequence i of seqs, its k nearest sequences j != i by the distance from seqs[i] to seqs[j] (k = 1..64;
+    max_dist, None for no cap, leaves out what lies farther), as a numpy record array (row, col, dist) sorted by (row,
+    dist, col), on rank 0 (None on other ranks).  Rows are independent: rank r takes its block of rows,
+    shard_range(len(seqs), world, r), against every sequence on its own GPU (StringEditDistance.JoinIndex.self_nearest,
+    the integer kernels), and the blocks are contiguous, so their concatenation is sorted by row.
+    join_fn(seqs, lo, hi, k, max_dist, userCosts) -> [(i, j, dist)] sorted replaces the engine (CPU tests), as for
+    neighbors; long_sequences=True serves sequences of 0..128 symbols, and join_fn is then called with long_seqs=True as
+    a further, keyword argument."""
+    import torch
+    if join_fn is None:
+        import StringEditDistance as SED
+
+        def join_fn(seqs, lo, hi, k, max_dist, userCosts, long_seqs=False):
+            ix = SED.join_index(seqs, userCosts, long_seqs=long_seqs)
+            try:
+                return ix.self_nearest(k, max_dist, (lo, hi))
+            finally:
+                ix.close()
+    lo, hi = shard_range(len(seqs), world, rank)
+    if hi <= lo:
+        hits = []
+    elif long_sequences:
+        hits = list(join_fn(seqs, lo, hi, k, max_dist, userCosts, long_seqs=True))
+    else:
+        hits = list(join_fn(seqs, lo, hi, k, max_dist, userCosts))
+    return _hits_to_rank0(hits, world, rank, device, torch)

@@ -335,10 +335,14 @@ class JoinIndex:
         ix.neighbors(2)                      # [(i, j, 1 / (1 + d))] for every i != j with d(seq i -> seq j) <= 2
         ix.search_many(queries, 2)           # per query, == search_within(query, collection, 2, True)
         ix.search(query, 2)
+        ix.nearest(8)                        # per sequence i, its 8 nearest [(j, 1 / (1 + d))], nearest first
+        ix.nearest_many(queries, 8)          # per query, its 8 nearest [(sequence, score)]
 
     Rows (i, the queries) are str1 and columns (j, the documents) str2, the direction of wf_score(query, doc).
     index_fn(sequences, user_cost) -> an object with self_join(max_dist, rows) -> [(i, j, d)] and
-    search(queries, max_dist) -> [(q, j, d)], both sorted, and close(), replaces the engine (CPU tests).  Not cached.
+    search(queries, max_dist) -> [(q, j, d)], both sorted, self_nearest(k, max_dist, rows) and search_nearest(queries, k,
+    max_dist) -> the same records sorted by (row, d, j), and close(), replaces the engine (CPU tests).  Not cached.
+    nearest and nearest_many take no route: they run the integer kernels (StringEditDistance.JoinIndex.self_nearest).
 
     route (the constructor's, and per call on neighbors, search_many, search; None = the constructor's): "int" (the
     default) runs the integer kernels, which serve dyadic cost tables over at most 8 symbols and raise SedError
@@ -404,6 +408,33 @@ class JoinIndex:
     def search(self, query, max_dist, route=None):
         return self.search_many([query], max_dist, route)[0]
 
+    def nearest(self, k, max_dist=None, rows=None):
+        """Per sequence i of rows = (lo, hi) (default: all), [(j, 1 / (1 + d))] for its k nearest sequences j != i by the
+        distance d from sequence i to sequence j, nearest first, ties going to the lower j; max_dist (None: no cap)
+        leaves out what lies farther, so a list may be shorter than k.  k = 1..64; exact."""
+        lo, hi = (0, len(self.seqs)) if rows is None else rows
+        if self._ix is None:  # (an empty collection: what the index would refuse is refused here)
+            SED.JoinIndex.check_k(k)
+            if (lo, hi) != (0, 0):
+                raise ValueError("rows=(%r, %r) is no range of the index's 0 sequences" % (lo, hi))
+            return []
+        out = [[] for _ in range(lo, hi)]
+        for i, j, d in self._ix.self_nearest(k, max_dist, rows):
+            out[i - lo].append((j, 1 / (1 + d)))
+        return out
+
+    def nearest_many(self, queries, k, max_dist=None):
+        """Per query, [(sequence, 1 / (1 + d))] for its k nearest documents, nearest first: nearest(query, seqs, k) for
+        all the queries from one engine call (ties go to the document that comes first in the collection)."""
+        queries = list(queries)
+        out = [[] for _ in queries]
+        if self._ix is None:
+            SED.JoinIndex.check_k(k)
+            return out
+        for q, j, d in self._ix.search_nearest(queries, k, max_dist):
+            out[q].append((self.seqs[j], 1 / (1 + d)))
+        return out
+
     def close(self):
         if self._ix is not None:
             self._ix.close()
@@ -415,6 +446,15 @@ def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None, rout
     ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, route=route, long_sequences=long_sequences)
     try:
         return ix.neighbors(max_dist)
+    finally:
+        ix.close()
+
+
+def nearest_neighbors(seqs_or_collection, k, max_dist=None, user_cost=False, index_fn=None, long_sequences=False):
+    """JoinIndex.nearest in one shot: builds an index over the sequences, takes every sequence's k nearest and closes it."""
+    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, long_sequences=long_sequences)
+    try:
+        return ix.nearest(k, max_dist)
     finally:
         ix.close()
 
