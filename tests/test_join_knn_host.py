@@ -275,3 +275,243 @@ def test_sharded_nearest_world_3_reassembles_world_1():
         p.join(60)
         assert p.exitcode == 0
     assert (rows, cols, dist) == (want["row"].tolist(), want["col"].tolist(), want["dist"].tolist())
+
+
+# ---- the envelope (tests/test_gpu_join_knn_envelope.py): its calls proved on the CPU before a device sees them ----
+
+def distinct_calls(**which):
+    """The envelope's calls, one per input of the models (the options change launches and kernels, not results)."""
+    seen = {}
+    for c in kc.envelope_calls(**which):
+        seen.setdefault(c.key(), c)
+    return list(seen.values())
+
+
+def model_inputs(c):
+    """bound_pass_model's arguments but for the order."""
+    s, cols, rows, D, self_join, lo = kc.call_inputs(c)
+    return [kc.scaled(D, s.S), kc.in_scope(D.shape, self_join, lo), [len(x) for x in rows], [len(x) for x in cols], s.ins_S,
+            s.del_S, c.k, kc.cut_of(c.T, s.S)]
+
+
+def sorted_bound(c):
+    s, cols, _, D, self_join, lo = kc.call_inputs(c)
+    return kc.pass1_model(D, [len(x) for x in cols], c.k, c.T, s.S, self_join, lo)
+
+
+def test_bisection_is_the_kth_smallest():
+    """kth_by_bisection against a sort: 1..64 lanes, values up to the largest a long index reaches, ties, lanes that
+    are no candidates, every k the lanes allow; and the starting bound's bit 15 is never kept."""
+    rng = np.random.default_rng(16)
+    for lanes in (1, 2, 31, 32, 33, 63, 64):
+        for top in (0, 1, 255, 8160, kc.TOP_LONG, 65535):
+            D = rng.integers(0, top + 1, size=(40, lanes))
+            D[::3] = D[::3] // 7 * 7  # ties
+            cand = rng.random((40, lanes)) < 0.8
+            for k in sorted({1, 2, lanes // 2, lanes - 1, lanes} - {0}):
+                x = kc.kth_by_bisection(D, cand, k)
+                for i in range(40):
+                    v = np.sort(D[i][cand[i]])
+                    if len(v) >= k:
+                        assert x[i] == v[k - 1], (lanes, top, k, i)
+    assert kc.kth_by_bisection([kc.TOP_LONG] * 64, [True] * 64, 64) == kc.TOP_LONG < 1 << 15
+    assert int(kc.kth_by_bisection([3, 1, 2], [True, False, True], 2)) == 3
+
+
+def test_bounds_are_the_same_in_every_schedule():
+    """On every call of the GPU envelope tests the bound pass ends at the same bounds whether its waves run in index
+    order, in reverse, all reading the starting bound, or in a random order reading stale bounds: those of the sorting
+    model.  This is sed_join_dev.h's "in every schedule", proved on the CPU.  The emit pass then appends the sorting
+    model's candidates and runs pass2_pairs' pairs; the bound pass runs at least as many pairs as the emit pass and at
+    most those of the schedule in which every wave reads the cut."""
+    calls = distinct_calls()
+    assert len(calls) > 400
+    for c in calls:
+        want, cand = sorted_bound(c)
+        stale = kc.call_model(c, "stale")[1]
+        mask, p2 = kc.call_emit(c)
+        for order in kc.ORDERS:
+            bound, p1, writes = kc.call_model(c, order)
+            assert np.array_equal(bound, want), (c, order)
+            assert p2 <= p1 <= stale, (c, order)
+            for _, x in writes:  # every value written is some wave's k-th smallest: no less than the row's bound
+                assert (x[x >= 0] >= bound[x >= 0]).all(), (c, order)
+        assert int(mask.sum()) == cand, c
+        s, cols, rows, D, self_join, lo = kc.call_inputs(c)
+        assert p2 == kc.pass2_pairs([len(x) for x in rows], [len(x) for x in cols], want, s.plan.ins, s.plan.dele, s.S, self_join, lo)
+        per_row = np.bincount(kc.expected_knn(D, c.k, c.T, s.S, self_join, lo)["row"] - lo, minlength=len(rows))
+        assert (per_row <= mask.sum(1)).all() and (per_row <= c.k).all(), c  # the candidates hold the answer
+
+
+def final_bounds(calls):
+    """[(call, row's final bound, the call's cut)] over the rows of the calls."""
+    out = []
+    for c in calls:
+        cut = kc.cut_of(c.T, kc.envelope_set(c.set).S)
+        out += [(c, int(b), cut) for b in kc.call_model(c)[0]]
+    return out
+
+
+def test_the_ladders_reach_every_bit_of_the_bisection():
+    """Every bit 0..14 is both kept and dropped in some final bound of the ladder calls; the far ladders' k = 64 ends at
+    the largest D * S either index reaches; bit 15 belongs to the starting bound 65535 alone."""
+    ladders = final_bounds(distinct_calls(group="ladders"))
+    lowered = [b for _, b, cut in ladders if b != cut]
+    for bit in range(15):
+        assert any(b >> bit & 1 for b in lowered) and any(not b >> bit & 1 for b in lowered), bit
+    for kind, top in (("short", kc.TOP_SHORT), ("long", kc.TOP_LONG)):
+        for name in kc.je.LIMITS:
+            far = [c for c in kc.envelope_calls("ladders", kind, name) if c.set[0] == "far"]
+            assert {c.k for c in far} >= set(kc.FAR_K)
+            for c in far:
+                s, cols, rows, D, _, _ = kc.call_inputs(c)
+                assert len(cols) == 64 and len(rows) == 1 and len({len(x) for x in cols}) == 1
+                bound = kc.call_model(c)[0]
+                assert bound[0] == np.sort(kc.scaled(D, s.S)[0])[c.k - 1]
+                if c.k == 64:
+                    assert bound[0] == top
+            if kind == "long":  # rounds 14 and 13 keep their bit, or the first bound is above 2^13 = what a loop from bit 12 ends at
+                assert min(kc.call_model(c)[0][0] for c in far) > 1 << 13
+    for c, b, cut in final_bounds(distinct_calls()):
+        assert b == cut or b < 1 << 15, c
+        assert cut <= kc.CUT_ALL
+
+
+def test_some_bounds_stay_at_the_cut_and_some_come_from_a_later_wave():
+    near = [c for c in kc.envelope_calls("ladders", "short") if c.set[0] == "near" and c.k == 64]
+    assert near
+    for c in near:  # 33 columns: no wave has 64
+        assert kc.call_model(c)[0].tolist() == [kc.CUT_ALL] and len(kc.call_inputs(c)[1]) == 33
+    later = 0
+    for c in distinct_calls(group="geometry") + distinct_calls(group="limits"):
+        bound, _, writes = kc.call_model(c, "stale")  # every wave with k columns within the cut writes its k-th smallest
+        first = dict(writes)[0]
+        later += int(((bound < np.where(first < 0, 1 << 20, first)) & (bound < kc.cut_of(c.T, kc.envelope_set(c.set).S))).sum())
+    assert later > 0
+
+
+@pytest.mark.parametrize("kind", ["short", "long"])
+def test_k_against_the_lanes_in_scope(kind):
+    """Identical sequences: a full wave that holds the row's own column has 63 in scope.  k = 63 tightens everywhere;
+    k = 64 only through a full wave that does not hold the row; in a search every full wave has 64."""
+    calls = kc.envelope_calls("scope", kind, "identical")
+    assert {(c.k, c.ncols, c.queries is None) for c in calls if c.note == ""} == {
+        (63, 130, True), (64, 130, True), (64, 130, False), (63, 66, True), (64, 66, True), (64, 66, False)}
+    for c in calls:
+        bound = kc.call_model(c)[0].tolist()
+        if c.note == "zero" or c.k == 63 or c.queries is not None or c.ncols == 130:
+            assert bound == [0] * len(bound), c
+        else:  # 66 columns: the one full wave holds rows 0..63 themselves; rows 64 and 65 see all 64 of it
+            assert bound == [kc.CUT_ALL] * 64 + [0, 0], c
+    ties = kc.envelope_calls("scope", kind, "ties")
+    assert len(ties) == 1 and ties[0].T == 0.0
+    bound = kc.call_model(ties[0])[0]
+    want = kc.expected_knn(kc.call_inputs(ties[0])[3], 8, 0.0, 1, True)
+    assert not bound.any() and len(want) == 8 * len(kc.tie_set()[1]) and not want["dist"].any()  # a cut of 0 with hits
+
+
+@pytest.mark.parametrize("name", ["i1_d254", "i254_d1"])
+@pytest.mark.parametrize("kind", ["short", "long"])
+def test_the_length_skip_of_pass_2_removes_whole_waves_and_keeps_others(kind, name):
+    gone = kept = 0
+    for c in distinct_calls(group="limits", kind=kind, case=name):
+        DS, ok, len_rows, len_cols, ins_S, del_S, k, cut = model_inputs(c)
+        bound = kc.call_model(c)[0]
+        go = ok & (kc.length_bound(len_rows, len_cols, ins_S, del_S) <= bound[:, None])
+        index = np.argsort(len_cols, kind="stable")
+        for w in range(0, len(index), kc.WAVE):
+            lanes = index[w:w + kc.WAVE]
+            gone += int((ok[:, lanes].any(1) & ~go[:, lanes].any(1)).sum())
+            kept += int(go[:, lanes].any(1).sum())
+        assert kc.call_emit(c)[1] == int(go.sum()) <= int(ok.sum())
+    assert gone > 0 and kept > 0
+
+
+def test_the_planner_runs_both_kernels_on_the_bit_parallel_tables():
+    for kind in ("short", "long"):
+        for name in ("costs ACGUN", "unit block", "one way"):
+            calls = kc.envelope_calls("bitpar", kind, name)
+            assert {(c.k, c.options) for c in calls if not c.note} == {(k, o) for k in (1, 8) for o in ((), kc.FORCED_DP)}
+            for c in calls:
+                assert kc.envelope_set(c.set).S > 1
+                assert kc.call_plan(c)["kernel"] == (1 if c.options == kc.FORCED_DP or c.note == "fifth" else 2), c
+            if name == "one way":
+                fifth = [c for c in calls if c.note == "fifth"]
+                assert len(fifth) == 2 and all(len(c.queries) == 1 for c in fifth)
+        for c in kc.envelope_calls("ladders", kind) + kc.envelope_calls("limits", kind):
+            assert kc.call_plan(c)["kernel"] == 1
+        for c in kc.envelope_calls("lanes", kind):
+            assert kc.call_plan(c)["kernel"] == (1 if c.options else 2)
+
+
+def test_cutoffs_beside_a_kth_distance():
+    for c in kc.envelope_calls("cutoffs"):
+        s, _, _, D, self_join, lo = kc.call_inputs(c)
+        n = len(kc.expected_knn(D, c.k, c.T, s.S, self_join, lo))
+        zero = len(kc.expected_knn(D, c.k, 0.0, s.S, self_join, lo))
+        assert {"at d": n == c.k, "below d": zero <= n < c.k, "tiny": n == zero, "zero": n == zero}[c.note], c
+
+
+# ---- bite checks: a restatement that is subtly wrong must disagree with the sorting model on some envelope call ----
+
+def bisection(D, cand, k, top=15, below=np.less, need=0):
+    """kc.kth_by_bisection with its three choices open: the first bit, the compare, the count asked for."""
+    D, cand = np.asarray(D, np.int64), np.asarray(cand, bool)
+    x = np.zeros(D.shape[:-1], np.int64)
+    for bit in range(top, -1, -1):
+        c = x | (1 << bit)
+        x = np.where((cand & below(D, c[..., None])).sum(-1) < k + need, c, x)
+    return x
+
+
+def mutant_model(c, mutant):
+    DS, ok, len_rows, len_cols, ins_S, del_S, k, cut = model_inputs(c)
+    kth = kc.kth_by_bisection
+    if mutant == "as written":
+        kth = bisection
+    elif mutant == "from bit 12":
+        kth = lambda D, cand, k: bisection(D, cand, k, top=12)
+    elif mutant == "D <= c":
+        kth = lambda D, cand, k: bisection(D, cand, k, below=np.less_equal)
+    elif mutant == "k - 1":
+        kth = lambda D, cand, k: bisection(D, cand, k, need=-1)
+    elif mutant == "no self rule":
+        ok = np.ones_like(ok)
+    elif mutant == "insert and delete swapped":
+        ins_S, del_S = del_S, ins_S
+    elif mutant == "D unshifted":
+        s = kc.envelope_set(c.set)
+        if s.S == 1 or kc.call_plan(c)["kernel"] != 2:
+            return None  # the shift is the bit-parallel kernel's
+        DS = DS >> (s.S.bit_length() - 1)
+    return kc.bound_pass_model(DS, ok, len_rows, len_cols, ins_S, del_S, k, cut, kth=kth)[0]
+
+
+MUTANTS = {"from bit 12": ("ladders", "long"), "D <= c": (), "k - 1": (), "no self rule": ("scope",),
+           "insert and delete swapped": ("limits",), "D unshifted": ("bitpar",)}
+
+
+def killers(mutant, calls):
+    out = []
+    for c in calls:
+        got = mutant_model(c, mutant)
+        if got is not None and not np.array_equal(got, sorted_bound(c)[0]):
+            out.append(c)
+    return out
+
+
+def test_the_open_bisection_is_the_model():
+    calls = distinct_calls(group="ladders", kind="long") + distinct_calls(group="scope")
+    assert not killers("as written", calls)
+
+
+@pytest.mark.parametrize("mutant", list(MUTANTS))
+def test_mutants_of_the_bound_pass_are_caught(mutant):
+    """Each mutant differs from the sorting model on the calls of the group built against it."""
+    where = MUTANTS[mutant]
+    calls = kc.envelope_calls(*where) if where else kc.envelope_calls("columns", "short")
+    dead = killers(mutant, [c for c in calls if not c.options or mutant == "D unshifted"][:60])
+    assert dead, mutant
+    if mutant == "from bit 12":  # what only the long far ladder sees: no other bound reaches 2^13
+        assert "far" in {c.set[0] for c in dead}
+        assert not killers(mutant, distinct_calls(kind="short")[::7])
