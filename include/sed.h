@@ -621,8 +621,7 @@ int sed_fit_long_route(int K, const double *sub, const uint8_t *sub_int, double 
  * (65535 groups of sed_join_rows_per_group rows; SED_OPT_JOIN_ROWS) run as further launches of the same call.
  * Not served: tables the conditions refuse (IUPAC: the _f64 calls below serve them), sequences over 32 symbols (the
  * sed_join_long_ calls below serve up to 128), edit scripts of the hits, the i < j half alone for symmetric tables, a
- * per-tile mix of the two variants; of the k-nearest calls below: an fp64 route (their selection works on integer
- * keys) and k > 64. */
+ * per-tile mix of the two variants; of the k-nearest calls below: k > 64. */
 typedef struct sed_join_index sed_join_index;
 typedef struct { int32_t row, col; double dist; } sed_join_hit;
 sed_join_index *sed_join_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
@@ -678,7 +677,8 @@ int sed_join_knn_search(sed_join_index *ix, const uint8_t *codes_q, const int64_
                         int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
 /* The last k-nearest call's per-row bounds after pass 1, on the integer scale (D * S): bounds[i] belongs to row row_lo + i
  * (query i), n = the call's rows exactly (else SED_E_ARG).  A call that launched nothing (no rows, or no columns) reports
- * floor(max_dist * S), clamped to 65535, for every row.  SED_E_STATE before the first k-nearest call that got past its plan. */
+ * floor(max_dist * S), clamped to 65535, for every row.  SED_E_STATE before the first k-nearest call that got past its
+ * plan, and when the last such call was an fp64 one (sed_join_knn_bounds_f64 reports those). */
 int sed_join_knn_bounds(const sed_join_index *ix, int32_t *bounds, int32_t n);
 /* The hits its pass 2 appended, before the trim.  SED_E_STATE as above. */
 int sed_join_knn_candidates(const sed_join_index *ix, int64_t *n);
@@ -691,7 +691,8 @@ int sed_join_knn_trim(sed_join_hit *hits, int64_t n, int32_t k, int64_t *kept);
 /* What a k-nearest call would decide, without a device: k, then sed_join_plan's arguments (long_index != 0: those of
  * sed_join_long_plan, with its out[6]).  k outside 1..64: SED_E_ARG before anything else is looked at; then
  * sed_join_plan's refusals in their order.  out[]: the plan of the join at max_dist, which bounds each pass from above.
- * sed_join_knn_plan_error: the text of this thread's last refusal, "" after a plan that passed. */
+ * sed_join_knn_plan_error: the text of this thread's last refusal (of this call or of sed_join_knn_f64_plan), "" after a
+ * plan that passed. */
 int sed_join_knn_plan(int long_index, int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
                       double del, int del_is_int, const int32_t *options, int noptions,
                       const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
@@ -719,6 +720,44 @@ int sed_join_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double
                       int64_t *found);
 int sed_join_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                         int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+/* The k nearest columns of every row on the fp64 route (an extension; it batches the same reference lines as
+ * sed_join_knn_self: wf_score(query, doc) over a whole collection, IRMethods.py:435-440 inside search_collection's loop,
+ * IRMethods.py:443-477, each a full wagnerFisher(str1, str2), StringEditDistance.py:133-224, followed by the sort that
+ * shows the best few): sed_join_knn_self / sed_join_knn_search for the cost tables and alphabets of sed_join_self_f64,
+ * on the same sed_join_index; calls of every kind may alternate on one index.
+ *   Order within a row: by (D, original column index), D = wagnerFisher(row, column).value in fp64, bit for bit, as
+ *   sed_join_self_f64 defines it; the result is the first min(k, the in-scope columns with D <= max_dist as a plain fp64
+ *   compare) of them, as records sorted by (row, dist, col).  max_dist = +inf: no cap; NaN or negative: SED_E_ARG; -0.0
+ *   counts as 0.  A distance that overflowed to +inf is an ordinary value: reported under max_dist = +inf, ordered last.
+ *   k = 1..64, checked with the arguments; then the fp64 join's refusals in the fp64 join's order.
+ * The cap protocol, the state errors, SED_OPT_JOIN_ROWS, the 65535-group limit and the device list that grows (pass 2
+ * then runs once more) are the integer k-nearest calls'; sed_join_knn_candidates, sed_join_knn_bound_time,
+ * sed_join_last_time and sed_join_pairs_run report these calls as they report those.
+ * The two passes are the integer calls' on a 64-bit key: every distance of this route is finite or +inf and >= +0, and
+ * the bit patterns of such doubles order, as unsigned 64-bit integers, exactly as the values do.  A row's bound is such
+ * a pattern (8 bytes a row), starts at max_dist's and is lowered by a 64-bit atomic minimum; nothing is scaled or
+ * rounded.  The length skip compares a table entry with the row's bound: low[33 n + m] <= bound (sed_join_f64_lower),
+ * the value sed_join_f64_keep compares with max_dist. */
+int sed_join_knn_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist, sed_join_hit *out,
+                          int64_t cap, int64_t *found);
+int sed_join_knn_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                            int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
+/* The last fp64 k-nearest call's per-row bounds after pass 1, as doubles: bounds[i] belongs to row row_lo + i (query i),
+ * n = the call's rows exactly (else SED_E_ARG).  A call that launched nothing reports max_dist for every row.
+ * SED_E_STATE before the first k-nearest call that got past its plan, and when the last such call was an integer one. */
+int sed_join_knn_bounds_f64(const sed_join_index *ix, double *bounds, int32_t n);
+/* What an fp64 k-nearest call would decide, without a device: k, then sed_join_f64_plan's arguments.  k outside 1..64:
+ * SED_E_ARG before anything else is looked at; then sed_join_f64_plan's refusals in their order.  out[]: the fp64 join's
+ * plan at max_dist, which bounds each pass from above.  The refusal's text: sed_join_knn_plan_error. */
+int sed_join_knn_f64_plan(int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                          double del, int del_is_int, const int32_t *options, int noptions,
+                          const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                          uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout);
+/* The table behind the fp64 length skip: low[33 n + m], n, m = 0..32, a value <= every distance of a row of n and a
+ * column of m symbols under these costs (finite, >= 0; anything else: SED_E_ARG): the border product when n = 0 or m = 0,
+ * fl(p - p 2^-40) for p = fl(|m - n| * cost) when n != m and p is finite and >= 2^-900, else 0.  sed_join_f64_keep's bit
+ * (n, m) is low[33 n + m] <= max_dist. */
+int sed_join_f64_lower(double ins, double del, double *low);
 /* What the fp64 calls would decide, without a device: sed_join_plan's arguments and out[] slots, with 0 = 0 (no scale)
  * and 1 = 3 (the fp64 kernel). */
 int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
@@ -759,7 +798,7 @@ int sed_join_route(int K, const double *sub, const uint8_t *sub_int, double ins,
  * faster by sed_join_index.  sed_join_long_plan's out[6] counts the cells executed.
  * Not served: tables the conditions refuse (there is no fp64 route for this index yet), sequences over 128 symbols, edit
  * scripts of the hits, the i < j half alone for symmetric tables, a per-tile mix of the two variants; of the k-nearest
- * calls below: an fp64 route (their selection works on integer keys) and k > 64. */
+ * calls below: an fp64 route (sed_join_knn_self_f64 / sed_join_knn_search_f64 serve the short index only) and k > 64. */
 typedef struct sed_join_long_index sed_join_long_index;
 sed_join_long_index *sed_join_long_index_create(sed_ctx *ctx, const uint8_t *codes, const int64_t *off, const int32_t *len,
                                                 int32_t nseqs);

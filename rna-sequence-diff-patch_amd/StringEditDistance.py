@@ -941,6 +941,14 @@ class _EngineJoin:
         self.ctx.set_costs(plan)
         return self.ix.search_f64(packed, max_dist)
 
+    def self_knn_f64(self, plan, k, max_dist, rows):
+        self.ctx.set_costs(plan)
+        return self.ix.self_knn_f64(k, max_dist, rows)
+
+    def search_knn_f64(self, plan, packed, k, max_dist):
+        self.ctx.set_costs(plan)
+        return self.ix.search_knn_f64(packed, k, max_dist)
+
     def close(self):
         self.ix.close()
 
@@ -961,7 +969,9 @@ class JoinIndex:
     self_nearest(k) and search_nearest(queries, k) return, for every row, its k nearest sequences instead (include/sed.h:
     sed_join_knn_self, sed_join_knn_search): [(row, j, dist)] sorted by (row, dist, j), nearest first, ties going to the
     lower j, at most k a row, k = 1..64; max_dist (None: no cap) leaves out what lies farther.  They run the integer
-    kernels, with long_seqs=True too, and on an index built f64=True refuse what those refuse."""
+    kernels, with long_seqs=True too, and on an index built f64=True refuse what those refuse; self_nearest_f64 and
+    search_nearest_f64 are the same calls through the fp64 kernel (include/sed.h: sed_join_knn_self_f64,
+    sed_join_knn_search_f64), as self_join_f64 / search_f64 are to self_join / search."""
 
     def __init__(self, seqs, userCosts=False, alphabet=None, engine=None, f64=False, long_seqs=False):
         self.seqs = list(seqs)
@@ -1026,7 +1036,7 @@ class JoinIndex:
         if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= JOIN_KNN_MAX_K:
             raise sedgpu.SedError("join: k = %r neighbours a row (1..%d)" % (k, JOIN_KNN_MAX_K))
 
-    def self_nearest(self, k, max_dist=None, rows=None):
+    def self_nearest(self, k, max_dist=None, rows=None, _dev="self_knn"):
         self.check_k(k)
         lo, hi = (0, len(self.seqs)) if rows is None else rows
         if not 0 <= lo <= hi <= len(self.seqs):
@@ -1034,10 +1044,10 @@ class JoinIndex:
         plan = self.plan(self.seqs[lo:hi])
         if lo == hi:
             return []
-        h = self._dev.self_knn(plan, k, math.inf if max_dist is None else max_dist, (lo, hi))
+        h = getattr(self._dev, _dev)(plan, k, math.inf if max_dist is None else max_dist, (lo, hi))
         return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
 
-    def search_nearest(self, queries, k, max_dist=None):
+    def search_nearest(self, queries, k, max_dist=None, _dev="search_knn"):
         self.check_k(k)
         queries = list(queries)
         for q, s in enumerate(queries):
@@ -1048,8 +1058,17 @@ class JoinIndex:
             return []
         ca, la = plan.encode_many(queries)
         packed = sedgpu.PackedPairs.from_concat(ca, la, np.zeros(0, np.uint8), np.zeros(len(la), np.int32))
-        h = self._dev.search_knn(plan, packed, k, math.inf if max_dist is None else max_dist)
+        h = getattr(self._dev, _dev)(plan, packed, k, math.inf if max_dist is None else max_dist)
         return list(zip(h["row"].tolist(), h["col"].tolist(), h["dist"].tolist()))
+
+    def self_nearest_f64(self, k, max_dist=None, rows=None):
+        """self_nearest() through the fp64 kernel (include/sed.h: sed_join_knn_self_f64): any table of costs >= 0; with
+        an index built f64=True, up to 16 symbols."""
+        return self.self_nearest(k, max_dist, rows, "self_knn_f64")
+
+    def search_nearest_f64(self, queries, k, max_dist=None):
+        """search_nearest() through the fp64 kernel (include/sed.h: sed_join_knn_search_f64)."""
+        return self.search_nearest(queries, k, max_dist, "search_knn_f64")
 
     def self_join_f64(self, max_dist, rows=None):
         """self_join() through the fp64 kernel (include/sed.h: sed_join_self_f64): any table of costs >= 0; with an
@@ -1081,8 +1100,8 @@ def join_index(seqs, userCosts=False, alphabet=None, engine=None, f64=False, lon
     """A JoinIndex over seqs (0..32 symbols each; long_seqs=True: 0..128, the integer route only): every pair within a
     distance, for clustering, de-duplication, neighbour graphs, or many queries against one collection.  engine(codes,
     off, lens) -> an object with self_join(plan, max_dist, (lo, hi)), search(plan, packed, max_dist), their
-    self_join_f64 / search_f64, self_knn(plan, k, max_dist, (lo, hi)) and search_knn(plan, packed, k, max_dist), all
-    returning sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU tests); under long_seqs=True it is
+    self_join_f64 / search_f64, self_knn(plan, k, max_dist, (lo, hi)) and search_knn(plan, packed, k, max_dist), their
+    self_knn_f64 / search_knn_f64, all returning sedgpu.JOIN_HIT_DTYPE records, and close() replaces the device (CPU tests); under long_seqs=True it is
     called with that keyword."""
     return JoinIndex(seqs, userCosts, alphabet, engine, f64, long_seqs)
 

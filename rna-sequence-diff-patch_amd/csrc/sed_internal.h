@@ -462,6 +462,22 @@ hipError_t sed_launch_join_knn(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev
 hipError_t sed_launch_join_long_knn(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_args &a,
                                     bool bitpar, bool emit);
 hipError_t sed_launch_join_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_f64_args &a);
+// The k nearest columns of every row on the fp64 route (include/sed.h: sed_join_knn_self_f64, sed_join_knn_search_f64):
+// the fp64 join's kernel under two other passes (sed_join_f64.hip).  j = the join's arguments, j.keep unused, j.max_dist
+// = the cap; bound[r], r indexed as for sed_join_knn_args, is a 64-bit word holding the bits of a double (finite or
+// +inf, >= +0: such bits order as the values do) and starts at j.max_dist's; low = 33 x 33 doubles on the device,
+// low[33 n + m] <= every distance of a row of n and a column of m symbols (sed_join_plan.h: sed_join_f64_lower_rule):
+// the length skip is low[33 n + m] <= bound[r], a compare.  Pass 1 (emit = false) lowers bound[r] to the smallest k-th
+// smallest in-scope distance any wave finds and appends nothing; pass 2 (emit = true) is the join with bound[r] in
+// place of j.max_dist.  Both add to count[1]; 1 <= k <= 64.
+struct sed_join_knn_f64_args {
+    sed_join_f64_args j;
+    unsigned long long *bound;
+    const double *low;
+    int32_t k;
+};
+hipError_t sed_launch_join_knn_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_f64_args &a,
+                                   bool emit);
 hipError_t sed_launch_traceback(const sed_launch &L, uint32_t *ops);
 // stripe-parallel traceback of few long pairs (per-cell codes): map[pd.map_off ...] per pair, ops zeroed first
 hipError_t sed_launch_traceback_stripes(const sed_launch &L, uint32_t *ops, uint32_t *map, int items, int kmax);

@@ -4,7 +4,8 @@
 // walks of the k-nearest calls, which the same kernel bodies are instantiated over.  One copy, so the
 // kernels report the same pairs under the same rule (sed_internal.h: sed_join_args, sed_join_f64_args).
 // sed_join_f64_kernel keeps a row loop of its own: handed this walk with its skip, distance and hit test as parameters
-// it compiled to another instruction schedule (profiles/kernel_shells/README.md).
+// it compiled to another instruction schedule (profiles/kernel_shells/README.md); its k-nearest passes live in that loop
+// too (sed_join_f64.hip), on the bits of the fp64 distance as a 64-bit key.
 #pragma once
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
@@ -132,6 +133,7 @@ struct sed_join_walk_knn {
 template <class Args>
 inline const sed_join_sides &sed_join_sides_of(const Args &a) { return a.s; }
 inline const sed_join_sides &sed_join_sides_of(const sed_join_knn_args &a) { return a.j.s; }
+inline const sed_join_sides &sed_join_sides_of(const sed_join_knn_f64_args &a) { return a.j.s; }
 
 // A join kernel over a's rows and columns: grid = (column blocks) x (row groups); the kernel's parameters are the rows,
 // their lengths, then `tables` (what the route reads through restrict pointers of its own), then a by value.

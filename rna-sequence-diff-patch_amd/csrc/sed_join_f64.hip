@@ -25,6 +25,9 @@
 // A hit is D <= max_dist, a plain fp64 compare; its record is (row, original column, D's low word, D's high word).
 // The append and the launch are sed_join_dev.h's; the row loop is this kernel's own copy of sed_join_rows there (the
 // shared walk, given the keep bit and the fp64 distance as parameters, compiled to another schedule).
+// The same kernel body serves the k-nearest calls of this route (include/sed.h: sed_join_knn_self_f64,
+// sed_join_knn_search_f64) as two further instantiations, chosen by `if constexpr`: the join's own instantiation
+// compiles to the instructions it had as a plain kernel.
 #include <hip/hip_ext.h>
 #include "sed_internal.h"
 #include "sed_dev.h"
@@ -34,13 +37,52 @@ namespace {
 
 constexpr int JF_K = SED_JOIN_F64_MAXK;
 
+// What the kernel is instantiated over (sed_join_dev.h's walks are the integer kernels'): the join itself, and the two
+// passes of the k-nearest calls (sed_internal.h: sed_join_knn_f64_args).  skip = what the length skip reads: the join's
+// keep words, or the passes' 33 x 33 table low[33 n + m] <= every D of a row of n and a column of m symbols.
+struct sed_join_f64_all {
+    using args = sed_join_f64_args;
+    using skip = unsigned long long;
+    static constexpr int pass = 0;
+    static __device__ __forceinline__ const sed_join_f64_args &join(const args &a) { return a; }
+};
+template <int PASS>
+struct sed_join_f64_knn {
+    using args = sed_join_knn_f64_args;
+    using skip = double;
+    static constexpr int pass = PASS;  // 1: the bound pass, 2: the emit pass
+    static __device__ __forceinline__ const sed_join_f64_args &join(const args &a) { return a.j; }
+};
+
+// The k nearest columns of every row (pass 1 and 2 below).  A distance is finite or +inf and >= +0, and the bit
+// patterns of such doubles order as unsigned 64-bit integers exactly as the values do (sign bit 0: exponent, then
+// fraction, most significant first; +inf = 0x7FF0..0 is above every finite one).  So bound[r] is a 64-bit word that
+// holds a double's bits, it starts at max_dist's, and the integer passes of sed_join_dev.h carry over with the bits as
+// the key: nothing is scaled or rounded.
+// Pass 1, the bound pass: per row b = bound[r] (a relaxed agent-scope atomic load, made uniform: other waves lower it
+// meanwhile, and a stale value is a larger one, which only prunes less).  A lane takes part when its column is in scope
+// and low[33 n + m] <= b; low <= D (sed_join_plan.h: sed_join_f64_lower_rule), so a lane left out has D > b and the
+// candidates {in scope, D <= b} are the same with or without the skip.  A wave with at least k candidates finds d_k,
+// their k-th smallest D: those k all lie <= b, so d_k is the wave's true k-th smallest among its columns in scope,
+// whatever b was, and it is >= the row's k-th smallest; one lane lowers bound[r] to it (64-bit unsigned atomicMin).  A
+// wave with fewer than k candidates has no k-th smallest <= b and writes nothing.  Take any schedule and let w* be the
+// wave of the smallest true k-th smallest d* among the waves that have k columns in scope within max_dist: every value
+// ever written is some wave's true k-th smallest, so bound[r] >= min(max_dist, d*) throughout, hence w* reads b >= d*,
+// counts its k columns <= d* as candidates, finds d* and writes it (or b = d* already).  So bound[r] ends as
+// min(max_dist, the smallest k-th smallest of any wave that has k in-scope columns within max_dist), in every schedule.
+// d_k by bisection on the key: bits 62..0 (bit 63, the sign, is 0), 63 rounds of compare, ballot and popcount; no loop
+// depends on the data or waits for another wave.
+// Pass 2, the emit pass: the join with b = bound[r] (final since pass 1 ended: one value for the whole wave) in place
+// of max_dist, in the skip and the hit test alike.  It appends exactly {D <= bound[r]}.
+template <class W>
 __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint32_t *__restrict__ rows,
                                                                       const int32_t *__restrict__ row_len,
                                                                       const double *__restrict__ sub,
-                                                                      const unsigned long long *__restrict__ keep,
-                                                                      const sed_join_f64_args a) {
+                                                                      const typename W::skip *__restrict__ keep,
+                                                                      const typename W::args wa) {
     // (rows, row_len, keep = a's, as restrict parameters: the hit list's stores cannot alias them, so their uniform
     // loads are scalar loads)
+    const sed_join_f64_args &a = W::join(wa);
     constexpr int MM = SED_JOIN_MAXLEN;
     static_assert(MM == 32 && JF_K == 16, "a record is two 16-byte words; a code indexes a table row of 16 doubles");
     __shared__ double tab[JF_K * JF_K];
@@ -64,8 +106,23 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint
     uint32_t ran = 0;
     for (int r = rbeg; r < rend; ++r) {
         const int n = row_len[r];  // (uniform: a scalar load)
-        const unsigned long long kn = keep[n];
-        const bool go = valid && !(a.s.self && orig == r) && ((kn >> m) & 1ull) != 0;
+        bool go;
+        double b = 0;  // (the passes: the row's bound, uniform)
+        if constexpr (W::pass == 0) {
+            const unsigned long long kn = keep[n];
+            go = valid && !(a.s.self && orig == r) && ((kn >> m) & 1ull) != 0;
+        } else {
+            unsigned long long bb;
+            if constexpr (W::pass == 1)
+                bb = __hip_atomic_load(wa.bound + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                bb = wa.bound[r];
+            // (the builtin returns an int: through uint32_t, or a low word with its top bit set would sign-extend)
+            bb = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)bb) |
+                 ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(bb >> 32)) << 32);
+            b = __longlong_as_double((long long)bb);
+            go = valid && !(a.s.self && orig == r) && keep[(SED_JOIN_MAXLEN + 1) * n + m] <= b;  // (a compare: no arithmetic)
+        }
         const unsigned long long gb = __builtin_amdgcn_ballot_w64(go);
         if (gb == 0) continue;  // no column of this wave can be within the cutoff of row r
         ran += (uint32_t)__popcll(gb);
@@ -105,7 +162,21 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint
             for (int j = 0; j < MM; j += 2 * s) V[j] = (m & s) ? V[j + s] : V[j];
         const double D = m == MM ? V[MM] : V[0];
         const unsigned long long bits = (unsigned long long)__double_as_longlong(D);
-        sed_join_append(a.out, go && D <= a.max_dist, r, orig, (uint32_t)bits, (uint32_t)(bits >> 32));
+        if constexpr (W::pass == 0) {
+            sed_join_append(a.out, go && D <= a.max_dist, r, orig, (uint32_t)bits, (uint32_t)(bits >> 32));
+        } else if constexpr (W::pass == 2) {
+            sed_join_append(a.out, go && D <= b, r, orig, (uint32_t)bits, (uint32_t)(bits >> 32));
+        } else {
+            const bool cand = go && D <= b;
+            if (__popcll(__builtin_amdgcn_ballot_w64(cand)) < wa.k) continue;
+            unsigned long long x = 0;  // the largest x with fewer than k candidates at key < x: the k-th smallest key
+#pragma unroll 1
+            for (int bit = 62; bit >= 0; --bit) {
+                const unsigned long long c = x | (1ull << bit);
+                if (__popcll(__builtin_amdgcn_ballot_w64(cand && bits < c)) < wa.k) x = c;
+            }
+            if (x < (unsigned long long)__double_as_longlong(b) && (threadIdx.x & 63) == 0) atomicMin(wa.bound + r, x);
+        }
     }
     if (ran != 0 && (threadIdx.x & 63) == 0) atomicAdd(a.out.count + 1, (unsigned long long)ran);
 }
@@ -113,5 +184,10 @@ __global__ __launch_bounds__(SED_JOIN_BLOCK) void sed_join_f64_kernel(const uint
 }  // namespace
 
 hipError_t sed_launch_join_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_f64_args &a) {
-    return sed_join_launch(sed_join_f64_kernel, stream, ev0, ev1, a, a.sub, a.keep);
+    return sed_join_launch(sed_join_f64_kernel<sed_join_f64_all>, stream, ev0, ev1, a, a.sub, a.keep);
+}
+
+hipError_t sed_launch_join_knn_f64(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_join_knn_f64_args &a, bool emit) {
+    return emit ? sed_join_launch(sed_join_f64_kernel<sed_join_f64_knn<2>>, stream, ev0, ev1, a, a.j.sub, a.low)
+                : sed_join_launch(sed_join_f64_kernel<sed_join_f64_knn<1>>, stream, ev0, ev1, a, a.j.sub, a.low);
 }

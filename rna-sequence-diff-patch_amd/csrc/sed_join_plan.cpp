@@ -1,6 +1,7 @@
 // sed_join_plan.cpp — the join planner (sed_join_plan.h): scale and cost rows, the kernel variant, the cutoff on the
 // integer scale, the launches and the pair counts of a similarity join.  No HIP call.  Also the device-free entry points
-// sed_join_plan, sed_join_long_plan, sed_join_f64_plan, sed_join_f64_keep and sed_join_route of include/sed.h.
+// sed_join_plan, sed_join_long_plan, sed_join_f64_plan, sed_join_f64_keep, sed_join_knn_f64_plan, sed_join_f64_lower and
+// sed_join_route of include/sed.h.
 #include "sed_join_plan.h"
 
 #include <algorithm>
@@ -207,21 +208,29 @@ int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::
     return SED_OK;
 }
 
-void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t keep[SED_JOIN_MAXLEN + 1]) {
+void sed_join_f64_lower_rule(double ins, double del, double low[(SED_JOIN_MAXLEN + 1) * (SED_JOIN_MAXLEN + 1)]) {
     const double tiny = std::ldexp(1.0, -900), shrink = std::ldexp(1.0, -40);
-    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n) {
-        keep[n] = 0;
+    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n)
         for (int m = 0; m <= SED_JOIN_MAXLEN; ++m) {
-            bool run = true;
+            double v = 0.0;
             if (n == 0 || m == 0) {  // D is this product itself (0.0 when n = m = 0)
-                run = (n == 0 ? (double)m * ins : (double)n * del) <= max_dist;
-            } else if (n != m && std::isfinite(max_dist)) {
+                v = n == 0 ? (double)m * ins : (double)n * del;
+            } else if (n != m) {
                 const double p = m > n ? (double)(m - n) * ins : (double)(n - m) * del;
                 // D > p (1 - 2^-46) >= fl(p - p 2^-40) for a finite p >= 2^-900 (p 2^-40 is exact there)
-                if (std::isfinite(p) && p >= tiny) run = !(p - p * shrink > max_dist);
+                if (std::isfinite(p) && p >= tiny) v = p - p * shrink;
             }
-            if (run) keep[n] |= (uint64_t)1 << m;
+            low[(SED_JOIN_MAXLEN + 1) * n + m] = v;
         }
+}
+
+void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t keep[SED_JOIN_MAXLEN + 1]) {
+    double low[(SED_JOIN_MAXLEN + 1) * (SED_JOIN_MAXLEN + 1)];
+    sed_join_f64_lower_rule(ins, del, low);
+    for (int n = 0; n <= SED_JOIN_MAXLEN; ++n) {
+        keep[n] = 0;
+        for (int m = 0; m <= SED_JOIN_MAXLEN; ++m)
+            if (low[(SED_JOIN_MAXLEN + 1) * n + m] <= max_dist) keep[n] |= (uint64_t)1 << m;
     }
 }
 
@@ -232,6 +241,7 @@ int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *l
         const int rc = sed_join_f64_costs_rule(c, plan, err);
         if (rc != SED_OK) return rc;
         plan->max_dist = max_dist;
+        sed_join_f64_lower_rule(plan->ins, plan->del, plan->low);
         sed_join_f64_keep_rule(plan->ins, plan->del, max_dist, plan->keep);
         return SED_OK;
     };
@@ -337,6 +347,31 @@ extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_in
     rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
                               nullptr);
     return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, std::min(nout, 6));
+}
+
+extern "C" int sed_join_knn_f64_plan(int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
+                                     double del, int del_is_int, const int32_t *options, int noptions,
+                                     const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
+                                     uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout) {
+    knn_plan_error.clear();
+    std::string *err = &knn_plan_error;
+    int rc = sed_join_knn_k_rule(k, err);
+    if (rc != SED_OK) return rc;
+    if (nout < 0 || (nout && !out)) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    sed_costs c;
+    sed_opts o;
+    rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+    if (rc != SED_OK) return sed_plan_fail(err, rc, "bad join arguments");
+    sed_join_f64_plan_t p;
+    rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
+                              err);
+    return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, std::min(nout, 6));
+}
+
+extern "C" int sed_join_f64_lower(double ins, double del, double *low) {
+    if (!low || !(std::isfinite(ins) && ins >= 0) || !(std::isfinite(del) && del >= 0)) return SED_E_ARG;
+    sed_join_f64_lower_rule(ins + 0.0, del + 0.0, low);
+    return SED_OK;
 }
 
 extern "C" int sed_join_f64_keep(double ins, double del, double max_dist, uint64_t *keep) {

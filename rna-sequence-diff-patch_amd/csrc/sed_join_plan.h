@@ -1,9 +1,8 @@
 // sed_join_plan.h — the device-free half of the similarity join (include/sed.h: sed_join_self, sed_join_search): what a
 // join decides from the cost model, the options, the lengths, the codes seen and the cutoff.  sed_join_plan.cpp calls no
 // HIP API (it shares sed_costs, sed_opts and sed_plan_fail with the batch planner, sed_plan.h, and nothing else); its
-// exports sed_join_plan, sed_join_long_plan, sed_join_knn_plan, sed_join_knn_trim, sed_join_f64_plan, sed_join_f64_keep and
-// sed_join_route run, and are tested,
-// without a device.  The integer rule takes its longest sequence as a parameter: SED_JOIN_MAXLEN for sed_join_self /
+// exports sed_join_plan, sed_join_long_plan, sed_join_knn_plan, sed_join_knn_trim, sed_join_f64_plan, sed_join_f64_keep,
+// sed_join_knn_f64_plan, sed_join_f64_lower and sed_join_route run, and are tested, without a device.  The integer rule takes its longest sequence as a parameter: SED_JOIN_MAXLEN for sed_join_self /
 // sed_join_search, SED_JOIN_LONG_MAXLEN for sed_join_long_self / sed_join_long_search (kernel: sed_join_long.hip).
 #pragma once
 #include "sed_plan.h"
@@ -60,6 +59,7 @@ struct sed_join_f64_plan_t : sed_join_counts {
     double sub[SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK] = {};  // row a = row symbol a, zeros past K
     double max_dist = 0;
     uint64_t keep[SED_JOIN_MAXLEN + 1] = {};  // keep[n] bit m: a row of n and a column of m symbols are computed
+    double low[(SED_JOIN_MAXLEN + 1) * (SED_JOIN_MAXLEN + 1)] = {};  // low[33 n + m]: what keep compares with max_dist
 };
 // The table alone: K <= SED_JOIN_F64_MAXK, every cost finite and >= 0; fills ins, del, sub.  Anything else: SED_E_RANGE,
 // *err names the bound or the cost.
@@ -70,8 +70,15 @@ int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::
 // so the pair is left out exactly when n, m, k >= 1, max_dist is finite, p = fl(k c) is finite and >= 2^-900, and
 // fl(p - p 2^-40) > max_dist.  With n = 0 or m = 0, D is the product fl(m insert) or fl(n delete) itself and the exact
 // compare decides.  keep[n] bit m = the pair is computed.  ins, del >= +0, max_dist >= 0 or +inf.
+// The value the rule compares is a table of its own, low[33 n + m] for n, m = 0..32: the border product when n = 0 or
+// m = 0; fl(p - p 2^-40) when n != m and p is finite and >= 2^-900; else 0.  low <= D for every pair of those lengths,
+// every entry is >= +0 and no NaN (a border product may be +inf), and keep[n] bit m = low[33 n + m] <= max_dist.  The
+// k-nearest calls of this route compare it with a row's moving bound on the device.
+void sed_join_f64_lower_rule(double ins, double del, double low[(SED_JOIN_MAXLEN + 1) * (SED_JOIN_MAXLEN + 1)]);
 void sed_join_f64_keep_rule(double ins, double del, double max_dist, uint64_t keep[SED_JOIN_MAXLEN + 1]);
-// The whole plan: sed_join_plan_of's arguments, checks and counts, under the rule above.
+// The whole plan: sed_join_plan_of's arguments, checks and counts, under the rule above.  It is the plan of this route's
+// k-nearest calls as it is (sed_join_knn_k_rule first): max_dist is the cap every row's bound starts from, low the table
+// the passes skip by, and run / cells count what one pass runs at most.
 int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_rows, int32_t nrows,
                          const int32_t *len_cols, int32_t ncols, bool self, uint32_t row_codes, uint32_t col_codes,
                          double max_dist, sed_join_f64_plan_t *plan, std::string *err);

@@ -1,6 +1,6 @@
 // sed_join_runtime.cpp — the similarity join's entry points of the C-ABI (include/sed.h): sed_join_index_* and
-// sed_join_self / sed_join_search, their _f64 siblings and their k-nearest forms sed_join_knn_* over a resident index of
-// short sequences, and sed_join_long_* over one of sequences of up to 128 symbols.  What a join runs is the join planner's decision (sed_join_plan.cpp), the
+// sed_join_self / sed_join_search, their _f64 siblings and the k-nearest forms of both, sed_join_knn_*, over a resident
+// index of short sequences, and sed_join_long_* over one of sequences of up to 128 symbols.  What a join runs is the join planner's decision (sed_join_plan.cpp), the
 // kernels are sed_join.hip, sed_join_f64.hip and sed_join_long.hip; here: pack, reserve, upload, launch, download, sort,
 // decode, on the context's stream (sed_runtime.h).  The two index types differ in one number, the record's length.
 #include "sed_join_plan.h"
@@ -33,6 +33,18 @@ struct JoinRec {  // one record of the device hit list (sed_internal.h: sed_join
 const size_t SPARE = 16;  // the spare bytes that end a record buffer (the kernels' row loads reach two words past a record)
 
 const size_t F64_TAB = SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK;  // the fp64 table's doubles
+const size_t F64_LOW = (SED_JOIN_MAXLEN + 1) * (SED_JOIN_MAXLEN + 1);  // its k-nearest calls' lower-bound table's
+
+uint64_t bits_of(double v) {
+    uint64_t b;
+    memcpy(&b, &v, sizeof b);
+    return b;
+}
+double double_of(uint64_t b) {
+    double v;
+    memcpy(&v, &b, sizeof v);
+    return v;
+}
 
 uint32_t code_bit(uint8_t c) { return 1u << (c < 31 ? c : 31); }
 }  // namespace
@@ -48,13 +60,17 @@ struct sed_join_index {
     // their lengths and original indices (columns of every join); a search's query records and lengths
     DevBuf d_rows, d_row_len, d_cols, d_col_len, d_col_orig, d_query;
     DevBuf d_tab, d_hits, d_count;
-    DevBuf d_bound;                // the k-nearest calls' bound of every row, indexed as the rows are
+    DevBuf d_bound;                // the k-nearest calls' bound of every row, indexed as the rows are (fp64 route: 8 bytes a row)
     std::vector<uint32_t> h_bound; // the last k-nearest call's bounds after pass 1, one a row of the call
+    std::vector<uint64_t> h_bound64;  // the same when that call took the fp64 route (knn_f64): the bits of a double each
+    bool knn_f64 = false;          // the last k-nearest call that got past its plan took the fp64 route
     std::vector<sed_join_hit> h_knn;  // its candidates, decoded, for the trim
     int64_t knn_candidates = -1;   // the hits its pass 2 appended; -1 before the first k-nearest call
     uint32_t h_tab[16] = {};       // the cost rows of the call under way (the upload's source)
     DevBuf d_f64;                  // the fp64 route's table and keep words, and their upload's source
     uint64_t h_f64[F64_TAB + SED_JOIN_MAXLEN + 1] = {};
+    DevBuf d_f64k;                 // its k-nearest calls': [the table | the lower-bound table], and their upload's source
+    double h_f64k[F64_TAB + F64_LOW] = {};
     std::vector<uint8_t> h_query;
     std::vector<JoinRec> h_hits;
     PinBuf pin;                    // the two counters' download
@@ -63,7 +79,7 @@ struct sed_join_index {
     ~sed_join_index() {
         pin.release();
         d_rows.release(); d_row_len.release(); d_cols.release(); d_col_len.release(); d_col_orig.release();
-        d_query.release(); d_tab.release(); d_f64.release(); d_hits.release(); d_count.release(); d_bound.release();
+        d_query.release(); d_tab.release(); d_f64.release(); d_f64k.release(); d_hits.release(); d_count.release(); d_bound.release();
     }
 };
 
@@ -73,7 +89,7 @@ struct sed_join_long_index : sed_join_index {};  // (a type of its own in the C-
 struct JoinCall {
     const sed_join_plan_t *pi = nullptr;
     const sed_join_f64_plan_t *pf = nullptr;
-    int32_t knn = 0;  // k of a k-nearest call (the integer plan), 0: a join
+    int32_t knn = 0;  // k of a k-nearest call (of either route), 0: a join
     int64_t launch_rows() const { return pi ? pi->launch_rows : pf->launch_rows; }
 };
 
@@ -98,56 +114,82 @@ static void join_cols(const sed_join_index *ix, sed_join_sides *s) {
     s->ncols = ix->nseqs;
 }
 
-// A k-nearest call once its rows are on the device (k.knn = k, k.pi the plan; s, nrows as join_run takes them): every
-// row's bound set to the plan's cut; per row launch pass 1 (the bounds) then pass 2 (the candidates {D <= bound[r]}) on
+// A k-nearest call once its rows are on the device (k.knn = k, k.pi or k.pf the plan; s, nrows as join_run takes them):
+// every row's bound set to the plan's cut (the fp64 route: to max_dist's bits, a 64-bit word a row); per row launch pass 1 (the bounds) then pass 2 (the candidates {D <= bound[r]}) on
 // the one stream; the counters, the bounds and the candidates come down; the trim keeps each row's first k by (D, col).
 // The device list is sized for the candidates: when pass 2 overflows it, it grows to the count the device reports and
 // pass 2 alone runs once more (the bounds are final), which the pairs counted leave out and the time spans.
 static int join_knn_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
                         int64_t *found) {
     sed_ctx *c = ix->ctx;
-    const sed_join_plan_t &plan = *k.pi;
+    const bool f64 = k.pf != nullptr;
     const int32_t first = s.row0;
     const size_t nbound = (size_t)first + (size_t)nrows;
     const size_t guess = 2 * (size_t)nrows * (size_t)k.knn + 1024;  // records: twice the answer and a little
-    if (!ix->d_count.reserve(16) || !ix->d_tab.reserve(sizeof ix->h_tab) || !ix->d_bound.reserve(nbound * sizeof(uint32_t)) ||
+    if (!ix->d_count.reserve(16) || !(f64 ? ix->d_f64k.reserve(sizeof ix->h_f64k) : ix->d_tab.reserve(sizeof ix->h_tab)) ||
+        !ix->d_bound.reserve(nbound * (f64 ? sizeof(uint64_t) : sizeof(uint32_t))) ||
         !ix->d_hits.reserve(guess * sizeof(JoinRec)) || !ix->pin.reserve(16, 64))
         return c->fail(SED_E_OOM, "device allocation failed (k-nearest join, %d rows)", nrows);
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
     join_cols(ix, &s);
-    sed_join_knn_args ka{};
+    sed_join_knn_args ka{};  // (one of ka and kf is filled and launched: the call's route)
+    sed_join_knn_f64_args kf{};
     ka.bound = (uint32_t *)ix->d_bound.p;
-    ka.k = k.knn;
-    const bool bitpar = plan.kernel == SED_JOIN_KERNEL_BITPAR;
+    kf.bound = (unsigned long long *)ix->d_bound.p;
+    ka.k = kf.k = k.knn;
+    const bool bitpar = !f64 && k.pi->kernel == SED_JOIN_KERNEL_BITPAR;
     const int64_t step = k.launch_rows();
     ix->knn_candidates = -1;  // (a call that fails from here on leaves nothing to report)
-    ix->h_bound.assign((size_t)nrows, 0u);
+    if (f64)
+        ix->h_bound64.assign((size_t)nrows, 0u);
+    else
+        ix->h_bound.assign((size_t)nrows, 0u);
+    const size_t bsize = f64 ? sizeof(uint64_t) : sizeof(uint32_t);
+    void *const d_first = (uint8_t *)ix->d_bound.p + (size_t)first * bsize;
+    void *const h_first = f64 ? (void *)ix->h_bound64.data() : (void *)ix->h_bound.data();
     uint64_t n = 0;
     for (int run = 0; run < 2; ++run) {  // (run 1: pass 2 again with room for what run 0 counted)
         const sed_join_list list{(uint4 *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
                                  (unsigned long long)(ix->d_hits.cap / sizeof(JoinRec))};
-        if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess ||
-            (e = join_int_args(ix, plan, list, &ka.j)) != hipSuccess ||
-            (run == 0 && (e = hipMemsetD32Async((hipDeviceptr_t)(ka.bound + first), plan.cut, (size_t)nrows, c->stream)) !=
-                             hipSuccess))
-            return c->hipfail(e, "upload (k-nearest join)");
+        if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess) return c->hipfail(e, "upload (k-nearest join)");
+        if (f64) {  // one block: [the table | the lower-bound table]; the bounds start as max_dist's bits
+            const sed_join_f64_plan_t &plan = *k.pf;
+            static_assert(sizeof ix->h_f64k == sizeof plan.sub + sizeof plan.low, "the upload's layout");
+            memcpy(ix->h_f64k, plan.sub, sizeof plan.sub);
+            memcpy(ix->h_f64k + F64_TAB, plan.low, sizeof plan.low);
+            kf.j.sub = (const double *)ix->d_f64k.p;
+            kf.low = (const double *)ix->d_f64k.p + F64_TAB;
+            kf.j.ins = plan.ins;
+            kf.j.del = plan.del;
+            kf.j.max_dist = plan.max_dist;
+            kf.j.out = list;
+            e = hipMemcpyAsync(ix->d_f64k.p, ix->h_f64k, sizeof ix->h_f64k, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess && run == 0) {
+                std::fill(ix->h_bound64.begin(), ix->h_bound64.end(), bits_of(plan.max_dist));
+                e = hipMemcpyAsync(d_first, h_first, (size_t)nrows * bsize, hipMemcpyHostToDevice, c->stream);
+            }
+        } else if ((e = join_int_args(ix, *k.pi, list, &ka.j)) == hipSuccess && run == 0) {
+            e = hipMemsetD32Async((hipDeviceptr_t)d_first, k.pi->cut, (size_t)nrows, c->stream);
+        }
+        if (e != hipSuccess) return c->hipfail(e, "upload (k-nearest join)");
         for (int64_t r = 0; r < nrows; r += step) {
             s.row0 = first + (int32_t)r;
             s.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
-            ka.j.s = s;
+            ka.j.s = kf.j.s = s;
             const bool head = r == 0, tail = r + step >= nrows;
             for (int emit = run; emit < 2; ++emit) {
                 hipEvent_t e0 = run == 0 && head && !emit ? ix->timer.ev[0] : nullptr;
                 hipEvent_t e1 = emit ? (tail ? ix->timer.ev[1] : nullptr) : (run == 0 && head ? ix->timer.ev[2] : nullptr);
-                e = ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long_knn(c->stream, e0, e1, ka, bitpar, emit != 0)
-                                                       : sed_launch_join_knn(c->stream, e0, e1, ka, bitpar, emit != 0);
+                e = f64 ? sed_launch_join_knn_f64(c->stream, e0, e1, kf, emit != 0)
+                    : ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long_knn(c->stream, e0, e1, ka, bitpar, emit != 0)
+                                                         : sed_launch_join_knn(c->stream, e0, e1, ka, bitpar, emit != 0);
                 if (e != hipSuccess) return c->hipfail(e, "k-nearest join kernel launch");
             }
         }
         if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-            (run == 0 && (e = hipMemcpyAsync(ix->h_bound.data(), ka.bound + first, (size_t)nrows * sizeof(uint32_t),
-                                             hipMemcpyDeviceToHost, c->stream)) != hipSuccess))
+            (run == 0 && (e = hipMemcpyAsync(h_first, d_first, (size_t)nrows * bsize, hipMemcpyDeviceToHost, c->stream)) !=
+                             hipSuccess))
             return c->hipfail(e, "download (k-nearest join)");
         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "k-nearest join kernel execution");
         ix->timer.timed = ix->timer.knn = true;
@@ -164,15 +206,24 @@ static int join_knn_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s,
                                        c->stream)) != hipSuccess ||
                    (e = hipStreamSynchronize(c->stream)) != hipSuccess))
         return c->hipfail(e, "download (k-nearest candidates)");
-    const double inv = std::ldexp(1.0, -plan.scale_log2);
+    const double inv = f64 ? 0.0 : std::ldexp(1.0, -k.pi->scale_log2);
     ix->h_knn.resize((size_t)n);
     for (size_t i = 0; i < (size_t)n; ++i) {
         const JoinRec &r = ix->h_hits[i];
-        if (r.row < (uint32_t)first || r.row >= (uint32_t)first + (uint32_t)nrows || r.col >= (uint32_t)ix->nseqs ||
-            r.D > ix->h_bound[r.row - (uint32_t)first] || r.D > (uint32_t)plan.cut || (s.self && r.row == r.col))
+        bool ok = r.row >= (uint32_t)first && r.row < (uint32_t)first + (uint32_t)nrows && r.col < (uint32_t)ix->nseqs &&
+                  !(s.self && r.row == r.col);
+        double dist = 0;
+        if (ok && f64) {  // (D, zero) = the double's low and high words, copied, not scaled; NaN fails the compares
+            dist = double_of((uint64_t)r.D | ((uint64_t)r.zero << 32));
+            ok = dist >= 0 && dist <= double_of(ix->h_bound64[r.row - (uint32_t)first]) && dist <= k.pf->max_dist;
+        } else if (ok) {
+            dist = (double)r.D * inv;
+            ok = r.D <= ix->h_bound[r.row - (uint32_t)first] && r.D <= (uint32_t)k.pi->cut;
+        }
+        if (!ok)
             return c->fail(SED_E_DEVICE, "k-nearest join: record %zu from the device is no candidate (row %u, column %u)", i,
                            r.row, r.col);
-        ix->h_knn[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, (double)r.D * inv};
+        ix->h_knn[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, dist};
     }
     int64_t kept = 0;
     if (sed_join_knn_trim(ix->h_knn.data(), (int64_t)n, k.knn, &kept) != SED_OK)
@@ -390,7 +441,11 @@ static int join_plan_call(sed_ctx *c, bool f64, const int32_t *len_rows, int32_t
 // A k-nearest call got past its plan: what sed_join_knn_bounds and sed_join_knn_candidates report until it has run
 static void join_knn_planned(sed_join_index *ix, const JoinCall &k, int32_t nrows) {
     if (!k.knn) return;
-    ix->h_bound.assign((size_t)nrows, (uint32_t)k.pi->cut);
+    ix->knn_f64 = k.pf != nullptr;
+    if (k.pf)
+        ix->h_bound64.assign((size_t)nrows, bits_of(k.pf->max_dist));
+    else
+        ix->h_bound.assign((size_t)nrows, (uint32_t)k.pi->cut);
     ix->knn_candidates = 0;
 }
 
@@ -512,9 +567,28 @@ int sed_join_knn_search(sed_join_index *ix, const uint8_t *codes_q, const int64_
 
 int sed_join_knn_bounds(const sed_join_index *ix, int32_t *bounds, int32_t n) {
     if (!ix || n < 0 || (n && !bounds)) return SED_E_ARG;
-    if (ix->knn_candidates < 0) return SED_E_STATE;
+    if (ix->knn_candidates < 0 || ix->knn_f64) return SED_E_STATE;
     if ((size_t)n != ix->h_bound.size()) return SED_E_ARG;
     for (int32_t i = 0; i < n; ++i) bounds[i] = (int32_t)ix->h_bound[(size_t)i];
+    return SED_OK;
+}
+
+// ---- the same on the fp64 route (the short index) ----
+int sed_join_knn_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist, sed_join_hit *out,
+                          int64_t cap, int64_t *found) {
+    return join_self(ix, true, &k, row_lo, row_hi, max_dist, out, cap, found);
+}
+
+int sed_join_knn_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
+                            int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
+    return join_search(ix, true, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+}
+
+int sed_join_knn_bounds_f64(const sed_join_index *ix, double *bounds, int32_t n) {
+    if (!ix || n < 0 || (n && !bounds)) return SED_E_ARG;
+    if (ix->knn_candidates < 0 || !ix->knn_f64) return SED_E_STATE;
+    if ((size_t)n != ix->h_bound64.size()) return SED_E_ARG;
+    for (int32_t i = 0; i < n; ++i) bounds[i] = double_of(ix->h_bound64[(size_t)i]);
     return SED_OK;
 }
 

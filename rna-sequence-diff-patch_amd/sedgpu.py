@@ -217,6 +217,15 @@ SIGNATURES = [
                                     _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
                                     _f64p, C.c_int]),
     ("sed_join_f64_keep", C.c_int, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_uint64)]),
+    ("sed_join_knn_self_f64", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64,
+                                        C.POINTER(C.c_int64)]),
+    ("sed_join_knn_search_f64", C.c_int, [C.c_void_p, _u8p, _i64p, _i32p, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
+                                          C.c_int64, C.POINTER(C.c_int64)]),
+    ("sed_join_knn_bounds_f64", C.c_int, [C.c_void_p, _f64p, C.c_int32]),
+    ("sed_join_knn_f64_plan", C.c_int, [C.c_int32, C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p,
+                                        C.c_int, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32,
+                                        C.c_double, _f64p, C.c_int]),
+    ("sed_join_f64_lower", C.c_int, [C.c_double, C.c_double, _f64p]),
     ("sed_join_route", C.c_int, [C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int, _i32p, C.c_int,
                                  _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32, C.c_double,
                                  C.c_char_p, C.c_int]),
@@ -776,27 +785,43 @@ class JoinIndex:
         """search() through the fp64 kernel (sed_join_search_f64)."""
         return self.search(packed, max_dist, cap, "sed_join_search_f64")
 
-    def self_knn(self, k, max_dist=math.inf, rows=None, cap=None):
+    def self_knn(self, k, max_dist=math.inf, rows=None, cap=None, _call=None):
         """For every i in rows = (lo, hi) (default: every sequence), the k sequences j != i of smallest distance(seq i ->
         seq j) among those within max_dist (sed_join_knn_self): JOIN_HIT_DTYPE records sorted by (row, dist, col), ties
         going to the lower column.  k = 1..64; exact.  cap as for self_join (None: room for k a row, which suffices)."""
         lo, hi = (0, self.nseqs) if rows is None else rows
-        _call = self._PREFIX + "knn_self"
+        _call = _call or self._PREFIX + "knn_self"
         fn = getattr(self._lib, _call)
         self._knn_rows = max(int(hi) - int(lo), 0)
         return self._hits(_call, lambda out, room, found: fn(
             self.ptr, int(lo), int(hi), int(k), float(max_dist), out, room, found),
             self._knn_rows * min(max(int(k), 0), 64) if cap is None else cap)
 
-    def search_knn(self, packed, k, max_dist=math.inf, cap=None):
+    def search_knn(self, packed, k, max_dist=math.inf, cap=None, _call=None):
         """For every query q, the k sequences of smallest distance(query q -> seq j) among those within max_dist
         (sed_join_knn_search); packed and cap as for search and self_knn."""
-        _call = self._PREFIX + "knn_search"
+        _call = _call or self._PREFIX + "knn_search"
         fn = getattr(self._lib, _call)
         self._knn_rows = packed.npairs
         return self._hits(_call, lambda out, room, found: fn(
             self.ptr, packed.codes_a, packed.off_a, packed.len_a, packed.npairs, int(k), float(max_dist), out, room, found),
             self._knn_rows * min(max(int(k), 0), 64) if cap is None else cap)
+
+    def self_knn_f64(self, k, max_dist=math.inf, rows=None, cap=None):
+        """self_knn() through the fp64 kernel (sed_join_knn_self_f64): the tables and alphabets (up to 16 symbols)
+        self_knn() refuses; the order is by (the oracle's double, col) and dist is that double, bit for bit."""
+        return self.self_knn(k, max_dist, rows, cap, "sed_join_knn_self_f64")
+
+    def search_knn_f64(self, packed, k, max_dist=math.inf, cap=None):
+        """search_knn() through the fp64 kernel (sed_join_knn_search_f64)."""
+        return self.search_knn(packed, k, max_dist, cap, "sed_join_knn_search_f64")
+
+    def knn_bounds_f64(self):
+        """The last self_knn_f64 / search_knn_f64 call's bound of every row after its first pass, as doubles, one per row
+        of the call (sed_join_knn_bounds_f64)."""
+        out = np.zeros(max(self._knn_rows, 1), np.float64)
+        self.ctx._check(self._lib.sed_join_knn_bounds_f64(self.ptr, out, self._knn_rows), "sed_join_knn_bounds_f64")
+        return out[:self._knn_rows]
 
     def knn_bounds(self):
         """The last self_knn / search_knn call's bound of every row after its first pass, on the integer scale (D * S),
@@ -852,6 +877,15 @@ class LongJoinIndex(JoinIndex):
 
     def search_f64(self, packed, max_dist, cap=None):
         raise SedError("the long join has no fp64 route yet (sed_join_long_search serves the integer route's tables)")
+
+    def self_knn_f64(self, k, max_dist=math.inf, rows=None, cap=None):
+        raise SedError("the long join has no fp64 route yet (sed_join_long_knn_self serves the integer route's tables)")
+
+    def search_knn_f64(self, packed, k, max_dist=math.inf, cap=None):
+        raise SedError("the long join has no fp64 route yet (sed_join_long_knn_search serves the integer route's tables)")
+
+    def knn_bounds_f64(self):
+        raise SedError("the long join has no fp64 route yet (sed_join_long_knn_bounds serves the integer route's calls)")
 
 
 JOIN_PLAN_FIELDS = ("scale", "kernel", "waves", "scope", "run", "cells")
@@ -929,6 +963,31 @@ def join_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_
     """What JoinIndex.self_join_f64 / search_f64 would decide, without a device (sed_join_f64_plan): join_plan's fields
     with scale = 0 (fp64 has none) and kernel = 3.  Arguments and errors as join_plan."""
     return join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist, "sed_join_f64_plan")
+
+
+def join_knn_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, k, max_dist):
+    """What JoinIndex.self_knn_f64 / search_knn_f64 would decide, without a device (sed_join_knn_f64_plan): k outside
+    1..64 raises SedError (.code = SED_E_ARG, the text names k), then join_f64_plan's refusals, with their text; the
+    fields are those of the fp64 join at max_dist, which bound each pass from above."""
+    out = np.zeros(len(JOIN_PLAN_FIELDS), np.float64)
+    rc = load().sed_join_knn_f64_plan(int(k), *_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes,
+                                                          max_dist), out, len(out))
+    if rc != 0:
+        err = SedError("sed_join_knn_f64_plan failed (%d): %s" % (rc, load().sed_join_knn_plan_error().decode()))
+        err.code = rc
+        raise err
+    return {f: (float(v) if f in ("scale", "cells") else int(v)) for f, v in zip(JOIN_PLAN_FIELDS, out)}
+
+
+def join_f64_lower(ins, dele):
+    """The table behind the fp64 route's length skip (sed_join_f64_lower): a 33 x 33 float64 array, [n, m] a value <=
+    every distance of a row of n and a column of m symbols under these costs; join_f64_keep(ins, dele, T) is
+    join_f64_lower(ins, dele) <= T."""
+    low = np.zeros(33 * 33, np.float64)
+    rc = load().sed_join_f64_lower(float(ins), float(dele), low)
+    if rc != 0:
+        raise _fit_fail("sed_join_f64_lower", rc)
+    return low.reshape(33, 33)
 
 
 def join_f64_keep(ins, dele, max_dist):

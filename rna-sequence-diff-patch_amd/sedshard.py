@@ -7,6 +7,8 @@ own inputs, runs the engine, and only the fixed-size per-pair results travel,
 once, to rank 0 (gather_to_rank0).  The same code runs over gloo on CPU tensors
 for the tests.
 """
+import math
+
 import numpy as np
 
 
@@ -121,23 +123,29 @@ def _hits_to_rank0(hits, world, rank, device, torch):
 
 
 def nearest_neighbors(seqs, k, max_dist=None, userCosts=False, world=1, rank=0, device=None, join_fn=None,
-                      long_sequences=False):
+                      long_sequences=False, route="int"):
     """For every sequence i of seqs, its k nearest sequences j != i by the distance from seqs[i] to seqs[j] (k = 1..64;
     max_dist, None for no cap, leaves out what lies farther), as a numpy record array (row, col, dist) sorted by (row,
     dist, col), on rank 0 (None on other ranks).  Rows are independent: rank r takes its block of rows,
-    shard_range(len(seqs), world, r), against every sequence on its own GPU (StringEditDistance.JoinIndex.self_nearest,
-    the integer kernels), and the blocks are contiguous, so their concatenation is sorted by row.
+    shard_range(len(seqs), world, r), against every sequence on its own GPU (StringEditDistance.JoinIndex.self_nearest
+    or, under route "f64" / "auto", self_nearest_f64), and the blocks are contiguous, so their concatenation is sorted by
+    row.  route: as neighbors takes it ("auto" asks with max_dist None as +inf); the fp64 route calls join_fn with
+    f64=True as a further, keyword argument, and with long_sequences=True "f64" and "auto" raise ValueError.
     join_fn(seqs, lo, hi, k, max_dist, userCosts) -> [(i, j, dist)] sorted replaces the engine (CPU tests), as for
     neighbors; long_sequences=True serves sequences of 0..128 symbols, and join_fn is then called with long_seqs=True as
     a further, keyword argument."""
     import torch
-    if join_fn is None:
+    if route not in ("int", "f64", "auto"):
+        raise ValueError("route must be one of int, f64, auto, not %r" % (route,))
+    if long_sequences and route != "int":
+        raise ValueError("the long join has no fp64 route yet: long_sequences=True takes route=\"int\", not %r" % (route,))
+    if join_fn is None or route == "auto":
         import StringEditDistance as SED
-
-        def join_fn(seqs, lo, hi, k, max_dist, userCosts, long_seqs=False):
-            ix = SED.join_index(seqs, userCosts, long_seqs=long_seqs)
+    if join_fn is None:
+        def join_fn(seqs, lo, hi, k, max_dist, userCosts, f64=False, long_seqs=False):
+            ix = SED.join_index(seqs, userCosts, f64=route != "int", long_seqs=long_seqs)
             try:
-                return ix.self_nearest(k, max_dist, (lo, hi))
+                return (ix.self_nearest_f64 if f64 else ix.self_nearest)(k, max_dist, (lo, hi))
             finally:
                 ix.close()
     lo, hi = shard_range(len(seqs), world, rank)
@@ -145,6 +153,9 @@ def nearest_neighbors(seqs, k, max_dist=None, userCosts=False, world=1, rank=0, 
         hits = []
     elif long_sequences:
         hits = list(join_fn(seqs, lo, hi, k, max_dist, userCosts, long_seqs=True))
+    elif (SED.join_route(seqs[lo:hi], seqs, math.inf if max_dist is None else max_dist, userCosts)
+          if route == "auto" else route) == "f64":
+        hits = list(join_fn(seqs, lo, hi, k, max_dist, userCosts, f64=True))
     else:
         hits = list(join_fn(seqs, lo, hi, k, max_dist, userCosts))
     return _hits_to_rank0(hits, world, rank, device, torch)

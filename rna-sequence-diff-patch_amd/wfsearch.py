@@ -342,16 +342,18 @@ class JoinIndex:
     index_fn(sequences, user_cost) -> an object with self_join(max_dist, rows) -> [(i, j, d)] and
     search(queries, max_dist) -> [(q, j, d)], both sorted, self_nearest(k, max_dist, rows) and search_nearest(queries, k,
     max_dist) -> the same records sorted by (row, d, j), and close(), replaces the engine (CPU tests).  Not cached.
-    nearest and nearest_many take no route: they run the integer kernels (StringEditDistance.JoinIndex.self_nearest).
 
-    route (the constructor's, and per call on neighbors, search_many, search; None = the constructor's): "int" (the
+    route (the constructor's, and per call on neighbors, search_many, search, nearest, nearest_many; None = the
+    constructor's): "int" (the
     default) runs the integer kernels, which serve dyadic cost tables over at most 8 symbols and raise SedError
     otherwise; "f64" runs the fp64 kernel, which serves any table of costs >= 0 over at most 16 symbols (IUPAC
     collections under costs.json); "auto" takes the integer call whenever it serves the join
     (StringEditDistance.join_route), so only a refusal turns into a result.  An index whose constructor route is "f64"
     or "auto" is built with f64=True (up to 16 symbols; index_fn is called with that keyword) and serves integer calls
     too; one built under the default keeps the 8-symbol bound, whatever route a later call names.  The fp64 route calls
-    the index's self_join_f64 / search_f64.
+    the index's self_join_f64 / search_f64, and self_nearest_f64 / search_nearest_f64 for nearest / nearest_many
+    (max_dist None counts as +inf when "auto" asks which route serves); where the integer route serves a table both
+    routes return identical lists.
 
     long_sequences=True serves sequences and queries of 0..128 symbols (tRNA, pre-miRNA hairpins, 5S rRNA) through the
     integer route's long kernel (StringEditDistance.join_index(..., long_seqs=True); index_fn is called with
@@ -408,7 +410,7 @@ class JoinIndex:
     def search(self, query, max_dist, route=None):
         return self.search_many([query], max_dist, route)[0]
 
-    def nearest(self, k, max_dist=None, rows=None):
+    def nearest(self, k, max_dist=None, rows=None, route=None):
         """Per sequence i of rows = (lo, hi) (default: all), [(j, 1 / (1 + d))] for its k nearest sequences j != i by the
         distance d from sequence i to sequence j, nearest first, ties going to the lower j; max_dist (None: no cap)
         leaves out what lies farther, so a list may be shorter than k.  k = 1..64; exact."""
@@ -419,11 +421,12 @@ class JoinIndex:
                 raise ValueError("rows=(%r, %r) is no range of the index's 0 sequences" % (lo, hi))
             return []
         out = [[] for _ in range(lo, hi)]
-        for i, j, d in self._ix.self_nearest(k, max_dist, rows):
+        f64 = self._f64(route, self.seqs[lo:hi], math.inf if max_dist is None else max_dist)
+        for i, j, d in (self._ix.self_nearest_f64 if f64 else self._ix.self_nearest)(k, max_dist, rows):
             out[i - lo].append((j, 1 / (1 + d)))
         return out
 
-    def nearest_many(self, queries, k, max_dist=None):
+    def nearest_many(self, queries, k, max_dist=None, route=None):
         """Per query, [(sequence, 1 / (1 + d))] for its k nearest documents, nearest first: nearest(query, seqs, k) for
         all the queries from one engine call (ties go to the document that comes first in the collection)."""
         queries = list(queries)
@@ -431,7 +434,8 @@ class JoinIndex:
         if self._ix is None:
             SED.JoinIndex.check_k(k)
             return out
-        for q, j, d in self._ix.search_nearest(queries, k, max_dist):
+        f64 = self._f64(route, queries, math.inf if max_dist is None else max_dist)
+        for q, j, d in (self._ix.search_nearest_f64 if f64 else self._ix.search_nearest)(queries, k, max_dist):
             out[q].append((self.seqs[j], 1 / (1 + d)))
         return out
 
@@ -450,9 +454,10 @@ def neighbors(seqs_or_collection, max_dist, user_cost=False, index_fn=None, rout
         ix.close()
 
 
-def nearest_neighbors(seqs_or_collection, k, max_dist=None, user_cost=False, index_fn=None, long_sequences=False):
+def nearest_neighbors(seqs_or_collection, k, max_dist=None, user_cost=False, index_fn=None, long_sequences=False,
+                      route="int"):
     """JoinIndex.nearest in one shot: builds an index over the sequences, takes every sequence's k nearest and closes it."""
-    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, long_sequences=long_sequences)
+    ix = JoinIndex(seqs_or_collection, user_cost, index_fn=index_fn, route=route, long_sequences=long_sequences)
     try:
         return ix.nearest(k, max_dist)
     finally:
