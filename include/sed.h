@@ -688,6 +688,19 @@ int sed_join_knn_bound_time(const sed_join_index *ix, float *kernel_ms);
 /* The trim and the sort alone, in place, without a device: hits[0 .. n) in any order -> sorted by (row, dist, col), each
  * row's first k; *kept = the records left.  k outside 1..64, n < 0, a NULL or a NaN dist: SED_E_ARG. */
 int sed_join_knn_trim(sed_join_hit *hits, int64_t n, int32_t k, int64_t *kept);
+/* What every join call does with the records it downloads, alone and without a device: validate, convert, order.
+ * records = n device records of four 32-bit words (row, col, w0, w1).  route = SED_JOIN_ROUTE_INT: dist = w0 *
+ * 2^-scale_log2 (scale_log2 0..8) and cap = the cutoff on the integer scale; SED_JOIN_ROUTE_F64: (w0, w1) are the low and
+ * high words of dist, copied, and cap = max_dist.  The call's rows are first_row .. first_row + nrows - 1, the columns
+ * 0 .. ncols - 1; self != 0: (i, i) is out of scope.  k = 0: a join, bounds unread, out sorted by (row, col); k = 1..64:
+ * a k-nearest call, bounds = its rows' bounds after pass 1 (nrows of them: uint32_t each on the integer route, double on
+ * fp64), out = sed_join_knn_trim's.  out has room for n hits; *kept = the hits left.
+ * SED_E_ARG: bad arguments.  SED_E_DEVICE: a record no kernel emits - a row outside the call, a column outside the
+ * index, (i, i) of a self join, a distance that is NaN, negative, above cap or above its row's bound, or a (row, col)
+ * reported twice among the hits left; why (why_len bytes, may be 0) names the record. */
+int sed_join_decode(const uint32_t *records, int64_t n, int route, int32_t scale_log2, double cap, int32_t first_row,
+                    int32_t nrows, int32_t ncols, int self, int32_t k, const void *bounds, sed_join_hit *out, int64_t *kept,
+                    char *why, int why_len);
 /* What a k-nearest call would decide, without a device: k, then sed_join_plan's arguments (long_index != 0: those of
  * sed_join_long_plan, with its out[6]).  k outside 1..64: SED_E_ARG before anything else is looked at; then
  * sed_join_plan's refusals in their order.  out[]: the plan of the join at max_dist, which bounds each pass from above.

@@ -1,12 +1,13 @@
 // sed_join_plan.cpp — the join planner (sed_join_plan.h): scale and cost rows, the kernel variant, the cutoff on the
-// integer scale, the launches and the pair counts of a similarity join.  No HIP call.  Also the device-free entry points
-// sed_join_plan, sed_join_long_plan, sed_join_f64_plan, sed_join_f64_keep, sed_join_knn_f64_plan, sed_join_f64_lower and
-// sed_join_route of include/sed.h.
+// integer scale, the launches and the pair counts of a similarity join, and the decode of its device records.  No HIP
+// call.  Also the device-free entry points of include/sed.h: the five plan exports (one body, join_plan_export),
+// sed_join_knn_trim, sed_join_decode, sed_join_f64_keep, sed_join_f64_lower and sed_join_route.
 #include "sed_join_plan.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 int sed_join_costs_rule(const sed_costs &c, int maxlen, sed_join_plan_t *plan, std::string *err) {
@@ -189,6 +190,63 @@ extern "C" int sed_join_knn_trim(sed_join_hit *hits, int64_t n, int32_t k, int64
     return SED_OK;
 }
 
+int sed_join_decode_of(const sed_join_decode_call &d, const sed_join_rec *rec, int64_t n, sed_join_hit *out, int64_t *kept,
+                       std::string *err) {
+    const bool f64 = d.route == SED_JOIN_ROUTE_F64, knn = d.k != 0;
+    if ((!f64 && d.route != SED_JOIN_ROUTE_INT) || n < 0 || (n && (!rec || !out)) || !kept || d.first < 0 || d.nrows < 0 ||
+        d.ncols < 0 || std::isnan(d.cap) || d.cap < 0 || (!f64 && (d.scale_log2 < 0 || d.scale_log2 > 8)) ||
+        (knn && (d.k < 1 || d.k > SED_JOIN_KNN_MAXK || (d.nrows && !d.bound))))
+        return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    const char *const form = knn ? "k-nearest join" : "join", *const what = knn ? "candidate" : "hit";
+    const uint32_t first = (uint32_t)d.first, end = first + (uint32_t)d.nrows;
+    const double inv = std::ldexp(1.0, -d.scale_log2);
+    for (int64_t i = 0; i < n; ++i) {
+        const sed_join_rec &r = rec[i];
+        bool ok = r.row >= first && r.row < end && r.col < (uint32_t)d.ncols && !(d.self && r.row == r.col);
+        double dist = 0;
+        if (ok && f64) {  // the two words are the double's low and high ones, copied, not scaled; NaN fails the compares
+            const uint64_t bits = (uint64_t)r.w0 | ((uint64_t)r.w1 << 32);
+            memcpy(&dist, &bits, sizeof dist);
+            double bound = d.cap;
+            if (knn) memcpy(&bound, (const uint8_t *)d.bound + sizeof bound * (r.row - first), sizeof bound);
+            ok = dist >= 0 && dist <= d.cap && dist <= bound;
+        } else if (ok) {
+            dist = (double)r.w0 * inv;
+            uint32_t bound = r.w0;
+            if (knn) memcpy(&bound, (const uint8_t *)d.bound + sizeof bound * (r.row - first), sizeof bound);
+            ok = (double)r.w0 <= d.cap && r.w0 <= bound;
+        }
+        if (!ok)
+            return sed_plan_fail(err, SED_E_DEVICE, "%s: record %lld from the device is no %s (row %u, column %u)", form,
+                                 (long long)i, what, r.row, r.col);
+        out[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, dist};
+    }
+    *kept = n;
+    if (knn) {
+        if (sed_join_knn_trim(out, n, d.k, kept) != SED_OK)
+            return sed_plan_fail(err, SED_E_DEVICE, "k-nearest join: the trim refused the device's records");
+    } else {
+        std::sort(out, out + n, [](const sed_join_hit &x, const sed_join_hit &y) { return x.row != y.row ? x.row < y.row : x.col < y.col; });
+    }
+    for (int64_t i = 1; i < *kept; ++i)
+        if (out[i - 1].row == out[i].row && out[i - 1].col == out[i].col)
+            return knn ? sed_plan_fail(err, SED_E_DEVICE, "k-nearest join: row %d reports column %d twice", out[i].row, out[i].col)
+                       : sed_plan_fail(err, SED_E_DEVICE, "join: record %lld from the device is no hit (row %d, column %d)",
+                                       (long long)i, out[i].row, out[i].col);
+    return SED_OK;
+}
+
+extern "C" int sed_join_decode(const uint32_t *records, int64_t n, int route, int32_t scale_log2, double cap, int32_t first_row,
+                               int32_t nrows, int32_t ncols, int self, int32_t k, const void *bounds, sed_join_hit *out,
+                               int64_t *kept, char *why, int why_len) {
+    if (why_len < 0 || (why_len && !why)) return SED_E_ARG;
+    std::string text;
+    const sed_join_decode_call d{route, scale_log2, cap, first_row, nrows, ncols, self != 0, k, bounds};
+    const int rc = sed_join_decode_of(d, (const sed_join_rec *)records, n, out, kept, &text);
+    if (why_len) std::snprintf(why, (size_t)why_len, "%s", text.c_str());
+    return rc;
+}
+
 // ---- the fp64 route ----
 int sed_join_f64_costs_rule(const sed_costs &c, sed_join_f64_plan_t *plan, std::string *err) {
     if (c.K > SED_JOIN_F64_MAXK)
@@ -273,100 +331,75 @@ static int join_plan_out(double scale, int kernel, const sed_join_counts &p, dou
     return SED_OK;
 }
 
-static thread_local std::string long_plan_error;  // sed_join_long_plan_error's text
+// The five plan exports' one body.  What an export is: its route (SED_JOIN_ROUTE_*), its longest sequence, k of a
+// k-nearest plan (NULL: a join's), the slots of out[] it fills (6, or 7 with lane_cells) and where a refusal's text goes
+// (NULL: nowhere).  The order: k, the out[] slots, the costs and options, then the route's whole plan.
+struct JoinPlanExport {
+    int route, maxlen;
+    const int32_t *k;
+    int nslots;
+    std::string *err;
+};
+// sed_join_plan's arguments after the export's own, in its order
+#define JOIN_PLAN_PARAMS                                                                                                       \
+    int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del, int del_is_int,                \
+        const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, \
+        int self, uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout
+#define JOIN_PLAN_ARGS                                                                                                  \
+    K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_rows, nrows, len_cols, ncols, self, \
+        row_codes_seen, col_codes_seen, max_dist, out, nout
 
-// sed_join_plan and sed_join_long_plan: the integer plan for sequences of up to maxlen symbols, nslots slots of it; *err
-// (may be NULL) gets a refusal's text
-static int join_plan_export(int maxlen, int nslots, std::string *err, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
-                            double del, int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
-                            int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
-                            uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
-    sed_costs c;
-    sed_opts o;
-    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc != SED_OK) return sed_plan_fail(err, rc, "bad join arguments");
-    sed_join_plan_t p;
-    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, maxlen, &p,
-                          err);
-    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, std::min(nout, nslots));
-}
-
-extern "C" int sed_join_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                             int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows, int32_t nrows,
-                             const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
-                             uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    return join_plan_export(SED_JOIN_MAXLEN, 6, nullptr, K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, len_rows,
-                            nrows, len_cols, ncols, self, row_codes_seen, col_codes_seen, max_dist, out, nout);
-}
-
-extern "C" int sed_join_long_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                                  int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
-                                  int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
-                                  uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    long_plan_error.clear();
-    return join_plan_export(SED_JOIN_LONG_MAXLEN, 7, &long_plan_error, K, sub, sub_int, ins, ins_is_int, del, del_is_int,
-                            options, noptions, len_rows, nrows, len_cols, ncols, self, row_codes_seen, col_codes_seen, max_dist,
-                            out, nout);
-}
-
-extern "C" const char *sed_join_long_plan_error(void) { return long_plan_error.c_str(); }
-
-static thread_local std::string knn_plan_error;  // sed_join_knn_plan_error's text
-
-extern "C" int sed_join_knn_plan(int long_index, int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins,
-                                 int ins_is_int, double del, int del_is_int, const int32_t *options, int noptions,
-                                 const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
-                                 uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    knn_plan_error.clear();
-    std::string *err = &knn_plan_error;
-    if (nout < 0 || (nout && !out)) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
-    sed_costs c;
-    sed_opts o;
-    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc != SED_OK) return sed_plan_fail(err, rc, "bad join arguments");
-    sed_join_plan_t p;
-    if ((rc = sed_join_knn_k_rule(k, err)) != SED_OK) return rc;
-    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist,
-                          long_index ? SED_JOIN_LONG_MAXLEN : SED_JOIN_MAXLEN, &p, err);
-    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, std::min(nout, long_index ? 7 : 6));
-}
-
-extern "C" const char *sed_join_knn_plan_error(void) { return knn_plan_error.c_str(); }
-
-extern "C" int sed_join_f64_plan(int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int, double del,
-                                 int del_is_int, const int32_t *options, int noptions, const int32_t *len_rows,
-                                 int32_t nrows, const int32_t *len_cols, int32_t ncols, int self, uint32_t row_codes_seen,
-                                 uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    if (nout < 0 || (nout && !out)) return SED_E_ARG;
-    sed_costs c;
-    sed_opts o;
-    int rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
+static int join_plan_export(const JoinPlanExport &x, JOIN_PLAN_PARAMS) {
+    if (x.err) x.err->clear();
+    int rc = x.k ? sed_join_knn_k_rule(*x.k, x.err) : SED_OK;
     if (rc != SED_OK) return rc;
-    sed_join_f64_plan_t p;
-    rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
-                              nullptr);
-    return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, std::min(nout, 6));
-}
-
-extern "C" int sed_join_knn_f64_plan(int32_t k, int K, const double *sub, const uint8_t *sub_int, double ins, int ins_is_int,
-                                     double del, int del_is_int, const int32_t *options, int noptions,
-                                     const int32_t *len_rows, int32_t nrows, const int32_t *len_cols, int32_t ncols, int self,
-                                     uint32_t row_codes_seen, uint32_t col_codes_seen, double max_dist, double *out, int nout) {
-    knn_plan_error.clear();
-    std::string *err = &knn_plan_error;
-    int rc = sed_join_knn_k_rule(k, err);
-    if (rc != SED_OK) return rc;
-    if (nout < 0 || (nout && !out)) return sed_plan_fail(err, SED_E_ARG, "bad join arguments");
+    if (nout < 0 || (nout && !out)) return sed_plan_fail(x.err, SED_E_ARG, "bad join arguments");
     sed_costs c;
     sed_opts o;
     rc = join_costs_of(K, sub, sub_int, ins, ins_is_int, del, del_is_int, options, noptions, &c, &o);
-    if (rc != SED_OK) return sed_plan_fail(err, rc, "bad join arguments");
-    sed_join_f64_plan_t p;
-    rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
-                              err);
-    return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, std::min(nout, 6));
+    if (rc != SED_OK) return sed_plan_fail(x.err, rc, "bad join arguments");
+    if (x.route == SED_JOIN_ROUTE_F64) {
+        sed_join_f64_plan_t p;
+        rc = sed_join_f64_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, &p,
+                                  x.err);
+        return rc != SED_OK ? rc : join_plan_out(0.0, SED_JOIN_KERNEL_F64, p, out, std::min(nout, x.nslots));
+    }
+    sed_join_plan_t p;
+    rc = sed_join_plan_of(c, o, len_rows, nrows, len_cols, ncols, self != 0, row_codes_seen, col_codes_seen, max_dist, x.maxlen,
+                          &p, x.err);
+    return rc != SED_OK ? rc : join_plan_out(std::ldexp(1.0, p.scale_log2), p.kernel, p, out, std::min(nout, x.nslots));
 }
+
+static thread_local std::string long_plan_error;  // sed_join_long_plan_error's text
+static thread_local std::string knn_plan_error;   // sed_join_knn_plan_error's text
+
+extern "C" int sed_join_plan(JOIN_PLAN_PARAMS) {
+    return join_plan_export({SED_JOIN_ROUTE_INT, SED_JOIN_MAXLEN, nullptr, 6, nullptr}, JOIN_PLAN_ARGS);
+}
+
+extern "C" int sed_join_long_plan(JOIN_PLAN_PARAMS) {
+    return join_plan_export({SED_JOIN_ROUTE_INT, SED_JOIN_LONG_MAXLEN, nullptr, 7, &long_plan_error}, JOIN_PLAN_ARGS);
+}
+
+extern "C" int sed_join_knn_plan(int long_index, int32_t k, JOIN_PLAN_PARAMS) {
+    const JoinPlanExport x{SED_JOIN_ROUTE_INT, long_index ? SED_JOIN_LONG_MAXLEN : SED_JOIN_MAXLEN, &k, long_index ? 7 : 6,
+                           &knn_plan_error};
+    return join_plan_export(x, JOIN_PLAN_ARGS);
+}
+
+extern "C" int sed_join_f64_plan(JOIN_PLAN_PARAMS) {
+    return join_plan_export({SED_JOIN_ROUTE_F64, SED_JOIN_MAXLEN, nullptr, 6, nullptr}, JOIN_PLAN_ARGS);
+}
+
+extern "C" int sed_join_knn_f64_plan(int32_t k, JOIN_PLAN_PARAMS) {
+    return join_plan_export({SED_JOIN_ROUTE_F64, SED_JOIN_MAXLEN, &k, 6, &knn_plan_error}, JOIN_PLAN_ARGS);
+}
+#undef JOIN_PLAN_PARAMS
+#undef JOIN_PLAN_ARGS
+
+extern "C" const char *sed_join_long_plan_error(void) { return long_plan_error.c_str(); }
+
+extern "C" const char *sed_join_knn_plan_error(void) { return knn_plan_error.c_str(); }
 
 extern "C" int sed_join_f64_lower(double ins, double del, double *low) {
     if (!low || !(std::isfinite(ins) && ins >= 0) || !(std::isfinite(del) && del >= 0)) return SED_E_ARG;

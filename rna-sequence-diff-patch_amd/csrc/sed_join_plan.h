@@ -1,9 +1,10 @@
 // sed_join_plan.h — the device-free half of the similarity join (include/sed.h: sed_join_self, sed_join_search): what a
 // join decides from the cost model, the options, the lengths, the codes seen and the cutoff.  sed_join_plan.cpp calls no
 // HIP API (it shares sed_costs, sed_opts and sed_plan_fail with the batch planner, sed_plan.h, and nothing else); its
-// exports sed_join_plan, sed_join_long_plan, sed_join_knn_plan, sed_join_knn_trim, sed_join_f64_plan, sed_join_f64_keep,
-// sed_join_knn_f64_plan, sed_join_f64_lower and sed_join_route run, and are tested, without a device.  The integer rule takes its longest sequence as a parameter: SED_JOIN_MAXLEN for sed_join_self /
-// sed_join_search, SED_JOIN_LONG_MAXLEN for sed_join_long_self / sed_join_long_search (kernel: sed_join_long.hip).
+// exports sed_join_plan, sed_join_long_plan, sed_join_knn_plan, sed_join_knn_trim, sed_join_decode, sed_join_f64_plan,
+// sed_join_f64_keep, sed_join_knn_f64_plan, sed_join_f64_lower and sed_join_route run, and are tested, without a device.
+// The integer rule takes its longest sequence as a parameter: SED_JOIN_MAXLEN for sed_join_self / sed_join_search,
+// SED_JOIN_LONG_MAXLEN for sed_join_long_self / sed_join_long_search (kernel: sed_join_long.hip).
 #pragma once
 #include "sed_plan.h"
 
@@ -50,6 +51,28 @@ int sed_join_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *len_r
 // is sed_join_plan_of as it is: plan->cut is the cap floor(max_dist S) every row's bound starts from, and run / cells /
 // lane_cells count what one pass runs at most (the bounds only take pairs away).
 int sed_join_knn_k_rule(int32_t k, std::string *err);
+
+// The decode of a call's device records, for every route and form: validate, convert, order.  The one place a wrong
+// record is refused before the caller sees it (DESIGN.md 3.6q lists the checks).
+struct sed_join_rec {  // one 16-byte record of the device list (sed_internal.h: sed_join_list)
+    uint32_t row, col, w0, w1;  // integer route: w0 = D on the scale, w1 unread; fp64: the distance's low and high words
+};
+struct sed_join_decode_call {
+    int route;           // SED_JOIN_ROUTE_INT or SED_JOIN_ROUTE_F64
+    int scale_log2;      // integer route: dist = D * 2^-scale_log2 (0..8); fp64: unread, the words are the double's bits
+    double cap;          // the plan's cut (integer route) or max_dist (fp64): no distance is above it
+    int32_t first, nrows, ncols;  // the call's rows are first .. first + nrows - 1, the index's columns 0 .. ncols - 1
+    bool self;           // a self join: (i, i) is out of scope
+    int32_t k;           // 0: a join; else k of a k-nearest call
+    const void *bound;   // k-nearest: the rows' bounds after pass 1, nrows of them: uint32_t each on the integer route,
+                         // a double each on fp64 (any alignment); a record is within its row's bound
+};
+// rec[0 .. n) -> out[0 .. n) (room for n hits), *kept = the hits left.  A join: sorted by (row, col).  A k-nearest
+// call: through sed_join_knn_trim, so sorted by (row, dist, col) and each row's first k.  Then no (row, col) occurs twice
+// among the hits left.  Bad arguments: SED_E_ARG; a record that fails a check: SED_E_DEVICE, *err names it.  Nothing in
+// out is promised after a refusal.
+int sed_join_decode_of(const sed_join_decode_call &d, const sed_join_rec *rec, int64_t n, sed_join_hit *out, int64_t *kept,
+                       std::string *err);
 
 // The fp64 route (include/sed.h: sed_join_self_f64, sed_join_search_f64; kernel: sed_join_f64.hip): any table of finite
 // costs >= 0 over at most SED_JOIN_F64_MAXK symbols.  There is no scale: a cell's value is the oracle's.

@@ -1,12 +1,14 @@
-// sed_join_runtime.cpp — the similarity join's entry points of the C-ABI (include/sed.h): sed_join_index_* and
-// sed_join_self / sed_join_search, their _f64 siblings and the k-nearest forms of both, sed_join_knn_*, over a resident
-// index of short sequences, and sed_join_long_* over one of sequences of up to 128 symbols.  What a join runs is the join planner's decision (sed_join_plan.cpp), the
-// kernels are sed_join.hip, sed_join_f64.hip and sed_join_long.hip; here: pack, reserve, upload, launch, download, sort,
-// decode, on the context's stream (sed_runtime.h).  The two index types differ in one number, the record's length.
+// sed_join_runtime.cpp — the similarity join's entry points of the C-ABI (include/sed.h): sed_join_index_*,
+// sed_join_self / sed_join_search, their _f64 siblings and the k-nearest forms of both (sed_join_knn_*) over a resident
+// index of short sequences, and sed_join_long_* over one of sequences of up to 128 symbols.  What a join runs is the
+// join planner's decision and what its records mean is the planner's decode (sed_join_plan.cpp); the kernels are
+// sed_join.hip, sed_join_f64.hip and sed_join_long.hip.  Here: pack, reserve, upload, launch, download, on the context's
+// stream (sed_runtime.h).  A call is three values - the index type (one number, the record's length), the numeric route
+// (JoinRoute) and the form (k = 0: a join, else the k nearest) - and one loop, join_run, runs every combination.
 #include "sed_join_plan.h"
 #include "sed_runtime.h"
 
-#include <cmath>
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -27,26 +29,16 @@ struct JoinTimer {  // the events around a call's launches, created on first use
         return hipSuccess;
     }
 };
-struct JoinRec {  // one record of the device hit list (sed_internal.h: sed_join_args)
-    uint32_t row, col, D, zero;  // (the fp64 route: D, zero = the distance's low and high words)
-};
+const size_t REC_BYTES = sizeof(sed_join_rec);  // one record of the device hit list (sed_internal.h: sed_join_list)
+static_assert(REC_BYTES == sizeof(uint4), "a record of the device list");
 const size_t SPARE = 16;  // the spare bytes that end a record buffer (the kernels' row loads reach two words past a record)
 
 const size_t F64_TAB = SED_JOIN_F64_MAXK * SED_JOIN_F64_MAXK;  // the fp64 table's doubles
 const size_t F64_LOW = (SED_JOIN_MAXLEN + 1) * (SED_JOIN_MAXLEN + 1);  // its k-nearest calls' lower-bound table's
 
-uint64_t bits_of(double v) {
-    uint64_t b;
-    memcpy(&b, &v, sizeof b);
-    return b;
-}
-double double_of(uint64_t b) {
-    double v;
-    memcpy(&v, &b, sizeof v);
-    return v;
-}
-
 uint32_t code_bit(uint8_t c) { return 1u << (c < 31 ? c : 31); }
+
+struct JoinRoute;
 }  // namespace
 
 struct sed_join_index {
@@ -59,273 +51,245 @@ struct sed_join_index {
     // the records in the caller's order and their lengths (rows of a self join); the records sorted by length (stable),
     // their lengths and original indices (columns of every join); a search's query records and lengths
     DevBuf d_rows, d_row_len, d_cols, d_col_len, d_col_orig, d_query;
-    DevBuf d_tab, d_hits, d_count;
-    DevBuf d_bound;                // the k-nearest calls' bound of every row, indexed as the rows are (fp64 route: 8 bytes a row)
-    std::vector<uint32_t> h_bound; // the last k-nearest call's bounds after pass 1, one a row of the call
-    std::vector<uint64_t> h_bound64;  // the same when that call took the fp64 route (knn_f64): the bits of a double each
-    bool knn_f64 = false;          // the last k-nearest call that got past its plan took the fp64 route
-    std::vector<sed_join_hit> h_knn;  // its candidates, decoded, for the trim
-    int64_t knn_candidates = -1;   // the hits its pass 2 appended; -1 before the first k-nearest call
-    uint32_t h_tab[16] = {};       // the cost rows of the call under way (the upload's source)
-    DevBuf d_f64;                  // the fp64 route's table and keep words, and their upload's source
-    uint64_t h_f64[F64_TAB + SED_JOIN_MAXLEN + 1] = {};
-    DevBuf d_f64k;                 // its k-nearest calls': [the table | the lower-bound table], and their upload's source
-    double h_f64k[F64_TAB + F64_LOW] = {};
+    DevBuf d_hits, d_count;
+    DevBuf d_block;                // the route's upload block (JoinRoute::fill) and its source
+    uint64_t h_block[F64_TAB + F64_LOW] = {};
+    DevBuf d_bound;                // the k-nearest calls' bound of every row, indexed as the rows are, JoinRoute::bound_bytes each
+    std::vector<uint64_t> h_bound; // the last k-nearest call's bounds after pass 1, packed as on the device: bound_rows of
+    int32_t bound_rows = 0;        // knn_route->bound_bytes each (a call that ran nothing: the bound every row starts from)
+    const JoinRoute *knn_route = nullptr;  // the route of the last k-nearest call that got past its plan
+    std::vector<sed_join_hit> h_knn;  // its candidates, decoded and trimmed
+    int64_t knn_candidates = -1;   // the hits its emit pass appended; -1 before the first k-nearest call
     std::vector<uint8_t> h_query;
-    std::vector<JoinRec> h_hits;
+    std::vector<sed_join_rec> h_hits;
     PinBuf pin;                    // the two counters' download
     JoinTimer timer;
     int64_t pairs_run = -1;
     ~sed_join_index() {
         pin.release();
         d_rows.release(); d_row_len.release(); d_cols.release(); d_col_len.release(); d_col_orig.release();
-        d_query.release(); d_tab.release(); d_f64.release(); d_f64k.release(); d_hits.release(); d_count.release(); d_bound.release();
+        d_query.release(); d_block.release(); d_hits.release(); d_count.release(); d_bound.release();
     }
 };
 
 struct sed_join_long_index : sed_join_index {};  // (a type of its own in the C-ABI: its records are 128 bytes)
 
-// What a call runs: the integer plan or the fp64 plan (exactly one is set)
+namespace {
+// What a call runs: its route, that route's plan, and the form
 struct JoinCall {
-    const sed_join_plan_t *pi = nullptr;
-    const sed_join_f64_plan_t *pf = nullptr;
-    int32_t knn = 0;  // k of a k-nearest call (of either route), 0: a join
-    int64_t launch_rows() const { return pi ? pi->launch_rows : pf->launch_rows; }
+    const JoinRoute *route = nullptr;
+    sed_join_plan_t pi;      // route->id == SED_JOIN_ROUTE_INT
+    sed_join_f64_plan_t pf;  // route->id == SED_JOIN_ROUTE_F64
+    const sed_join_counts *counts = nullptr;  // what both plans share, of the one that is filled
+    int32_t knn = 0;         // k of a k-nearest call, 0: a join
+    int maxlen = SED_JOIN_MAXLEN;  // the index type
 };
 
-// The integer route's arguments but for the sides: the cost rows' upload, the plan's numbers, the list
-static hipError_t join_int_args(sed_join_index *ix, const sed_join_plan_t &plan, const sed_join_list &list, sed_join_args *a) {
-    memcpy(ix->h_tab, plan.sp.row, sizeof ix->h_tab);
-    a->tab = (const uint2 *)ix->d_tab.p;
-    a->ins = plan.sp.ins;
-    a->del = plan.sp.del;
-    a->umap = plan.sp.umap;
-    a->shift = plan.scale_log2;
-    a->cut = plan.cut;
-    a->out = list;
-    return hipMemcpyAsync(ix->d_tab.p, ix->h_tab, sizeof ix->h_tab, hipMemcpyHostToDevice, ix->ctx->stream);
+// The launch arguments of either route in their k-nearest form; a join launches the .j of its route's
+union JoinArgs {
+    sed_join_knn_args i;
+    sed_join_knn_f64_args f;
+};
+
+// Everything join_run does that depends on the numeric route.  A new route is a new row of this table.
+struct JoinRoute {
+    int id;                 // SED_JOIN_ROUTE_*
+    size_t bound_bytes;     // a row's bound on the device (the kernels read it at this width)
+    size_t block_bytes[2];  // the upload block of a join [0] and of a k-nearest call [1]
+    // the route's plan of the call into k, the refusal's text in the context
+    int (*plan)(sed_ctx *c, const sed_join_index *ix, const int32_t *len_rows, int32_t nrows, bool self, uint32_t row_codes,
+                double max_dist, JoinCall *k);
+    // the upload block's content (h_block) and the arguments but for the sides, from the plan
+    void (*fill)(const JoinCall &k, uint64_t *h_block, const void *d_block, void *d_bound, const sed_join_list &list, JoinArgs *a);
+    // one launch over the rows of s: a join's one pass, or a k-nearest call's bound (emit = false) or emit pass
+    hipError_t (*launch)(const JoinCall &k, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, JoinArgs *a, const sed_join_sides &s,
+                         bool emit);
+    uint64_t (*bound0)(const JoinCall &k);  // the bound every row starts from, as a 64-bit fill word
+    void (*decode)(const JoinCall &k, sed_join_decode_call *d);  // how a record's trailing words become a distance
+};
+
+// ---- the integer route: the block is the 64 bytes of cost rows; a bound is D on the scale, 4 bytes ----
+int int_plan(sed_ctx *c, const sed_join_index *ix, const int32_t *len_rows, int32_t nrows, bool self, uint32_t row_codes,
+             double max_dist, JoinCall *k) {
+    k->counts = &k->pi;
+    return sed_join_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes, max_dist,
+                            ix->maxlen, &k->pi, &c->err);
+}
+void int_fill(const JoinCall &k, uint64_t *h_block, const void *d_block, void *d_bound, const sed_join_list &list, JoinArgs *a) {
+    const sed_join_plan_t &p = k.pi;
+    static_assert(sizeof p.sp.row == 64, "the upload's layout");
+    memcpy(h_block, p.sp.row, sizeof p.sp.row);
+    sed_join_args &j = a->i.j;
+    j.tab = (const uint2 *)d_block;
+    j.ins = p.sp.ins;
+    j.del = p.sp.del;
+    j.umap = p.sp.umap;
+    j.shift = p.scale_log2;
+    j.cut = p.cut;
+    j.out = list;
+    a->i.bound = (uint32_t *)d_bound;
+    a->i.k = k.knn;
+}
+hipError_t int_launch(const JoinCall &k, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, JoinArgs *a, const sed_join_sides &s,
+                      bool emit) {
+    a->i.j.s = s;
+    const bool bitpar = k.pi.kernel == SED_JOIN_KERNEL_BITPAR, lng = k.maxlen == SED_JOIN_LONG_MAXLEN;
+    if (!k.knn) return lng ? sed_launch_join_long(stream, ev0, ev1, a->i.j, bitpar) : sed_launch_join(stream, ev0, ev1, a->i.j, bitpar);
+    return lng ? sed_launch_join_long_knn(stream, ev0, ev1, a->i, bitpar, emit)
+               : sed_launch_join_knn(stream, ev0, ev1, a->i, bitpar, emit);
+}
+uint64_t int_bound0(const JoinCall &k) { return (uint64_t)(uint32_t)k.pi.cut * 0x100000001ull; }
+void int_decode(const JoinCall &k, sed_join_decode_call *d) {
+    d->scale_log2 = k.pi.scale_log2;
+    d->cap = k.pi.cut;
 }
 
-// The columns' side of every launch
-static void join_cols(const sed_join_index *ix, sed_join_sides *s) {
-    s->cols = ix->d_cols.p;
-    s->col_len = (const int32_t *)ix->d_col_len.p;
-    s->col_orig = (const int32_t *)ix->d_col_orig.p;
-    s->ncols = ix->nseqs;
+// ---- the fp64 route: the block is [sub | keep] for a join, [sub | low] for a k-nearest call; a bound is a double's bits ----
+int f64_plan(sed_ctx *c, const sed_join_index *ix, const int32_t *len_rows, int32_t nrows, bool self, uint32_t row_codes,
+             double max_dist, JoinCall *k) {
+    k->counts = &k->pf;
+    return sed_join_f64_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes, max_dist,
+                                &k->pf, &c->err);
 }
+void f64_fill(const JoinCall &k, uint64_t *h_block, const void *d_block, void *d_bound, const sed_join_list &list, JoinArgs *a) {
+    const sed_join_f64_plan_t &p = k.pf;
+    static_assert(sizeof p.sub == F64_TAB * 8 && sizeof p.low == F64_LOW * 8 && sizeof p.keep <= sizeof p.low, "the upload's layout");
+    memcpy(h_block, p.sub, sizeof p.sub);
+    sed_join_f64_args &j = a->f.j;
+    j.sub = (const double *)d_block;
+    if (k.knn) {
+        memcpy(h_block + F64_TAB, p.low, sizeof p.low);
+        a->f.low = (const double *)d_block + F64_TAB;
+    } else {
+        memcpy(h_block + F64_TAB, p.keep, sizeof p.keep);
+        j.keep = (const unsigned long long *)d_block + F64_TAB;
+    }
+    j.ins = p.ins;
+    j.del = p.del;
+    j.max_dist = p.max_dist;
+    j.out = list;
+    a->f.bound = (unsigned long long *)d_bound;
+    a->f.k = k.knn;
+}
+hipError_t f64_launch(const JoinCall &k, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, JoinArgs *a, const sed_join_sides &s,
+                      bool emit) {
+    a->f.j.s = s;
+    return k.knn ? sed_launch_join_knn_f64(stream, ev0, ev1, a->f, emit) : sed_launch_join_f64(stream, ev0, ev1, a->f.j);
+}
+uint64_t f64_bound0(const JoinCall &k) {
+    uint64_t b;
+    memcpy(&b, &k.pf.max_dist, sizeof b);
+    return b;
+}
+void f64_decode(const JoinCall &k, sed_join_decode_call *d) { d->cap = k.pf.max_dist; }
 
-// A k-nearest call once its rows are on the device (k.knn = k, k.pi or k.pf the plan; s, nrows as join_run takes them):
-// every row's bound set to the plan's cut (the fp64 route: to max_dist's bits, a 64-bit word a row); per row launch pass 1 (the bounds) then pass 2 (the candidates {D <= bound[r]}) on
-// the one stream; the counters, the bounds and the candidates come down; the trim keeps each row's first k by (D, col).
-// The device list is sized for the candidates: when pass 2 overflows it, it grows to the count the device reports and
-// pass 2 alone runs once more (the bounds are final), which the pairs counted leave out and the time spans.
-static int join_knn_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
-                        int64_t *found) {
+const JoinRoute ROUTE_INT = {SED_JOIN_ROUTE_INT, sizeof(uint32_t), {64, 64}, int_plan, int_fill, int_launch, int_bound0, int_decode};
+const JoinRoute ROUTE_F64 = {SED_JOIN_ROUTE_F64, sizeof(uint64_t), {8 * (F64_TAB + SED_JOIN_MAXLEN + 1), 8 * (F64_TAB + F64_LOW)},
+                             f64_plan, f64_fill, f64_launch, f64_bound0, f64_decode};
+
+// What a HIP failure's text calls the steps of either form
+struct JoinSteps {
+    const char *upload, *launch, *download, *execution, *records;
+};
+const JoinSteps STEPS[2] = {
+    {"upload (join)", "join kernel launch", "download (join)", "join kernel execution", "download (join hits)"},
+    {"upload (k-nearest join)", "k-nearest join kernel launch", "download (k-nearest join)", "k-nearest join kernel execution",
+     "download (k-nearest candidates)"}};
+}  // namespace
+
+// What every call runs once its rows are on the device.  s holds the rows (rows, row_len, row0, self); nrows rows from
+// s.row0 on.  A k-nearest call (k.knn = k): every row's bound starts at the route's cap; per row step, the bound pass
+// then the emit pass (the candidates within bound[r]) on the one stream; the counters and the bounds come down.  Its
+// device list is sized for the candidates: when the emit pass overflows it, it grows to the count the device reports and
+// the emit pass alone runs once more (the bounds are final), which the pairs counted leave out and the time spans.  A
+// join is the same with the emit pass alone, the cap as every row's bound, the list the caller's cap long and no second
+// attempt: an overflow goes back as SED_E_RANGE before any record is downloaded.
+static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
+                    int64_t *found) {
     sed_ctx *c = ix->ctx;
-    const bool f64 = k.pf != nullptr;
+    const JoinRoute &rt = *k.route;
+    const bool knn = k.knn != 0;
+    const JoinSteps &step_of = STEPS[knn];
     const int32_t first = s.row0;
-    const size_t nbound = (size_t)first + (size_t)nrows;
-    const size_t guess = 2 * (size_t)nrows * (size_t)k.knn + 1024;  // records: twice the answer and a little
-    if (!ix->d_count.reserve(16) || !(f64 ? ix->d_f64k.reserve(sizeof ix->h_f64k) : ix->d_tab.reserve(sizeof ix->h_tab)) ||
-        !ix->d_bound.reserve(nbound * (f64 ? sizeof(uint64_t) : sizeof(uint32_t))) ||
-        !ix->d_hits.reserve(guess * sizeof(JoinRec)) || !ix->pin.reserve(16, 64))
-        return c->fail(SED_E_OOM, "device allocation failed (k-nearest join, %d rows)", nrows);
+    const size_t block = rt.block_bytes[knn], bbytes = knn ? (size_t)nrows * rt.bound_bytes : 0;
+    // the list's records: twice a k-nearest call's answer and a little; a join's: what the caller has room for
+    const size_t room = knn ? 2 * (size_t)nrows * (size_t)k.knn + 1024 : std::max<size_t>((size_t)cap, 1);
+    if ((!knn && (uint64_t)cap > SIZE_MAX / REC_BYTES) || !ix->d_count.reserve(16) || !ix->d_block.reserve(block) ||
+        !ix->d_bound.reserve(knn ? ((size_t)first + (size_t)nrows) * rt.bound_bytes : 0) || !ix->d_hits.reserve(room * REC_BYTES) ||
+        !ix->pin.reserve(16, 64))
+        return knn ? c->fail(SED_E_OOM, "device allocation failed (k-nearest join, %d rows)", nrows)
+                   : c->fail(SED_E_OOM, "device allocation failed (join, room for %lld hits)", (long long)cap);
     hipError_t e = hipSuccess;
     if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
-    join_cols(ix, &s);
-    sed_join_knn_args ka{};  // (one of ka and kf is filled and launched: the call's route)
-    sed_join_knn_f64_args kf{};
-    ka.bound = (uint32_t *)ix->d_bound.p;
-    kf.bound = (unsigned long long *)ix->d_bound.p;
-    ka.k = kf.k = k.knn;
-    const bool bitpar = !f64 && k.pi->kernel == SED_JOIN_KERNEL_BITPAR;
-    const int64_t step = k.launch_rows();
-    ix->knn_candidates = -1;  // (a call that fails from here on leaves nothing to report)
-    if (f64)
-        ix->h_bound64.assign((size_t)nrows, 0u);
-    else
-        ix->h_bound.assign((size_t)nrows, 0u);
-    const size_t bsize = f64 ? sizeof(uint64_t) : sizeof(uint32_t);
-    void *const d_first = (uint8_t *)ix->d_bound.p + (size_t)first * bsize;
-    void *const h_first = f64 ? (void *)ix->h_bound64.data() : (void *)ix->h_bound.data();
+    s.cols = ix->d_cols.p;  // the columns' side of every launch
+    s.col_len = (const int32_t *)ix->d_col_len.p;
+    s.col_orig = (const int32_t *)ix->d_col_orig.p;
+    s.ncols = ix->nseqs;
+    JoinArgs a;
+    memset(&a, 0, sizeof a);
+    void *const d_first = (uint8_t *)ix->d_bound.p + (size_t)first * rt.bound_bytes;
+    const int64_t step = k.counts->launch_rows;
+    if (knn) ix->knn_candidates = -1;  // (a call that fails from here on leaves nothing to report)
     uint64_t n = 0;
-    for (int run = 0; run < 2; ++run) {  // (run 1: pass 2 again with room for what run 0 counted)
+    for (int attempt = 0;; ++attempt) {  // (attempt 1, k-nearest alone: the emit pass again with room for what attempt 0 counted)
         const sed_join_list list{(uint4 *)ix->d_hits.p, (unsigned long long *)ix->d_count.p,
-                                 (unsigned long long)(ix->d_hits.cap / sizeof(JoinRec))};
-        if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess) return c->hipfail(e, "upload (k-nearest join)");
-        if (f64) {  // one block: [the table | the lower-bound table]; the bounds start as max_dist's bits
-            const sed_join_f64_plan_t &plan = *k.pf;
-            static_assert(sizeof ix->h_f64k == sizeof plan.sub + sizeof plan.low, "the upload's layout");
-            memcpy(ix->h_f64k, plan.sub, sizeof plan.sub);
-            memcpy(ix->h_f64k + F64_TAB, plan.low, sizeof plan.low);
-            kf.j.sub = (const double *)ix->d_f64k.p;
-            kf.low = (const double *)ix->d_f64k.p + F64_TAB;
-            kf.j.ins = plan.ins;
-            kf.j.del = plan.del;
-            kf.j.max_dist = plan.max_dist;
-            kf.j.out = list;
-            e = hipMemcpyAsync(ix->d_f64k.p, ix->h_f64k, sizeof ix->h_f64k, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess && run == 0) {
-                std::fill(ix->h_bound64.begin(), ix->h_bound64.end(), bits_of(plan.max_dist));
-                e = hipMemcpyAsync(d_first, h_first, (size_t)nrows * bsize, hipMemcpyHostToDevice, c->stream);
-            }
-        } else if ((e = join_int_args(ix, *k.pi, list, &ka.j)) == hipSuccess && run == 0) {
-            e = hipMemsetD32Async((hipDeviceptr_t)d_first, k.pi->cut, (size_t)nrows, c->stream);
-        }
-        if (e != hipSuccess) return c->hipfail(e, "upload (k-nearest join)");
-        for (int64_t r = 0; r < nrows; r += step) {
+                                 knn ? (unsigned long long)(ix->d_hits.cap / REC_BYTES) : (unsigned long long)cap};
+        const int pass0 = knn && attempt == 0 ? 0 : 1;  // this attempt's passes: pass0 .. 1 (0: the bounds, 1: emit)
+        rt.fill(k, ix->h_block, ix->d_block.p, ix->d_bound.p, list, &a);
+        if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(ix->d_block.p, ix->h_block, block, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
+            (pass0 == 0 && (e = hipMemcpyAsync(d_first, ix->h_bound.data(), bbytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess))
+            return c->hipfail(e, step_of.upload);  // (h_bound: every row's starting bound, join_knn_planned)
+        for (int64_t r = 0; r < nrows; r += step) {  // the events bracket the launches
             s.row0 = first + (int32_t)r;
             s.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
-            ka.j.s = kf.j.s = s;
-            const bool head = r == 0, tail = r + step >= nrows;
-            for (int emit = run; emit < 2; ++emit) {
-                hipEvent_t e0 = run == 0 && head && !emit ? ix->timer.ev[0] : nullptr;
-                hipEvent_t e1 = emit ? (tail ? ix->timer.ev[1] : nullptr) : (run == 0 && head ? ix->timer.ev[2] : nullptr);
-                e = f64 ? sed_launch_join_knn_f64(c->stream, e0, e1, kf, emit != 0)
-                    : ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long_knn(c->stream, e0, e1, ka, bitpar, emit != 0)
-                                                         : sed_launch_join_knn(c->stream, e0, e1, ka, bitpar, emit != 0);
-                if (e != hipSuccess) return c->hipfail(e, "k-nearest join kernel launch");
+            const bool head = attempt == 0 && r == 0, tail = r + step >= nrows;
+            for (int pass = pass0; pass < 2; ++pass) {
+                hipEvent_t e0 = head && pass == pass0 ? ix->timer.ev[0] : nullptr;
+                hipEvent_t e1 = pass ? (tail ? ix->timer.ev[1] : nullptr) : (head ? ix->timer.ev[2] : nullptr);
+                if ((e = rt.launch(k, c->stream, e0, e1, &a, s, pass != 0)) != hipSuccess) return c->hipfail(e, step_of.launch);
             }
         }
         if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-            (run == 0 && (e = hipMemcpyAsync(h_first, d_first, (size_t)nrows * bsize, hipMemcpyDeviceToHost, c->stream)) !=
-                             hipSuccess))
-            return c->hipfail(e, "download (k-nearest join)");
-        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "k-nearest join kernel execution");
-        ix->timer.timed = ix->timer.knn = true;
+            (pass0 == 0 && (e = hipMemcpyAsync(ix->h_bound.data(), d_first, bbytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess))
+            return c->hipfail(e, step_of.download);
+        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, step_of.execution);
+        ix->timer.timed = true;
+        ix->timer.knn = knn;
         n = ((const uint64_t *)ix->pin.p)[0];
-        if (run == 0) ix->pairs_run = (int64_t)((const uint64_t *)ix->pin.p)[1];
+        if (attempt == 0) ix->pairs_run = (int64_t)((const uint64_t *)ix->pin.p)[1];
         if (n <= list.cap) break;
-        if (run == 1) return c->fail(SED_E_DEVICE, "k-nearest join: %llu candidates after room was made for them", (unsigned long long)n);
-        if (n > SIZE_MAX / sizeof(JoinRec) || !ix->d_hits.reserve((size_t)n * sizeof(JoinRec)))
+        if (!knn) {
+            *found = (int64_t)n;
+            return c->fail(SED_E_RANGE, "join: found %lld hits, cap %lld: call again with room for them", (long long)n, (long long)cap);
+        }
+        if (attempt == 1) return c->fail(SED_E_DEVICE, "k-nearest join: %llu candidates after room was made for them", (unsigned long long)n);
+        if (n > SIZE_MAX / REC_BYTES || !ix->d_hits.reserve((size_t)n * REC_BYTES))
             return c->fail(SED_E_OOM, "device allocation failed (k-nearest join, room for %llu candidates)", (unsigned long long)n);
     }
-    ix->knn_candidates = (int64_t)n;
-    ix->h_hits.resize((size_t)n);
-    if (n != 0 && ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(JoinRec), hipMemcpyDeviceToHost,
-                                       c->stream)) != hipSuccess ||
-                   (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-        return c->hipfail(e, "download (k-nearest candidates)");
-    const double inv = f64 ? 0.0 : std::ldexp(1.0, -k.pi->scale_log2);
-    ix->h_knn.resize((size_t)n);
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        const JoinRec &r = ix->h_hits[i];
-        bool ok = r.row >= (uint32_t)first && r.row < (uint32_t)first + (uint32_t)nrows && r.col < (uint32_t)ix->nseqs &&
-                  !(s.self && r.row == r.col);
-        double dist = 0;
-        if (ok && f64) {  // (D, zero) = the double's low and high words, copied, not scaled; NaN fails the compares
-            dist = double_of((uint64_t)r.D | ((uint64_t)r.zero << 32));
-            ok = dist >= 0 && dist <= double_of(ix->h_bound64[r.row - (uint32_t)first]) && dist <= k.pf->max_dist;
-        } else if (ok) {
-            dist = (double)r.D * inv;
-            ok = r.D <= ix->h_bound[r.row - (uint32_t)first] && r.D <= (uint32_t)k.pi->cut;
-        }
-        if (!ok)
-            return c->fail(SED_E_DEVICE, "k-nearest join: record %zu from the device is no candidate (row %u, column %u)", i,
-                           r.row, r.col);
-        ix->h_knn[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, dist};
-    }
-    int64_t kept = 0;
-    if (sed_join_knn_trim(ix->h_knn.data(), (int64_t)n, k.knn, &kept) != SED_OK)
-        return c->fail(SED_E_DEVICE, "k-nearest join: the trim refused the device's records");
-    for (int64_t i = 1; i < kept; ++i)
-        if (ix->h_knn[i - 1].row == ix->h_knn[i].row && ix->h_knn[i - 1].col == ix->h_knn[i].col)
-            return c->fail(SED_E_DEVICE, "k-nearest join: row %d reports column %d twice", ix->h_knn[i].row, ix->h_knn[i].col);
-    *found = kept;
-    if (kept > cap)
-        return c->fail(SED_E_RANGE, "join: found %lld hits, cap %lld: call again with room for them", (long long)kept,
-                       (long long)cap);
-    if (kept) memcpy(out, ix->h_knn.data(), (size_t)kept * sizeof(sed_join_hit));
-    return SED_OK;
-}
-
-// What all joins share once their rows are on the device: the plan's launches, the counters, the hit list.
-// s holds the rows (rows, row_len, row0, self); nrows rows from s.row0 on.
-static int join_run(sed_join_index *ix, const JoinCall &k, sed_join_sides s, int32_t nrows, sed_join_hit *out, int64_t cap,
-                    int64_t *found) {
-    if (k.knn) return join_knn_run(ix, k, s, nrows, out, cap, found);
-    sed_ctx *c = ix->ctx;
-    if ((uint64_t)cap > SIZE_MAX / sizeof(JoinRec) || !ix->d_count.reserve(16) ||
-        !(k.pi ? ix->d_tab.reserve(sizeof ix->h_tab) : ix->d_f64.reserve(sizeof ix->h_f64)) ||
-        !ix->d_hits.reserve(std::max<size_t>((size_t)cap * sizeof(JoinRec), sizeof(JoinRec))) || !ix->pin.reserve(16, 64))
-        return c->fail(SED_E_OOM, "device allocation failed (join, room for %lld hits)", (long long)cap);
-    hipError_t e = hipSuccess;
-    if ((e = ix->timer.begin()) != hipSuccess) return c->hipfail(e, "event create");
-    if ((e = hipMemsetAsync(ix->d_count.p, 0, 16, c->stream)) != hipSuccess) return c->hipfail(e, "upload (join)");
-    join_cols(ix, &s);
-    const sed_join_list list{(uint4 *)ix->d_hits.p, (unsigned long long *)ix->d_count.p, (unsigned long long)cap};
-    sed_join_args a{};  // (one of a and f is filled and launched: the call's route)
-    sed_join_f64_args f{};
-    if (k.pi) {
-        e = join_int_args(ix, *k.pi, list, &a);
-    } else {  // one block: [the table | the keep words]
-        const sed_join_f64_plan_t &plan = *k.pf;
-        static_assert(sizeof ix->h_f64 == sizeof plan.sub + sizeof plan.keep, "the upload's layout");
-        memcpy(ix->h_f64, plan.sub, sizeof plan.sub);
-        memcpy(ix->h_f64 + F64_TAB, plan.keep, sizeof plan.keep);
-        e = hipMemcpyAsync(ix->d_f64.p, ix->h_f64, sizeof ix->h_f64, hipMemcpyHostToDevice, c->stream);
-        f.sub = (const double *)ix->d_f64.p;
-        f.keep = (const unsigned long long *)ix->d_f64.p + F64_TAB;
-        f.ins = plan.ins;
-        f.del = plan.del;
-        f.max_dist = plan.max_dist;
-        f.out = list;
-    }
-    if (e != hipSuccess) return c->hipfail(e, "upload (join)");
-    const int32_t first = s.row0;
-    const int64_t step = k.launch_rows();
-    for (int64_t r = 0; r < nrows; r += step) {  // the events bracket the launches
-        s.row0 = first + (int32_t)r;
-        s.nrows = (int32_t)std::min<int64_t>(step, nrows - r);
-        hipEvent_t e0 = r == 0 ? ix->timer.ev[0] : nullptr, e1 = r + step >= nrows ? ix->timer.ev[1] : nullptr;
-        if (!k.pi) {
-            f.s = s;
-            e = sed_launch_join_f64(c->stream, e0, e1, f);
-        } else {
-            a.s = s;
-            const bool bitpar = k.pi->kernel == SED_JOIN_KERNEL_BITPAR;
-            e = ix->maxlen == SED_JOIN_LONG_MAXLEN ? sed_launch_join_long(c->stream, e0, e1, a, bitpar)
-                                                   : sed_launch_join(c->stream, e0, e1, a, bitpar);
-        }
-        if (e != hipSuccess) return c->hipfail(e, "join kernel launch");
-    }
-    if ((e = hipMemcpyAsync(ix->pin.p, ix->d_count.p, 16, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (join)");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hipfail(e, "join kernel execution");
-    ix->timer.timed = true;
-    ix->timer.knn = false;
-    const uint64_t n = ((const uint64_t *)ix->pin.p)[0];
-    ix->pairs_run = (int64_t)((const uint64_t *)ix->pin.p)[1];
-    *found = (int64_t)n;
-    if (n > (uint64_t)cap)
-        return c->fail(SED_E_RANGE, "join: found %lld hits, cap %lld: call again with room for them", (long long)n,
-                       (long long)cap);
+    if (knn)
+        ix->knn_candidates = (int64_t)n;
+    else
+        *found = (int64_t)n;
     if (n == 0) return SED_OK;
     ix->h_hits.resize((size_t)n);
-    if ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * sizeof(JoinRec), hipMemcpyDeviceToHost, c->stream)) !=
-            hipSuccess ||
+    if ((e = hipMemcpyAsync(ix->h_hits.data(), ix->d_hits.p, (size_t)n * REC_BYTES, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
-        return c->hipfail(e, "download (join hits)");
-    std::sort(ix->h_hits.begin(), ix->h_hits.end(),
-              [](const JoinRec &x, const JoinRec &y) { return x.row != y.row ? x.row < y.row : x.col < y.col; });
-    const double inv = k.pi ? std::ldexp(1.0, -k.pi->scale_log2) : 0.0;
-    for (size_t i = 0; i < (size_t)n; ++i) {
-        const JoinRec &r = ix->h_hits[i];
-        double dist;
-        bool within;
-        if (k.pi) {
-            within = r.D <= (uint32_t)k.pi->cut;
-            dist = (double)r.D * inv;
-        } else {  // (D, zero) = the double's low and high words, copied, not scaled; NaN fails the compare
-            const uint64_t bits = (uint64_t)r.D | ((uint64_t)r.zero << 32);
-            memcpy(&dist, &bits, sizeof dist);
-            within = dist <= k.pf->max_dist;
-        }
-        if (r.row < (uint32_t)first || r.row >= (uint32_t)first + (uint32_t)nrows || r.col >= (uint32_t)ix->nseqs || !within ||
-            (i > 0 && ix->h_hits[i - 1].row == r.row && ix->h_hits[i - 1].col == r.col))
-            return c->fail(SED_E_DEVICE, "join: record %zu from the device is no hit (row %u, column %u)", i, r.row, r.col);
-        out[i] = sed_join_hit{(int32_t)r.row, (int32_t)r.col, dist};
+        return c->hipfail(e, step_of.records);
+    sed_join_hit *hits = out;  // a join's n hits fit the caller's room; a k-nearest call's candidates are trimmed first
+    if (knn) {
+        ix->h_knn.resize((size_t)n);
+        hits = ix->h_knn.data();
     }
+    sed_join_decode_call d{rt.id, 0, 0.0, first, nrows, ix->nseqs, s.self != 0, k.knn, ix->h_bound.data()};
+    rt.decode(k, &d);
+    int64_t kept = 0;
+    const int rc = sed_join_decode_of(d, ix->h_hits.data(), (int64_t)n, hits, &kept, &c->err);
+    if (rc != SED_OK) return rc;
+    *found = kept;
+    if (kept > cap)
+        return c->fail(SED_E_RANGE, "join: found %lld hits, cap %lld: call again with room for them", (long long)kept, (long long)cap);
+    if (knn && kept) memcpy(out, hits, (size_t)kept * sizeof(sed_join_hit));
     return SED_OK;
 }
 
@@ -425,48 +389,34 @@ int32_t sed_join_long_index_seqs(const sed_join_long_index *ix) { return ix ? ix
 
 }  // extern "C"
 
-// The plan of a call under either route (f64: the fp64 planner), the refusal's text in the context
-static int join_plan_call(sed_ctx *c, bool f64, const int32_t *len_rows, int32_t nrows, const sed_join_index *ix, bool self,
-                          uint32_t row_codes, double max_dist, sed_join_plan_t *pi, sed_join_f64_plan_t *pf, JoinCall *k) {
-    if (f64) {
-        k->pf = pf;
-        return sed_join_f64_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes,
-                                    max_dist, pf, &c->err);
-    }
-    k->pi = pi;
-    return sed_join_plan_of(c->costs, c->opt, len_rows, nrows, ix->len.data(), ix->nseqs, self, row_codes, ix->codes, max_dist,
-                            ix->maxlen, pi, &c->err);
-}
-
-// A k-nearest call got past its plan: what sed_join_knn_bounds and sed_join_knn_candidates report until it has run
-static void join_knn_planned(sed_join_index *ix, const JoinCall &k, int32_t nrows) {
+// A call got past its plan: nothing found, nothing run yet; and what sed_join_knn_bounds and sed_join_knn_candidates
+// report of a k-nearest call until it has run: every row's bound where it starts, no candidate
+static void join_planned(sed_join_index *ix, const JoinCall &k, int32_t nrows, int64_t *found) {
+    *found = 0;
+    ix->pairs_run = 0;
     if (!k.knn) return;
-    ix->knn_f64 = k.pf != nullptr;
-    if (k.pf)
-        ix->h_bound64.assign((size_t)nrows, bits_of(k.pf->max_dist));
-    else
-        ix->h_bound.assign((size_t)nrows, (uint32_t)k.pi->cut);
+    ix->knn_route = k.route;
+    ix->bound_rows = nrows;
+    ix->h_bound.assign(((size_t)nrows * k.route->bound_bytes + 7) / 8, k.route->bound0(k));
     ix->knn_candidates = 0;
 }
 
 // (knn: NULL for a join, else k of the k-nearest call)
-static int join_self(sed_join_index *ix, bool f64, const int32_t *knn, int32_t row_lo, int32_t row_hi, double max_dist,
+static int join_self(sed_join_index *ix, const JoinRoute &rt, const int32_t *knn, int32_t row_lo, int32_t row_hi, double max_dist,
                      sed_join_hit *out, int64_t cap, int64_t *found) {
     if (!ix) return SED_E_ARG;
     sed_ctx *c = ix->ctx;
     int rc = join_enter(c, 0 <= row_lo && row_lo <= row_hi && row_hi <= ix->nseqs && cap >= 0 && (cap == 0 || out) && found,
                         knn);
     if (rc != SED_OK) return rc;
-    sed_join_plan_t pi;
-    sed_join_f64_plan_t pf;
     JoinCall k;
+    k.route = &rt;
     k.knn = knn ? *knn : 0;
+    k.maxlen = ix->maxlen;
     const int32_t nrows = row_hi - row_lo;
-    rc = join_plan_call(c, f64, ix->len.data() + row_lo, nrows, ix, true, ix->codes, max_dist, &pi, &pf, &k);
+    rc = rt.plan(c, ix, ix->len.data() + row_lo, nrows, true, ix->codes, max_dist, &k);
     if (rc != SED_OK) return rc;
-    *found = 0;
-    ix->pairs_run = 0;
-    join_knn_planned(ix, k, nrows);
+    join_planned(ix, k, nrows, found);
     if (nrows == 0) return SED_OK;
     sed_join_sides s{};
     s.rows = ix->d_rows.p;
@@ -476,7 +426,7 @@ static int join_self(sed_join_index *ix, bool f64, const int32_t *knn, int32_t r
     return join_run(ix, k, s, nrows, out, cap, found);
 }
 
-static int join_search(sed_join_index *ix, bool f64, const int32_t *knn, const uint8_t *codes_q, const int64_t *off_q,
+static int join_search(sed_join_index *ix, const JoinRoute &rt, const int32_t *knn, const uint8_t *codes_q, const int64_t *off_q,
                        const int32_t *len_q, int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap,
                        int64_t *found) {
     if (!ix) return SED_E_ARG;
@@ -496,15 +446,13 @@ static int join_search(sed_join_index *ix, bool f64, const int32_t *knn, const u
         for (int j = 0; j < len_q[q]; ++j) qcodes |= code_bit(ix->h_query[REC * (size_t)q + j] = codes_q[off_q[q] + j]);
     }
     if (nqueries) memcpy(&ix->h_query[o_len], len_q, sizeof(int32_t) * (size_t)nqueries);
-    sed_join_plan_t pi;
-    sed_join_f64_plan_t pf;
     JoinCall k;
+    k.route = &rt;
     k.knn = knn ? *knn : 0;
-    rc = join_plan_call(c, f64, len_q, nqueries, ix, false, qcodes, max_dist, &pi, &pf, &k);
+    k.maxlen = ix->maxlen;
+    rc = rt.plan(c, ix, len_q, nqueries, false, qcodes, max_dist, &k);
     if (rc != SED_OK) return rc;
-    *found = 0;
-    ix->pairs_run = 0;
-    join_knn_planned(ix, k, nqueries);
+    join_planned(ix, k, nqueries, found);
     if (nqueries == 0 || ix->nseqs == 0) return SED_OK;
     if (!ix->d_query.reserve(qbytes)) return c->fail(SED_E_OOM, "device allocation failed (join, %d queries)", nqueries);
     hipError_t e = hipMemcpyAsync(ix->d_query.p, ix->h_query.data(), qbytes, hipMemcpyHostToDevice, c->stream);
@@ -517,26 +465,35 @@ static int join_search(sed_join_index *ix, bool f64, const int32_t *knn, const u
     return join_run(ix, k, s, nqueries, out, cap, found);
 }
 
+// sed_join_knn_bounds and its siblings: the last k-nearest call's bounds, when that call took route rt
+static int join_knn_bounds(const sed_join_index *ix, const JoinRoute &rt, void *bounds, int32_t n) {
+    if (!ix || n < 0 || (n && !bounds)) return SED_E_ARG;
+    if (ix->knn_candidates < 0 || ix->knn_route != &rt) return SED_E_STATE;
+    if (n != ix->bound_rows) return SED_E_ARG;
+    if (n) memcpy(bounds, ix->h_bound.data(), (size_t)n * rt.bound_bytes);
+    return SED_OK;
+}
+
 extern "C" {
 
 int sed_join_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
                   int64_t *found) {
-    return join_self(ix, false, nullptr, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, ROUTE_INT, nullptr, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out, int64_t cap,
                       int64_t *found) {
-    return join_self(ix, true, nullptr, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, ROUTE_F64, nullptr, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                     int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, false, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, ROUTE_INT, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                         int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, true, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, ROUTE_F64, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_last_time(const sed_join_index *ix, float *kernel_ms) {
@@ -557,40 +514,28 @@ int32_t sed_join_rows_per_group(void) { return SED_JOIN_G; }
 // ---- the k nearest columns of every row (the integer route of either index type) ----
 int sed_join_knn_self(sed_join_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist, sed_join_hit *out,
                       int64_t cap, int64_t *found) {
-    return join_self(ix, false, &k, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, ROUTE_INT, &k, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_knn_search(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                         int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, false, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, ROUTE_INT, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
-int sed_join_knn_bounds(const sed_join_index *ix, int32_t *bounds, int32_t n) {
-    if (!ix || n < 0 || (n && !bounds)) return SED_E_ARG;
-    if (ix->knn_candidates < 0 || ix->knn_f64) return SED_E_STATE;
-    if ((size_t)n != ix->h_bound.size()) return SED_E_ARG;
-    for (int32_t i = 0; i < n; ++i) bounds[i] = (int32_t)ix->h_bound[(size_t)i];
-    return SED_OK;
-}
+int sed_join_knn_bounds(const sed_join_index *ix, int32_t *bounds, int32_t n) { return join_knn_bounds(ix, ROUTE_INT, bounds, n); }
 
 // ---- the same on the fp64 route (the short index) ----
 int sed_join_knn_self_f64(sed_join_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist, sed_join_hit *out,
                           int64_t cap, int64_t *found) {
-    return join_self(ix, true, &k, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, ROUTE_F64, &k, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_knn_search_f64(sed_join_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                             int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, true, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, ROUTE_F64, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
-int sed_join_knn_bounds_f64(const sed_join_index *ix, double *bounds, int32_t n) {
-    if (!ix || n < 0 || (n && !bounds)) return SED_E_ARG;
-    if (ix->knn_candidates < 0 || !ix->knn_f64) return SED_E_STATE;
-    if ((size_t)n != ix->h_bound64.size()) return SED_E_ARG;
-    for (int32_t i = 0; i < n; ++i) bounds[i] = double_of(ix->h_bound64[(size_t)i]);
-    return SED_OK;
-}
+int sed_join_knn_bounds_f64(const sed_join_index *ix, double *bounds, int32_t n) { return join_knn_bounds(ix, ROUTE_F64, bounds, n); }
 
 int sed_join_knn_candidates(const sed_join_index *ix, int64_t *n) {
     if (!ix || !n) return SED_E_ARG;
@@ -607,12 +552,12 @@ int sed_join_knn_bound_time(const sed_join_index *ix, float *kernel_ms) {
 
 int sed_join_long_knn_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, int32_t k, double max_dist,
                            sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_self(ix, false, &k, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, ROUTE_INT, &k, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_long_knn_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                              int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, false, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, ROUTE_INT, &k, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_long_knn_bounds(const sed_join_long_index *ix, int32_t *bounds, int32_t n) { return sed_join_knn_bounds(ix, bounds, n); }
@@ -624,12 +569,12 @@ int sed_join_long_knn_bound_time(const sed_join_long_index *ix, float *kernel_ms
 // ---- sequences of up to 128 symbols: the calls above over the other index type (the integer route only) ----
 int sed_join_long_self(sed_join_long_index *ix, int32_t row_lo, int32_t row_hi, double max_dist, sed_join_hit *out,
                        int64_t cap, int64_t *found) {
-    return join_self(ix, false, nullptr, row_lo, row_hi, max_dist, out, cap, found);
+    return join_self(ix, ROUTE_INT, nullptr, row_lo, row_hi, max_dist, out, cap, found);
 }
 
 int sed_join_long_search(sed_join_long_index *ix, const uint8_t *codes_q, const int64_t *off_q, const int32_t *len_q,
                          int32_t nqueries, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found) {
-    return join_search(ix, false, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
+    return join_search(ix, ROUTE_INT, nullptr, codes_q, off_q, len_q, nqueries, max_dist, out, cap, found);
 }
 
 int sed_join_long_last_time(const sed_join_long_index *ix, float *kernel_ms) { return sed_join_last_time(ix, kernel_ms); }

@@ -205,6 +205,8 @@ SIGNATURES = [
     ("sed_join_knn_candidates", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("sed_join_knn_bound_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("sed_join_knn_trim", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    ("sed_join_decode", C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p, C.c_int]),
     ("sed_join_knn_plan", C.c_int, [C.c_int, C.c_int32, C.c_int, _f64p, _u8p, C.c_double, C.c_int, C.c_double, C.c_int,
                                     _i32p, C.c_int, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int, C.c_uint32, C.c_uint32,
                                     C.c_double, _f64p, C.c_int]),
@@ -906,31 +908,34 @@ def _join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_cod
                                          int(bool(self_join)), int(row_codes), int(col_codes), float(max_dist))
 
 
-def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist, _call="sed_join_plan"):
+def _join_plan_call(name, head, args, error=None, lane_cells=False):
+    """The plan dict of one join _plan export: head = what it takes before _join_args' arguments (args), error = the
+    export that holds a refusal's text (None: it has no such channel), lane_cells: it fills the seventh slot."""
+    fields = JOIN_PLAN_FIELDS + (("lane_cells",) if lane_cells else ())
+    out = np.zeros(len(fields), np.float64)
+    rc = getattr(load(), name)(*head, *_join_args(*args), out, len(out))
+    if rc != 0:
+        if error is None:
+            raise _fit_fail(name, rc)
+        err = SedError("%s failed (%d): %s" % (name, rc, getattr(load(), error)().decode()))
+        err.code = rc
+        raise err
+    return {f: (float(v) if f in ("scale", "cells", "lane_cells") else int(v)) for f, v in zip(fields, out)}
+
+
+def join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
     """What JoinIndex.self_join / search would decide, without a device (sed_join_plan): {field: number} over
     JOIN_PLAN_FIELDS.  costs and options as plan_routes takes them; row_codes / col_codes from codes_seen.  Raises
     SedError carrying the SED_E_* code (.code) the join would fail with."""
-    out = np.zeros(len(JOIN_PLAN_FIELDS), np.float64)
-    rc = getattr(load(), _call)(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
-                                out, len(out))
-    if rc != 0:
-        raise _fit_fail(_call, rc)
-    return {k: (float(v) if k in ("scale", "cells") else int(v)) for k, v in zip(JOIN_PLAN_FIELDS, out)}
+    return _join_plan_call("sed_join_plan", (), (costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist))
 
 
 def join_long_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
     """What LongJoinIndex.self_join / search would decide, without a device (sed_join_long_plan): join_plan's fields for
     lengths 0..128, and "lane_cells", the cells the waves execute with their blocks of 32 columns and their spare lanes.
     Arguments and errors as join_plan; the SedError also carries the refusal's text (sed_join_long_plan_error)."""
-    fields = JOIN_PLAN_FIELDS + ("lane_cells",)
-    out = np.zeros(len(fields), np.float64)
-    rc = load().sed_join_long_plan(*_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
-                                   out, len(out))
-    if rc != 0:
-        err = SedError("sed_join_long_plan failed (%d): %s" % (rc, load().sed_join_long_plan_error().decode()))
-        err.code = rc
-        raise err
-    return {k: (float(v) if k in ("scale", "cells", "lane_cells") else int(v)) for k, v in zip(fields, out)}
+    return _join_plan_call("sed_join_long_plan", (), (costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                           "sed_join_long_plan_error", True)
 
 
 def join_knn_trim(hits, k):
@@ -944,39 +949,51 @@ def join_knn_trim(hits, k):
     return out[:kept.value]
 
 
+def join_decode(records, route, cap, rows, ncols, self_join, scale_log2=0, k=0, bounds=None):
+    """What every join call does with the records it downloads, without a device (sed_join_decode): records = an (n, 4)
+    uint32 array of (row, col, w0, w1); route = "int" (dist = w0 * 2^-scale_log2, cap = the cutoff on that scale) or
+    "f64" ((w0, w1) = the double's low and high words, cap = max_dist); rows = (first, nrows) of the call.  k = 0: a
+    join's hits sorted by (row, col); k >= 1: a k-nearest call's, trimmed, under bounds (one per row: integers on the
+    "int" route, doubles on "f64").  Returns JOIN_HIT_DTYPE records; a record no kernel emits raises SedError (.code =
+    SED_E_DEVICE, the text names it), bad arguments SedError with .code = SED_E_ARG."""
+    rec = np.ascontiguousarray(records, np.uint32).reshape(-1, 4)
+    first, nrows = rows
+    out = np.zeros(max(len(rec), 1), JOIN_HIT_DTYPE)
+    kept = C.c_int64()
+    why = C.create_string_buffer(256)
+    b = None if bounds is None else np.ascontiguousarray(bounds, np.float64 if route == "f64" else np.uint32)
+    rc = load().sed_join_decode(rec.ctypes.data if len(rec) else None, len(rec), {v: r for r, v in JOIN_ROUTES.items()}[route],
+                                int(scale_log2), float(cap), int(first), int(nrows), int(ncols), int(bool(self_join)), int(k),
+                                None if b is None or not len(b) else b.ctypes.data, out.ctypes.data, C.byref(kept), why, len(why))
+    if rc != 0:
+        err = SedError("sed_join_decode failed (%d): %s" % (rc, why.value.decode()))
+        err.code = rc
+        raise err
+    return out[:kept.value]
+
+
 def join_knn_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, k, max_dist, long_index=False):
     """What JoinIndex.self_knn / search_knn (long_index: LongJoinIndex's) would decide, without a device
     (sed_join_knn_plan): k outside 1..64 raises SedError (.code = SED_E_ARG, the text names k), then join_plan's (or
     join_long_plan's) refusals; the fields are those of the join at max_dist, which bound each pass from above."""
-    fields = JOIN_PLAN_FIELDS + (("lane_cells",) if long_index else ())
-    out = np.zeros(len(fields), np.float64)
-    rc = load().sed_join_knn_plan(int(bool(long_index)), int(k), *_join_args(costs, options, len_rows, len_cols, self_join,
-                                                                            row_codes, col_codes, max_dist), out, len(out))
-    if rc != 0:
-        err = SedError("sed_join_knn_plan failed (%d): %s" % (rc, load().sed_join_knn_plan_error().decode()))
-        err.code = rc
-        raise err
-    return {f: (float(v) if f in ("scale", "cells", "lane_cells") else int(v)) for f, v in zip(fields, out)}
+    return _join_plan_call("sed_join_knn_plan", (int(bool(long_index)), int(k)),
+                           (costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                           "sed_join_knn_plan_error", bool(long_index))
 
 
 def join_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist):
     """What JoinIndex.self_join_f64 / search_f64 would decide, without a device (sed_join_f64_plan): join_plan's fields
     with scale = 0 (fp64 has none) and kernel = 3.  Arguments and errors as join_plan."""
-    return join_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist, "sed_join_f64_plan")
+    return _join_plan_call("sed_join_f64_plan", (), (costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist))
 
 
 def join_knn_f64_plan(costs, options, len_rows, len_cols, self_join, row_codes, col_codes, k, max_dist):
     """What JoinIndex.self_knn_f64 / search_knn_f64 would decide, without a device (sed_join_knn_f64_plan): k outside
     1..64 raises SedError (.code = SED_E_ARG, the text names k), then join_f64_plan's refusals, with their text; the
     fields are those of the fp64 join at max_dist, which bound each pass from above."""
-    out = np.zeros(len(JOIN_PLAN_FIELDS), np.float64)
-    rc = load().sed_join_knn_f64_plan(int(k), *_join_args(costs, options, len_rows, len_cols, self_join, row_codes, col_codes,
-                                                          max_dist), out, len(out))
-    if rc != 0:
-        err = SedError("sed_join_knn_f64_plan failed (%d): %s" % (rc, load().sed_join_knn_plan_error().decode()))
-        err.code = rc
-        raise err
-    return {f: (float(v) if f in ("scale", "cells") else int(v)) for f, v in zip(JOIN_PLAN_FIELDS, out)}
+    return _join_plan_call("sed_join_knn_f64_plan", (int(k),),
+                           (costs, options, len_rows, len_cols, self_join, row_codes, col_codes, max_dist),
+                           "sed_join_knn_plan_error")
 
 
 def join_f64_lower(ins, dele):

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../include/sed.h"
@@ -103,6 +104,46 @@ int main() {
     expect("sed_join_f64_plan code", sed_join_f64_plan(COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0x200, 1.5, out, 6), SED_E_ARG);
     expect("sed_join_f64_keep", sed_join_f64_keep(0.1, 0.2, 0.3, keep), SED_OK);
     expect("sed_join_f64_keep NaN", sed_join_f64_keep(1.0, 1.0, std::nan(""), keep), SED_E_ARG);
+    const int32_t jl[] = {0, 33, 127, 128}, jl_bad[] = {5, 129};
+    expect("sed_join_long_plan", sed_join_long_plan(COSTS(unit, join_rows3, 1), jl, 4, jl, 4, 1, 0xF, 0xF, 3.0, out, 7), SED_OK);
+    expect("sed_join_long_plan length", sed_join_long_plan(COSTS(unit, nullptr, 0), jl_bad, 2, jl, 4, 0, 0xF, 0xF, 3.0, out, 7), SED_E_ARG);
+    expect("sed_join_long_plan text", *sed_join_long_plan_error() != 0, 1);
+    expect("sed_join_knn_plan", sed_join_knn_plan(0, 64, COSTS(unit, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, INFINITY, out, 6), SED_OK);
+    expect("sed_join_knn_plan long", sed_join_knn_plan(1, 1, COSTS(unit, nullptr, 0), jl, 4, jl, 4, 1, 0xF, 0xF, 2.0, out, 7), SED_OK);
+    expect("sed_join_knn_plan k=65", sed_join_knn_plan(0, 65, COSTS(unit, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 2.0, nullptr, 6), SED_E_ARG);
+    expect("sed_join_knn_plan K=9", sed_join_knn_plan(0, 1, COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 2.0, out, 6), SED_E_RANGE);
+    expect("sed_join_knn_f64_plan", sed_join_knn_f64_plan(3, COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0x1FF, 0xF, 1.5, out, 6), SED_OK);
+    expect("sed_join_knn_f64_plan k=0", sed_join_knn_f64_plan(0, COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0x1FF, 0xF, 1.5, out, 6), SED_E_ARG);
+    expect("sed_join_knn_f64_plan K=17", sed_join_knn_f64_plan(3, COSTS(k17, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 1.5, out, 6), SED_E_RANGE);
+    expect("sed_join_knn_plan_error", *sed_join_knn_plan_error() != 0, 1);
+    std::vector<double> low(33 * 33);
+    expect("sed_join_f64_lower", sed_join_f64_lower(0.1, 0.2, low.data()), SED_OK);
+    expect("sed_join_f64_lower inf", sed_join_f64_lower(1.0, INFINITY, low.data()), SED_E_ARG);
+    sed_join_hit hits[] = {{1, 4, 2.0}, {0, 3, 1.0}, {1, 2, 2.0}, {1, 9, 0.5}, {0, 5, 1.0}};
+    int64_t kept = 0;
+    expect("sed_join_knn_trim", sed_join_knn_trim(hits, 5, 2, &kept), SED_OK);
+    expect("sed_join_knn_trim kept", (int)kept, 4);
+    expect("sed_join_knn_trim k=0", sed_join_knn_trim(hits, 5, 0, &kept), SED_E_ARG);
+    // the decode: a join on each route, a k-nearest call on each (the fp64 bounds at an odd address), and their refusals
+    const uint32_t rec_int[] = {12, 3, 7, 0, 10, 19, 0, 0, 12, 0, 65535, 0, 13, 13, 1, 0};
+    const uint32_t rec_f64[] = {11, 4, 0, 0x3FF00000u, 10, 2, 0, 0x7FF00000u, 11, 1, 0, 0x3FF00000u};  // 1.0, +inf, 1.0
+    const uint32_t b_int[] = {0, 0, 65535, 1};
+    unsigned char b_raw[4 * sizeof(double) + 1];
+    const double b_f64[] = {INFINITY, 1.0, 0.0, 0.0};
+    memcpy(b_raw + 1, b_f64, sizeof b_f64);
+    sed_join_hit dec[4];
+    expect("sed_join_decode int", sed_join_decode(rec_int, 4, SED_JOIN_ROUTE_INT, 8, 65535.0, 10, 4, 20, 0, 0, nullptr, dec, &kept, why, sizeof why), SED_OK);
+    expect("sed_join_decode int kept", (int)kept, 4);
+    expect("sed_join_decode f64", sed_join_decode(rec_f64, 3, SED_JOIN_ROUTE_F64, 0, INFINITY, 10, 4, 20, 1, 0, nullptr, dec, &kept, why, sizeof why), SED_OK);
+    expect("sed_join_decode knn int", sed_join_decode(rec_int, 4, SED_JOIN_ROUTE_INT, 0, 65535.0, 10, 4, 20, 0, 1, b_int, dec, &kept, why, sizeof why), SED_OK);
+    expect("sed_join_decode knn int kept", (int)kept, 3);
+    expect("sed_join_decode knn f64", sed_join_decode(rec_f64, 3, SED_JOIN_ROUTE_F64, 0, INFINITY, 10, 4, 20, 1, 64, b_raw + 1, dec, &kept, why, sizeof why), SED_OK);
+    expect("sed_join_decode empty", sed_join_decode(nullptr, 0, SED_JOIN_ROUTE_INT, 0, 1.0, 0, 0, 0, 0, 0, nullptr, nullptr, &kept, nullptr, 0), SED_OK);
+    expect("sed_join_decode self (13, 13)", sed_join_decode(rec_int, 4, SED_JOIN_ROUTE_INT, 8, 65535.0, 10, 4, 20, 1, 0, nullptr, dec, &kept, why, 8), SED_E_DEVICE);
+    expect("sed_join_decode row outside", sed_join_decode(rec_int, 4, SED_JOIN_ROUTE_INT, 0, 65535.0, 11, 3, 20, 0, 0, nullptr, dec, &kept, why, sizeof why), SED_E_DEVICE);
+    expect("sed_join_decode above the cap", sed_join_decode(rec_f64, 3, SED_JOIN_ROUTE_F64, 0, 1e308, 10, 4, 20, 1, 0, nullptr, dec, &kept, why, sizeof why), SED_E_DEVICE);
+    expect("sed_join_decode above a bound", sed_join_decode(rec_int, 4, SED_JOIN_ROUTE_INT, 0, 65535.0, 10, 4, 20, 0, 1, b_int + 1, dec, &kept, why, 0), SED_E_DEVICE);
+    expect("sed_join_decode k=65", sed_join_decode(rec_int, 4, SED_JOIN_ROUTE_INT, 0, 65535.0, 10, 4, 20, 0, 65, b_int, dec, &kept, why, sizeof why), SED_E_ARG);
     expect("sed_join_route int", sed_join_route(COSTS(unit, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, INFINITY, why, sizeof why), SED_JOIN_ROUTE_INT);
     expect("sed_join_route f64", sed_join_route(COSTS(k9, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 0.0, why, sizeof why), SED_JOIN_ROUTE_F64);
     expect("sed_join_route neither", sed_join_route(COSTS(k17, nullptr, 0), jr, 7, jc, 10, 0, 0xF, 0xF, 2.0, why, sizeof why), SED_E_RANGE);

@@ -1,6 +1,8 @@
 """Host time per call of the fit and join entry points, one library against another (SED_LIBRARY), for a change that
-must leave it alone: the eight index calls (search / hits x short / long x integer / fp64), the two pair calls and the
-four join calls, each on the smallest workload of its own tools/fit_*_ab.py or tools/join*_ab.py.
+must leave it alone: the eight index calls (search / hits x short / long x integer / fp64), the two pair calls and ten
+join calls (self / search x integer / fp64; the k-nearest self and search calls, the fp64 k-nearest self call; the long
+index's self, search and k-nearest self calls), each on the smallest workload of its own tools/fit_*_ab.py or
+tools/join*_ab.py.
 
 A library is a process (sedgpu binds one per process), so the two alternate as processes, --rounds of each: every
 process builds the same seeded inputs, warms every call up once and then times --runs calls of each with a host clock
@@ -9,7 +11,7 @@ each library, the base library's spread (the least and the largest of its own ti
 other library's median lies within it.  Kernel ms (HIP events) ride along to show what share of the call is host time.
 
     python tools/route_refactor_ab.py --base tools/ab_libs/parent.so [--new rna-sequence-diff-patch_amd/libsed.so]
-                                      [--rounds 3] [--runs 7] [--out profiles/route_refactor]
+                                      [--base-package DIR] [--rounds 3] [--runs 7] [--out profiles/route_refactor]
 
 Writes ab.json and README.md into --out."""
 import argparse
@@ -20,10 +22,12 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "rna-sequence-diff-patch_amd"), os.path.join(REPO, "oracle")):
+# SED_AB_PACKAGE: the folder of the sedgpu.py a worker imports (--base-package sets it for the base library's workers)
+for p in (os.environ.get("SED_AB_PACKAGE") or os.path.join(REPO, "rna-sequence-diff-patch_amd"), os.path.join(REPO, "oracle")):
     if p not in sys.path:
         sys.path.insert(0, p)
 IUPAC = "AGCUYRWSKMDVHBN"
+KNN_K = 8  # tools/join_knn_ab.py, join_knn_f64_ab.py
 
 
 def worker(a):
@@ -47,6 +51,9 @@ def worker(a):
     q_long = sedgpu.PackedPairs([long_], [np.zeros(0, np.uint8)])
     pairs = sedgpu.PackedPairs([short] * a.texts, docs)
     q_join = sedgpu.PackedPairs(seqs[:64], [np.zeros(0, np.uint8)] * len(seqs[:64]))
+    rng_long = np.random.default_rng(a.seqs + 60)          # tools/join_long_ab.py, join_knn_ab.py: 60..90 symbols
+    seqs_long = [rng_long.integers(0, 4, size=int(n)).astype(np.uint8) for n in rng_long.integers(60, 91, size=a.seqs)]
+    q_join_long = sedgpu.PackedPairs(seqs_long[:64], [np.zeros(0, np.uint8)] * 64)
     ctx = sedgpu.context()
     out = {}
 
@@ -73,7 +80,16 @@ def worker(a):
         jx = sedgpu.JoinIndex.from_seqs(ctx, seqs)
         measure("join_self" + sfx, lambda: getattr(jx, "self_join" + sfx)(2.0), jx.last_ms)
         measure("join_search" + sfx, lambda: getattr(jx, "search" + sfx)(q_join, 2.0), jx.last_ms)
+        measure("join_knn_self" + sfx, lambda: getattr(jx, "self_knn" + sfx)(KNN_K), jx.last_ms)
+        if not f64:
+            measure("join_knn_search", lambda: jx.search_knn(q_join, KNN_K), jx.last_ms)
         jx.close()
+        if not f64:  # (the long index has the integer route alone)
+            lx = sedgpu.LongJoinIndex.from_seqs(ctx, seqs_long)
+            measure("join_long_self", lambda: lx.self_join(8.0), lx.last_ms)
+            measure("join_long_search", lambda: lx.search(q_join_long, 8.0), lx.last_ms)
+            measure("join_long_knn_self", lambda: lx.self_knn(KNN_K), lx.last_ms)
+            lx.close()
     ctx.close()
     print("RESULT " + json.dumps(out), flush=True)
 
@@ -88,6 +104,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", default=os.path.join(REPO, "tools", "ab_libs", "parent.so"))
     ap.add_argument("--new", default=os.path.join(REPO, "rna-sequence-diff-patch_amd", "libsed.so"))
+    ap.add_argument("--base-package", default=None, help="the folder of the base commit's own sedgpu.py, when the base "
+                    "library lacks an export this tree's sedgpu.py binds")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--texts", type=int, default=8192)
@@ -103,6 +121,8 @@ def main():
     for r in range(a.rounds):
         for k, path in libs.items():  # a fresh child per library and round, one at a time
             env = dict(os.environ, SED_LIBRARY=path)
+            if k == "base" and a.base_package:
+                env["SED_AB_PACKAGE"] = os.path.abspath(a.base_package)
             cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--runs", str(a.runs), "--texts", str(a.texts),
                    "--length", str(a.length), "--seqs", str(a.seqs)]
             p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True, timeout=600)
@@ -131,7 +151,7 @@ def main():
 
 
 def readme(r):
-    out = ["# Host time per call before and after the route refactor", "",
+    out = ["# Host time per call, one library against another", "",
            "Written by `tools/route_refactor_ab.py`; the raw numbers are in `ab.json`.", "",
            "base = the parent commit's library, new = this tree's; the kernels are the same objects, so only the host code"
            " around them differs.  Each library ran in %d processes of its own, alternating with the other's; every process"
@@ -139,8 +159,10 @@ def readme(r):
            " (a host clock around a call that ends in the stream's synchronise).  Spread = the least and the largest of base's"
            " own %d timed calls.  Kernel ms are the engine's HIP events for the same calls." % (r["rounds"], r["runs"], r["rounds"] * r["runs"]),
            "", "Workloads: the fit calls, one query (28 symbols; long: 76) against %d texts of %d nt, the pair calls the same"
-           " %d pairs; the join calls, %d sequences of 24..32 symbols at T = 2 (search: 64 query rows).  Integer routes under"
-           " `user_costs.json` over ACGU, fp64 routes under `costs.json` over the 15 IUPAC symbols." % (r["texts"], r["length"], r["texts"], r["seqs"]),
+           " %d pairs; the join calls, %d sequences of 24..32 symbols at T = 2 (search: 64 query rows), the k-nearest calls"
+           " on the same at k = %d, the long index's calls on as many sequences of 60..90 symbols at T = 8 and k = %d.  Integer"
+           " routes under `user_costs.json` over ACGU, fp64 routes under `costs.json` over the 15 IUPAC symbols."
+           % (r["texts"], r["length"], r["texts"], r["seqs"], KNN_K, KNN_K),
            "", "| entry point | base median ms | base spread (min .. max) | new median ms | new median against base's spread |"
            " base / new round medians | kernel ms base / new |", "|---|---|---|---|---|---|---|"]
     for name, e in r["entries"].items():
