@@ -1,5 +1,5 @@
 // sed_ck_tile.h — recomputing one 64 x 64 tile from the forward kernels' checkpoints, and walking its codes: what the
-// checkpoint traceback (sed_cktb.hip: sed_traceback_ck_kernel) and the SPLIT route's code tiles (sed_kernels.hip:
+// checkpoint traceback (sed_cktb.hip: sed_traceback_ck_kernel) and the SPLIT route's code tiles (sed_tb.hip:
 // sed_ck_codes_kernel) share.
 #pragma once
 #include "sed_i32_keys.h"

@@ -202,17 +202,9 @@ hipError_t sed_launch_traceback_ck(const sed_launch &L, uint32_t *ops, const sed
     const sed_band *bd = L.band;
     const int2 *win = L.band && L.bsuf ? L.bwin : nullptr;  // (refined windows only: the static ones are restated)
     const int ws = L.bstripes;
-    switch (L.R) {
-    case 4:
-        SED_LAUNCH(sed_traceback_ck_kernel<4>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd, win, ws);
-        break;
-    case 8:
-        SED_LAUNCH(sed_traceback_ck_kernel<8>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd, win, ws);
-        break;
-    case 16:
-        SED_LAUNCH(sed_traceback_ck_kernel<16>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm, bd, win, ws);
-        break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return sed_for_R<4, 8, 16>(L.R, [&](auto r) {
+        SED_LAUNCH(sed_traceback_ck_kernel<decltype(r)::value>, grid, block, 0, L, L.pd, L.npairs, a, b, L.tb, L.res, ops, prm,
+                   bd, win, ws);
+        return hipGetLastError();
+    });
 }

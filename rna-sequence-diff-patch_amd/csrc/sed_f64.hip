@@ -606,13 +606,11 @@ static hipError_t launch_f64_R(const sed_launch &L, const double *gtab, const se
 template <bool TB, bool TYPED, bool FULL = false>
 static hipError_t launch_f64_split(const sed_launch &L, const double *gtab, const sed_f64_params &prm,
                                    const sed_full_out &fo = sed_full_out{}) {
-    if (L.R == 2)
-        SED_LAUNCH((sed_wf_f64_split_kernel<2, TB, TYPED, FULL>), dim3(L.ntasks), dim3(128), 0, L, L.pd, L.tasks,
-                   (const uint8_t *)L.seqa, (const uint8_t *)L.seqb, L.tb, L.bnd, L.res, gtab, prm, fo);
-    else if (L.R == 4)
-        SED_LAUNCH((sed_wf_f64_split_kernel<4, TB, TYPED, FULL>), dim3(L.ntasks), dim3(128), 0, L, L.pd, L.tasks,
-               (const uint8_t *)L.seqa, (const uint8_t *)L.seqb, L.tb, L.bnd, L.res, gtab, prm, fo);
-    return hipGetLastError();
+    return sed_for_R<2, 4>(L.R, [&](auto r) {
+        SED_LAUNCH((sed_wf_f64_split_kernel<decltype(r)::value, TB, TYPED, FULL>), dim3(L.ntasks), dim3(128), 0, L, L.pd,
+                   L.tasks, (const uint8_t *)L.seqa, (const uint8_t *)L.seqb, L.tb, L.bnd, L.res, gtab, prm, fo);
+        return hipGetLastError();
+    });
 }
 
 hipError_t sed_launch_f64_full(const sed_launch &L, const double *gtab, const sed_f64_params &prm, bool typed,
@@ -628,35 +626,26 @@ hipError_t sed_launch_f64_full(const sed_launch &L, const double *gtab, const se
 hipError_t sed_launch_f64(const sed_launch &L, const double *gtab, const sed_f64_params &prm, bool typed) {
     const bool tb = L.tb != nullptr;
     if (L.ntasks > 0) {
-        if (L.R != 2 && L.R != 4) return hipErrorInvalidValue;
         if (typed) return tb ? launch_f64_split<true, true>(L, gtab, prm) : launch_f64_split<false, true>(L, gtab, prm);
         return tb ? launch_f64_split<true, false>(L, gtab, prm) : launch_f64_split<false, false>(L, gtab, prm);
     }
-    switch (L.R) {
-#define CASE(RR)                                                                                    \
-    case RR:                                                                                        \
-        if (typed) return tb ? launch_f64_R<RR, true, true>(L, gtab, prm)                           \
-                             : launch_f64_R<RR, false, true>(L, gtab, prm);                         \
-        return tb ? launch_f64_R<RR, true, false>(L, gtab, prm) : launch_f64_R<RR, false, false>(L, gtab, prm);
-        CASE(4) CASE(8)  // (R = 16: 206 VGPRs, 2 waves per SIMD, iupac 5.22-5.25 against 5.04-5.06 ms at R = 8)
-#undef CASE
-    default: return hipErrorInvalidValue;
-    }
+    // (R = 16: 206 VGPRs, 2 waves per SIMD, iupac 5.22-5.25 against 5.04-5.06 ms at R = 8)
+    return sed_for_R<4, 8>(L.R, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (typed) return tb ? launch_f64_R<R, true, true>(L, gtab, prm) : launch_f64_R<R, false, true>(L, gtab, prm);
+        return tb ? launch_f64_R<R, true, false>(L, gtab, prm) : launch_f64_R<R, false, false>(L, gtab, prm);
+    });
 }
 
 hipError_t sed_launch_f64_seg(const sed_launch &L, const double *gtab, const sed_f64_params &prm, bool typed,
                               const int32_t *idx, int nidx) {
     const bool tb = L.tb != nullptr;
     const sed_full_out none{};
-    switch (L.R) {
-#define CASE(RR)                                                                                               \
-    case RR:                                                                                                   \
-        if (typed) return tb ? launch_f64_R<RR, true, true, false, 16>(L, gtab, prm, none, idx, nidx)          \
-                             : launch_f64_R<RR, false, true, false, 16>(L, gtab, prm, none, idx, nidx);        \
-        return tb ? launch_f64_R<RR, true, false, false, 16>(L, gtab, prm, none, idx, nidx)                    \
-                  : launch_f64_R<RR, false, false, false, 16>(L, gtab, prm, none, idx, nidx);
-        CASE(4) CASE(8)
-#undef CASE
-    default: return hipErrorInvalidValue;
-    }
+    return sed_for_R<4, 8>(L.R, [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        if (typed) return tb ? launch_f64_R<R, true, true, false, 16>(L, gtab, prm, none, idx, nidx)
+                             : launch_f64_R<R, false, true, false, 16>(L, gtab, prm, none, idx, nidx);
+        return tb ? launch_f64_R<R, true, false, false, 16>(L, gtab, prm, none, idx, nidx)
+                  : launch_f64_R<R, false, false, false, 16>(L, gtab, prm, none, idx, nidx);
+    });
 }

@@ -1,8 +1,8 @@
 // sed_i32_keys.h — the integer (packed-key) cell machinery that more than one kernel family uses: the dot-product
 // update candidate and its hazard fence, the row ladders, one column step of a lane's rows (i32_step), the borders,
 // the sink decode, the conversions from forward keys to traceback keys, the ramp sentinels and the stripe kernel's
-// group of steps (i32_group).  Users: sed_kernels.hip (stripe / SPLIT, CHAIN, the tracebacks' ladder
-// patterns) and, through sed_ck_tile.h, sed_ck_codes_kernel and sed_cktb.hip.
+// group of steps (i32_group).  Users: sed_kernels.hip (stripe / SPLIT, CHAIN), sed_tb.hip (the tracebacks'
+// ladder patterns; through sed_ck_tile.h, sed_ck_codes_kernel) and, through sed_ck_tile.h, sed_cktb.hip.
 #pragma once
 #include "sed_internal.h"
 #include "sed_dev.h"

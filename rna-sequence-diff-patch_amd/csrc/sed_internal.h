@@ -121,6 +121,14 @@ struct sed_full_out {
 // use it include <hip/hip_ext.h> (the host-compiled runtime does not)
 #define SED_LAUNCH(kernel, grid, block, shmem, L, ...) \
     hipExtLaunchKernelGGL(kernel, grid, block, shmem, (L).stream, (L).ev0, (L).ev1, 0, __VA_ARGS__)
+// The runtime's rows per lane as a template argument, for every launcher: f(std::integral_constant<int, R>{}) for the R
+// of Rs... that equals rows, hipErrorInvalidValue for any other.  A generic f is instantiated for every R of the list and
+// no other, so a site's list is the set of kernels it builds.
+template <int... Rs, class F> inline hipError_t sed_for_R(int rows, F f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((rows == Rs && ((e = f(std::integral_constant<int, Rs>{})), true)) || ...);
+    return e;
+}
 
 struct sed_launch {
     const sed_pair_desc *pd;
@@ -304,17 +312,8 @@ __host__ __device__ inline int sed_fit_long_rows(int P) {  // the smallest R wit
     while (64 * R < P) R *= 2;
     return R;
 }
-// `rows` as a compile-time R for the long launchers: f(std::integral_constant<int, R>), or an error for no such R
-template <class F> inline hipError_t sed_fit_long_with_rows(int rows, F f) {
-    switch (rows) {
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    case 16: return f(std::integral_constant<int, 16>{});
-    case 32: return f(std::integral_constant<int, 32>{});
-    }
-    return hipErrorInvalidValue;
-}
+// `rows` as a compile-time R for the long launchers (sed_for_R over the R of sed_fit_long_rows)
+template <class F> inline hipError_t sed_fit_long_with_rows(int rows, F f) { return sed_for_R<2, 4, 8, 16, 32>(rows, f); }
 hipError_t sed_launch_fit_index_long(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,
                                      const int32_t *qlist, int rows, const sed_fit_params &fp);
 hipError_t sed_launch_fit_index_long_hits(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const sed_fit_index_args &a,

@@ -1,4 +1,4 @@
-"""CPU model of sed_ck_codes_kernel's code re-layout (sed_kernels.hip, config 2's checkpoint route).
+"""CPU model of sed_ck_codes_kernel's code re-layout (sed_tb.hip, config 2's checkpoint route).
 
 A tile's sweep leaves lane r (= 4b + rr: forward lane 16Q + b, row rr) with the codes of sweep steps 0..127 in W[8]
 (step sigma at W[sigma >> 4] bits 2 (sigma & 15)).  The kernel takes each lane's 64 codes from sweep step

@@ -710,6 +710,40 @@ def test_checkpoint_two_residency_rounds_every_pair(gpu, tables):
     _check_all(plan, packed, d, ii, ln, ops)
 
 
+@pytest.mark.parametrize("arm,R", [("x2", 32), ("f64", 8), ("seg", 8)])
+def test_launcher_rows_no_other_test_forces(gpu, tables, arm, R):
+    """The launchers' rows-per-lane arms no other test forces (the table in profiles/i32_units/README.md): the two
+    pairs per wave kernel at R = 32 (distance only, pairs of equal n), the fp64 wave kernel with its per-cell-code
+    traceback at R = 8, and the fp64 16-lane segments with theirs at R = 8 (segments take more than 256 wave pairs, so
+    260 here, 6 elsewhere).  n = SW R + 1 rows, SW the lanes a pair runs on: two stripes, so the bottom-row hand-over
+    and the sink's lane and row arithmetic are live; m in 65..130, two 64-step chunks.  Every pair against the oracle,
+    scripts op by op."""
+    SW, count = (16, 260) if arm == "seg" else (64, 6)
+    alphabet = "ACGU" if arm == "x2" else "AGCUYRWSKMDVHBN"  # (costs.json over IUPAC symbols: the fp64 mode)
+    plan = sedcost.build_plan(tables[arm == "x2"], [alphabet], [alphabet])
+    rng = np.random.default_rng(5900 + R + SW)
+    A = [rng.integers(0, plan.K, size=SW * R + 1).astype(np.uint8) for _ in range(count)]
+    B = [rng.integers(0, plan.K, size=int(rng.integers(65, 131))).astype(np.uint8) for _ in range(count)]
+    gpu.set_costs(plan)
+    packed = sedgpu.PackedPairs(A, B)
+    opts = {sedgpu.SED_OPT_ROWS_PER_LANE: R}
+    opts.update({sedgpu.SED_OPT_SEG: 1} if arm == "seg" else {sedgpu.SED_OPT_SPLIT: 2})
+    for k, v in opts.items():
+        gpu.set_option(k, v)
+    try:
+        b, (d, ii, ln, ops) = _batch_run(gpu, packed, arm != "x2", no_len=arm == "x2")
+        try:
+            assert b.mode in (("i32",) if arm == "x2" else ("f64", "f64-typed"))
+            assert b.rows_per_lane == R and b.split_tasks == 0
+            assert (b.packed_pairs, b.segment_pairs) == {"x2": (count, 0), "f64": (0, 0), "seg": (0, count)}[arm]
+        finally:
+            b.close()
+    finally:
+        for k in opts:
+            gpu.set_option(k, 0)
+    _check_all(plan, packed, d, ii, ln, ops, script=arm != "x2", no_len=arm == "x2")
+
+
 @pytest.mark.parametrize("name", plan_route_cases.GPU_NAMES)
 def test_getters_agree_with_the_device_free_planner(gpu, name):
     """A created batch (nothing runs) reports through every sed_batch_* getter what sed_plan_routes computes for the

@@ -63,7 +63,7 @@ def _oracle_scripts(table, items):
 
 @pytest.mark.parametrize("name", INT)
 def test_integer_split_members_hold_and_have_three_stripes(name):
-    """The band map and compose kernels return for pairs of fewer than three stripes (sed_kernels.hip: K < 3), so every
+    """The band map and compose kernels return for pairs of fewer than three stripes (sed_tb.hip: K < 3), so every
     member of the integer SPLIT batch has three at its R = 4; the delete runs at columns 64 and 65 cross both stripe
     borders and the stairs the second."""
     items = pc.split_batch(name)

@@ -1,7 +1,8 @@
 """Per-kernel register, LDS and scratch use of libsed.so's gfx950 code objects (the AMDGPU metadata notes):
 name, VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes per lane, and the waves per SIMD the VGPR count allows; then
 the kernel's fingerprint: its instruction count and a short hash of its disassembled instruction stream (mnemonics
-and operands as llvm-objdump -d prints them, without addresses and encodings).  Lines are sorted by demangled name,
+and operands as llvm-objdump -d prints them, without addresses and encodings, and without the s_nop / s_code_end fill
+between a kernel's end and the next function's alignment).  Lines are sorted by demangled name,
 so two libraries compare with plain diff:
 
     python tools/kernel_resources.py [libsed.so [name substring]]
@@ -69,6 +70,9 @@ def fingerprints(lib_path):
             if mn == "...":  # llvm-objdump's mark for a run of zero padding after a code object's last kernel
                 continue
             streams.setdefault(fn, []).append("%s %s\n" % (mn, ", ".join(ops)))
+    for lines in streams.values():  # the fill up to the next function's alignment belongs to the layout, not the kernel
+        while lines and lines[-1].split()[0] in ("s_nop", "s_code_end"):
+            lines.pop()
     return {fn: (len(lines), hashlib.sha256("".join(lines).encode()).hexdigest()[:12]) for fn, lines in streams.items()}
 
 
