@@ -757,7 +757,7 @@ int sed_join_knn_search_f64(sed_join_index *ix, const uint8_t *codes_q, const in
                             int32_t nqueries, int32_t k, double max_dist, sed_join_hit *out, int64_t cap, int64_t *found);
 /* The last fp64 k-nearest call's per-row bounds after pass 1, as doubles: bounds[i] belongs to row row_lo + i (query i),
  * n = the call's rows exactly (else SED_E_ARG).  A call that launched nothing reports max_dist for every row.
- * SED_E_STATE before the first k-nearest call that got past its plan, and when the last such call was an integer one. */
+ * No bound is negative: a max_dist of -0.0 is reported as +0.0.  SED_E_STATE before the first k-nearest call that got past its plan, and when the last such call was an integer one. */
 int sed_join_knn_bounds_f64(const sed_join_index *ix, double *bounds, int32_t n);
 /* What an fp64 k-nearest call would decide, without a device: k, then sed_join_f64_plan's arguments.  k outside 1..64:
  * SED_E_ARG before anything else is looked at; then sed_join_f64_plan's refusals in their order.  out[]: the fp64 join's

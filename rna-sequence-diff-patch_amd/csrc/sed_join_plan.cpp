@@ -298,7 +298,9 @@ int sed_join_f64_plan_of(const sed_costs &c, const sed_opts &o, const int32_t *l
     auto rule = [&]() -> int {
         const int rc = sed_join_f64_costs_rule(c, plan, err);
         if (rc != SED_OK) return rc;
-        plan->max_dist = max_dist;
+        // (-0.0 + 0.0 = +0.0: the k-nearest passes start every row's bound from these bits and order bounds as unsigned
+        // keys, whose sign bit is 0; as -0.0 the starting bound lay above every key and was reported as -0.0)
+        plan->max_dist = max_dist + 0.0;
         sed_join_f64_lower_rule(plan->ins, plan->del, plan->low);
         sed_join_f64_keep_rule(plan->ins, plan->del, max_dist, plan->keep);
         return SED_OK;

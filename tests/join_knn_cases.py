@@ -487,9 +487,10 @@ def envelope_calls(group=None, kind=None, case=None):
             (case is None or c.case == case)]
 
 
-def call_inputs(call):
-    """(the set, the index's columns, the call's rows, D of rows against columns, self join?, the first row)."""
-    s = envelope_set(call.set)
+def call_inputs(call, set_of=envelope_set):
+    """(the set, the index's columns, the call's rows, D of rows against columns, self join?, the first row); set_of: the
+    sets the call's name is looked up in (join_knn_f64_envelope.py has its own)."""
+    s = set_of(call.set)
     cols = s.cols if call.ncols is None else s.cols[:call.ncols]
     if call.queries is None:
         lo, hi = call.rows or (0, len(cols))

@@ -89,11 +89,12 @@ def low_of(low, len_rows, len_cols):
     return np.asarray(low)[np.asarray(len_rows, np.int64)[:, None], np.asarray(len_cols, np.int64)[None, :]]
 
 
-def bound_pass_model(D, ok, len_rows, len_cols, low, k, T, order="sequential", kth=kth_by_bisection):
+def bound_pass_model(D, ok, len_rows, len_cols, low, k, T, order="sequential", kth=kth_by_bisection, read=None):
     """sed_join_f64.hip's pass 1 wave by wave, as join_knn_cases.bound_pass_model states the integer one: per wave and row
     b = the bound read; go = ok && low[n][m] <= b; nothing when no lane goes; cand = go && D <= b; nothing when fewer
-    than k candidates; x = the bisection on the keys; atomicMin(bound[r], x) when x < b's key.  `order` as there.  Returns
-    (the final bounds as doubles, the pairs the pass ran)."""
+    than k candidates; x = the bisection on the keys; atomicMin(bound[r], x) when x < b's key.  `order` as there.  `read`
+    (tests of the tests): what a wave makes of the 64-bit word it loaded, the identity in the kernel.  Returns (the final
+    bounds as doubles, the pairs the pass ran)."""
     D, ok = np.asarray(D, np.float64), np.asarray(ok, bool)
     K = keys(D)
     R = D.shape[0]
@@ -116,6 +117,8 @@ def bound_pass_model(D, ok, len_rows, len_cols, low, k, T, order="sequential", k
             b = np.stack(history)[rng.integers(len(history), size=R), np.arange(R)]
         else:
             b = bound
+        if read is not None:
+            b = read(b)
         bd = b.view(np.float64)
         go = ok[:, lanes] & (lo[:, lanes] <= bd[:, None])
         pairs += int(go.sum())
@@ -127,10 +130,13 @@ def bound_pass_model(D, ok, len_rows, len_cols, low, k, T, order="sequential", k
     return bound.view(np.float64), pairs
 
 
-def emit_pass_model(D, ok, len_rows, len_cols, low, bound):
+def emit_pass_model(D, ok, len_rows, len_cols, low, bound, read=None):
     """Pass 2: go = ok && low[n][m] <= bound[r]; (the candidates' mask go && D <= bound[r], the pairs run, the (wave,
-    row) that no lane went for)."""
-    b = np.asarray(bound, np.float64)[:, None]
+    row) that no lane went for).  `read` as in bound_pass_model."""
+    b = np.ascontiguousarray(bound, np.float64)
+    if read is not None:
+        b = read(b.view(np.uint64)).view(np.float64)
+    b = b[:, None]
     go = np.asarray(ok, bool) & (low_of(low, len_rows, len_cols) <= b)
     index = np.argsort(np.asarray(len_cols), kind="stable")
     skipped = sum(int((~go[:, index[w:w + WAVE]].any(1)).sum()) for w in range(0, len(index), WAVE))
