@@ -297,23 +297,29 @@ bool unit_costs(const sed_costs &c) {
 // A set of at most 4 codes with unit costs among themselves (insert = delete = 1.0, every mismatch 1.0, every match
 // the int 0), as a bit mask, greedily in code order; 0 when insert / delete are not 1.0.  A pair whose symbols all
 // lie in it has the unit-cost distance whatever the other symbols cost (config 5 with N: the pairs without N).
+// The first code always joins an empty set, so a pass that ends with that code alone starts again at the next one:
+// codes follow the first occurrences of the batch's symbols, and a batch whose first symbol is N has the same subset
+// as one whose first symbol is A.
 uint32_t unit_subset(const sed_costs &c) {
     if (c.K > SED_MAX_K || c.ins_int || c.del_int || c.ins != 1.0 || c.del != 1.0) return 0;
-    uint32_t S = 0;
-    int cnt = 0;
-    for (int a = 0; a < c.K && cnt < 4; ++a) {
-        bool ok = c.sub_int[a * c.K + a] && c.sub[a * c.K + a] == 0;
-        for (int bb = 0; bb < c.K && ok; ++bb)
-            if ((S >> bb) & 1u) {
-                const int e1 = a * c.K + bb, e2 = bb * c.K + a;
-                ok = !c.sub_int[e1] && c.sub[e1] == 1.0 && !c.sub_int[e2] && c.sub[e2] == 1.0;
+    for (int first = 0; first + 1 < c.K; ++first) {
+        uint32_t S = 0;
+        int cnt = 0;
+        for (int a = first; a < c.K && cnt < 4; ++a) {
+            bool ok = c.sub_int[a * c.K + a] && c.sub[a * c.K + a] == 0;
+            for (int bb = first; bb < a && ok; ++bb)
+                if ((S >> bb) & 1u) {
+                    const int e1 = a * c.K + bb, e2 = bb * c.K + a;
+                    ok = !c.sub_int[e1] && c.sub[e1] == 1.0 && !c.sub_int[e2] && c.sub[e2] == 1.0;
+                }
+            if (ok) {
+                S |= 1u << a;
+                ++cnt;
             }
-        if (ok) {
-            S |= 1u << a;
-            ++cnt;
         }
+        if (cnt >= 2) return S;
     }
-    return cnt >= 2 ? S : 0;
+    return 0;
 }
 
 // Dyadic costs over at most 8 symbols (sed_lane.hip: sed_lane_scaled_kernel): the smallest S = 2^k (k <= 8) that makes
